@@ -27,7 +27,13 @@ streams its sub-basins (the cut basin's trunk rides in its owner's stream some d
 exchanged once per day, rank 0 gathers the outlet block.  TRMC_BENCH_PIPELINE=two-plans times round 5's pipeline
 (troute_amd.sequence.DaySequence: a plan and its clone taking turns) as the headline instead.
 
-Prints ONE JSON line: BASELINE.json's metric (segment-timesteps/s) plus
+Prints ONE JSON line: BASELINE.json's metric (segment-timesteps/s), ms_per_step (wall milliseconds of one timed day) and the
+stream's shape.  A plain run does only that: it builds the plan, tunes it on day N, warms up, times `--steps` days and prints
+the line.  `--dump-outputs DIR` also writes the last timed day's products -- what a caller of the stream receives -- as
+DIR/outlet_hydrographs.npy [outlets, nsteps] and DIR/final_state.npy [segments, 3] (float32; float64 with --precision 64, then
+a fixed seeded sample of the state's rows, DIR/final_state_rows.npy, keeps the files within 64 MB; several ranks: rank 0's
+outlet hydrographs only).  The inputs are seeded: the same arguments give the same inputs in every run.
+`--full` adds every other leg below (each one still switched off by its own --no-* option):
   roofline          the day (all launches of one day of the stream) and, under dominant_kernel, k_mc_tile by itself against the
                     8 TB/s HBM roofline: HIP events on the tile stream around every timed day's launches; traffic and valu: counter
                     passes of this very command (rocprofv3 --pmc) over the last window
@@ -109,7 +115,37 @@ def parse():
     ap.add_argument("--no-persistence-sweep", action="store_true", help="skip the legs with less persistent forcing")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline duration")
     ap.add_argument("--cpu-threads", type=int, default=0, help="OpenMP threads of the CPU baseline (default: one per CPU the cgroup grants, at most the physical cores)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg beside the headline (untuned plan, other pipelines, checker, CPU baseline, counter passes, ...)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed day's products (outlet hydrographs, final state) as DIR/<name>.npy")
+    a = ap.parse_args()
+    if not a.full:      # a plain run: the headline alone
+        a.no_cpu_baseline = a.no_full_ts = a.no_parity_mode = a.no_diffusive = a.no_dropin = a.no_tolerance = True
+        a.no_parity_full = a.no_traffic = a.no_persistence_sweep = True
+    return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, hyd, final):
+    """The last timed day's products as out_dir/<name>.npy; the final state's rows are sampled (fixed seed, sorted) when the
+    whole of both would exceed DUMP_LIMIT_BYTES, and the sampled rows are written beside them."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"outlet_hydrographs": np.ascontiguousarray(hyd)}
+    if final is not None:
+        final = np.ascontiguousarray(final)
+        room = DUMP_LIMIT_BYTES - arrays["outlet_hydrographs"].nbytes - 3 * 4096     # (and the files' headers)
+        if final.nbytes > room:
+            row_bytes = final.itemsize * final.shape[1] + 8          # (+ its index in final_state_rows, float64)
+            keep = max(0, room // row_bytes)
+            rows = np.sort(np.random.default_rng(0).choice(final.shape[0], size=keep, replace=False))
+            arrays["final_state_rows"] = rows.astype(np.float64)
+            final = final[rows]
+        arrays["final_state"] = final
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def cpu_quota():
@@ -642,10 +678,12 @@ def main():
         return r._state_plans[0].download_final_state() if use_dist else r.plan0.download_final_state()
     state_n = state_after_day_n(router)
     router.upload(a.nsteps, qlat_b, None)              # day N+1, warm
-    unt = timed(router, True, usteps, 1)
-    untuned = {"value": rate(unt), "unit": "segment-timesteps/s", "ms_per_step": unt["el"] / usteps * 1e3,
-               "ms_main": unt["ms_main"], "roofline_frac": frac(unt),
-               "window": "day N+1, warm start (the headline's window) on the plan built from the topology alone"}
+    untuned = None
+    if a.full or a.headline_only:
+        unt = timed(router, True, usteps, 1)
+        untuned = {"value": rate(unt), "unit": "segment-timesteps/s", "ms_per_step": unt["el"] / usteps * 1e3,
+                   "ms_main": unt["ms_main"], "roofline_frac": frac(unt),
+                   "window": "day N+1, warm start (the headline's window) on the plan built from the topology alone"}
     # the days of the timed sequence (a ring of distinct days in page-locked memory: see 3.)
     from troute_amd.sequence import DaySequence, pinned_like
     ndays = max(2 if a.headline_only else 4, min(int(os.environ.get("TRMC_BENCH_DAYS", "10")), a.steps + a.warmup))
@@ -658,7 +696,7 @@ def main():
     assert np.array_equal(ring[0], qlat_b) or a.persistence is not None
     t_days = time.perf_counter() - t0
     # ... and the headline's own protocol -- the sequence of days, plan and clone -- on that plan, before it is rebuilt
-    if not use_dist and not a.headline_only and not a.no_retune and a.precision == 32:
+    if a.full and not use_dist and not a.headline_only and not a.no_retune and a.precision == 32:
         try:
             with DaySequence(router, a.nsteps, a.qts) as us:
                 us.run(ring, state_n, max(6, len(ring)), 0)
@@ -733,6 +771,12 @@ def main():
     dayseq = DaySequence(router, a.nsteps, a.qts, nchunks=a.chunks, output_stride=ostride,
                          timeline=bool(os.environ.get("TRMC_BENCH_DEBUG")))
     srouter, stream_ring, stream_err = None, None, None
+    dumped = None                                      # (--dump-outputs: the last timed day's products, copied off their ring)
+
+    def keep_products(res):
+        if a.dump_outputs and rank == 0:
+            return (np.array(res["hyd"], copy=True), None if use_dist else np.array(res["final"], copy=True))
+        return None
     if use_stream:
         try:
             srouter = make_router(hint, True, None, None, stream=True)
@@ -741,6 +785,7 @@ def main():
                 stream_ring = rs.prepare_days(ring) if use_dist else ring
                 rs.run(stream_ring, state_n, 2, 0, prepared=True)   # (untimed: the ring of day slots, the page-locked product rings)
                 sseq = rs.run(stream_ring, state_n, a.steps, a.warmup, prepared=True)
+                dumped = keep_products(sseq)
             sinfo = sseq["info"]
             tpd = sinfo["tiles_per_day"]
             nrouted = int(srouter._rowsS.shape[0]) if use_dist else nseg
@@ -765,9 +810,10 @@ def main():
     if use_dist and not use_stream:
         local_ring = dayseq.prepare_days(ring)          # (this rank's rows of every day, page-locked: outside the clock)
         seq = dayseq.run(local_ring, state_n, a.steps, a.warmup, prepared=True)
+        dumped = keep_products(seq)
         head = {"el": seq["el"], "ms_main": float(np.mean(seq["ms_main"])), "ms_total": seq["el"] / a.steps * 1e3,
                 "launches": router.last_stats["phase0"]["main_launches"], "stats": router.last_stats, "hyd": seq["hyd"], "steps": a.steps}
-    elif not use_dist and not (use_stream and a.headline_only):
+    elif not use_dist and not (use_stream and (a.headline_only or not a.full)):
         # round 5's pipeline -- a plan and its clone taking turns (DaySequence) -- beside the stream (`pipeline_two_plans`), or as
         # the headline itself (TRMC_BENCH_PIPELINE=two-plans)
         # (untimed: the clone's window buffers -- 19 GB of planes and result -- and both plans' copy streams and page-locked
@@ -783,6 +829,7 @@ def main():
                              "one launch per timestep"}
         if not use_stream:
             seq = oseq
+            dumped = keep_products(seq)
             # (ms_main of the sequence: the WALL time per day, every kernel, copy and hand-over of the pipeline in it -- the events
             # around a single window also span what the neighbouring day's kernels take of the device while they overlap it)
             head = {"el": seq["el"], "ms_main": seq["el"] / a.steps * 1e3, "ms_total": seq["el"] / a.steps * 1e3,
@@ -825,6 +872,8 @@ def main():
     if hyd is None:                                 # (a rank other than 0 of a multi-GPU job does not fetch the outlet block)
         hyd = np.zeros((0, a.nsteps), np.float32)
     assert np.isfinite(hyd).all()
+    if dumped is not None:
+        dump_outputs(a.dump_outputs, *dumped)
     if a.headline_only:            # (a counter pass of pmc_counters(): the last windows of the process are the headline's)
         if rank == 0:
             json_out.write(json.dumps({"metric": "segment-timesteps/sec, CONUS NHD 2.7M-seg MC", "value": rate(head),
@@ -857,8 +906,10 @@ def main():
             chk = dayseq.run(local_ring[:2], state_n, 2, 0, prepared=True)
             if rank == 0:
                 dist_outlets = (np.array(router._out_rows, copy=True), np.array(chk["hyd"], copy=True))
-    router.upload(a.nsteps, qlat_b, None if use_dist else state_n)   # (the legs below route day N+1 again and again on the one plan)
-    resident = timed(router, True, max(1, min(a.steps, 3)), 1)
+    resident = None
+    if a.full:
+        router.upload(a.nsteps, qlat_b, None if use_dist else state_n)   # (the legs below route day N+1 again and again on the one plan)
+        resident = timed(router, True, max(1, min(a.steps, 3)), 1)
     value = rate(head)
     info = router.plan0.info()
     stats = head["stats"]
@@ -869,12 +920,13 @@ def main():
         allr = comm.all_gather_host(np.array([head["ms_main"], float(seg0)], dtype=np.float64))
         per_rank = [{"rank": i, "ms_main": float(t[0]), "segment_steps": int(t[1])} for i, t in enumerate(allr)]
 
-    extra = {"value_tolerance": None, "value_resident": {"value": rate(resident), "unit": "segment-timesteps/s",
+    extra = {"value_tolerance": None, "value_resident": None if resident is None else {
+                                "value": rate(resident), "unit": "segment-timesteps/s",
                                 "ms_per_step": resident["el"] / resident["steps"] * 1e3, "ms_main": resident["ms_main"],
                                 "what": "the same windows with every result left in HBM (no copy to the host in the clock)"},
              "copied_per_step": f"outlet hydrographs [{len(net['net_sizes'])} x {a.nsteps}] + final state [{nseg} x 3] into page-locked "
                                 "host arrays on a copy stream beside the next window; the last window's copy is waited for inside the clock"}
-    if not use_dist:
+    if a.full and not use_dist:
         if not a.no_parity_mode:
             w = timed(router, True, 2, 1, d2h="full")
             extra["parity_mode"] = {"value": rate(w), "unit": "segment-timesteps/s", "ms_per_step": w["el"] / 2 * 1e3,

@@ -86,9 +86,23 @@ def _worker(rank, world, port, tmp, short):
     dist.destroy_process_group()
 
 
+def spawn_ranks(target, world, args):
+    """`world` fresh processes running target(rank, *args), started by the standard library: the test process itself never
+    imports torch (its bundled librccl.so.1 would be the one the package's communicator loads in the tests that follow)"""
+    import multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    ps = [ctx.Process(target=target, args=(r,) + tuple(args)) for r in range(world)]
+    [p.start() for p in ps]
+    [p.join(300) for p in ps]
+    alive = [p for p in ps if p.is_alive()]
+    for p in alive:
+        p.terminate()
+        p.join()
+    assert not alive and all(p.exitcode == 0 for p in ps), [p.exitcode for p in ps]
+
+
 @pytest.mark.parametrize("short", [True, False])
 def test_world2_gloo_equals_single_process(tmp_path, short):
-    import torch.multiprocessing as mp
     from oracle_plan import OraclePlan
     from troute_amd.distributed import ShardedRouter
     net = small_conus()
@@ -98,7 +112,7 @@ def test_world2_gloo_equals_single_process(tmp_path, short):
     rows1, hyd1 = single.route(12, short)
     assert rows1.shape[0] == 40                                     # one outlet per independent network
     port = 29500 + (os.getpid() % 2000) + (1 if short else 0)
-    mp.spawn(_worker, args=(2, port, str(tmp_path), short), nprocs=2, join=True)
+    spawn_ranks(_worker, 2, (2, port, str(tmp_path), short))
     outs = [np.load(tmp_path / f"out_{r}.npz") for r in range(2)]
     assert int(outs[0]["ncut"]) > 0 and (bool(outs[0]["has_trunk"]) or bool(outs[1]["has_trunk"]))
     for o in outs:                                                  # every rank ends with the full gather
@@ -180,7 +194,6 @@ def test_world2_gloo_stream_of_days_equals_single_process(tmp_path, stride):
     protocol -- the trunk's lag agreed by an all-reduce over every rank's cut rows, the cut-edge hydrographs of day e exchanged
     when every rank's cut rows are through it, the drain after the last day -- against seven days routed one by one on one
     process.  The stand-in checks the schedule the way the library does and poisons rows whose inflows arrive too late."""
-    import torch.multiprocessing as mp
     from oracle_plan import OraclePlan
     from troute_amd.distributed import ShardedRouter
     net = small_conus()
@@ -200,7 +213,7 @@ def test_world2_gloo_stream_of_days_equals_single_process(tmp_path, stride):
         want_s.append(state)
         want_f.append(f)
     port = 31500 + (os.getpid() % 2000) + (7 if stride else 0)
-    mp.spawn(_stream_worker, args=(2, port, str(tmp_path), stride), nprocs=2, join=True)
+    spawn_ranks(_stream_worker, 2, (2, port, str(tmp_path), stride))
     outs = [np.load(tmp_path / f"stream_{r}.npz") for r in range(2)]
     assert int(outs[0]["ncut"]) > 0 and (bool(outs[0]["has_trunk"]) or bool(outs[1]["has_trunk"]))
     assert int(outs[0]["dc"]) == int(outs[1]["dc"]) >= 1 and int(outs[0]["lag"]) == int(outs[1]["lag"])

@@ -4,6 +4,9 @@ Every check here runs on CPU.  Fixtures were produced by tests/golden/make_fixtu
 reference Fortran compiled in the dev container (oracle/Makefile `ref`); when those builds are
 present (dev container) the live comparison runs too.
 """
+import hashlib
+import os
+
 import numpy as np
 import pytest
 
@@ -77,16 +80,32 @@ def test_as_shipped_kernel_is_only_statistically_comparable():
     assert np.quantile(rel[m], 0.9) < 1e-2
 
 
-@pytest.mark.skipif(not O.have_ref("libmc_ref_qj0_f32.so"), reason="oracle/_ref not built (needs /root/reference)")
-def test_live_against_ref_builds_on_fresh_vectors():
+def fresh_vectors():
+    """100 000 of the kernel vectors drawn again with their flows jittered (seeded)"""
     rng = np.random.default_rng(123)
     n = 100_000
     x = X32[rng.integers(0, X32.shape[0], n)].copy()
     x[:, 1:5] *= rng.uniform(0.5, 2.0, (n, 4)).astype(np.float32)     # jitter the flows
     x[:, 14] *= rng.uniform(0.5, 2.0, n).astype(np.float32)
-    assert np.array_equal(bits(O.segments(x)), bits(O.ref_segments(x, "libmc_ref_qj0_f32.so")))
-    x64 = x.astype(np.float64)
-    assert np.array_equal(bits(O.segments(x64)), bits(O.ref_segments(x64, "libmc_ref_qj0_f64.so")))
+    return x
+
+
+def digest(a):
+    """SHA-256 of the bits of an output array (what tests/golden/make_ref_recordings.py records of the reference's)"""
+    return hashlib.sha256(bits(np.ascontiguousarray(a)).tobytes()).hexdigest()
+
+
+def test_live_against_ref_builds_on_fresh_vectors():
+    """restated kernel == reference Fortran (canonical Qj_0) on fresh vectors, fp32 and fp64, bit for bit: against the digest
+    of the reference's outputs recorded in tests/golden/reference_recordings.npz, and live where oracle/_ref is present"""
+    rec = np.load(os.path.join(H.GOLDEN, "reference_recordings.npz"))
+    x = fresh_vectors()
+    for xs, sfx in ((x, "f32"), (x.astype(np.float64), "f64")):
+        got = O.segments(xs)
+        assert digest(got) == str(rec["fresh_vectors_sha256_" + sfx])
+        name = f"libmc_ref_qj0_{sfx}.so"
+        if O.have_ref(name):
+            assert np.array_equal(bits(got), bits(O.ref_segments(xs, name)))
 
 
 @pytest.mark.parametrize("short", [True, False])

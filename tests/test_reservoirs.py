@@ -44,30 +44,58 @@ def test_graph_collapse_equals_reference():
     assert all([lk] in [list(r) for rl in reaches_bytw.values() for r in rl] for lk in lakes)   # lakes are singletons
 
 
-@pytest.mark.skipif(not O.have_ref("liblp_ref.so"), reason="oracle/_ref not built (needs /root/reference)")
-def test_oracle_levelpool_equals_reference_fortran_live():
-    lp = C.CDLL(O.ref_path("liblp_ref.so"))
-    lp.get_lp_handle.restype = C.c_void_p
-    f = C.c_float
+LP_PERIODS = 40
+
+
+def levelpool_cases():
+    """every lake of the domain with its parameter row, its initial water elevation and LP_PERIODS lognormal inflows"""
     lakes, wbody_cols = lake_tables()
     rng = np.random.default_rng(2)
     for k in range(len(lakes)):
         a = wbody_cols[k].astype(np.float32)
         par = np.array([a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], 10.0], np.float32)
         h0 = np.float32(a[4] + np.float32(np.float32(a[1] - a[4]) * a[8]))
+        inflows = [np.float32(rng.lognormal(0, 2)) for _ in range(LP_PERIODS)]
+        yield int(lakes[k]), par, h0, inflows
+
+
+def reference_levelpool_runs(lp):
+    """(outflow, water elevation) [lakes, LP_PERIODS] float32 of the reference Fortran level pool (liblp_ref.so, bind_lp.f90)
+    over levelpool_cases() -- what tests/golden/make_ref_recordings.py records"""
+    lp.get_lp_handle.restype = C.c_void_p
+    f = C.c_float
+    outs, hs = [], []
+    for lake, par, h0, inflows in levelpool_cases():
         hv = C.c_void_p(lp.get_lp_handle())
         we_ = f(float(h0))
         lp.init_lp(hv, C.byref(we_), *[C.byref(f(float(v))) for v in (par[0], par[6], par[5], par[7], par[8], par[4], par[3],
-                                                                     par[2], par[1])], C.byref(C.c_int(int(lakes[k]))),
+                                                                     par[2], par[1])], C.byref(C.c_int(lake)),
                    C.byref(C.c_int(1)))
-        Hr, Hm = f(float(h0)), np.float32(h0)
-        for _ in range(40):
-            inflow = np.float32(rng.lognormal(0, 2))
+        Hr = f(float(h0))
+        outs.append([])
+        hs.append([])
+        for inflow in inflows:
             out = f(0)
             lp.run_lp(hv, C.byref(f(float(inflow))), C.byref(f(0.0)), C.byref(Hr), C.byref(out), C.byref(f(300.0)))
-            q, Hm = O.levelpool(inflow, 300.0, Hm, par)
-            assert np.float32(out.value).tobytes() == q.tobytes() and np.float32(Hr.value).tobytes() == Hm.tobytes()
+            outs[-1].append(out.value)
+            hs[-1].append(Hr.value)
         lp.free_lp(hv)
+    return np.array(outs, np.float32), np.array(hs, np.float32)
+
+
+def test_oracle_levelpool_equals_reference_fortran_live():
+    """the restated level pool == the reference Fortran, bit for bit: against its outputs recorded in
+    tests/golden/reference_recordings.npz, and live where the reference build (oracle/_ref) is present"""
+    rec = np.load(os.path.join(H.GOLDEN, "reference_recordings.npz"))
+    wants = [(rec["levelpool_out"], rec["levelpool_h"])]
+    if O.have_ref("liblp_ref.so"):
+        wants.append(reference_levelpool_runs(C.CDLL(O.ref_path("liblp_ref.so"))))
+    for k, (lake, par, h0, inflows) in enumerate(levelpool_cases()):
+        Hm = np.float32(h0)
+        for i, inflow in enumerate(inflows):
+            q, Hm = O.levelpool(inflow, 300.0, Hm, par)
+            for want_q, want_h in wants:
+                assert want_q[k, i].tobytes() == q.tobytes() and want_h[k, i].tobytes() == Hm.tobytes()
 
 
 def reservoir_case(nts=288):

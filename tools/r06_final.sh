@@ -11,7 +11,7 @@ rm -f gpurun_out/tolerance_report.json
 grep -n "passed\|failed\|FAILED" $out/pytest.log | tail -8
 cp gpurun_out/tolerance_report.json $out/ 2>/dev/null
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-( time python bench.py --steps ${BENCH_STEPS:-20} ) > $out/bench.json 2> $out/bench.err
+( time python bench.py --full --steps ${BENCH_STEPS:-20} ) > $out/bench.json 2> $out/bench.err
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r06z/bench.json').read().strip().splitlines()[-1])
@@ -35,6 +35,6 @@ find $out -name '*.db' -delete
 head -30 gpurun_out/r06_rocprofv3_summary.txt | cut -c1-180
 tail -8 gpurun_out/r06_rocprofv3_summary.txt | cut -c1-220
 for n in 2 8; do
-  ( time timeout 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port 2957$n bench.py --gpus $n --steps 3 --warmup 1 --no-full-ts ) > $out/bench_gpus$n.json 2> $out/bench_gpus$n.err
+  ( time timeout 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port 2957$n bench.py --gpus $n --full --steps 3 --warmup 1 --no-full-ts ) > $out/bench_gpus$n.json 2> $out/bench_gpus$n.err
   echo "gpus $n rc=$? $(tail -c 300 $out/bench_gpus$n.json)"
 done
