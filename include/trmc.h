@@ -189,11 +189,12 @@ int trmc_plan_create_ex(int64_t nseg, const int64_t *up_ptr, const int64_t *up_i
  *                  device one launch does not fill (a rank of a multi-GPU job); measured slower at 32, 16 and 8.
  *   stream_split   s > 0: in a stream of windows the slices from level s on are launched on the clusters' stream instead of the
  *                  tile stream (an experiment: 3 % faster on CONUS on one GPU, twice as slow on a rank of eight; default 0).
- *   velocity_on_demand  != 0: in a stream of windows begun without full_output, a step's velocity is formed only where it is
- *                  handed on -- at the kept steps of output_stride, or nowhere when the products are hydrographs and final
- *                  states.  The velocity feeds nothing (MCsingleSegStime_f2py_NOLOOP.f90:163-169 computes it from the final
- *                  depth; the next step takes velp and does not read it), so every product keeps its bits; a tenth of a step's
- *                  instructions are not issued (CONUS: 12.3 instead of 13.5 ms per day).  Default 0: every step forms it.
+ *   velocity_on_demand  >= 0 (default): in a stream of windows begun without full_output, a step's velocity is formed only
+ *                  where it is handed on -- at the kept steps of output_stride, or nowhere when the products are hydrographs and
+ *                  final states.  The velocity feeds nothing (MCsingleSegStime_f2py_NOLOOP.f90:163-169 computes it from the final
+ *                  depth; the next step takes velp and does not read it), so every product keeps its bits, and a tenth of a
+ *                  step's instructions are not issued.  < 0: every step forms it anyway (an A/B override).  Streams with
+ *                  full_output, single windows and the dataflow engine always form every velocity.
  *   tail_sort      < 0: keep the per-level order below the tiled levels of a hinted short-timestep plan (default: by cost).
  *   stem_min_rows  general-mode dataflow plans: basins whose longest path has at least so many rows are laid out stem-last
  *                  (0 = default 1 024, < 0 = off).

@@ -48,6 +48,7 @@ ARITH_EXACT, ARITH_TOLERANCE = 0, 1
 # Environment variables the HOST layer maps onto trmc_plan_options when a plan is created (tests and A/B measurements; the
 # library itself reads none of them).  name -> (field, how): "off0" = the variable's 0 means "off" (the field's < 0), any
 # other number is the value; "int" = the number as it is; "flag" = 1 when the variable is "1".
+# (TRMC_VELOCITY_ON_DEMAND: a stream without full_output forms velocities at its kept steps only by default; -1 = at every step)
 OPTION_ENV = {
     "TRMC_WIDE_MIN_ROWS": ("wide_min_rows", "off0"), "TRMC_WIDE_LEVELS": ("wide_levels", "int"), "TRMC_WIDE_K": ("wide_k", "int"),
     "TRMC_MID_MIN_ROWS": ("mid_min_rows", "off0"), "TRMC_MID_LEVELS": ("mid_levels", "int"), "TRMC_MID_K": ("mid_k", "int"),

@@ -242,7 +242,7 @@ int trmc_plan_create_opt(int64_t nseg, const int64_t *up_ptr, const int64_t *up_
         po.cluster_late_lag = std::max(0, o.cluster_late_lag);
         po.stream_split = std::max(0, o.stream_split);
         po.hot_wave_rows = std::max(0, std::min(64, o.hot_wave_rows));
-        po.velocity_on_demand = o.velocity_on_demand != 0;
+        po.velocity_on_demand = o.velocity_on_demand;
         po.sequence = o.sequence_mode != 0;
         po.flow_overlap = o.flow_overlap != 0;
         po.flow_lean = o.flow_lean;

@@ -159,9 +159,10 @@ inline void launch_tile(hipStream_t st, const StepArgs<T> &a, int32_t p0, int32_
     const unsigned home = (unsigned)((p1 - p0 + kTileBlock - 1) / kTileBlock);
     const dim3 grid(home + (a.hot_list ? (unsigned)a.hot_home : 0u)), block(kTileBlock);
     const bool dec = a.dec != nullptr;
+    const bool lazy = a.v_every != 0 && !a.out; // (velocity where it is handed on only: the LAZYV instances assemble no full result)
     if constexpr (sizeof(T) == 4) {
         if (tol) {
-            if (a.v_every != 0) {
+            if (lazy) {
                 if (dec) hipLaunchKernelGGL((k_mc_tile<T, true, true, true>), grid, block, 0, st, a, p0, p1, tile, K);
                 else hipLaunchKernelGGL((k_mc_tile<T, true, false, true>), grid, block, 0, st, a, p0, p1, tile, K);
             } else if (dec) hipLaunchKernelGGL((k_mc_tile<T, true, true>), grid, block, 0, st, a, p0, p1, tile, K);
@@ -169,7 +170,7 @@ inline void launch_tile(hipStream_t st, const StepArgs<T> &a, int32_t p0, int32_
             return;
         }
     }
-    if (a.v_every != 0) { // (velocity where it is handed on only)
+    if (lazy) {
         if (dec) hipLaunchKernelGGL((k_mc_tile<T, false, true, true>), grid, block, 0, st, a, p0, p1, tile, K);
         else hipLaunchKernelGGL((k_mc_tile<T, false, false, true>), grid, block, 0, st, a, p0, p1, tile, K);
         return;
@@ -185,9 +186,10 @@ inline void launch_ctile(hipStream_t st, const StepArgs<T> &a, const int32_t *cb
 {
     const dim3 grid((unsigned)(b1 - b0)), block(kTileBlock);
     const bool dec = a.dec != nullptr;
+    const bool lazy = a.v_every != 0 && !a.out;
     if constexpr (sizeof(T) == 4) {
         if (tol) {
-            if (a.v_every != 0) {
+            if (lazy) {
                 if (dec) hipLaunchKernelGGL((k_mc_ctile<T, true, true, true>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);
                 else hipLaunchKernelGGL((k_mc_ctile<T, true, false, true>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);
             } else if (dec) hipLaunchKernelGGL((k_mc_ctile<T, true, true>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);
@@ -195,7 +197,7 @@ inline void launch_ctile(hipStream_t st, const StepArgs<T> &a, const int32_t *cb
             return;
         }
     }
-    if (a.v_every != 0) {
+    if (lazy) {
         if (dec) hipLaunchKernelGGL((k_mc_ctile<T, false, true, true>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);
         else hipLaunchKernelGGL((k_mc_ctile<T, false, false, true>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);
         return;

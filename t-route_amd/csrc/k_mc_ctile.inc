@@ -20,7 +20,7 @@
 // are no hot rows here -- a row routed by another block could not hand its flow over.
 // Same bits as every other path: the same segment steps on the same inputs (tests run all of them against the oracle).
 template <class T, bool TOL = false, bool DEC = false, bool LAZYV = false>
-__global__ void __launch_bounds__(kTileBlock, sizeof(T) == 4 ? TRMC_TILE_WAVES : 1)
+__global__ void __launch_bounds__(kTileBlock, sizeof(T) == 4 ? (LAZYV ? TRMC_TILE_WAVES_LAZY : TRMC_TILE_WAVES) : 1)
 k_mc_ctile(const StepArgs<T> a, const int32_t *__restrict__ cblk_ptr, const int32_t cb0, const int32_t tile, const int32_t K)
 {
     using M = typename DevMath<T, TOL>::type;
@@ -102,11 +102,11 @@ k_mc_ctile(const StepArgs<T> a, const int32_t *__restrict__ cblk_ptr, const int3
     if (active) s_x[(size_t)((t_lo - 1) & 1) * kTileBlock + sl] = q_prev;
     __syncthreads();
     T *q_up = q_tm + (size_t)(t_lo - 1) * np;
-    const int32_t v_every = LAZYV ? cold->v_every : 0; // (see StepArgs)
-    int32_t v_left = (LAZYV && v_every > 0) ? (v_every - 1) - ((t_lo - 1) % v_every) : 0;
+    const int32_t v_every = (LAZYV && DEC) ? cold->v_every : 0; // (see StepArgs and k_mc_tile)
+    int32_t v_left = v_every > 0 ? (v_every - 1) - ((t_lo - 1) % v_every) : 0;
     for (int32_t t = t_lo; t <= t_hi; ++t, q_up += np) {
-        bool want_v = true;
-        if constexpr (LAZYV) {
+        bool want_v = false;
+        if constexpr (LAZYV && DEC) {
             want_v = v_every > 0 && v_left == 0;
             if (v_every > 0) v_left = v_left == 0 ? v_every - 1 : v_left - 1;
         }
@@ -149,7 +149,7 @@ k_mc_ctile(const StepArgs<T> a, const int32_t *__restrict__ cblk_ptr, const int3
                 f.quc = qup;
                 f.qdp = q_prev;
                 f.ql = ql;
-                const trmc::StepResult<T> r = trmc::mc_segment_step<T, M>(p, c, f, d_prev, m, want_v);
+                const trmc::StepResult<T> r = trmc::mc_segment_step<T, M>(p, c, f, d_prev, m, !LAZYV);
                 q_new = r.qdc;
                 v_new = r.velc;
                 d_new = r.depthc;
@@ -183,7 +183,8 @@ k_mc_ctile(const StepArgs<T> a, const int32_t *__restrict__ cblk_ptr, const int3
             }
             q_prev = q_new;
             d_prev = d_new;
-            if (DEC || a.out) { // stage (q, v, d) of step t; a run ends when kTileStage steps are staged and at the tile's last step
+            if (LAZYV && want_v && it_last > 0) v_new = trmc::step_velocity<T, M>(p, c, d_new, m); // (as k_mc_tile)
+            if (DEC || (!LAZYV && a.out)) { // stage (q, v, d) of step t; a run ends when kTileStage steps are staged and at the tile's last step
                 // (a.out == nullptr: a stream of windows whose callers take products only -- nothing of the full result is assembled)
                 T *so = s_out + (size_t)(staged * 3) * kTileBlock + threadIdx.x;
                 so[0] = q_new;
@@ -193,7 +194,7 @@ k_mc_ctile(const StepArgs<T> a, const int32_t *__restrict__ cblk_ptr, const int3
                 if (staged == kTileStage || t == t_hi) {
                     T *dst = out_row + (size_t)(t - staged) * 3;
                     const T *si = s_out + threadIdx.x;
-                    if (!a.out) {
+                    if (LAZYV || !a.out) {
                     } else if (a.out_vec && (staged & 3) == 0) {
                         for (int j = 0; j < 3 * staged / 4; ++j) {
                             float4 v;

@@ -59,7 +59,9 @@ template <class T> struct StepArgs {
     // tile kernels: which steps' VELOCITY anybody is handed -- 0: every step (the full result is assembled, or nobody said otherwise);
     // n > 0: the multiples of n (a stream that keeps every n-th step of (q, v, d) and nothing else of it); < 0: none (a stream
     // whose products are hydrographs and final states).  The velocity feeds nothing: a step that is not handed on need not
-    // form it (step_velocity: a division, a root, a logarithm and a power -- a tenth of a step's instructions).
+    // form it (step_velocity: a division, a root, a logarithm and a power -- a tenth of a step's instructions).  Set by
+    // stream_args for every stream begun without full_output (trmc_plan_options.velocity_on_demand < 0: left 0); != 0 only
+    // where out == nullptr -- the LAZYV instances of the tile kernels assemble no full result.
     int32_t v_every;
     // k_mc_tile, hot rows: rows of class >= 3 at the end of a tile are routed by blocks of their own in the next one.  Three
     // lists of positions [3][hot_cap] and their lengths [3], used in turn: a launch reads `hot_cur`, appends to the next and
@@ -302,12 +304,17 @@ constexpr int64_t kMidDefaultRowsPerCu = 0; // default threshold of the second t
 // latencies with other wavefronts and is close to its issue limit at four
 #define TRMC_TILE_WAVES 5
 #endif
+#ifndef TRMC_TILE_WAVES_LAZY // ... of the LAZYV instances (a stream without full_output: no velocity in the step loop, nothing
+// staged unless DEC).  Registers per lane at 5 / 6 wavefronts (spilled): k_mc_tile 95 (2) / 80 (24), k_mc_ctile 89 (0) / 80 (9);
+// the CONUS stream, median of five interleaved runs: 13.43 / 13.49 ms per day
+#define TRMC_TILE_WAVES_LAZY TRMC_TILE_WAVES
+#endif
 #ifndef TRMC_HOT_WAVE_MAX // a wavefront with at least so many hot rows keeps them (k_mc_tile's epilogue); measured on the CONUS
 // sequence, ms per day on the cost-ordered / the unordered plan: 6: 16.06 / 17.55, 16: 16.07 / 17.33, 40: 16.06 / 17.36
 #define TRMC_HOT_WAVE_MAX 16
 #endif
 template <class T, bool TOL = false, bool DEC = false, bool LAZYV = false> // (LAZYV: StepArgs::v_every != 0)
-__global__ void __launch_bounds__(kTileBlock, sizeof(T) == 4 ? TRMC_TILE_WAVES : 1)
+__global__ void __launch_bounds__(kTileBlock, sizeof(T) == 4 ? (LAZYV ? TRMC_TILE_WAVES_LAZY : TRMC_TILE_WAVES) : 1)
 k_mc_tile(const StepArgs<T> a, const int32_t s_begin, const int32_t s_end, const int32_t tile, const int32_t K)
 {
     using M = typename DevMath<T, TOL>::type;
@@ -428,11 +435,13 @@ k_mc_tile(const StepArgs<T> a, const int32_t s_begin, const int32_t s_end, const
     // (asking for the upstream flows of step t + 1 while step t is computed -- they were all written by earlier launches -- was built
     // and measured in round 6: the CONUS stream 14.3 ms per day against 13.9, the ranks of an 8-way partition 2.76 against 2.70: two
     // more live registers in a kernel that already spills four cost more than the L2 trip they take off the chain)
-    const int32_t v_every = LAZYV ? cold->v_every : 0;
-    int32_t v_left = (LAZYV && v_every > 0) ? (v_every - 1) - ((t_lo - 1) % v_every) : 0; // steps before the next one whose velocity is wanted
+    // LAZYV: a stream that assembles no full result (a.out == nullptr).  The step's velocity is formed out of line, behind the
+    // step's stores, and only at the steps whose velocity is kept (DEC); without DEC nothing is staged and none of it is compiled.
+    const int32_t v_every = (LAZYV && DEC) ? cold->v_every : 0;
+    int32_t v_left = v_every > 0 ? (v_every - 1) - ((t_lo - 1) % v_every) : 0; // steps before the next one whose velocity is wanted
     for (int32_t t = t_lo; t <= t_hi; ++t, q_up += np) {
-        bool want_v = true;
-        if constexpr (LAZYV) {
+        bool want_v = false;
+        if constexpr (LAZYV && DEC) {
             want_v = v_every > 0 && v_left == 0;
             if (v_every > 0) v_left = v_left == 0 ? v_every - 1 : v_left - 1;
         }
@@ -470,7 +479,7 @@ k_mc_tile(const StepArgs<T> a, const int32_t s_begin, const int32_t s_end, const
             f.quc = qup;
             f.qdp = q_prev;
             f.ql = ql;
-            const trmc::StepResult<T> r = trmc::mc_segment_step<T, M>(p, c, f, d_prev, m, want_v);
+            const trmc::StepResult<T> r = trmc::mc_segment_step<T, M>(p, c, f, d_prev, m, !LAZYV);
             q_new = r.qdc;
             v_new = r.velc;
             d_new = r.depthc;
@@ -503,7 +512,10 @@ k_mc_tile(const StepArgs<T> a, const int32_t s_begin, const int32_t s_end, const
         }
         q_prev = q_new;
         d_prev = d_new;
-        if (DEC || a.out) { // stage (q, v, d) of step t; a run ends when kTileStage steps are staged and at the tile's last step
+        // (LAZYV: the velocity of a kept step, from the depth the step ended on -- what mc_segment_step forms; 0 where the step
+        // had no flow, iters == 0, as there.  Nudging changes the flow only.)
+        if (LAZYV && want_v && it_last > 0) v_new = trmc::step_velocity<T, M>(p, c, d_new, m);
+        if (DEC || (!LAZYV && a.out)) { // stage (q, v, d) of step t; a run ends when kTileStage steps are staged and at the tile's last step
             // (a.out == nullptr: a stream of windows whose callers take products only -- nothing of the full result is assembled)
             T *so = s_out + (size_t)(staged * 3) * kTileBlock + threadIdx.x;
             so[0] = q_new;
@@ -513,7 +525,7 @@ k_mc_tile(const StepArgs<T> a, const int32_t s_begin, const int32_t s_end, const
             if (staged == kTileStage || t == t_hi) {
                 T *dst = out_row + (size_t)(t - staged) * 3;
                 const T *si = s_out + threadIdx.x;
-                if (!a.out) {
+                if (LAZYV || !a.out) {
                 } else if (a.out_vec && (staged & 3) == 0) { // (float: 3 * staged values = 3 * staged / 4 pieces of 16 bytes)
                     for (int j = 0; j < 3 * staged / 4; ++j) {
                         float4 v;

@@ -127,8 +127,10 @@ template <class T> StepArgs<T> stream_args(trmc_plan *pl, const StreamRun &S, in
         a.dec_stride = S.dec_stride;
         a.dec_keep = S.dec_keep;
     }
-    // (trmc_plan_options.velocity_on_demand: nobody is handed a velocity but the kept steps' -- or nobody at all)
-    if (pl->opt.velocity_on_demand && !S.want_out) a.v_every = S.dec_stride > 0 ? S.dec_stride : -1;
+    // A stream that assembles no full result hands nobody a velocity but the kept steps' of output_stride -- or nobody at all
+    // (hydrographs and final states are flows and depths): only those steps form it.  trmc_plan_options.velocity_on_demand < 0
+    // has every step form it anyway (A/B).
+    if (!S.want_out && pl->opt.velocity_on_demand >= 0) a.v_every = S.dec_stride > 0 ? S.dec_stride : -1;
     // the in-block partition and the hot rows: as in a window (route_advance_t); the buffers were made by trmc_stream_begin
     if (pl->cls_last.p) a.cls_last = (uint8_t *)pl->cls_last.p;
     return a;
