@@ -528,10 +528,12 @@ int trmc_stream_gather(trmc_plan *pl, int64_t day, int32_t rowset, void *dst_dev
     if (st != pst) {
         HIP_TRY(hipEventRecord(S.ev_gat, pst));
         HIP_TRY(hipStreamWaitEvent(st, S.ev_gat, 0));
-        if (S.W > 0 && S.C > 0) { // (rows of the slices are on the tile stream)
-            HIP_TRY(hipEventRecord(S.ev_gat, pl->wstream));
-            HIP_TRY(hipStreamWaitEvent(st, S.ev_gat, 0));
-        }
+    }
+    // rows of the slices are on the tile stream, and the last launch queued there may still run while the clusters' stream is
+    // done with the day (cluster launch g waits for slab launch g - 1 only): the gather waits for it -- on pst as well
+    if (S.W > 0 && st != pl->wstream) {
+        HIP_TRY(hipEventRecord(S.ev_gat, pl->wstream));
+        HIP_TRY(hipStreamWaitEvent(st, S.ev_gat, 0));
     }
     const int32_t slot = (int32_t)(day % S.slots);
     if (pl->precision == 32)

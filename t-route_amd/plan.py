@@ -350,9 +350,10 @@ class RoutingPlan:
         (page-locked arrays or None), the device pointer of its boundary rows' flows.  Returns the day's number in the stream."""
         if qlat.dtype != self.dtype or not qlat.flags.c_contiguous or qlat.ndim != 2 or qlat.shape[0] != self.nseg:
             raise ValueError(f"qlat must be a C-contiguous {np.dtype(self.dtype).name} array of shape ({self.nseg}, nq)")
-        day = self.stream_info()["days_pushed"]
-        self._stream_keep[day] = (qlat, hyd, q0, fvd)          # (alive while the copies may be in flight)
-        for old in [k for k in self._stream_keep if isinstance(k, int) and k < day - 8]:
+        info = self.stream_info()
+        day = info["days_pushed"]
+        self._stream_keep[day] = (qlat, hyd, q0, fvd)          # (alive while the copies may be in flight: a day's products are
+        for old in [k for k in self._stream_keep if isinstance(k, int) and k < day - max(8, info["slots"])]:   # queued up to `slots` days on)
             del self._stream_keep[old]
         _lib.check(_lib.lib().trmc_stream_push(self._h, _lib.ptr(qlat), qlat.shape[1], C.c_void_p(boundary_q_ptr or 0),
                                                -1 if rowset is None else int(rowset), _lib.ptr(hyd), _lib.ptr(q0), _lib.ptr(fvd)))
@@ -375,8 +376,11 @@ class RoutingPlan:
             return np.zeros((0, self._nsteps), dtype=self.dtype)
         dev = self.info()["device"]
         buf = X.DeviceBuffer(dev, n * self._nsteps * np.dtype(self.dtype).itemsize)
-        self.stream_gather(day, rowset, buf.ptr)
-        return buf.download((n, self._nsteps), self.dtype, stream=self.stream())
+        st = self.stream()
+        # (the gather on the stream the download is queued on: behind the launches of both compute streams, whichever of them
+        # the stream's last launch is on)
+        self.stream_gather(day, rowset, buf.ptr, stream=st)
+        return buf.download((n, self._nsteps), self.dtype, stream=st)
 
     def stream_boundary_host(self, day, flows):
         """The boundary rows' flows of `day` [nboundary, nsteps] from a host array."""

@@ -118,3 +118,43 @@ def flow_engine(precision=32):
     """True when plans of this precision run on the dataflow engine (k_mc_flow), False on the level engine."""
     import os
     return precision == 32 and os.environ.get("TRMC_ENGINE", "flow") != "levels"
+
+
+def reference_day_by_day(to, params, days, q0, nsteps, qts, checksums=False):
+    """The reference's run-set loop on the CPU, one window per day (oracle.reference_windows, its decomposition into ordered
+    sub-networks formed once): yields per day (q [nseg, nsteps + 1], the next day's q0 [nseg, 3], (chk_v, chk_d) or None) --
+    q column 0 is the day's initial flow, the state is new_q0 (q_T, q_T, depth_T)."""
+    from oracle import oracle as O
+    from troute_amd.synthetic import upstream_csr
+    ref_name = "libmc_ref_qj0_f32.so" if O.have_ref("libmc_ref_qj0_f32.so") else None
+    order_ptr, job_ptr, rows = O.ordered_subnetworks(to, 10000)
+    up_ptr, up_idx = upstream_csr(to)
+    state = np.ascontiguousarray(q0, dtype=np.float32)
+    for ql in days:
+        q, d, _, _ = O.cpu_baseline_route(nsteps, qts, True, order_ptr, job_ptr, rows, up_ptr, up_idx, params, ql, state,
+                                          ref_name=ref_name, checksums=checksums)
+        state = np.ascontiguousarray(np.stack([q[:, -1], q[:, -1], d], axis=1))
+        chk = (O.cpu_baseline_route.chk_v.copy(), O.cpu_baseline_route.chk_d.copy()) if checksums else None
+        yield q, state, chk
+
+
+def stream_days(r, make_day, nsteps, qts, q0, extra=2, pinned=True, ndays=None, min_days=0, **kw):
+    """Route days make_day(0), make_day(1), ... through one RouteStream until the ring of day slots has wrapped (slots + extra
+    days; or `ndays` days).  Returns (outlet rows, {day: (hyd, final[, fvd]) copies}, the days routed, stream_info at the start)."""
+    from troute_amd.sequence import RouteStream, pinned_like
+    got, days, start = {}, [], {}
+    with RouteStream(r, nsteps, qts, **kw) as rs:
+        def feed():
+            k = 0
+            while k == 0 or k < (ndays or max(min_days, rs.info["slots"] + extra)):
+                if k == 1:
+                    start.update(rs.info)
+                d = make_day(k)
+                days.append(d)
+                yield pinned_like(d) if pinned else d
+                k += 1
+        for item in rs.route(feed(), q0):
+            got[item[0]] = tuple(None if x is None else np.array(x, copy=True) for x in item[1:])
+        rows = np.array(rs.outlet_rows, copy=True)
+    assert sorted(got) == list(range(len(days))) and (ndays or len(days) >= start["slots"] + extra)
+    return rows, got, days, start

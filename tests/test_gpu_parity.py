@@ -523,8 +523,9 @@ def test_conus_full_size_samples_bit_identical_to_oracle(conus, short, plan_mode
 
 
 def test_conus_bench_sequence_day_n_plus_1_bit_identical_to_oracle(conus):
-    """The configuration bench.py TIMES, replayed step for step at full size and checked against the oracle where the
-    bench is timed: day N-1 from a cold start on the plan built from the topology alone -> day N warm, with cost
+    """bench.py's tuning sequence, replayed step for step at full size on PLAIN WINDOWS (route_resident: k_mc_step, not the
+    stream of days the headline times -- that one is test_conus_stream_every_segment_bit_identical_to_reference) and checked
+    against the oracle on the window that follows it: day N-1 from a cold start on the plan built from the topology alone -> day N warm, with cost
     collection -> the plan rebuilt with that hint (assume_short_ts plan at 2.7 M rows: the level engine, k_mc_step, rows
     of a level grouped by cost) -> spun up again through days N-1 and N -> day N+1, warm.  A sub-collection of whole
     networks routed alone by the oracle through the same three days must equal what the GPU holds for them on day N+1:
@@ -666,6 +667,90 @@ def test_conus_every_segment_bit_identical_to_reference(conus):
         assert_bit_identical(hyd, ref["q"][rows, 1:], "outlet hydrographs gathered by the two-rank job")
 
 
+def test_conus_stream_every_segment_bit_identical_to_reference(conus):
+    """The configuration bench.py TIMES (bench.py, sections 1-3): a router built from the topology alone routes day N-1 cold and
+    day N with cost collection; the stream router is built with that hint and NO options (ShardedRouter(stream=True): cluster
+    rows 128, slices from 1024 rows, at most 32 of them, 16 steps per tile) and streams the days after day N from the state the
+    tuned plan's spin-up leaves, their forcing derived day by day as the bench's ring is (synthetic.forcing(previous=)).
+    Products only -- the LAZYV instances of k_mc_tile / k_mc_ctile, the kernels of the headline -- for more days than the ring
+    has slots: every outlet hydrograph and the final state of every row, every day, against the reference Fortran routed on
+    the CPU one day at a time from the state it handed itself (oracle.reference_windows' loop).  The same days with the hourly
+    block (output_stride=12): its flows against the reference's every 12th step; two of them as full results: every flow, the
+    velocity and depth series (exact checksums), the final state -- and the hourly velocity and depth against them."""
+    from troute_amd import synthetic
+    from troute_amd.distributed import ShardedRouter
+    from troute_amd.sequence import pinned_like
+    net, up_ptr, up_idx = conus
+    to, params = net["to"], net["params"]
+    nseg = to.shape[0]
+    nsteps, qts = 288, 12
+    qlat_s = net["qlat"]
+    nq = qlat_s.shape[1]
+    qlat_a = synthetic.forcing(nseg, nq, synthetic.DEFAULT_SEED + 1, previous=qlat_s)
+    q0 = np.zeros((nseg, 3), np.float32)
+    r = ShardedRouter(to, params, assume_short_ts=True)
+    r.upload(nsteps, qlat_s, q0)
+    r.route_resident(qts, True)                      # day N-1, cold
+    r.upload(nsteps, qlat_a, None)                   # day N, warm, cost collection on
+    r.collect_cost(True)
+    r.route_resident(qts, True)
+    hint = r.iteration_hint()
+    r.close()
+    r = ShardedRouter(to, params, cost_hint=hint, assume_short_ts=True)
+    r.upload(nsteps, qlat_s, q0)                     # the tuned plan's spin-up: the stream starts from the state after day N
+    r.route_resident(qts, True)
+    r.upload(nsteps, qlat_a, None)
+    r.route_resident(qts, True)
+    state_n = r.plan0.download_final_state()
+    r.close()
+    days = []
+
+    def make_day(k):
+        if k >= len(days):
+            days.append(synthetic.forcing(nseg, nq, synthetic.DEFAULT_SEED + 2 + k, previous=days[-1] if days else qlat_a))
+        return days[k]
+    s = ShardedRouter(to, params, cost_hint=hint, stream=True)
+    P = s.stream_plan(0)
+    lag, W, C = P.lags()
+    hot0 = P.hot_rows()
+    rows, prod, _, info = H.stream_days(s, make_day, nsteps, qts, state_n)
+    hot1 = P.hot_rows()
+    assert W > 0 and C > 0 and info["wide_levels"] == W and info["cluster_levels"] == C and info["tiles_per_day"] == 18, info
+    assert hot1 > hot0, "the stream never routed a row from the hot list"
+    ndays = len(days)
+    assert ndays >= info["slots"] + 2
+    _, hourly, _, _ = H.stream_days(s, make_day, nsteps, qts, state_n, ndays=ndays, output_stride=12)
+    # two days as full results (on the same plan; a full CONUS day is 9.4 GB: two host arrays, not a ring of them)
+    P.upload_forcing(nsteps, days[0], state_n)
+    P.stream_begin(nsteps, qts, full_output=True)
+    full = [_lib.result_empty((nseg, nsteps, 3), np.float32, always_pinned=True) for _ in range(2)]
+    fins = [_lib.result_empty((nseg, 3), np.float32, always_pinned=True) for _ in range(2)]
+    for d in range(2):
+        P.stream_push(pinned_like(days[d]), q0=fins[d], fvd=full[d])
+    P.stream_flush()
+    P.stream_wait(0)
+    P.stream_wait(1)
+    P.stream_end()
+    s.close()
+    for w, (q, state, chk) in enumerate(H.reference_day_by_day(to, params, days, state_n, nsteps, qts, checksums=True)):
+        assert_bit_identical(prod[w][0], q[rows, 1:], f"stream day {w}: outlet hydrographs (products only)")
+        assert_bit_identical(prod[w][1], state, f"stream day {w}: final state of every row (products only)")
+        assert_bit_identical(hourly[w][0], prod[w][0], f"stream day {w}: outlet hydrographs (hourly)")
+        assert_bit_identical(hourly[w][1], state, f"stream day {w}: final state (hourly)")
+        assert_bit_identical(hourly[w][2][:, :, 0], q[:, 12::12], f"stream day {w}: hourly flows of every row")
+        if w < 2:
+            for lo in range(0, nseg, 200000):
+                assert_bit_identical(np.ascontiguousarray(full[w][lo:lo + 200000, :, 0]), q[lo:lo + 200000, 1:],
+                                     f"stream day {w}: every flow, rows {lo}..")
+            assert np.array_equal(O.series_checksum(full[w][:, :, 1]), chk[0]), f"stream day {w}: velocity series of some row"
+            assert np.array_equal(O.series_checksum(full[w][:, :, 2]), chk[1]), f"stream day {w}: depth series of some row"
+            assert_bit_identical(fins[w], state, f"stream day {w}: final state (full result)")
+            assert_bit_identical(hourly[w][2][:, :, 1:], full[w][:, 11::12, 1:], f"stream day {w}: hourly velocity and depth")
+        del q
+    print(f"\nCONUS stream: W={W} C={C} tiles_per_day={info['tiles_per_day']} slots={info['slots']} lag_max={info['lag_max']} "
+          f"days={ndays} hot_rows {hot0}->{hot1}")
+
+
 def test_conus_general_mode_every_segment_bit_identical_to_reference(conus):
     """The GENERAL mode (assume_short_ts=False, the reference's configuration default, compute_parameters.py:47) at full
     size: every one of the 2 729 077 segments through a 288-step day from the cold start on the dataflow engine -- on the
@@ -765,21 +850,10 @@ def test_cost_hinted_plan_order_changes_nothing(short, engine, monkeypatch):
     assert (cost >= np.minimum(last, 3)).all() and (cost[last >= 2] >= 2).all() and (cost == 0).any()
 
 
-@pytest.mark.parametrize("engine", ENGINES)
-@pytest.mark.parametrize("short", [True, False])
-def test_extreme_parameters_and_depths_around_the_fast_division_guard(short, engine, monkeypatch):
-    """The hydraulic point drops the scaling / fix-up steps of its divisions when a plan-wide parameter check and a
-    per-call depth test hold (DevMathF::fast_ok, trmc.hip); the oracle always divides plainly.  Forests with parameters
-    log-uniform over the whole admitted range [2**-14, 2**17] (twcc / ncc sometimes 0) and initial depths from 1e-12 to
-    1e4 -- on both sides of the depth test -- must agree bit for bit; one parameter outside the range switches the
-    plan to plain divisions, same results.  Both engines."""
-    set_engine(monkeypatch, engine)
-    rng = np.random.default_rng(77)
-    nseg = 70000
+def extreme_inputs(rng, nseg):
+    """a random forest (to), parameters log-uniform over the whole admitted range [2**-14, 2**17] (twcc / ncc sometimes 0),
+    forcing [nseg, 3] and initial depths from 1e-12 to 1e4 -- on both sides of the fast-division depth test"""
     to = H.random_network(rng, nseg)
-    _, _, ups = H.reaches_from_to(to)
-    up_ptr, up_idx = csr_from_lists(ups)
-    lvl, _, _ = topology_levels(up_ptr, up_idx)
 
     def logu(lo, hi, n):
         return np.exp(rng.uniform(np.log(lo), np.log(hi), n))
@@ -794,6 +868,22 @@ def test_extreme_parameters_and_depths_around_the_fast_division_guard(short, eng
     params = params.astype(np.float32)
     qlat = logu(1e-9, 5.0, (nseg, 3)).astype(np.float32) * (rng.random((nseg, 3)) > 0.2)
     q0 = np.stack([logu(1e-9, 50.0, nseg), logu(1e-9, 50.0, nseg), logu(1e-12, 1e4, nseg)], 1).astype(np.float32)
+    return to, params, qlat, q0
+
+
+@pytest.mark.parametrize("engine", ENGINES)
+@pytest.mark.parametrize("short", [True, False])
+def test_extreme_parameters_and_depths_around_the_fast_division_guard(short, engine, monkeypatch):
+    """The hydraulic point drops the scaling / fix-up steps of its divisions when a plan-wide parameter check and a
+    per-call depth test hold (DevMathF::fast_ok, trmc.hip); the oracle always divides plainly.  Forests with parameters
+    log-uniform over the whole admitted range [2**-14, 2**17] (twcc / ncc sometimes 0) and initial depths from 1e-12 to
+    1e4 -- on both sides of the depth test -- must agree bit for bit; one parameter outside the range switches the
+    plan to plain divisions, same results.  Both engines."""
+    set_engine(monkeypatch, engine)
+    to, params, qlat, q0 = extreme_inputs(np.random.default_rng(77), 70000)
+    _, _, ups = H.reaches_from_to(to)
+    up_ptr, up_idx = csr_from_lists(ups)
+    lvl, _, _ = topology_levels(up_ptr, up_idx)
     nsteps, qts = 12, 4
     want = O.network_by_segment(nsteps, qts, up_ptr, up_idx, lvl, params, q0, qlat, short, det=True)[:, 1:, :]
     fin = np.isfinite(want).all(axis=(1, 2))

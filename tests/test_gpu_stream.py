@@ -245,12 +245,14 @@ def test_stream_lowercolorado_bit_identical_to_reference_golden():
     assert np.array_equal(bits(out[g["probes"]]), bits(g["shortts_f32_probes"][:, 1:, :]))
 
 
-@pytest.mark.parametrize("stride", [None, 8])
-def test_a_stream_on_two_ranks_equals_the_days_routed_one_by_one(stride):
+@pytest.mark.parametrize("stride,exchange", [pytest.param(None, None, id="None"), pytest.param(8, None, id="8"),
+                                             pytest.param(None, "host", id="None-host"), pytest.param(8, "host", id="8-host")])
+def test_a_stream_on_two_ranks_equals_the_days_routed_one_by_one(stride, exchange):
     """Two ranks (threads) on one device over the shared-memory transport: every rank streams its sub-basins, the trunk rides in
     its owner's stream behind them, the cut-edge hydrographs are all-gathered once a day; rank 0 gets every day's outlet
     hydrographs of the WHOLE network, every rank the final state of its rows -- and, with an output stride, every n-th step of its
-    rows' (q, v, d) a day later (the ring then holds a slot more on every rank)."""
+    rows' (q, v, d) a day later (the ring then holds a slot more on every rank).  exchange="host": the cut-edge hydrographs go
+    through the host (stream_gather_host, comm.all_gather_rows_host) instead of the device collective."""
     net = synthetic.generate(nseg=20000, nnet=60, seed=11, nq=3)
     nseg = net["to"].shape[0]
     nsteps, qts, ndays = 32, 16, 7
@@ -269,7 +271,8 @@ def test_a_stream_on_two_ranks_equals_the_days_routed_one_by_one(stride):
             r = ShardedRouter(net["to"], net["params"], rank=rank, world=world, device=0, stream=True, options={"wide_min_rows": 64, "wide_k": 8})
             r.enable_device_exchange(comm)
             got = {}
-            with RouteStream(r, nsteps, qts, output_stride=stride) as rs:
+            with RouteStream(r, nsteps, qts, output_stride=stride, exchange=exchange) as rs:
+                assert rs.exchange == (exchange or "device")
                 for item in rs.route(seq_days, q0):
                     day, hyd, fin = item[:3]
                     got[day] = (None if hyd is None else np.array(hyd, copy=True), np.array(fin[0], copy=True),

@@ -192,3 +192,65 @@ def test_conus_every_segment_within_the_stated_tolerance_of_the_reference():
     record("conus_day_n_plus_1", rep)
     assert np.isfinite(q).all()
     assert rep["inside_rtol1e-4"] >= FRAC_DAY and rep["inside_rtol3e-2"] >= FRAC_ANY and rep["inside_rtol1e-1"] == 1.0, rep
+
+
+def test_conus_stream_within_the_stated_tolerance_of_the_reference():
+    """The stream of days in tolerance arithmetic at full size (ShardedRouter(stream=True, options={"arithmetic": "tolerance"}),
+    products only: the TOL + LAZYV instances of k_mc_tile / k_mc_ctile): the three bench days from the cold start, every day's
+    outlet hydrographs and the last day's final state, against the reference Fortran routed on the CPU day by day; then the
+    same days with the last one as a full result -- the flow of every row at every step within the stated tolerance."""
+    from troute_amd import _lib, synthetic
+    from troute_amd.distributed import ShardedRouter
+    from troute_amd.sequence import pinned_like
+    net = synthetic.generate(cache_dir=os.environ.get("TRMC_CACHE", "/tmp/trmc_cache"))
+    to, params = net["to"], net["params"]
+    nseg = to.shape[0]
+    nsteps, qts = 288, 12
+    qlat_s = net["qlat"]
+    qlat_a = synthetic.forcing(nseg, qlat_s.shape[1], synthetic.DEFAULT_SEED + 1, previous=qlat_s)
+    qlat_b = synthetic.forcing(nseg, qlat_s.shape[1], synthetic.DEFAULT_SEED + 2, previous=qlat_a)
+    days = [qlat_s, qlat_a, qlat_b]
+    q0 = np.zeros((nseg, 3), np.float32)
+    s = ShardedRouter(to, params, stream=True, options={"arithmetic": "tolerance"})
+    P = s.stream_plan(0)
+    assert P.arithmetic == "tolerance"
+    lag, W, C = P.lags()
+    assert W > 0 and C > 0
+    rows, prod, _, info = H.stream_days(s, lambda k: days[k], nsteps, qts, q0, ndays=len(days))
+    P.upload_forcing(nsteps, days[0], q0)
+    P.stream_begin(nsteps, qts, full_output=True)
+    full = _lib.result_empty((nseg, nsteps, 3), np.float32, always_pinned=True)
+    for d in range(len(days)):
+        P.stream_push(pinned_like(days[d]), fvd=full if d == len(days) - 1 else None)
+    P.stream_flush()
+    P.stream_wait(len(days) - 1)
+    P.stream_end()
+    s.close()
+    rep = {"segments": int(nseg), "steps": nsteps, "days": len(days), "wide_levels": W, "cluster_levels": C,
+           "tiles_per_day": info["tiles_per_day"]}
+    for w, (q, state, _) in enumerate(H.reference_day_by_day(to, params, days, q0, nsteps, qts)):
+        want = q[rows, 1:]
+        d_day = distribution(prod[w][0], want, RTOL_DAY, ATOL_DAY)
+        d_any = distribution(prod[w][0], want, RTOL_ANY, ATOL_ANY)
+        d_max = distribution(prod[w][0], want, RTOL_MAX, ATOL_MAX)
+        rep[f"day{w}_outlets"] = {"within_rtol1e-4": d_day, "inside_rtol3e-2": d_any["inside"], "inside_rtol1e-1": d_max["inside"]}
+        assert np.isfinite(prod[w][0]).all() and np.isfinite(prod[w][1]).all(), w
+        assert d_day["inside"] >= FRAC_DAY and d_any["inside"] >= FRAC_ANY and d_max["inside"] == 1.0, (w, d_day, d_any, d_max)
+        if w == len(days) - 1:
+            inside = [0, 0, 0]
+            for lo in range(0, nseg, 200000):
+                g, t = full[lo:lo + 200000, :, 0].astype(np.float64), q[lo:lo + 200000, 1:].astype(np.float64)
+                err = np.abs(g - t)
+                for i, (rt, at) in enumerate(((RTOL_DAY, ATOL_DAY), (RTOL_ANY, ATOL_ANY), (RTOL_MAX, ATOL_MAX))):
+                    inside[i] += int((err <= at + rt * np.abs(t)).sum())
+            total = nseg * nsteps
+            rep.update({"flows": total, "inside_rtol1e-4": inside[0] / total, "inside_rtol3e-2": inside[1] / total,
+                        "inside_rtol1e-1": inside[2] / total,
+                        "final_state": distribution(prod[w][1][:, [0, 2]], state[:, [0, 2]], RTOL_DAY, ATOL_DAY),
+                        "final_flow": distribution(prod[w][1][:, 0], state[:, 0], RTOL_DAY, ATOL_DAY)})
+            assert np.isfinite(full[:, :, 0]).all()
+            assert_full = rep["inside_rtol1e-4"] >= FRAC_DAY and rep["inside_rtol3e-2"] >= FRAC_ANY and rep["inside_rtol1e-1"] == 1.0
+            record("conus_stream_products_only", rep)
+            assert assert_full, rep
+            assert rep["final_flow"]["inside"] >= FRAC_DAY, rep["final_flow"]
+        del q
