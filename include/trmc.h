@@ -407,6 +407,53 @@ int trmc_set_reservoirs(trmc_plan *plan, int64_t nres, const int64_t *res_rows, 
 int trmc_download_reservoir_inflow(trmc_plan *plan, void *inflow_out);
 
 /*
+ * Reservoir data assimilation on top of the level pool, for the staged window: hybrid persistence of gage
+ * observations (reservoir types 2 USGS, 3 USACE) and RFC forecast series (types 4 RFC, 5 glacially dammed lake).
+ * Reference: the reservoir branch of the network loop, mc_reach.pyx:548-710, with reservoir_hybrid_da
+ * (fast_reach/reservoir_hybrid_da.py) and reservoir_RFC_da (fast_reach/reservoir_RFC_da.py:193-319); arithmetic types:
+ * csrc/reservoir_da.hpp.  Precision 32 plans only.  At every step the level-pool step runs first; the data-
+ * assimilation step then replaces its outflow and water elevation and moves the reservoir's state on.
+ *   kind      [nres]  per reservoir of trmc_set_reservoirs: 0 = level pool only, 2 / 3 / 4 / 5 = the reservoir type
+ *   table_row [nres]  its row in the table of its kind (usgs: 2, usace: 3, rfc: 4 and 5); ignored for kind 0
+ * A table (NULL or n = 0: none) has n rows of ncol entries:
+ *   usgs, usace: obs [n][ncol] observations (NaN = none), time [ncol] their times in seconds from the window's
+ *                start, state [n][4] = update_time prev_persisted_outflow persistence_index persistence_update_time
+ *   rfc:         obs [n][ncol] the series, state [n] = update_time, ipar [n][5] = timeseries_idx totalCounts
+ *                use_forecast da_timestep rfc_persist_days; time unused
+ * Everything is copied.  Must follow trmc_set_reservoirs (which drops the tables); nres = 0 drops them too.  The
+ * lookback is 48 h, the intervals 3600 s and 86400 s, the persistence limit 11, as the loop calls the functions.
+ */
+typedef struct trmc_reservoir_da_table {
+    int64_t n, ncol;
+    const float *obs, *time, *state;
+    const int32_t *ipar;
+} trmc_reservoir_da_table;
+int trmc_set_reservoir_da(trmc_plan *plan, int64_t nres, const int32_t *kind, const int32_t *table_row,
+                          const trmc_reservoir_da_table *usgs, const trmc_reservoir_da_table *usace,
+                          const trmc_reservoir_da_table *rfc);
+/* The state the routed window left, per reservoir of the plan: state_out [nres][4] (the four values above; RFC
+ * reservoirs: [0] = update_time), timeseries_idx_out [nres].  Times are in seconds from the START of the window
+ * (the loop's return shifts them by its length, mc_reach.pyx:820-837).  D2H. */
+int trmc_download_reservoir_da(trmc_plan *plan, float *state_out, int32_t *timeseries_idx_out);
+/*
+ * Batch of n independent data-assimilation steps on the device, through the device functions the step kernels call.
+ *   TRMC_RESERVOIR_DA_HYBRID: obs [n][ncol], time [n][ncol],
+ *       fin [n][12] = now prev_persisted_outflow persistence_update_time persistence_index levelpool_outflow inflow
+ *                     routing_period lake_area(km2) max_depth orifice_elevation initial_water_elevation update_time
+ *       fout [n][6] = outflow persisted_outflow water_elevation update_time persistence_index persistence_update_time
+ *       (iin, iout unused)
+ *   TRMC_RESERVOIR_DA_RFC: obs [n][ncol] (time unused),
+ *       fin [n][9] = now update_time inflow water_elevation levelpool_outflow levelpool_water_elevation lake_area(km2)
+ *                    max_water_elevation routing_period
+ *       iin [n][6] = use_forecast timeseries_idx totalCounts da_timestep rfc_persist_days reservoir_type
+ *       fout [n][3] = outflow water_elevation update_time;  iout [n] = timeseries_idx
+ */
+#define TRMC_RESERVOIR_DA_HYBRID 2
+#define TRMC_RESERVOIR_DA_RFC 4
+int trmc_reservoir_da_steps(int device, int kind, int64_t n, int64_t ncol, const float *obs, const float *time,
+                            const float *fin, const int32_t *iin, float *fout, int32_t *iout);
+
+/*
  * Streamflow nudging at gages for the staged window.  Reference: simple_da
  * (src/troute-routing/troute/routing/fast_reach/simple_da.pyx:22-95) applied to the gage segment after
  * its reach has been routed for the timestep (mc_reach.pyx:761-796).  Which of simple_da's three

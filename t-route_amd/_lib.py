@@ -89,6 +89,15 @@ def plan_options(options=None):
 
 
 _vp, _i64, _i32, _int = C.c_void_p, C.c_int64, C.c_int32, C.c_int
+
+
+class ReservoirDaTable(C.Structure):
+    """trmc_reservoir_da_table (include/trmc.h)"""
+    _fields_ = [("n", C.c_int64), ("ncol", C.c_int64), ("obs", C.c_void_p), ("time", C.c_void_p), ("state", C.c_void_p),
+                ("ipar", C.c_void_p)]
+
+
+RESERVOIR_DA_HYBRID, RESERVOIR_DA_RFC = 2, 4
 _P = C.POINTER
 # name -> (restype, argtypes); must list every symbol include/trmc.h declares
 SIGNATURES = {
@@ -126,6 +135,9 @@ SIGNATURES = {
     "trmc_set_boundary_flow_device": (_int, [_vp, _int, _vp]),
     "trmc_set_reservoirs": (_int, [_vp, _i64, _vp, _vp, C.c_double]),
     "trmc_download_reservoir_inflow": (_int, [_vp, _vp]),
+    "trmc_set_reservoir_da": (_int, [_vp, _i64, _vp, _vp, _P(ReservoirDaTable), _P(ReservoirDaTable), _P(ReservoirDaTable)]),
+    "trmc_download_reservoir_da": (_int, [_vp, _vp, _vp]),
+    "trmc_reservoir_da_steps": (_int, [_int, _int, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "trmc_set_nudging": (_int, [_vp, _int, _i64, _vp, _vp, _vp, _vp]),
     "trmc_set_nudging_successors": (_int, [_vp, C.c_int64, _vp]),
     "trmc_download_nudge": (_int, [_vp, _vp]),

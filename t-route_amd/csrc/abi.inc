@@ -401,7 +401,7 @@ void trmc_plan_destroy(trmc_plan *pl)
             pl->rowsets.clear();
             for (DevBuf *b : {&pl->dec, &pl->fetch_hyd, &pl->fetch_q0, &pl->fetch_fvd, &pl->it_prev, &pl->it_sum, &pl->d_state, &pl->ticket, &pl->dbg, &pl->cuq_head, &pl->d_gran,
                               &pl->raw_of_pos, &pl->da_raw, &pl->gage_of_pos, &pl->da_mode, &pl->da_a, &pl->da_w, &pl->da_nudge, &pl->res_of_pos,
-                              &pl->res_par, &pl->res_inflow, &pl->in_qlat, &pl->in_q0, &pl->in_bfvd, &pl->qlat_tm, &pl->qlat_alt, &pl->tm, &pl->out, &pl->scratch,
+                              &pl->res_par, &pl->res_inflow, &pl->res_da, &pl->in_qlat, &pl->in_q0, &pl->in_bfvd, &pl->qlat_tm, &pl->qlat_alt, &pl->tm, &pl->out, &pl->scratch,
                               &pl->gathered, &pl->cls_last, &pl->hot_list, &pl->hot_cnt})
                 b->release();
         }
@@ -424,7 +424,7 @@ void trmc_plan_destroy(trmc_plan *pl)
     if (pl->ev_fetch_done) (void)hipEventDestroy(pl->ev_fetch_done);
     if (pl->ev_gather) (void)hipEventDestroy(pl->ev_gather);
     for (DevBuf *b : {&pl->lagk, &pl->cblk_ptr, &pl->params, &pl->up_ptr, &pl->up_idx, &pl->up2, &pl->level, &pl->row_of_pos, &pl->pos_of_row, &pl->it_prev, &pl->it_sum, &pl->lag, &pl->d_state, &pl->ticket, &pl->ticket_map, &pl->rank, &pl->dbg, &pl->prio, &pl->cuq_ptr, &pl->cuq_blk, &pl->cuq_head, &pl->cu_index, &pl->cuq_perm, &pl->d_gran, &pl->raw_of_pos, &pl->da_raw, &pl->gage_of_pos,
-                      &pl->da_mode, &pl->da_a, &pl->da_w, &pl->da_nudge, &pl->res_of_pos, &pl->res_par, &pl->res_inflow,
+                      &pl->da_mode, &pl->da_a, &pl->da_w, &pl->da_nudge, &pl->res_of_pos, &pl->res_par, &pl->res_inflow, &pl->res_da,
                       &pl->in_qlat, &pl->in_q0, &pl->in_bfvd, &pl->qlat_tm, &pl->qlat_alt, &pl->tm, &pl->out, &pl->scratch, &pl->gathered, &pl->cls_last, &pl->hot_list, &pl->hot_cnt})
         b->release();
     for (auto &e : pl->ev)
@@ -815,6 +815,7 @@ int trmc_set_reservoirs(trmc_plan *pl, int64_t nres, const int64_t *res_rows, co
     if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
     if (nres < 0) return fail(TRMC_EINVAL, "nres < 0");
     pl->nres = 0;
+    pl->res_da_on = false; // (the tables of trmc_set_reservoir_da belong to the reservoirs they were set for)
     if (nres == 0) return 0;
     if (!res_rows || !par) return fail(TRMC_EINVAL, "res_rows/par is NULL");
     if (int rc = use_device(pl)) return rc;
@@ -845,6 +846,124 @@ int trmc_download_reservoir_inflow(trmc_plan *pl, void *inflow_out)
     if (int rc = use_device(pl)) return rc;
     HIP_TRY(hipMemcpy(inflow_out, pl->res_inflow.p, (size_t)pl->nres * pl->routed_nsteps * pl->esz, hipMemcpyDeviceToHost));
     return 0;
+}
+
+int trmc_set_reservoir_da(trmc_plan *pl, int64_t nres, const int32_t *kind, const int32_t *table_row,
+                          const trmc_reservoir_da_table *usgs, const trmc_reservoir_da_table *usace, const trmc_reservoir_da_table *rfc)
+{
+    if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
+    pl->res_da_on = false;
+    if (nres == 0) return 0;
+    if (nres != pl->nres) return fail(TRMC_ESTATE, "trmc_set_reservoirs (same nres) must precede trmc_set_reservoir_da");
+    if (!kind || !table_row) return fail(TRMC_EINVAL, "kind/table_row is NULL");
+    if (pl->precision != 32 || pl->opt.tol)
+        return fail(TRMC_EINVAL, "reservoir data assimilation needs a precision 32 plan in the exact arithmetic");
+    if (pl->run.active) return fail(TRMC_ESTATE, "a routing window is in progress");
+    const trmc_reservoir_da_table none{};
+    const trmc_reservoir_da_table *tab[3] = {usgs ? usgs : &none, usace ? usace : &none, rfc ? rfc : &none};
+    const char *const tname[3] = {"usgs", "usace", "rfc"};
+    int64_t off[3], time_off[3] = {0, 0, 0};
+    int64_t floats = nres * (int64_t)(sizeof(trmc::ResDaRec) / sizeof(float)); // the float rows begin behind the records
+    for (int k = 0; k < 3; ++k) {
+        const trmc_reservoir_da_table &t = *tab[k];
+        if (t.n < 0 || t.ncol < 0) return fail(TRMC_EINVAL, std::string(tname[k]) + " table: n/ncol < 0");
+        if (t.n > 0 && (t.ncol < 1 || t.ncol > INT32_MAX)) return fail(TRMC_EINVAL, std::string(tname[k]) + " table: rows without columns");
+        if (t.n > 0 && (!t.obs || !t.state || (k < 2 && !t.time) || (k == 2 && !t.ipar)))
+            return fail(TRMC_EINVAL, std::string(tname[k]) + " table: a pointer is NULL");
+        off[k] = floats;
+        floats += t.n * t.ncol;
+        if (k < 2) {
+            time_off[k] = floats;
+            floats += t.n > 0 ? t.ncol : 0;
+        }
+    }
+    std::vector<float> host((size_t)floats, 0.0f);
+    trmc::ResDaRec *rec = reinterpret_cast<trmc::ResDaRec *>(host.data());
+    std::vector<uint8_t> used[3];
+    for (int k = 0; k < 3; ++k) {
+        used[k].assign((size_t)tab[k]->n, 0);
+        if (tab[k]->n > 0) std::memcpy(host.data() + off[k], tab[k]->obs, (size_t)(tab[k]->n * tab[k]->ncol) * sizeof(float));
+        if (k < 2 && tab[k]->n > 0) std::memcpy(host.data() + time_off[k], tab[k]->time, (size_t)tab[k]->ncol * sizeof(float));
+    }
+    bool any = false;
+    for (int64_t i = 0; i < nres; ++i) {
+        trmc::ResDaRec r{};
+        r.kind = kind[i];
+        if (r.kind == 0) {
+            rec[i] = r;
+            continue;
+        }
+        if (r.kind < 2 || r.kind > 5) return fail(TRMC_EINVAL, "reservoir " + std::to_string(i) + ": kind must be 0 or 2..5");
+        const int k = r.kind == 2 ? 0 : (r.kind == 3 ? 1 : 2);
+        const trmc_reservoir_da_table &t = *tab[k];
+        const int64_t j = table_row[i];
+        if (j < 0 || j >= t.n)
+            return fail(TRMC_EINVAL, "reservoir " + std::to_string(i) + ": no row " + std::to_string(j) + " in the " + tname[k] + " table");
+        if (used[k][(size_t)j]) return fail(TRMC_EINVAL, std::string("two reservoirs on one row of the ") + tname[k] + " table");
+        used[k][(size_t)j] = 1;
+        r.ncol = (int32_t)t.ncol;
+        r.obs_off = off[k] + j * t.ncol;
+        r.time_off = time_off[k];
+        if (k < 2) {
+            const float *s = t.state + 4 * j;
+            r.update_time = s[0];
+            r.prev_persisted = s[1];
+            r.persistence_index = s[2];
+            r.persistence_update_time = s[3];
+        } else {
+            const int32_t *p = t.ipar + 5 * j;
+            r.update_time = t.state[j];
+            r.timeseries_idx = p[0];
+            r.total_counts = p[1];
+            r.use_forecast = p[2];
+            r.da_timestep = p[3];
+            r.persist_days = p[4];
+            if (r.timeseries_idx < 0 || r.timeseries_idx >= r.ncol)
+                return fail(TRMC_EINVAL, "rfc table row " + std::to_string(j) + ": timeseries_idx outside the series");
+        }
+        rec[i] = r;
+        any = true;
+    }
+    if (!any) return 0;
+    if (int rc = use_device(pl)) return rc;
+    if (int rc = pl->res_da.ensure(host.size() * sizeof(float))) return rc;
+    HIP_TRY(hipMemcpy(pl->res_da.p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+    pl->res_da_on = true;
+    pl->routed_nsteps = -1;
+    return 0;
+}
+
+int trmc_download_reservoir_da(trmc_plan *pl, float *state_out, int32_t *timeseries_idx_out)
+{
+    if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
+    if (pl->routed_nsteps < 0) return fail(TRMC_ESTATE, "nothing routed yet");
+    if (pl->nres == 0 || !pl->res_da_on) return fail(TRMC_ESTATE, "the routed window had no reservoir data-assimilation tables");
+    if (!state_out || !timeseries_idx_out) return fail(TRMC_EINVAL, "state_out/timeseries_idx_out is NULL");
+    if (int rc = use_device(pl)) return rc;
+    std::vector<trmc::ResDaRec> rec((size_t)pl->nres);
+    HIP_TRY(hipMemcpy(rec.data(), pl->res_da.p, rec.size() * sizeof(trmc::ResDaRec), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < rec.size(); ++i) {
+        state_out[4 * i + 0] = rec[i].update_time;
+        state_out[4 * i + 1] = rec[i].prev_persisted;
+        state_out[4 * i + 2] = rec[i].persistence_index;
+        state_out[4 * i + 3] = rec[i].persistence_update_time;
+        timeseries_idx_out[i] = rec[i].timeseries_idx;
+    }
+    return 0;
+}
+
+int trmc_reservoir_da_steps(int device, int kind, int64_t n, int64_t ncol, const float *obs, const float *time, const float *fin,
+                            const int32_t *iin, float *fout, int32_t *iout)
+{
+    if (kind != TRMC_RESERVOIR_DA_HYBRID && kind != TRMC_RESERVOIR_DA_RFC) return fail(TRMC_EINVAL, "bad kind");
+    if (n < 0) return fail(TRMC_EINVAL, "n < 0");
+    if (n == 0) return 0;
+    if (ncol < 1 || ncol > INT32_MAX) return fail(TRMC_EINVAL, "ncol must be >= 1");
+    const bool hybrid = kind == TRMC_RESERVOIR_DA_HYBRID;
+    if (!obs || !fin || !fout || (hybrid && !time) || (!hybrid && (!iin || !iout))) return fail(TRMC_EINVAL, "an array pointer is NULL");
+    if (int rc = check_device(device)) return rc;
+    HIP_TRY(hipSetDevice(device));
+    return reservoir_da_steps(hybrid, n, (int32_t)ncol, obs, time, fin, iin, fout, iout);
 }
 
 int trmc_set_nudging(trmc_plan *pl, int nsteps, int64_t ngage, const int64_t *gage_rows, const uint8_t *mode,

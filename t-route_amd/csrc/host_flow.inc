@@ -131,6 +131,7 @@ FlowArgs flow_args(trmc_plan *pl, int nsteps, int qts, bool short_ts)
     a.res_par = (const float *)pl->res_par.p;
     a.res_inflow = (float *)pl->res_inflow.p;
     a.res_dt = (float)pl->res_dt;
+    a.res_da = (pl->nres > 0 && pl->res_da_on) ? pl->res_da.p : nullptr;
     const bool da = pl->ngage > 0;
     a.gage_of_pos = da ? (const int32_t *)pl->gage_of_pos.p : nullptr;
     a.da_mode = (const uint8_t *)pl->da_mode.p;
@@ -278,7 +279,12 @@ int flow_route_advance(trmc_plan *pl, int t_end)
             HIP_TRY(hipMemsetAsync(a.cuq_head, 0, (size_t)pl->ncuq * sizeof(int32_t), st));
         }
         const dim3 grid((unsigned)pl->topo.nblocks), block(kFlowBlock);
-        if (pl->opt.tol) {
+        if (a.res_da) { // (exact arithmetic: trmc_set_reservoir_da)
+            if (lean && a.lag) hipLaunchKernelGGL((k_mc_flow_lean_rda<true>), grid, block, 0, st, a, r.t_done, t_end);
+            else if (lean) hipLaunchKernelGGL((k_mc_flow_lean_rda<false>), grid, block, 0, st, a, r.t_done, t_end);
+            else if (r.short_ts) hipLaunchKernelGGL((k_mc_flow_rda<true>), grid, block, 0, st, a, r.t_done, t_end);
+            else hipLaunchKernelGGL((k_mc_flow_rda<false>), grid, block, 0, st, a, r.t_done, t_end);
+        } else if (pl->opt.tol) {
             if (lean && a.lag)
                 hipLaunchKernelGGL((k_mc_flow_lean<true, true>), grid, block, 0, st, a, r.t_done, t_end);
             else if (lean)

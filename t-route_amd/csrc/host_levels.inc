@@ -103,6 +103,7 @@ template <class T> StepArgs<T> step_args(trmc_plan *pl, int nsteps, int qts)
     a.res_par = (const T *)pl->res_par.p;
     a.res_inflow = (T *)pl->res_inflow.p;
     a.res_dt = (T)pl->res_dt;
+    a.res_da = (pl->nres > 0 && pl->res_da_on) ? pl->res_da.p : nullptr;
     const bool da = pl->ngage > 0;
     a.gage_of_pos = da ? (const int32_t *)pl->gage_of_pos.p : nullptr;
     a.da_mode = (const uint8_t *)pl->da_mode.p;
@@ -137,6 +138,13 @@ inline void launch_step_m(hipStream_t st, const StepArgs<T> &a, int32_t s0, int3
 {
     const int64_t n = (int64_t)s1 - s0;
     const dim3 grid((unsigned)((n + kStepBlock - 1) / kStepBlock)), block(kStepBlock);
+    if constexpr (sizeof(T) == 4 && !TOL) {
+        if (a.res_da) { // (trmc_set_reservoir_da: exact fp32 plans only)
+            if (SHORT && a.lag) hipLaunchKernelGGL((k_mc_step_rda<SHORT, SHORT>), grid, block, 0, st, a, s0, s1, d, (d - 1) / a.qts);
+            else hipLaunchKernelGGL((k_mc_step_rda<SHORT, false>), grid, block, 0, st, a, s0, s1, d, (d - 1) / a.qts);
+            return;
+        }
+    }
     if (SHORT && a.lag)
         hipLaunchKernelGGL((k_mc_step<T, SHORT, SHORT, TOL>), grid, block, 0, st, a, s0, s1, d, (d - 1) / a.qts);
     else
@@ -161,6 +169,11 @@ inline void launch_tile(hipStream_t st, const StepArgs<T> &a, int32_t p0, int32_
     const bool dec = a.dec != nullptr;
     const bool lazy = a.v_every != 0 && !a.out; // (velocity where it is handed on only: the LAZYV instances assemble no full result)
     if constexpr (sizeof(T) == 4) {
+        if (a.res_da) { // (never a stream's window, never the tolerance arithmetic: trmc_set_reservoir_da, stream_begin)
+            if (dec) hipLaunchKernelGGL((k_mc_tile_rda<true>), grid, block, 0, st, a, p0, p1, tile, K);
+            else hipLaunchKernelGGL((k_mc_tile_rda<false>), grid, block, 0, st, a, p0, p1, tile, K);
+            return;
+        }
         if (tol) {
             if (lazy) {
                 if (dec) hipLaunchKernelGGL((k_mc_tile<T, true, true, true>), grid, block, 0, st, a, p0, p1, tile, K);
@@ -188,6 +201,11 @@ inline void launch_ctile(hipStream_t st, const StepArgs<T> &a, const int32_t *cb
     const bool dec = a.dec != nullptr;
     const bool lazy = a.v_every != 0 && !a.out;
     if constexpr (sizeof(T) == 4) {
+        if (a.res_da) { // (see launch_tile)
+            if (dec) hipLaunchKernelGGL((k_mc_ctile_rda<true>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);
+            else hipLaunchKernelGGL((k_mc_ctile_rda<false>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);
+            return;
+        }
         if (tol) {
             if (lazy) {
                 if (dec) hipLaunchKernelGGL((k_mc_ctile<T, true, true, true>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);

@@ -32,6 +32,68 @@ template <class T> int segments_t(int64_t n, const void *in, void *out, bool tol
     return rc;
 }
 
+// trmc_reservoir_da_steps: n independent data-assimilation steps, one thread each, through the device functions the step
+// kernels call (reservoir_da.hpp); `hybrid` picks the step kind.  Row layouts: HybridIn / HybridOut, RfcIn / RfcOut.
+__global__ void __launch_bounds__(kBlock)
+k_reservoir_da_steps(bool hybrid, int64_t n, int32_t ncol, const float *obs, const float *time, const float *fin, const int32_t *iin,
+                     float *fout, int32_t *iout)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    if (hybrid) {
+        const float *p = fin + i * 12;
+        const trmc::HybridIn in{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], p[10], p[11]};
+        const trmc::HybridOut o = trmc::hybrid_da_step(obs + i * ncol, time + i * ncol, ncol, in);
+        float *q = fout + i * 6;
+        q[0] = o.outflow;
+        q[1] = o.persisted_outflow;
+        q[2] = o.water_elevation;
+        q[3] = o.update_time;
+        q[4] = o.persistence_index;
+        q[5] = o.persistence_update_time;
+    } else {
+        const float *p = fin + i * 9;
+        const int32_t *k = iin + i * 6;
+        const trmc::RfcIn in{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], k[0], k[1], k[2], k[3], k[4], k[5]};
+        const trmc::RfcOut o = trmc::rfc_da_step(obs + i * ncol, ncol, in);
+        float *q = fout + i * 3;
+        q[0] = o.outflow;
+        q[1] = o.water_elevation;
+        q[2] = o.update_time;
+        iout[i] = o.timeseries_idx;
+    }
+}
+
+int reservoir_da_steps(bool hybrid, int64_t n, int32_t ncol, const float *obs, const float *time, const float *fin, const int32_t *iin,
+                       float *fout, int32_t *iout)
+{
+    const size_t nin = hybrid ? 12 : 9, nout = hybrid ? 6 : 3, row = (size_t)n * (size_t)ncol * sizeof(float);
+    DevBuf dobs, dtime, dfin, diin, dfout, diout;
+    int rc = dobs.ensure(row);
+    if (!rc && hybrid) rc = dtime.ensure(row);
+    if (!rc) rc = dfin.ensure((size_t)n * nin * sizeof(float));
+    if (!rc) rc = dfout.ensure((size_t)n * nout * sizeof(float));
+    if (!rc && !hybrid) rc = diin.ensure((size_t)n * 6 * sizeof(int32_t));
+    if (!rc && !hybrid) rc = diout.ensure((size_t)n * sizeof(int32_t));
+    if (!rc) {
+        hipError_t e = hipMemcpy(dobs.p, obs, row, hipMemcpyHostToDevice);
+        if (e == hipSuccess && hybrid) e = hipMemcpy(dtime.p, time, row, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(dfin.p, fin, (size_t)n * nin * sizeof(float), hipMemcpyHostToDevice);
+        if (e == hipSuccess && !hybrid) e = hipMemcpy(diin.p, iin, (size_t)n * 6 * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_reservoir_da_steps, dim3(blocks_for(n)), dim3(kBlock), 0, 0, hybrid, n, ncol, (const float *)dobs.p,
+                               (const float *)dtime.p, (const float *)dfin.p, (const int32_t *)diin.p, (float *)dfout.p, (int32_t *)diout.p);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipMemcpy(fout, dfout.p, (size_t)n * nout * sizeof(float), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && !hybrid) e = hipMemcpy(iout, diout.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(TRMC_EHIP, std::string("trmc_reservoir_da_steps: ") + hipGetErrorString(e));
+    }
+    for (DevBuf *b : {&dobs, &dtime, &dfin, &diin, &dfout, &diout}) b->release();
+    return rc;
+}
+
 // trmc_plan_chain_from: time row `src_row` of one plan's planes -> time row 0 of another's, positions [lo, hi) (same order)
 template <class T>
 __global__ void __launch_bounds__(kBlock)

@@ -19,9 +19,23 @@
 // cost class like k_mc_tile's (the LDS slots are indexed by POSITION, so it does not matter which thread routes a row); there
 // are no hot rows here -- a row routed by another block could not hand its flow over.
 // Same bits as every other path: the same segment steps on the same inputs (tests run all of them against the oracle).
+template <class T, bool TOL, bool DEC, bool LAZYV, bool RDA> // (see mc_step_rows)
+__device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_t *__restrict__ cblk_ptr, int32_t cb0, int32_t tile, int32_t K);
 template <class T, bool TOL = false, bool DEC = false, bool LAZYV = false>
 __global__ void __launch_bounds__(kTileBlock, sizeof(T) == 4 ? (LAZYV ? TRMC_TILE_WAVES_LAZY : TRMC_TILE_WAVES) : 1)
 k_mc_ctile(const StepArgs<T> a, const int32_t *__restrict__ cblk_ptr, const int32_t cb0, const int32_t tile, const int32_t K)
+{
+    mc_ctile_rows<T, TOL, DEC, LAZYV, false>(a, cblk_ptr, cb0, tile, K);
+}
+template <bool DEC>
+__global__ void __launch_bounds__(kTileBlock, TRMC_TILE_WAVES)
+k_mc_ctile_rda(const StepArgs<float> a, const int32_t *__restrict__ cblk_ptr, const int32_t cb0, const int32_t tile, const int32_t K)
+{
+    mc_ctile_rows<float, false, DEC, false, true>(a, cblk_ptr, cb0, tile, K);
+}
+template <class T, bool TOL, bool DEC, bool LAZYV, bool RDA>
+__device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_t *__restrict__ cblk_ptr, const int32_t cb0,
+                                              const int32_t tile, const int32_t K)
 {
     using M = typename DevMath<T, TOL>::type;
     const ColdArgs<StepArgs<T>> cold = cold_args<StepArgs<T>>();
@@ -139,6 +153,12 @@ k_mc_ctile(const StepArgs<T> a, const int32_t *__restrict__ cblk_ptr, const int3
                 const trmc::LevelPoolParams<T> lp{rp[0], rp[1], rp[2], rp[3], rp[4], rp[5], rp[6], rp[7], rp[8]};
                 T H = d_prev;
                 q_new = trmc::levelpool_step<T, M>(qup, T(0), cold->res_dt, H, lp, m);
+                if constexpr (RDA) { // (see k_mc_step)
+                    void *const da = cold->res_da;
+                    const trmc::ResDaResult r = trmc::reservoir_da_row(da, ri, t, qup, d_prev, cold->res_dt, rp, q_new, H);
+                    q_new = r.outflow;
+                    H = r.water_elevation;
+                }
                 v_new = T(0);
                 d_new = H;
                 cold->res_inflow[(size_t)ri * (size_t)cold->nsteps + (size_t)(t - 1)] = qup;

@@ -54,6 +54,7 @@ struct FlowArgs {
     const float *res_par;
     float *res_inflow;
     float res_dt;
+    void *res_da;                  // nullptr, or the data-assimilation tables of the reservoirs (reservoir_da.hpp)
     const int32_t *gage_of_pos;
     const uint8_t *da_mode;
     const float *da_a, *da_w;
@@ -184,9 +185,22 @@ __device__ __forceinline__ float flow_edge_get(FlowEdge &e, const unsigned long 
     return __uint_as_float((uint32_t)v);
 }
 
+template <bool SHORT, bool TOL, bool RDA> // (RDA: reservoir data-assimilation tables, kernels of their own -- see mc_step_rows)
+__device__ __forceinline__ void mc_flow_rows(const FlowArgs &a, int32_t t0, int32_t t1);
 template <bool SHORT, bool TOL = false>
 __global__ void __launch_bounds__(kFlowBlock, TRMC_FLOW_WAVES)
 k_mc_flow(const FlowArgs a, const int32_t t0, const int32_t t1) // routes the launches / steps (t0, t1] of the window
+{
+    mc_flow_rows<SHORT, TOL, false>(a, t0, t1);
+}
+template <bool SHORT>
+__global__ void __launch_bounds__(kFlowBlock, TRMC_FLOW_WAVES)
+k_mc_flow_rda(const FlowArgs a, const int32_t t0, const int32_t t1)
+{
+    mc_flow_rows<SHORT, false, true>(a, t0, t1);
+}
+template <bool SHORT, bool TOL, bool RDA>
+__device__ __forceinline__ void mc_flow_rows(const FlowArgs &a, const int32_t t0, const int32_t t1)
 {
     using M = std::conditional_t<TOL, DevMathTolFlow, DevMathFlow>;
     const FlowCold cold = cold_args<FlowArgs>(); // (see cold_args: what the loop rarely needs is not kept in registers)
@@ -355,6 +369,12 @@ k_mc_flow(const FlowArgs a, const int32_t t0, const int32_t t1) // routes the la
             const trmc::LevelPoolParams<float> lp{rp[0], rp[1], rp[2], rp[3], rp[4], rp[5], rp[6], rp[7], rp[8]};
             float H = d_prev;
             q_new = trmc::levelpool_step<float, M>(f.quc, 0.0f, cold->res_dt, H, lp, m);
+            if constexpr (RDA) { // hybrid persistence / RFC series, mc_reach.pyx:555-703
+                void *const da = cold->res_da;
+                const trmc::ResDaResult r = trmc::reservoir_da_row(da, ri, t, f.quc, d_prev, cold->res_dt, rp, q_new, H);
+                q_new = r.outflow;
+                H = r.water_elevation;
+            }
             d_new = H;
             cold->res_inflow[(size_t)ri * (size_t)cold->nsteps + (size_t)(t - 1)] = f.quc;
             it_last = 0;
@@ -504,9 +524,22 @@ __device__ __forceinline__ int32_t lean_pick_block(const FlowArgs &a)
     return -1; // (cannot happen: as many workgroups as blocks)
 }
 
+template <bool LAG, bool TOL, bool RDA> // (see mc_flow_rows)
+__device__ __forceinline__ void mc_flow_lean_rows(const FlowArgs &a, int32_t t0, int32_t t1);
 template <bool LAG, bool TOL = false>
 __global__ void __launch_bounds__(kFlowBlock, TRMC_LEAN_WAVES)
 k_mc_flow_lean(const FlowArgs a, const int32_t t0, const int32_t t1)
+{
+    mc_flow_lean_rows<LAG, TOL, false>(a, t0, t1);
+}
+template <bool LAG>
+__global__ void __launch_bounds__(kFlowBlock, TRMC_LEAN_WAVES)
+k_mc_flow_lean_rda(const FlowArgs a, const int32_t t0, const int32_t t1)
+{
+    mc_flow_lean_rows<LAG, false, true>(a, t0, t1);
+}
+template <bool LAG, bool TOL, bool RDA>
+__device__ __forceinline__ void mc_flow_lean_rows(const FlowArgs &a, const int32_t t0, const int32_t t1)
 {
     using M = std::conditional_t<TOL, DevMathTolFlow, DevMathFlow>;
     const FlowCold cold = cold_args<FlowArgs>(); // (see cold_args: what the loop rarely needs is not kept in registers)
@@ -636,6 +669,12 @@ k_mc_flow_lean(const FlowArgs a, const int32_t t0, const int32_t t1)
             const trmc::LevelPoolParams<float> lp{rp[0], rp[1], rp[2], rp[3], rp[4], rp[5], rp[6], rp[7], rp[8]};
             float H = d_prev;
             q_new = trmc::levelpool_step<float, M>(qup, 0.0f, cold->res_dt, H, lp, m);
+            if constexpr (RDA) { // (see k_mc_flow)
+                void *const da = cold->res_da;
+                const trmc::ResDaResult r = trmc::reservoir_da_row(da, ri, t, qup, d_prev, cold->res_dt, rp, q_new, H);
+                q_new = r.outflow;
+                H = r.water_elevation;
+            }
             d_new = H;
             cold->res_inflow[(size_t)ri * (size_t)nsteps + (size_t)(t - 1)] = qup;
             its &= 0x00ffffffu;

@@ -33,6 +33,7 @@ template <class T> struct StepArgs {
     const T *res_par;
     T *res_inflow;
     T res_dt;
+    void *res_da; // nullptr, or the window's data-assimilation tables of those reservoirs (reservoir_da.hpp, trmc_set_reservoir_da)
     // streamflow nudging at gage positions (nullptr = off), tables [gage][nsteps], see trmc_set_nudging
     const int32_t *gage_of_pos;
     const uint8_t *da_mode;
@@ -120,9 +121,26 @@ constexpr int kStepBlock = TRMC_STEP_BLOCK;
 // transpose trails the last step launch: CONUS day 22.3 ms with tiles of 128 steps, 21.7 with 64, 21.5 with 32
 #define TRMC_EMIT_TILE 32
 #endif
+// The rows of a launch are routed by mc_step_rows; the kernels are thin instances of it.  RDA: the window has reservoir
+// data-assimilation tables (StepArgs::res_da) -- kernels of their own (k_mc_step_rda), so that the ones every other window runs are
+// compiled without the call: it would cost them registers and stack whether a table is there or not.
+template <class T, bool SHORT, bool LAG, bool TOL, bool RDA>
+__device__ __forceinline__ void mc_step_rows(const StepArgs<T> &a, int32_t s_begin, int32_t s_end, int32_t diag, int32_t ql_col);
 template <class T, bool SHORT, bool LAG = false, bool TOL = false>
 __global__ void __launch_bounds__(kStepBlock)
 k_mc_step(const StepArgs<T> a, const int32_t s_begin, const int32_t s_end, const int32_t diag, const int32_t ql_col)
+{
+    mc_step_rows<T, SHORT, LAG, TOL, false>(a, s_begin, s_end, diag, ql_col);
+}
+template <bool SHORT, bool LAG = false>
+__global__ void __launch_bounds__(kStepBlock)
+k_mc_step_rda(const StepArgs<float> a, const int32_t s_begin, const int32_t s_end, const int32_t diag, const int32_t ql_col)
+{
+    mc_step_rows<float, SHORT, LAG, false, true>(a, s_begin, s_end, diag, ql_col);
+}
+template <class T, bool SHORT, bool LAG, bool TOL, bool RDA>
+__device__ __forceinline__ void mc_step_rows(const StepArgs<T> &a, const int32_t s_begin, const int32_t s_end, const int32_t diag,
+                                             const int32_t ql_col)
 {   // ql_col: the lateral-inflow column (diag - 1) / qts of a launch whose rows are all at step diag (SHORT, no lag) -- formed
     // by the host: an integer division by a run-time divisor is some 35 instructions per thread
     using M = typename DevMath<T, TOL>::type;
@@ -221,7 +239,13 @@ k_mc_step(const StepArgs<T> a, const int32_t s_begin, const int32_t s_end, const
                 const T *rp = a.res_par + (size_t)ri * 9;
                 const trmc::LevelPoolParams<T> lp{rp[0], rp[1], rp[2], rp[3], rp[4], rp[5], rp[6], rp[7], rp[8]};
                 T H = depthp; // a reservoir row keeps its water elevation in the depth slot
-                const T outflow = trmc::levelpool_step<T, M>(f.quc, T(0), a.res_dt, H, lp, m);
+                T outflow = trmc::levelpool_step<T, M>(f.quc, T(0), a.res_dt, H, lp, m);
+                if constexpr (RDA) {
+                    void *const da = cold_args<StepArgs<T>>()->res_da; // hybrid persistence / RFC series, mc_reach.pyx:555-703
+                    const trmc::ResDaResult r = trmc::reservoir_da_row(da, ri, t, f.quc, depthp, a.res_dt, rp, outflow, H);
+                    outflow = r.outflow;
+                    H = r.water_elevation;
+                }
                 a.q_tm[row_c + s] = outflow;
                 a.v_tm[row_c + s] = T(0);
                 a.d_tm[row_c + s] = H;
@@ -313,9 +337,23 @@ constexpr int64_t kMidDefaultRowsPerCu = 0; // default threshold of the second t
 // sequence, ms per day on the cost-ordered / the unordered plan: 6: 16.06 / 17.55, 16: 16.07 / 17.33, 40: 16.06 / 17.36
 #define TRMC_HOT_WAVE_MAX 16
 #endif
+template <class T, bool TOL, bool DEC, bool LAZYV, bool RDA> // (see mc_step_rows)
+__device__ __forceinline__ void mc_tile_rows(const StepArgs<T> &a, int32_t s_begin, int32_t s_end, int32_t tile, int32_t K);
 template <class T, bool TOL = false, bool DEC = false, bool LAZYV = false> // (LAZYV: StepArgs::v_every != 0)
 __global__ void __launch_bounds__(kTileBlock, sizeof(T) == 4 ? (LAZYV ? TRMC_TILE_WAVES_LAZY : TRMC_TILE_WAVES) : 1)
 k_mc_tile(const StepArgs<T> a, const int32_t s_begin, const int32_t s_end, const int32_t tile, const int32_t K)
+{
+    mc_tile_rows<T, TOL, DEC, LAZYV, false>(a, s_begin, s_end, tile, K);
+}
+template <bool DEC>
+__global__ void __launch_bounds__(kTileBlock, TRMC_TILE_WAVES)
+k_mc_tile_rda(const StepArgs<float> a, const int32_t s_begin, const int32_t s_end, const int32_t tile, const int32_t K)
+{
+    mc_tile_rows<float, false, DEC, false, true>(a, s_begin, s_end, tile, K);
+}
+template <class T, bool TOL, bool DEC, bool LAZYV, bool RDA>
+__device__ __forceinline__ void mc_tile_rows(const StepArgs<T> &a, const int32_t s_begin, const int32_t s_end, const int32_t tile,
+                                             const int32_t K)
 {
     using M = typename DevMath<T, TOL>::type;
     const ColdArgs<StepArgs<T>> cold = cold_args<StepArgs<T>>(); // (see cold_args: what the loop rarely needs is not kept in registers)
@@ -469,6 +507,12 @@ k_mc_tile(const StepArgs<T> a, const int32_t s_begin, const int32_t s_end, const
             const trmc::LevelPoolParams<T> lp{rp[0], rp[1], rp[2], rp[3], rp[4], rp[5], rp[6], rp[7], rp[8]};
             T H = d_prev;
             q_new = trmc::levelpool_step<T, M>(qup, T(0), cold->res_dt, H, lp, m);
+            if constexpr (RDA) { // (see k_mc_step)
+                void *const da = cold->res_da;
+                const trmc::ResDaResult r = trmc::reservoir_da_row(da, ri, t, qup, d_prev, cold->res_dt, rp, q_new, H);
+                q_new = r.outflow;
+                H = r.water_elevation;
+            }
             v_new = T(0);
             d_new = H;
             cold->res_inflow[(size_t)ri * (size_t)cold->nsteps + (size_t)(t - 1)] = qup;

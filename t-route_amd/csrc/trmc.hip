@@ -43,6 +43,7 @@
 #include "det_pow64.h"
 #include "mc_segment.hpp"
 #include "levelpool.hpp"
+#include "reservoir_da.hpp"
 #include "topology.hpp"
 #include "internal.hpp"
 
@@ -179,6 +180,8 @@ struct trmc_plan {
     DevBuf res_of_pos, res_par, res_inflow;             // level-pool reservoirs of the plan
     int64_t nres = 0;
     double res_dt = 0.0;
+    DevBuf res_da;                       // data-assimilation tables of those reservoirs for the staged window (reservoir_da.hpp)
+    bool res_da_on = false;
     int64_t ngage = 0;
     int64_t nraw = 0;                    // gages inside a reach whose successor reads the un-nudged flow (general mode)
     DevBuf raw_of_pos, da_raw;

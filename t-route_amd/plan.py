@@ -251,6 +251,46 @@ class RoutingPlan:
         _lib.check(_lib.lib().trmc_set_reservoirs(self._h, self._nres, _lib.ptr(res_rows), _lib.ptr(par),
                                                   float(routing_period)))
 
+    def set_reservoir_da(self, kind, table_row, usgs=None, usace=None, rfc=None):
+        """Data-assimilation tables of the plan's reservoirs for the staged window (include/trmc.h trmc_set_reservoir_da;
+        after set_reservoirs).  kind / table_row [nres]; usgs, usace: None or (obs [n, ncol], time [ncol], state [n, 4]);
+        rfc: None or (series [n, ncol], update_time [n], ipar [n, 5])."""
+        if self.precision != 32:
+            raise NotImplementedError("reservoir data assimilation (reservoir types 2..5) on a precision 64 plan: the reference "
+                                      "has no double-precision form of this branch")
+        kind = np.ascontiguousarray(kind, dtype=np.int32)
+        table_row = np.ascontiguousarray(table_row, dtype=np.int32)
+        if kind.shape != (getattr(self, "_nres", 0),) or table_row.shape != kind.shape:
+            raise ValueError("kind and table_row must be [nres] of set_reservoirs")
+        keep, tabs = [kind, table_row], []
+        for t, hybrid in ((usgs, True), (usace, True), (rfc, False)):
+            s = _lib.ReservoirDaTable()
+            if t is not None and len(t[0]):
+                obs = np.ascontiguousarray(t[0], dtype=np.float32)
+                n, ncol = obs.shape
+                if hybrid:
+                    time, state, ipar = np.ascontiguousarray(t[1], dtype=np.float32), np.ascontiguousarray(t[2], dtype=np.float32), None
+                    if time.shape != (ncol,) or state.shape != (n, 4):
+                        raise ValueError("hybrid table: time must be [ncol], state [n, 4]")
+                else:
+                    time, state, ipar = None, np.ascontiguousarray(t[1], dtype=np.float32), np.ascontiguousarray(t[2], dtype=np.int32)
+                    if state.shape != (n,) or ipar.shape != (n, 5):
+                        raise ValueError("rfc table: update_time must be [n], ipar [n, 5]")
+                keep += [obs, time, state, ipar]
+                s.n, s.ncol = n, ncol
+                s.obs, s.time, s.state, s.ipar = (None if a is None else a.ctypes.data for a in (obs, time, state, ipar))
+            tabs.append(s)
+        _lib.check(_lib.lib().trmc_set_reservoir_da(self._h, kind.shape[0], _lib.ptr(kind), _lib.ptr(table_row),
+                                                    C.byref(tabs[0]), C.byref(tabs[1]), C.byref(tabs[2])))
+
+    def download_reservoir_da(self):
+        """(state [nres, 4] float32, timeseries_idx [nres] int32) the routed window left: include/trmc.h
+        trmc_download_reservoir_da -- times in seconds from the start of the window."""
+        state = np.zeros((getattr(self, "_nres", 0), 4), dtype=np.float32)
+        idx = np.zeros(state.shape[0], dtype=np.int32)
+        _lib.check(_lib.lib().trmc_download_reservoir_da(self._h, _lib.ptr(state), _lib.ptr(idx)))
+        return state, idx
+
     def download_reservoir_inflow(self):
         out = np.zeros((getattr(self, "_nres", 0), self._nsteps), dtype=self.dtype)
         _lib.check(_lib.lib().trmc_download_reservoir_inflow(self._h, _lib.ptr(out)))
@@ -609,3 +649,32 @@ def segments(inputs, device=0, arithmetic="exact", with_iterations=False):
     _lib.check(_lib.lib().trmc_segments_ex(device, precision, {"exact": _lib.ARITH_EXACT, "tolerance": _lib.ARITH_TOLERANCE}[arithmetic],
                                            inputs.shape[0], _lib.ptr(inputs), _lib.ptr(out), _lib.ptr(iters)))
     return (out, iters) if with_iterations else out
+
+
+def reservoir_da_steps(kind, obs, time, fin, iin=None, device=0):
+    """Batch of independent reservoir data-assimilation steps on the GPU (include/trmc.h trmc_reservoir_da_steps), through the
+    device functions the step kernels call.  kind "hybrid": obs, time [n, ncol], fin [n, 12] -> [n, 6]; kind "rfc": obs
+    [n, ncol], fin [n, 9], iin [n, 6] -> ([n, 3], timeseries_idx [n])."""
+    hybrid = {"hybrid": True, "rfc": False}[kind]
+    obs = np.ascontiguousarray(obs, dtype=np.float32)
+    fin = np.ascontiguousarray(fin, dtype=np.float32)
+    n = fin.shape[0]
+    if obs.ndim != 2 or obs.shape[0] != n or fin.shape != (n, 12 if hybrid else 9):
+        raise ValueError("obs must be [n, ncol], fin [n, 12] (hybrid) or [n, 9] (rfc)")
+    if hybrid:
+        time = np.ascontiguousarray(time, dtype=np.float32)
+        if time.shape != obs.shape:
+            raise ValueError("time must have the shape of obs")
+        iin = iout = None
+    else:
+        time = None
+        iin = np.ascontiguousarray(iin, dtype=np.int32)
+        if iin.shape != (n, 6):
+            raise ValueError("iin must be [n, 6]")
+        iout = np.zeros(n, dtype=np.int32)
+    fout = np.zeros((n, 6 if hybrid else 3), dtype=np.float32)
+    _lib.mark_hip_started()
+    _lib.check(_lib.lib().trmc_reservoir_da_steps(device, _lib.RESERVOIR_DA_HYBRID if hybrid else _lib.RESERVOIR_DA_RFC, n,
+                                                  obs.shape[1], _lib.ptr(obs), _lib.ptr(time), _lib.ptr(fin), _lib.ptr(iin),
+                                                  _lib.ptr(fout), _lib.ptr(iout)))
+    return fout if hybrid else (fout, iout)

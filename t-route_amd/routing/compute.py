@@ -20,8 +20,10 @@ What is different, on purpose (MI355X-first, SURVEY.md 8b "Threading"):
     per network, compute.py:1399-1467) is done once for the whole table.
 Level-pool waterbodies (``waterbodies_df``, reservoir type 1) are routed and gage observations
 (``usgs_df`` / ``lastobs_df``, streamflow nudging) are prepared as the reference prepares them
-(``_prep_da_dataframes``, ``_prep_da_positions_byreach``); reservoir data-assimilation DataFrames raise
-NotImplementedError, as does the diffusive branch.
+(``_prep_da_dataframes``, ``_prep_da_positions_byreach``), and so are the reservoir data-assimilation DataFrames of
+hybrid-persistence (USGS, USACE) and RFC reservoirs (``_prep_reservoir_da_dataframes``: tables and state per call, reservoir
+types demoted to level pool where a table is empty).  NotImplementedError: ``great_lakes_df``; a reservoir observation
+table that arrives without its ``*_param_df``; what the kernel callable refuses (mc_reach.py).
 """
 from collections import defaultdict
 
@@ -79,6 +81,56 @@ def _prep_da_positions_byreach(reach_list, gage_index):
                 reach_key.append(i)
                 gage_i.append(where[s])
     return reach_key, np.asarray(gage_i, dtype=np.intp)
+
+
+def _prep_reservoir_da_dataframes(reservoir_usgs_df, reservoir_usgs_param_df, reservoir_usace_df, reservoir_usace_param_df,
+                                  reservoir_rfc_df, reservoir_rfc_param_df, waterbody_types_df_sub, t0, from_files,
+                                  exclude_segments=None):
+    """Reservoir data-assimilation tables and state of the waterbodies of one sub-domain, as arrays for the kernel callable.
+
+    Same name, arguments and returns as the reference helper (compute.py:142-295) WITHOUT its Great Lakes part: the
+    arguments ``great_lakes_df, great_lakes_param_df, great_lakes_climatology_df`` (between ``reservoir_rfc_param_df`` and
+    ``waterbody_types_df_sub`` there) are not taken, and the six returns ``gl_df_sub, gl_parm_lake_id_sub, gl_param_flows_sub,
+    gl_param_time_sub, gl_param_update_time_sub, gl_climatology_df_sub`` (between ``reservoir_rfc_persist_days`` and
+    ``waterbody_types_df_sub`` there) are not made; nor is type 6 demoted to 1 -- the kernel callable refuses it.
+
+    Returns the 21-tuple: USGS (observations of the type-2 waterbodies, times of the table's columns in seconds from t0,
+    update_time, prev_persisted_outflow, persistence_update_time, persistence_index), the same six for USACE (type 3), RFC
+    (series of the type-4 waterbodies, totalCounts, file list, use_rfc, timeseries_idx, update_time, da_timestep,
+    rfc_persist_days), and ``waterbody_types_df_sub`` -- changed in place: where a table is empty its type becomes 1, level
+    pool (2 without USGS observations, 3 without USACE ones, 4 without series when not from_files)."""
+    import pandas as pd
+    types = waterbody_types_df_sub
+
+    def none():
+        return pd.DataFrame().to_numpy().reshape(0,)
+
+    def of_type(code):
+        sub = types[types["reservoir_type"] == code].index
+        return list(set(sub).difference(set(exclude_segments))) if exclude_segments else sub
+
+    out = []
+    for df, param_df, code in ((reservoir_usgs_df, reservoir_usgs_param_df, 2), (reservoir_usace_df, reservoir_usace_param_df, 3)):
+        if not df.empty:
+            sub = of_type(code)
+            out += [df.loc[sub], np.array([(stamp - t0).total_seconds() for stamp in df.columns])]
+            out += [param_df[c].loc[sub].to_numpy() for c in ("update_time", "prev_persisted_outflow", "persistence_update_time",
+                                                               "persistence_index")]
+        else:
+            out += [pd.DataFrame(), none(), none(), none(), none(), none()]
+            if not types.empty:
+                types.loc[types["reservoir_type"] == code] = 1
+    if not reservoir_rfc_df.empty:
+        sub = of_type(4)
+        out += [reservoir_rfc_df.loc[sub], reservoir_rfc_param_df["totalCounts"].loc[sub].to_numpy(),
+                reservoir_rfc_param_df["file"].loc[sub].to_list()]
+        out += [reservoir_rfc_param_df[c].loc[sub].to_numpy() for c in ("use_rfc", "timeseries_idx", "update_time", "da_timestep",
+                                                                        "rfc_persist_days")]
+    else:
+        out += [pd.DataFrame(), none(), [], none(), none(), none(), none(), none()]
+        if not from_files and not types.empty:
+            types.loc[types["reservoir_type"] == 4] = 1
+    return tuple(out) + (types,)
 
 
 def compute_nhd_routing_v02(
@@ -146,12 +198,16 @@ def compute_nhd_routing_v02(
     """
     if parallel_compute_method not in _PARALLEL_METHODS and parallel_compute_method is not None:
         raise ValueError(f"unknown parallel_compute_method {parallel_compute_method!r}")
-    for name, df in (("reservoir_usgs_df", reservoir_usgs_df), ("reservoir_usace_df", reservoir_usace_df),
-                     ("reservoir_rfc_df", reservoir_rfc_df), ("great_lakes_df", great_lakes_df)):
-        if not _is_empty(df):
+    if not _is_empty(great_lakes_df):
+        raise NotImplementedError("great_lakes_df is not empty: Great Lakes data assimilation is outside the Muskingum-Cunge "
+                                  "path this package replaces")
+    for name, df, pdf in (("reservoir_usgs_df", reservoir_usgs_df, reservoir_usgs_param_df),
+                          ("reservoir_usace_df", reservoir_usace_df, reservoir_usace_param_df),
+                          ("reservoir_rfc_df", reservoir_rfc_df, reservoir_rfc_param_df)):
+        if not _is_empty(df) and _is_empty(pdf):
             raise NotImplementedError(
-                f"{name} is not empty: reservoir data assimilation (hybrid persistence, RFC forecasts, Great "
-                "Lakes) is outside the Muskingum-Cunge path this package replaces")
+                f"{name} is not empty but {name[:-2]}param_df is: reservoir data assimilation needs the state table "
+                "(update times, persisted outflow, persistence index) beside the observations")
     offnetwork_upstreams = sorted(int(k) for k in flowveldepth_interorder) if flowveldepth_interorder else []
 
     # ---- what depends on the NETWORK only is made once per set of caller objects (nwm_route hands the same dictionaries and
@@ -214,6 +270,25 @@ def compute_nhd_routing_v02(
         gage_args = (e_f2, e_i1, e_i1, e_i1, e_f1, e_f1)
     # the result in the order that groups the table's rows by tailwater (a network's block is then a slice of it), permuted on the
     # device as it is decimated -- when every row of the table belongs to a tailwater of the call and is in the result
+    # reservoir data assimilation: tables, state and the (possibly demoted) reservoir types of THIS call -- compute.py:1470-1506
+    # per tailwater, here for every waterbody of the call; nothing of it is kept with the network
+    res_da_args = (e_f2, e_i1, e_f1, e_f1, e_f1, e_f1, e_f1,
+                   e_f2, e_i1, e_f1, e_f1, e_f1, e_f1, e_f1,
+                   e_f2, e_i1, e_i1, [], e_i1, e_i1, e_f1, e_i1, e_i1)
+    if len(lake_segs) and not _is_empty(waterbody_types_df):
+        edf = pd.DataFrame()
+        types_df_sub = waterbody_types_df.loc[lake_segs, ["reservoir_type"]].copy()
+        p = _prep_reservoir_da_dataframes(
+            edf if _is_empty(reservoir_usgs_df) else reservoir_usgs_df, reservoir_usgs_param_df,
+            edf if _is_empty(reservoir_usace_df) else reservoir_usace_df, reservoir_usace_param_df,
+            edf if _is_empty(reservoir_rfc_df) else reservoir_rfc_df, reservoir_rfc_param_df, types_df_sub, t0, from_files)
+        types_sub = p[20].values.astype("int32")
+        f32a, i32a = (lambda a: np.asarray(a).astype("float32")), (lambda a: np.asarray(a).astype("int32"))
+        res_da_args = (
+            p[0].values.astype("float32"), p[0].index.values.astype("int32"), f32a(p[1]), f32a(p[2]), f32a(p[3]), f32a(p[4]), f32a(p[5]),
+            p[6].values.astype("float32"), p[6].index.values.astype("int32"), f32a(p[7]), f32a(p[8]), f32a(p[9]), f32a(p[10]), f32a(p[11]),
+            p[12].values.astype("float32"), p[12].index.values.astype("int32"), i32a(p[13]), p[14], i32a(p[15]), i32a(p[16]),
+            f32a(p[17]), i32a(p[18]), i32a(p[19]))
     grouped = not upstream_results and not ngage and net["order"].shape[0] == nseg and bool(net["bounds"][0] == 0)
     r = compute_network_structured(
         nts, dt, qts_subdivisions, reaches_wTypes, upstream_connections, ids, table_cols,
@@ -221,9 +296,7 @@ def compute_nhd_routing_v02(
         types_sub, bool(waterbody_type_specified),
         t0.strftime('%Y-%m-%d_%H:%M:%S') if hasattr(t0, "strftime") else str(t0),
         *gage_args, da_parameter_dict.get("da_decay_coefficient", 0) if da_parameter_dict else 0,
-        e_f2, e_i1, e_f1, e_f1, e_f1, e_f1, e_f1,
-        e_f2, e_i1, e_f1, e_f1, e_f1, e_f1, e_f1,
-        e_f2, e_i1, e_i1, [], e_i1, e_i1, e_f1, e_i1, e_i1,
+        *res_da_args,
         e_i1, e_i1, e_f1, e_i1, e_f1, e_i1, e_i1, e_f2,
         upstream_results, assume_short_ts, return_courant, from_files=from_files, precision=precision, device=device,
         output_stride=output_stride, result_order=net["order"] if grouped else None, nan_is_zero=True)
@@ -261,14 +334,21 @@ def compute_nhd_routing_v02(
     no_gage = (np.asarray([], dtype=np.int64), np.full(0, np.nan, "float32"), np.full(0, np.nan, "float32"))
     no_nudge = np.zeros((0, nts + 1), dtype="float32")
     gage_owner = owner[np.maximum(gage_row, 0)] if ngage else None
+
+    def state_of(k, tup, empty):
+        """the rows of a reservoir state tuple (mc_reach.pyx:820-837) whose waterbody belongs to tailwater k"""
+        if len(tup[0]) == 0:
+            return empty
+        mine = net["owner"][np.searchsorted(ids, np.asarray(tup[0], dtype=np.int64))] == k
+        return tuple(np.asarray(a)[mine] for a in tup)
     results = []
     for k in range(len(tws)):
         lo, hi = int(bounds[k]), int(bounds[k + 1])
         if ngage:
             gk = np.flatnonzero((gage_row >= 0) & (gage_owner == k))                          # this network's gages
             gt = (np.asarray(gage_ids)[gk], np.asarray(lastobs_times)[gk], np.asarray(lastobs_values)[gk])
-        results.append((ids_o[lo:hi], fvd_o[lo:hi], 0, gt if ngage else no_gage, e5, e5, up_o[lo:hi], e3,
-                        nudge[gk] if ngage else no_nudge, e4))
+        results.append((ids_o[lo:hi], fvd_o[lo:hi], 0, gt if ngage else no_gage, state_of(k, r[4], e5), state_of(k, r[5], e5),
+                        up_o[lo:hi], state_of(k, r[7], e3), nudge[gk] if ngage else no_nudge, e4))
     return results, subnetwork_list
 
 

@@ -6,9 +6,14 @@ return of the reference's Cython function
 :811-845) and can be registered in the reference's ``_compute_func_map``
 (src/troute-routing/troute/routing/compute.py:21-26) -- see INTEGRATION.md.
 
-Implemented: the MC branch, streamflow nudging at gages (simple_da) and level-pool
-reservoir reaches (reach_type 1 with reservoir type 1).  Hybrid-persistence, RFC and
-Great Lakes reservoir data assimilation raise NotImplementedError.  All arithmetic
+Implemented: the MC branch, streamflow nudging at gages (simple_da), level-pool
+reservoir reaches (reach_type 1 with reservoir type 1) and reservoir data assimilation on
+top of the level pool: hybrid persistence (types 2 USGS, 3 USACE) and RFC series (types 4, 5 with
+``from_files=False``), mc_reach.pyx:548-710.  NotImplementedError: Great Lakes (type 6); types 4 / 5 with
+``from_files=True`` (the reference's Fortran RFC object reads its files itself); a type 2..5 waterbody on a
+``precision=64`` plan, or one that has no row in the matching ``reservoir_*_wbody_idx`` (the reference dies
+with an IndexError there).  A type-5 waterbody is looked up in the RFC tables like a type-4 one (the
+reference's loop looks the row up for type 4 only and reuses whatever row it looked up last).  All arithmetic
 runs in libtrmc.so on the GPU; there is no Python fallback.
 """
 import numpy as np
@@ -445,18 +450,40 @@ def compute_network_structured(
 
     # ---- level-pool reservoirs (mc_reach.pyx:283-356): one-node reaches of type 1 ----------------------
     res_rows, res_par, res_q0 = [], [], []
+    res_kind, res_trow = [], []     # data assimilation: reservoir type (0 = level pool only) and row in that type's table
     if any_res:
         wb = np.asarray(wbody_cols, dtype=np.float64)
         rtypes = np.asarray(reservoir_types)
+        da_index = {2: ("reservoir_usgs_wbody_idx", np.asarray(reservoir_usgs_wbody_idx).reshape(-1)),
+                    3: ("reservoir_usace_wbody_idx", np.asarray(reservoir_usace_wbody_idx).reshape(-1)),
+                    4: ("reservoir_rfc_wbody_idx", np.asarray(reservoir_rfc_wbody_idx).reshape(-1))}
+        da_index[5] = da_index[4]
         for reach, rt in reaches_wTypes:
             if rt != 1:
                 continue
             my_id = binary_find(data_idx, reach)[0]
             wbody_index = binary_find(lake_numbers_col, reach)[0]
-            if reservoir_type_specified and rtypes.size and int(rtypes[wbody_index][0]) != 1:
-                raise NotImplementedError(
-                    f"waterbody {reach[0]}: reservoir type {int(rtypes[wbody_index][0])} (hybrid persistence / RFC "
-                    "forecast / Great Lakes data assimilation) is outside this engine; level pool (type 1) only")
+            rtype = int(rtypes[wbody_index][0]) if reservoir_type_specified and rtypes.size else 1
+            kind, trow = 0, 0
+            if rtype != 1:
+                name, idx = da_index.get(rtype, (None, None))
+                hit = np.flatnonzero(idx == int(lake_numbers_col[wbody_index])) if idx is not None else np.zeros(0, np.int64)
+                if rtype in (4, 5) and from_files and hit.size:
+                    raise NotImplementedError(
+                        f"waterbody {reach[0]}: reservoir type {rtype} with from_files=True (the reference's RFC object reads its "
+                        "forecast files itself) is outside this engine; pass the series with from_files=False")
+                if hit.size == 0:
+                    raise NotImplementedError(
+                        f"waterbody {reach[0]}: reservoir type {rtype} "
+                        + ("(Great Lakes data assimilation) is outside this engine" if name is None else
+                           f"has no row in {name} (hybrid persistence / RFC forecast data assimilation needs its tables)"))
+                if precision != 32:
+                    raise NotImplementedError(
+                        f"waterbody {reach[0]}: reservoir type {rtype} on a precision 64 plan (the reference has no double-"
+                        "precision form of its reservoir data assimilation)")
+                kind, trow = rtype, int(hit[0])
+            res_kind.append(kind)
+            res_trow.append(trow)
             a = wb[wbody_index].astype(np.float32)     # levelpool.pyx:63-73: area max_depth orifice_area
             #   orifice_coefficient orifice_elevation weir_coefficient weir_elevation weir_length ifd (qd0) h0
             h0 = a[10]
@@ -552,6 +579,21 @@ def compute_network_structured(
                       bool(assume_short_ts), tuple(res_rows), engine, token=plan_token) as plan:
         if res_rows:
             plan.set_reservoirs(res_rows, np.asarray(res_par, dtype=dtype), dt)
+        res_da = any(res_kind)
+        if res_da:       # (per call, never kept with the plan: observations and state are the window's)
+            f32c, i32c = (lambda a: np.asarray(a, dtype=np.float32)), (lambda a: np.asarray(a, dtype=np.int32))
+            hyb = lambda obs, time, ut, prev, index, put: (     # noqa: E731
+                f32c(obs), f32c(time), np.stack([f32c(ut), f32c(prev), f32c(index), f32c(put)], axis=1))
+            plan.set_reservoir_da(
+                res_kind, res_trow,
+                hyb(reservoir_usgs_obs, reservoir_usgs_time, reservoir_usgs_update_time, reservoir_usgs_prev_persisted_flow,
+                    reservoir_usgs_persistence_index, reservoir_usgs_persistence_update_time) if 2 in res_kind else None,
+                hyb(reservoir_usace_obs, reservoir_usace_time, reservoir_usace_update_time, reservoir_usace_prev_persisted_flow,
+                    reservoir_usace_persistence_index, reservoir_usace_persistence_update_time) if 3 in res_kind else None,
+                (f32c(reservoir_rfc_obs), f32c(reservoir_rfc_update_time),
+                 np.stack([i32c(reservoir_rfc_timeseries_idx), i32c(reservoir_rfc_totalCounts), i32c(reservoir_rfc_use_forecast),
+                           i32c(reservoir_rfc_da_timestep), i32c(reservoir_rfc_persist_days)], axis=1))
+                if (4 in res_kind or 5 in res_kind) else None)
         plan.set_nan_is_zero(bool(nan_is_zero))
         plan.upload_forcing(nsteps, qlat_values, q0, boundary_fvd)
         if nudging is not None:
@@ -580,6 +622,7 @@ def compute_network_structured(
         if nudging is not None:
             nudge[nudging[4], 1:] = plan.download_nudge()
         res_inflow = plan.download_reservoir_inflow() if res_rows else None
+        da_state, da_tsidx = plan.download_reservoir_da() if res_da else (None, None)
         stats = plan.stats()
 
     out_dtype = np.float32 if precision == 32 else np.float64
@@ -596,6 +639,22 @@ def compute_network_structured(
     t_end = nsteps * dt
     f32 = lambda a: np.asarray(a, dtype="float32")  # noqa: E731
     i32 = lambda a: np.asarray(a, dtype="int32")  # noqa: E731
+    # the reservoir data-assimilation state the loop hands back (mc_reach.pyx:820-837): the caller's arrays, the rows of
+    # this network's reservoirs as the window left them
+    hyb_state = {k: [f32(a).copy() for a in arrs] for k, arrs in (
+        (2, (reservoir_usgs_update_time, reservoir_usgs_prev_persisted_flow, reservoir_usgs_persistence_index,
+             reservoir_usgs_persistence_update_time)),
+        (3, (reservoir_usace_update_time, reservoir_usace_prev_persisted_flow, reservoir_usace_persistence_index,
+             reservoir_usace_persistence_update_time)))}
+    rfc_ut, rfc_tsidx = f32(reservoir_rfc_update_time).copy(), i32(reservoir_rfc_timeseries_idx).copy()
+    if res_da:
+        t_end = float(np.float32(nsteps) * np.float32(dt))       # (a C float product in the loop)
+        for k, (kind, trow) in enumerate(zip(res_kind, res_trow)):
+            if kind in (2, 3):
+                for j in range(4):
+                    hyb_state[kind][j][trow] = da_state[k, j]
+            elif kind in (4, 5):
+                rfc_ut[trow], rfc_tsidx[trow] = da_state[k, 0], da_tsidx[k]
     result = (
         np.asarray(data_idx, dtype=np.intp)[fill_index_mask] if result_order is None else np.asarray(data_idx, dtype=np.intp)[result_order],
         flowveldepth,
@@ -607,23 +666,23 @@ def compute_network_structured(
         ),
         (
             i32(reservoir_usgs_wbody_idx),
-            f32(reservoir_usgs_update_time) - t_end,
-            f32(reservoir_usgs_prev_persisted_flow),
-            f32(reservoir_usgs_persistence_index),
-            f32(reservoir_usgs_persistence_update_time) - t_end,
+            hyb_state[2][0] - t_end,
+            hyb_state[2][1],
+            hyb_state[2][2],
+            hyb_state[2][3] - t_end,
         ),
         (
             i32(reservoir_usace_wbody_idx),
-            f32(reservoir_usace_update_time) - t_end,
-            f32(reservoir_usace_prev_persisted_flow),
-            f32(reservoir_usace_persistence_index),
-            f32(reservoir_usace_persistence_update_time) - t_end,
+            hyb_state[3][0] - t_end,
+            hyb_state[3][1],
+            hyb_state[3][2],
+            hyb_state[3][3] - t_end,
         ),
         upstream,
         (
             i32(reservoir_rfc_wbody_idx),
-            f32(reservoir_rfc_update_time) - t_end,
-            i32(reservoir_rfc_timeseries_idx),
+            rfc_ut - t_end,
+            rfc_tsidx,
         ),
         nudge,
         (
