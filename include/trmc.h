@@ -174,7 +174,7 @@ int trmc_plan_create_ex(int64_t nseg, const int64_t *up_ptr, const int64_t *up_i
  *                  would otherwise sit in (1.5 % of the rows of an unordered CONUS plan are in half of its wavefronts); those
  *                  blocks are the first of the launch.  0 = default (on when the in-block partition is), > 0 = on, < 0 = off.
  *   cluster_rows   (since ABI 18) > 0: a plan created with TRMC_PLAN_SHORT_TS on the level engine lays the rows BELOW its wide
- *                  levels out in clusters -- connected pieces of the network of at most so many rows (at most 128 = one workgroup)
+ *                  levels out in clusters -- connected pieces of the network of at most so many rows (at most 128)
  *                  -- and routes them wide_k steps per launch as well (k_mc_ctile: flows inside a cluster through LDS, a cluster
  *                  level one tile behind the one that feeds it) instead of one launch per timestep: what a STREAM of windows
  *                  needs (trmc_stream_*; there wide_min_rows may be small -- more levels in slices cost nothing).  0 (default):
@@ -308,7 +308,8 @@ int trmc_topology_levels_hinted(int64_t nseg, const int64_t *up_ptr, const int64
 
 /* Host-only (since ABI 18): the CLUSTER ORDER a short-timestep plan of the level engine is laid out in (trmc_plan_options.cluster_rows;
  * csrc/topology.hpp).  The leading levels of at least wide_min_rows rows (at most wide_max_levels of them) stay level slices; the
- * rows below them form clusters of at most cluster_rows rows, packed into blocks of one cluster level each.  lag_of_row[nseg]:
+ * rows below them form clusters of at most cluster_rows rows, packed into blocks of one cluster level each (here: of at most
+ * cluster_rows rows; a plan packs them up to the width of its kernel's workgroup, trmc_plan_cluster_blocks).  lag_of_row[nseg]:
  * tiles a row runs behind level 0 (-1 for boundary rows) -- a row only reads rows of its own block with its own lag, or rows
  * with a smaller one; block_of_row[nseg]: its cluster block, -1 in the slices.  Outputs may be NULL.
  * Reference analogue: build_subnetworks (nhd_network.py:691-771). */
@@ -344,6 +345,10 @@ int trmc_plan_info(const trmc_plan *plan, int64_t *nseg, int64_t *nseg_routed,
 /* A plan in cluster order (trmc_plan_options.cluster_rows): lag_of_row[nseg] = tiles every row runs behind the headwaters (-1:
  * boundary row), the number of levels kept as slices, the number of cluster levels.  Pointers may be NULL. */
 int trmc_plan_lags(const trmc_plan *plan, int32_t *lag_of_row, int32_t *wide_levels, int32_t *cluster_levels);
+/* ... and its cluster blocks: block_of_row[nseg] = the cluster block that routes the row (-1: a row of the slices, a boundary row)
+ * -- one workgroup of k_mc_ctile, whole clusters of one cluster level; *block_width = the most rows such a block holds (the
+ * workgroup's threads, a build-time constant of the library); *cluster_blocks = their number.  Pointers may be NULL. */
+int trmc_plan_cluster_blocks(const trmc_plan *plan, int32_t *block_of_row, int32_t *block_width, int32_t *cluster_blocks);
 /* level_of_row[nseg] (-1 for boundary rows); plan_pos_of_row[nseg] = position in
  * the level-major device order.  Either pointer may be NULL. */
 int trmc_plan_levels(const trmc_plan *plan, int32_t *level_of_row, int64_t *plan_pos_of_row);

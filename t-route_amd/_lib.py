@@ -130,6 +130,7 @@ SIGNATURES = {
     "trmc_plan_info": (_int, [_vp, _P(_i64), _P(_i64), _P(_i32), _P(_i32), _P(_i32)]),
     "trmc_plan_levels": (_int, [_vp, _vp, _vp]),
     "trmc_plan_lags": (_int, [_vp, _vp, _P(_i32), _P(_i32)]),
+    "trmc_plan_cluster_blocks": (_int, [_vp, _vp, _P(_i32), _P(_i32)]),
     "trmc_upload_forcing": (_int, [_vp, _int, _vp, _i64, _vp, _vp]),
     "trmc_upload_forcing_packed": (_int, [_vp, _int, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "trmc_set_boundary_flow_device": (_int, [_vp, _int, _vp]),
@@ -218,7 +219,7 @@ SIGNATURES_DW = {
 _LIB = None
 # entry points that never touch the HIP runtime (everything else may initialise it: single_hw_queue_per_priority must know)
 _HOST_ONLY = {"trmc_last_error", "trmc_abi_version", "trmc_topology_levels", "trmc_topology_levels_hinted", "trmc_topology_blocks", "trmc_topology_clusters",
-              "trmc_topology_blocks_general", "trmc_get_stats", "trmc_plan_info", "trmc_plan_levels", "trmc_plan_lags", "trmc_plan_engine",
+              "trmc_topology_blocks_general", "trmc_get_stats", "trmc_plan_info", "trmc_plan_levels", "trmc_plan_lags", "trmc_plan_cluster_blocks", "trmc_plan_engine",
               "trmc_plan_arithmetic", "trmc_stream_info", "trdw_last_error", "trdw_last_timing", "trdw_configure", "trmc_comm_info"}
 
 

@@ -45,7 +45,7 @@ int trmc_topology_clusters(int64_t nseg, const int64_t *up_ptr, const int64_t *u
                            int64_t *plan_pos_of_row, int32_t *lag_of_row, int32_t *block_of_row, int32_t *wide_levels,
                            int32_t *cluster_levels, int32_t *cluster_blocks)
 {
-    if (cluster_rows <= 0 || cluster_rows > kTileBlock) return fail(TRMC_EINVAL, "cluster_rows must be in [1, 128]");
+    if (cluster_rows <= 0 || cluster_rows > kClusterRowsMax) return fail(TRMC_EINVAL, "cluster_rows must be in [1, 128]");
     trmc::Topology t;
     std::string err;
     const int rc = trmc::build_topology(nseg, up_ptr, up_idx, boundary, t, err, cost_hint, 0, true, kWideMaxLevels, wide_min_rows,
@@ -238,7 +238,7 @@ int trmc_plan_create_opt(int64_t nseg, const int64_t *up_ptr, const int64_t *up_
         // (the cluster order is for plans whose windows follow each other as a stream, trmc_stream_*: a single window pays for the
         // clusters' skew with some thirty small launches at its end -- CONUS: 20.7 ms alone against 16.8 with one launch per
         // step -- so a plan only gets it when asked)
-        po.cluster_rows = o.cluster_rows > 0 ? std::min<int32_t>(o.cluster_rows, kTileBlock) : 0;
+        po.cluster_rows = o.cluster_rows > 0 ? std::min<int32_t>(o.cluster_rows, kClusterRowsMax) : 0;
         po.cluster_late_lag = std::max(0, o.cluster_late_lag);
         po.stream_split = std::max(0, o.stream_split);
         po.hot_wave_rows = std::max(0, std::min(64, o.hot_wave_rows));
@@ -282,7 +282,7 @@ int trmc_plan_create_opt(int64_t nseg, const int64_t *up_ptr, const int64_t *up_
     if (pl->flow && (flags & TRMC_PLAN_FULL_TS)) stem_min_rows = o.stem_min_rows < 0 ? 0 : (o.stem_min_rows > 0 ? o.stem_min_rows : 1024);
     const int trc = trmc::build_topology(nseg, up_ptr, up_idx, boundary, pl->topo, err, cost_hint, pl->flow ? kFlowBlock : 0, tiers,
                                          (tiers && !pl->flow) ? kWideMaxLevels : 0, wide_min_rows, wide_max_levels, stem_min_rows,
-                                         mid_min_rows, mid_max_levels, cluster_rows, pl->opt.cluster_late_lag);
+                                         mid_min_rows, mid_max_levels, cluster_rows, pl->opt.cluster_late_lag, kCtileBlock);
     if (trc) {
         delete pl;
         return fail(trc == -2 ? TRMC_ECYCLE : TRMC_EINVAL, err);
@@ -626,6 +626,22 @@ int trmc_plan_lags(const trmc_plan *pl, int32_t *lag_of_row, int32_t *wide_level
         lag_of_row[r] = t.level_of_row[r] < 0 ? -1 : t.lagk_of_pos[(size_t)t.pos_of_row[r]];
     if (wide_levels) *wide_levels = t.cl_from_level;
     if (cluster_levels) *cluster_levels = t.ncl;
+    return 0;
+}
+
+int trmc_plan_cluster_blocks(const trmc_plan *pl, int32_t *block_of_row, int32_t *block_width, int32_t *cluster_blocks)
+{
+    if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
+    const trmc::Topology &t = pl->topo;
+    if (t.cl_rows <= 0) return fail(TRMC_EINVAL, "the plan is not in cluster order (trmc_plan_options.cluster_rows)");
+    const int32_t nb = t.ncl > 0 ? (int32_t)t.cblk_ptr.size() - 1 : 0;
+    if (block_of_row) {
+        for (int64_t r = 0; r < pl->nseg; ++r) block_of_row[r] = -1;
+        for (int32_t b = 0; b < nb; ++b)
+            for (int32_t p = t.cblk_ptr[(size_t)b]; p < t.cblk_ptr[(size_t)b + 1]; ++p) block_of_row[t.row_of_pos[(size_t)p]] = b;
+    }
+    if (block_width) *block_width = kCtileBlock;
+    if (cluster_blocks) *cluster_blocks = nb;
     return 0;
 }
 

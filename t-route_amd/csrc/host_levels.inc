@@ -197,7 +197,7 @@ template <class T>
 inline void launch_ctile(hipStream_t st, const StepArgs<T> &a, const int32_t *cblk_ptr, int32_t b0, int32_t b1, int32_t tile, int32_t K,
                          bool tol)
 {
-    const dim3 grid((unsigned)(b1 - b0)), block(kTileBlock);
+    const dim3 grid((unsigned)(b1 - b0)), block(kCtileBlock);
     const bool dec = a.dec != nullptr;
     const bool lazy = a.v_every != 0 && !a.out;
     if constexpr (sizeof(T) == 4) {

@@ -6,7 +6,7 @@
 // above it by a whole tile -- affordable for the six levels that hold three quarters of the CONUS network, not for the 3 532
 // narrow ones below them, which until round 6 took one launch per timestep (k_mc_step: 288 launches that wait for each other,
 // thirteen columns re-read at every step, a transposing pass for their results).  The plan now lays those rows out in
-// CLUSTERS (topology.hpp, cluster_rows): connected pieces of the network of at most kTileBlock rows.  The rows of a cluster sit
+// CLUSTERS (topology.hpp, cluster_rows): connected pieces of the network of at most 128 rows.  The rows of a cluster sit
 // in ONE block and advance together: a flow that stays inside the cluster goes from thread to thread through LDS (two step
 // slots, one barrier per step), only a flow that ENTERS the cluster is read from the time-major plane -- and its row belongs to
 // a cluster level (or a slice) that runs at least one tile ahead, exactly k_mc_tile's argument.  A chain of the network climbs a
@@ -14,21 +14,39 @@
 // 18 + 6 + 29 - 1 launches of this kind instead of 23 + 288, and all of a row's work is k_mc_tile's: parameters and state in
 // registers, the forcing once per column, results staged in LDS and written as 96-byte runs of out[row][step][q,v,d].
 //
-// One block = one cluster block of the plan (cblk_ptr): up to kTileBlock rows of ONE cluster level -- a block's rows share
-// their lag, hence their steps: the barriers inside the time loop are uniform.  Threads take the block's rows by descending
-// cost class like k_mc_tile's (the LDS slots are indexed by POSITION, so it does not matter which thread routes a row); there
-// are no hot rows here -- a row routed by another block could not hand its flow over.
+// One block = one cluster block of the plan (cblk_ptr): whole clusters of ONE cluster level, up to kCtileBlock rows of them -- a
+// block's rows share their lag, hence their steps: the barriers inside the time loop are uniform.  Threads take the block's rows
+// by descending cost class like k_mc_tile's (the LDS slots are indexed by POSITION, so it does not matter which thread routes a
+// row); there are no hot rows here -- a row routed by another block could not hand its flow over.
 // Same bits as every other path: the same segment steps on the same inputs (tests run all of them against the oracle).
+//
+// kCtileBlock, the threads of a block, is the number of rows the class partition deals over wavefronts -- NOT the size of a
+// cluster (cluster_rows, at most kClusterRowsMax: what decides how many cluster levels a chain climbs).  A wavefront's step costs
+// what its costliest lane's does, and these rows are the big rivers: the partition puts a block's costly rows into its first
+// wavefronts, so the wider the block, the smaller the share of its wavefronts that a handful of costly rows spoil (the slices
+// have the hot list for that).  The plan packs whole clusters into blocks of this capacity (topology.hpp, cluster_block_rows).
+// Measured on the CONUS stream, ms per day, one run each on one box: 128: 13.42, 256: 12.88, 512: 12.75, 1024: 12.99 (the parent
+// commit beside them: 13.44); DESIGN.md section 7 has the interleaved A/B -- and what the counters say: the clusters issue 8 % fewer
+// instructions at 512, but most of the gain is k_mc_tile's, whose launches no longer share their first third with all of the
+// clusters' wavefronts (a launch of this kernel now lasts as long as the slices' beside it).  -DTRMC_CTILE_BLOCK=<width> builds another.
+#ifndef TRMC_CTILE_BLOCK
+#define TRMC_CTILE_BLOCK 512
+#endif
+constexpr int kCtileBlock = TRMC_CTILE_BLOCK;
+constexpr int kClusterRowsMax = 128; // the most rows of a cluster (trmc_plan_options.cluster_rows)
+static_assert(kCtileBlock % 64 == 0 && kCtileBlock >= kClusterRowsMax && kCtileBlock <= 1024,
+              "TRMC_CTILE_BLOCK: whole wavefronts, at least one cluster, at most one workgroup");
+constexpr int kCtileStage = kCtileBlock > 512 ? kTileStage / 2 : kTileStage; // (steps staged per run: fp64 rows of 1024 threads within a CU's LDS)
 template <class T, bool TOL, bool DEC, bool LAZYV, bool RDA> // (see mc_step_rows)
 __device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_t *__restrict__ cblk_ptr, int32_t cb0, int32_t tile, int32_t K);
 template <class T, bool TOL = false, bool DEC = false, bool LAZYV = false>
-__global__ void __launch_bounds__(kTileBlock, sizeof(T) == 4 ? (LAZYV ? TRMC_TILE_WAVES_LAZY : TRMC_TILE_WAVES) : 1)
+__global__ void __launch_bounds__(kCtileBlock, sizeof(T) == 4 ? (LAZYV ? TRMC_TILE_WAVES_LAZY : TRMC_TILE_WAVES) : 1)
 k_mc_ctile(const StepArgs<T> a, const int32_t *__restrict__ cblk_ptr, const int32_t cb0, const int32_t tile, const int32_t K)
 {
     mc_ctile_rows<T, TOL, DEC, LAZYV, false>(a, cblk_ptr, cb0, tile, K);
 }
 template <bool DEC>
-__global__ void __launch_bounds__(kTileBlock, TRMC_TILE_WAVES)
+__global__ void __launch_bounds__(kCtileBlock, TRMC_TILE_WAVES)
 k_mc_ctile_rda(const StepArgs<float> a, const int32_t *__restrict__ cblk_ptr, const int32_t cb0, const int32_t tile, const int32_t K)
 {
     mc_ctile_rows<float, false, DEC, false, true>(a, cblk_ptr, cb0, tile, K);
@@ -40,8 +58,9 @@ __device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_
     using M = typename DevMath<T, TOL>::type;
     const ColdArgs<StepArgs<T>> cold = cold_args<StepArgs<T>>();
     __shared__ uint64_t s_tab[TRMC_POW_TAB_WORDS];
-    __shared__ T s_out[3 * kTileStage * kTileBlock]; // [step slot * 3 + c][thread]
-    __shared__ T s_x[2 * kTileBlock];                // [step & 1][position in the block]: the flows the cluster hands on
+    // (an instance that stages nothing -- LAZYV without DEC: a stream whose callers take products only -- declares one element)
+    __shared__ T s_out[(DEC || !LAZYV) ? 3 * kCtileStage * kCtileBlock : 1]; // [step slot * 3 + c][thread]
+    __shared__ T s_x[2 * kCtileBlock];                // [step & 1][position in the block]: the flows the cluster hands on
     M m{stage_pow_tables(s_tab), false};
     m.sane = a.sane;
 
@@ -58,7 +77,7 @@ __device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_
         const int32_t c = active ? (int32_t)(a.cls_last[s] & 0x7f) : 0x80;
         const int32_t key = (c & 0x80) ? 8 : 7 - min(c, 7);
         bool none;
-        s = lo + block_partition_by_class<kTileBlock>(key, none);
+        s = lo + block_partition_by_class<kCtileBlock>(key, none);
         active = !none;
     }
     // issue priority by cost, as in k_mc_tile -- and never below 1: a cluster's rows wait for each other at every step
@@ -113,7 +132,7 @@ __device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_
     const bool count_cost = a.it_sum != nullptr;
     int32_t it_acc = 0, it_last = 0, staged = 0;
     bool over_last = false;
-    if (active) s_x[(size_t)((t_lo - 1) & 1) * kTileBlock + sl] = q_prev;
+    if (active) s_x[(size_t)((t_lo - 1) & 1) * kCtileBlock + sl] = q_prev;
     __syncthreads();
     T *q_up = q_tm + (size_t)(t_lo - 1) * np;
     const int32_t v_every = (LAZYV && DEC) ? cold->v_every : 0; // (see StepArgs and k_mc_tile)
@@ -133,7 +152,7 @@ __device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_
             }
             --ql_left;
             // junction sum in the reference's order (mc_reach.pyx:499-502), every term from where it lives
-            const T *const sx = s_x + (size_t)((t - 1) & 1) * kTileBlock;
+            const T *const sx = s_x + (size_t)((t - 1) & 1) * kCtileBlock;
             T qup = T(0);
             if (u.x >= 0) qup += in0 >= 0 ? at(sx, (uint32_t)in0) : at(q_up, (uint32_t)u.x * (uint32_t)sizeof(T));
             if (uy >= 0) qup += in1 >= 0 ? at(sx, (uint32_t)in1) : at(q_up, (uint32_t)uy * (uint32_t)sizeof(T));
@@ -193,7 +212,7 @@ __device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_
             }
             asm volatile("" : "+v"(ob));
             at(q_up + np, ob) = q_new;
-            s_x[(size_t)(t & 1) * kTileBlock + sl] = q_new;
+            s_x[(size_t)(t & 1) * kCtileBlock + sl] = q_new;
             if (t == t_hi) {
                 at(cold->d_tm + (size_t)slot * (size_t)cold->slot_tm + (size_t)t * np, ob) = d_new;
                 if (cold->seq_slots > 1 && t == cold->nsteps) { // the day ends: the next one starts from here
@@ -204,28 +223,28 @@ __device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_
             q_prev = q_new;
             d_prev = d_new;
             if (LAZYV && want_v && it_last > 0) v_new = trmc::step_velocity<T, M>(p, c, d_new, m); // (as k_mc_tile)
-            if (DEC || (!LAZYV && a.out)) { // stage (q, v, d) of step t; a run ends when kTileStage steps are staged and at the tile's last step
+            if (DEC || (!LAZYV && a.out)) { // stage (q, v, d) of step t; a run ends when kCtileStage steps are staged and at the tile's last step
                 // (a.out == nullptr: a stream of windows whose callers take products only -- nothing of the full result is assembled)
-                T *so = s_out + (size_t)(staged * 3) * kTileBlock + threadIdx.x;
+                T *so = s_out + (size_t)(staged * 3) * kCtileBlock + threadIdx.x;
                 so[0] = q_new;
-                so[kTileBlock] = v_new;
-                so[2 * kTileBlock] = d_new;
+                so[kCtileBlock] = v_new;
+                so[2 * kCtileBlock] = d_new;
                 ++staged;
-                if (staged == kTileStage || t == t_hi) {
+                if (staged == kCtileStage || t == t_hi) {
                     T *dst = out_row + (size_t)(t - staged) * 3;
                     const T *si = s_out + threadIdx.x;
                     if (LAZYV || !a.out) {
                     } else if (a.out_vec && (staged & 3) == 0) {
                         for (int j = 0; j < 3 * staged / 4; ++j) {
                             float4 v;
-                            v.x = (float)si[(4 * j + 0) * kTileBlock];
-                            v.y = (float)si[(4 * j + 1) * kTileBlock];
-                            v.z = (float)si[(4 * j + 2) * kTileBlock];
-                            v.w = (float)si[(4 * j + 3) * kTileBlock];
+                            v.x = (float)si[(4 * j + 0) * kCtileBlock];
+                            v.y = (float)si[(4 * j + 1) * kCtileBlock];
+                            v.z = (float)si[(4 * j + 2) * kCtileBlock];
+                            v.w = (float)si[(4 * j + 3) * kCtileBlock];
                             reinterpret_cast<float4 *>(dst)[j] = v;
                         }
                     } else {
-                        for (int32_t e = 0; e < 3 * staged; ++e) dst[e] = si[e * kTileBlock];
+                        for (int32_t e = 0; e < 3 * staged; ++e) dst[e] = si[e * kCtileBlock];
                     }
                     if constexpr (DEC) {
                         const int32_t ds = cold->dec_stride;
@@ -233,9 +252,9 @@ __device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_
                             if (k > cold->dec_keep) continue;
                             const int32_t kslot = k * ds - (t - staged) - 1;
                             T *dd = cold->dec + (size_t)slot * (size_t)cold->slot_dec + ((size_t)cold->row_of_pos[su] * (size_t)cold->dec_keep + (size_t)(k - 1)) * 3;
-                            dd[0] = si[(kslot * 3 + 0) * kTileBlock];
-                            dd[1] = si[(kslot * 3 + 1) * kTileBlock];
-                            dd[2] = si[(kslot * 3 + 2) * kTileBlock];
+                            dd[0] = si[(kslot * 3 + 0) * kCtileBlock];
+                            dd[1] = si[(kslot * 3 + 1) * kCtileBlock];
+                            dd[2] = si[(kslot * 3 + 2) * kCtileBlock];
                         }
                     }
                     staged = 0;

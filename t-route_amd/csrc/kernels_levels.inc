@@ -358,7 +358,8 @@ __device__ __forceinline__ void mc_tile_rows(const StepArgs<T> &a, const int32_t
     using M = typename DevMath<T, TOL>::type;
     const ColdArgs<StepArgs<T>> cold = cold_args<StepArgs<T>>(); // (see cold_args: what the loop rarely needs is not kept in registers)
     __shared__ uint64_t s_tab[TRMC_POW_TAB_WORDS];
-    __shared__ T s_out[3 * kTileStage * kTileBlock]; // [step slot * 3 + c][thread]
+    // (an instance that stages nothing -- LAZYV without DEC: a stream whose callers take products only -- declares one element)
+    __shared__ T s_out[(DEC || !LAZYV) ? 3 * kTileStage * kTileBlock : 1]; // [step slot * 3 + c][thread]
     M m{stage_pow_tables(s_tab), false};
     m.sane = a.sane;
 

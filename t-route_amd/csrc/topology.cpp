@@ -13,7 +13,8 @@ namespace trmc {
 int build_topology(int64_t nseg, const int64_t *up_ptr, const int64_t *up_idx,
                    const uint8_t *boundary, Topology &t, std::string &err, const uint8_t *cost_hint, int32_t block_rows,
                    bool cost_tiers, int32_t boundary_floor, int64_t wide_min_rows, int32_t wide_max_levels, int32_t stem_min_rows,
-                   int64_t mid_min_rows, int32_t mid_max_levels, int32_t cluster_rows, int32_t cluster_late_lag)
+                   int64_t mid_min_rows, int32_t mid_max_levels, int32_t cluster_rows, int32_t cluster_late_lag,
+                   int32_t cluster_block_rows)
 {
     if (nseg < 0 || nseg >= std::numeric_limits<int32_t>::max()) {
         err = "nseg out of range";
@@ -505,6 +506,7 @@ int build_topology(int64_t nseg, const int64_t *up_ptr, const int64_t *up_idx,
         t.lagk_of_pos.assign(nseg, 0);
         if (W < t.nlevels) {
             const int32_t B = cluster_rows;
+            const int32_t BB = std::max(cluster_rows, cluster_block_rows); // rows a cluster BLOCK holds: whole clusters of one level
             // cluster level and cluster of every row below the slices, in Kahn order (`queue`: every row after the rows
             // draining into it)
             std::vector<int32_t> cl(nseg, -1), root(nseg), size(nseg, 1);
@@ -594,12 +596,13 @@ int build_topology(int64_t nseg, const int64_t *up_ptr, const int64_t *up_idx,
                 });
                 bins.clear();
                 fill.clear();
-                // best fit: the fullest block that still takes the cluster (by_free[f]: blocks with f rows free)
-                std::vector<std::vector<int32_t>> by_free((size_t)B + 1);
+                // best fit: the fullest block that still takes the cluster (by_free[f]: blocks with f rows free) -- first of all;
+                // the cost order above only decides among clusters, so the blocks of a level fill up
+                std::vector<std::vector<int32_t>> by_free((size_t)BB + 1);
                 for (const int32_t k : cs) {
                     const int32_t n = (int32_t)members[(size_t)k].size();
                     int32_t b = -1;
-                    for (int32_t f = n; f <= B && b < 0; ++f)
+                    for (int32_t f = n; f <= BB && b < 0; ++f)
                         if (!by_free[(size_t)f].empty()) {
                             b = by_free[(size_t)f].back();
                             by_free[(size_t)f].pop_back();
@@ -611,7 +614,7 @@ int build_topology(int64_t nseg, const int64_t *up_ptr, const int64_t *up_idx,
                     }
                     bins[(size_t)b].push_back(k);
                     fill[(size_t)b] += n;
-                    by_free[(size_t)(B - fill[(size_t)b])].push_back(b);
+                    by_free[(size_t)(BB - fill[(size_t)b])].push_back(b);
                 }
                 t.cblk_of_cl[(size_t)c] = (int32_t)t.cblk_ptr.size();
                 for (const auto &bin : bins) {
@@ -637,6 +640,7 @@ int build_topology(int64_t nseg, const int64_t *up_ptr, const int64_t *up_idx,
         for (int32_t l = 0; l < W; ++l)
             for (int32_t q = t.lvl_ptr[l]; q < t.lvl_ptr[l + 1]; ++q) t.lagk_of_pos[q] = l;
         t.cl_rows = cluster_rows;
+        t.cblk_rows = std::max(cluster_rows, cluster_block_rows);
         t.cl_from_level = W;
     } else
     // the rows below the leading wide levels: by descending cost across levels (topology.hpp, wide_min_rows)

@@ -46,7 +46,8 @@ struct Topology {
                                          // (the general mode starts them FIRST, see build_topology)
     // CLUSTER ORDER of the rows below the leading wide levels (build_topology with cluster_rows > 0; a short-timestep plan of
     // the level engine only): see below
-    int32_t cl_rows = 0;                 // 0: none; else the most rows a cluster block holds
+    int32_t cl_rows = 0;                 // 0: none; else the most rows a cluster holds
+    int32_t cblk_rows = 0;               // ... and the most rows a cluster block holds (whole clusters of one cluster level)
     int32_t cl_from_level = 0;           // W: the levels below it are level slices, the rows of the deeper ones are in clusters
     int32_t ncl = 0;                     // cluster levels: cluster level c runs W + c tiles behind level 0
     std::vector<int32_t> cblk_ptr;       // [ncblk + 1] plan positions: cluster block b holds [cblk_ptr[b], cblk_ptr[b + 1])
@@ -107,9 +108,11 @@ struct Topology {
 // it; else m = the highest cluster level among the rows draining into it, if the clusters of that level among them and the
 // row itself fit into one cluster (they are merged); else m + 1 (a new cluster).  A chain of the network therefore climbs one
 // cluster level per cluster_rows rows it collects, not one per row: the 3 538 levels of the synthetic CONUS network become
-// 6 slices + 29 cluster levels of 128 rows.  Clusters of one level are packed into blocks of at most cluster_rows rows (by
-// descending cost hint, so that a block holds clusters of one cost), blocks are ordered by cluster level: a launch takes a
-// contiguous range of them.  cluster_late_lag > 0: a row fed by a boundary row (or marked late) runs at least so many tiles
+// 6 slices + 29 cluster levels of 128 rows.  Whole clusters of one level are packed into blocks of at most cluster_block_rows rows
+// (0: cluster_rows; the plan passes the width of k_mc_ctile's workgroup, which deals a block's rows over its wavefronts by cost
+// class -- the size of a cluster decides the lags, the size of a block only who shares a workgroup): the costliest clusters
+// first, each into the fullest block that still takes it, so the blocks of a level fill up; blocks are ordered by cluster
+// level: a launch takes a contiguous range of them.  cluster_late_lag > 0: a row fed by a boundary row (or marked late) runs at least so many tiles
 // behind level 0 -- the trunk of a cut basin, whose inflows from other GPUs arrive a day or two after they were routed
 // (troute_amd.sequence).  Results do not depend on it.  Reference analogue: build_subnetworks (nhd_network.py:691-771) --
 // there sub-networks of 10 000 segments handed from one order to the next by the host, here of 128 rows pipelined in time.
@@ -117,6 +120,6 @@ int build_topology(int64_t nseg, const int64_t *up_ptr, const int64_t *up_idx,
                    const uint8_t *boundary, Topology &topo, std::string &err, const uint8_t *cost_hint = nullptr,
                    int32_t block_rows = 0, bool cost_tiers = true, int32_t boundary_floor = 0, int64_t wide_min_rows = 0,
                    int32_t wide_max_levels = 0, int32_t stem_min_rows = 0, int64_t mid_min_rows = 0, int32_t mid_max_levels = 0,
-                   int32_t cluster_rows = 0, int32_t cluster_late_lag = 0);
+                   int32_t cluster_rows = 0, int32_t cluster_late_lag = 0, int32_t cluster_block_rows = 0);
 
 } // namespace trmc

@@ -185,6 +185,14 @@ class RoutingPlan:
         _lib.check(_lib.lib().trmc_plan_lags(self._h, _lib.ptr(lag), C.byref(w), C.byref(c)))
         return lag, w.value, c.value
 
+    def cluster_blocks(self):
+        """A plan in cluster order: (the cluster block that routes every row [-1: a row of the slices, a boundary row], the most
+        rows a block holds, the number of blocks) -- include/trmc.h, trmc_plan_cluster_blocks."""
+        blk = np.empty(self.nseg, dtype=np.int32)
+        w, nb = C.c_int32(0), C.c_int32(0)
+        _lib.check(_lib.lib().trmc_plan_cluster_blocks(self._h, _lib.ptr(blk), C.byref(w), C.byref(nb)))
+        return blk, w.value, nb.value
+
     def stats(self):
         s = _lib.Stats()
         _lib.check(_lib.lib().trmc_get_stats(self._h, C.byref(s)))
