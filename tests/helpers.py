@@ -114,6 +114,44 @@ def reaches_from_to(to):
     return reaches, heads_up, ups
 
 
+# (short, engine) of the LowerColorado table tests: set_engine below
+TABLE_ENGINES = [(True, None), (False, None), (True, "levels"), (True, "levels-wide"), (True, "levels-mid"), (True, "levels-clusters"),
+                 (True, "levels-slices+clusters")]
+
+
+def set_engine(engine, monkeypatch):
+    """The engine parametrisation of the LowerColorado table tests (test_reservoirs, test_nudging, test_reservoir_da_network):
+    None = the default (the dataflow kernels at this size); "levels" = k_mc_step; "levels-wide" = the level engine with its wide
+    levels several steps per launch under a level skew (k_mc_tile); "levels-mid" = the same with a second tier below the wide
+    levels, fewer steps per launch under its own skew (k_mc_tile twice, then k_mc_step); "levels-clusters" = a plan in cluster
+    order without slices: every row a cluster row of k_mc_ctile, clusters of 24 rows, 7 steps per launch (288 = 41 x 7 + 1: the
+    last tile is short); "levels-slices+clusters" = the same below leading levels of at least 32 rows, which k_mc_tile routes
+    as slices with the cluster order's lags for levels.  Returns True for the engines in cluster order: their windows report
+    every routed row as routed in tiles (cluster_stats)."""
+    if not engine:
+        return False
+    monkeypatch.setenv("TRMC_ENGINE", "levels")
+    monkeypatch.setenv("TRMC_PLAN_CACHE", "0")
+    monkeypatch.setenv("TRMC_WIDE_K", "7")
+    if engine in ("levels-clusters", "levels-slices+clusters"):
+        monkeypatch.setenv("TRMC_CLUSTER_ROWS", "24")
+        monkeypatch.setenv("TRMC_WIDE_MIN_ROWS", "0" if engine == "levels-clusters" else "32")
+        return True
+    assert engine in ("levels", "levels-wide", "levels-mid"), engine
+    monkeypatch.setenv("TRMC_WIDE_MIN_ROWS", "0" if engine == "levels" else ("64" if engine.endswith("mid") else "32"))
+    monkeypatch.setenv("TRMC_MID_MIN_ROWS", "8" if engine.endswith("mid") else "0")
+    monkeypatch.setenv("TRMC_MID_K", "3")
+    return False
+
+
+def cluster_stats(stats, engine, nts):
+    """A window on a plan in cluster order: no row took a one-step launch -- the window's stats count every routed row's
+    every step as routed in tiles, which the library reports only when the cluster tiles ran (csrc/host_levels.inc,
+    route_end_t) -- and the slices exist exactly where the engine asks for them."""
+    assert stats["wide_segment_steps"] == stats["nseg_routed"] * nts, stats
+    assert (stats["wide_levels"] > 0) == (engine == "levels-slices+clusters"), stats
+
+
 def flow_engine(precision=32):
     """True when plans of this precision run on the dataflow engine (k_mc_flow), False on the level engine."""
     import os

@@ -87,18 +87,11 @@ def gaged_lowercolorado(ngage=60, gmax=200, seed=8):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("short,engine", [(True, None), (False, None), (True, "levels"), (True, "levels-wide"), (True, "levels-mid")])
+@pytest.mark.parametrize("short,engine", H.TABLE_ENGINES)
 def test_gpu_nudging_bit_identical_to_oracle(short, engine, monkeypatch):
-    """engine: None = the default (dataflow engine at this size); "levels" = k_mc_step; "levels-wide" = the level engine with
-    its wide levels several steps per launch under a level skew (k_mc_tile); "levels-mid" = the same with a second tier
-    below the wide levels, fewer steps per launch under its own skew"""
-    if engine:
-        monkeypatch.setenv("TRMC_ENGINE", "levels")
-        monkeypatch.setenv("TRMC_PLAN_CACHE", "0")
-        monkeypatch.setenv("TRMC_WIDE_MIN_ROWS", "0" if engine == "levels" else ("64" if engine.endswith("mid") else "32"))
-        monkeypatch.setenv("TRMC_WIDE_K", "7")
-        monkeypatch.setenv("TRMC_MID_MIN_ROWS", "8" if engine.endswith("mid") else "0")
-        monkeypatch.setenv("TRMC_MID_K", "3")
+    """engine: helpers.set_engine -- the dataflow engine, k_mc_step, k_mc_tile in one and two tiers, and the plans in cluster order
+    (k_mc_ctile's nudging epilogue, with and without slices above the clusters)"""
+    clusters = H.set_engine(engine, monkeypatch)
     from troute_amd.routing.fast_reach.mc_reach import compute_network_structured, mc_only_args
     lc, reaches, net, gage_ids, upos, upr, upg, usgs, lv0, lt0 = gaged_lowercolorado()
     decay = 120.0
@@ -106,7 +99,9 @@ def test_gpu_nudging_bit_identical_to_oracle(short, engine, monkeypatch):
                         assume_short_ts=short)
     args[16], args[17], args[18], args[19] = usgs, upos, upr, upg
     args[20], args[21], args[22] = lv0, lt0, decay
-    r = compute_network_structured(*args)
+    r = compute_network_structured(*args, return_stats=True)
+    if clusters:
+        H.cluster_stats(r[-1], engine, lc.nts)
     fvd = r[1].reshape(lc.nseg, lc.nts, 3)
 
     row = {int(s): i for i, s in enumerate(lc.ids)}

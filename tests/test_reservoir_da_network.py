@@ -12,19 +12,7 @@ import test_reservoirs as TR
 NET = np.load(os.path.join(H.GOLDEN, "reservoir_da_network.npz"))
 NET_GENERAL = np.load(os.path.join(H.GOLDEN, "reservoir_da_network_general.npz"))
 NTS = int(NET["nts"])
-ENGINES = [(True, None), (False, None), (True, "levels"), (True, "levels-wide"), (True, "levels-mid")]
-
-
-def set_engine(engine, monkeypatch):
-    """the engine parametrisation of test_reservoirs.test_gpu_reservoirs_bit_identical_to_oracle: None = the default (the
-    dataflow kernels), "levels" = k_mc_step, "levels-wide" = k_mc_tile, "levels-mid" = k_mc_tile in two tiers / k_mc_ctile"""
-    if engine:
-        monkeypatch.setenv("TRMC_ENGINE", "levels")
-        monkeypatch.setenv("TRMC_PLAN_CACHE", "0")
-        monkeypatch.setenv("TRMC_WIDE_MIN_ROWS", "0" if engine == "levels" else ("64" if engine.endswith("mid") else "32"))
-        monkeypatch.setenv("TRMC_WIDE_K", "7")
-        monkeypatch.setenv("TRMC_MID_MIN_ROWS", "8" if engine.endswith("mid") else "0")
-        monkeypatch.setenv("TRMC_MID_K", "3")
+ENGINES = H.TABLE_ENGINES          # (helpers.set_engine: what each of them routes the window with)
 
 
 def golden(short, key):
@@ -100,10 +88,12 @@ def check_state(r, short):
 @pytest.mark.gpu
 @pytest.mark.parametrize("short,engine", ENGINES)
 def test_gpu_reservoir_da_bit_identical_to_reference_loop(short, engine, monkeypatch):
-    set_engine(engine, monkeypatch)
+    clusters = H.set_engine(engine, monkeypatch)
     from troute_amd.routing.fast_reach.mc_reach import compute_network_structured
     c = da_case(NTS, short)
-    r = compute_network_structured(*da_args(c), from_files=False)
+    r = compute_network_structured(*da_args(c), from_files=False, return_stats=True)
+    if clusters:
+        H.cluster_stats(r[-1], engine, NTS)
     check_against_golden(r, short)
     check_state(r, short)
     assert set(NET["types"].tolist()) == {1, 2, 3, 4, 5}
@@ -125,16 +115,19 @@ def test_gpu_empty_tables_and_demoted_types_equal_level_pool(short):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("short,engine", [(True, None), (False, None), (True, "levels-mid")])
+@pytest.mark.parametrize("short,engine", [(True, None), (False, None), (True, "levels-mid"), (True, "levels-clusters"),
+                                          (True, "levels-slices+clusters")])
 def test_gpu_two_windows_equal_one_long_window(short, engine, monkeypatch):
     """the reference's run-set loop: window 2 starts from window 1's last column (new_q0), its final pool elevations and the
     state tuples it returned, with the observation times counted from the new start -- and lands on the one long window"""
-    set_engine(engine, monkeypatch)
+    clusters = H.set_engine(engine, monkeypatch)
     from troute_amd.routing.fast_reach.mc_reach import compute_network_structured
     half = NTS // 2
     c = da_case(half, short)
     lc, ids, dv, ql, q0, reaches, net, lakes, wbody_cols, lakeset, _ = c["case"]
-    r1 = compute_network_structured(*da_args(c), from_files=False)
+    r1 = compute_network_structured(*da_args(c), from_files=False, return_stats=True)
+    if clusters:
+        H.cluster_stats(r1[-1], engine, half)
     check_against_golden(r1, short, 0, half)
     n = len(ids)
     last = r1[1].reshape(n, half, 3)[:, -1]
@@ -148,7 +141,9 @@ def test_gpu_two_windows_equal_one_long_window(short, engine, monkeypatch):
     assert half % lc.qts == 0
     ql2 = ql[:, half // lc.qts:]
     t2 = tables(t_shift=half * lc.dt, state=(r1[4], r1[5], r1[7]))
-    r2 = compute_network_structured(*da_args(c2, tables_=t2, q0=q0_2, ql=ql2), from_files=False)
+    r2 = compute_network_structured(*da_args(c2, tables_=t2, q0=q0_2, ql=ql2), from_files=False, return_stats=True)
+    if clusters:
+        H.cluster_stats(r2[-1], engine, half)
     check_against_golden(r2, short, half, NTS)
     check_state(r2, short)
 

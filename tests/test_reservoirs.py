@@ -121,18 +121,11 @@ def reservoir_case(nts=288):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("short,engine", [(True, None), (False, None), (True, "levels"), (True, "levels-wide"), (True, "levels-mid")])
+@pytest.mark.parametrize("short,engine", H.TABLE_ENGINES)
 def test_gpu_reservoirs_bit_identical_to_oracle(short, engine, monkeypatch):
-    """engine: None = the default (dataflow engine at this size); "levels" = k_mc_step; "levels-wide" = the level engine with
-    its wide levels several steps per launch under a level skew (k_mc_tile); "levels-mid" = the same with a second tier
-    below the wide levels, fewer steps per launch under its own skew"""
-    if engine:
-        monkeypatch.setenv("TRMC_ENGINE", "levels")
-        monkeypatch.setenv("TRMC_PLAN_CACHE", "0")
-        monkeypatch.setenv("TRMC_WIDE_MIN_ROWS", "0" if engine == "levels" else ("64" if engine.endswith("mid") else "32"))
-        monkeypatch.setenv("TRMC_WIDE_K", "7")
-        monkeypatch.setenv("TRMC_MID_MIN_ROWS", "8" if engine.endswith("mid") else "0")
-        monkeypatch.setenv("TRMC_MID_K", "3")
+    """engine: helpers.set_engine -- the dataflow engine, k_mc_step, k_mc_tile in one and two tiers, and the plans in cluster order
+    (k_mc_ctile's reservoir branch, with and without slices above the clusters)"""
+    clusters = H.set_engine(engine, monkeypatch)
     from troute_amd.routing.fast_reach.mc_reach import compute_network_structured, mc_only_args
     lc, ids, dv, ql, q0, reaches, net, lakes, wbody_cols, lakeset, nts = reservoir_case()
     args = mc_only_args(nts, lc.dt, lc.qts, reaches, net, ids, lc.data_cols, dv, q0, ql, assume_short_ts=short)
@@ -141,7 +134,9 @@ def test_gpu_reservoirs_bit_identical_to_oracle(short, engine, monkeypatch):
     args[11] = wbody_cols
     args[13] = np.ones((len(lakes), 1), np.int32)
     args[14] = False
-    r = compute_network_structured(*args)
+    r = compute_network_structured(*args, return_stats=True)
+    if clusters:
+        H.cluster_stats(r[-1], engine, nts)
     fvd = r[1].reshape(len(ids), nts, 3)
 
     row = {int(s): i for i, s in enumerate(ids)}
