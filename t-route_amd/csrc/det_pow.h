@@ -102,6 +102,25 @@ TRMC_DP_FN float trmc_sp_from_bits(uint32_t u)
     return x;
 }
 
+/* A double constant of the two polynomials.  On the device the value is formed in scalar registers at the place of its use
+ * (two s_mov_b32: no vector instruction): left to itself the compiler keeps every one of them in a register pair of its own
+ * for the whole of a kernel's time loop -- twenty-eight scalar registers in the tile kernels, which then park the lane masks
+ * and address parts of the loop in lanes of a vector register and read them back at every step (v_readlane / v_writelane:
+ * vector instructions, what those kernels are bound by).  The value is the literal's, bit for bit; only where it comes from
+ * changes.  (A constant that shares its fused multiply-add with another one stays a literal: the instruction reads one
+ * scalar operand, the second would be moved into vector registers at every use.) */
+#if defined(__HIP_DEVICE_COMPILE__)
+template <uint64_t BITS> __device__ __forceinline__ double trmc_dp_scalar_const()
+{
+    uint32_t lo, hi;
+    asm volatile("s_mov_b32 %0, %2\n\ts_mov_b32 %1, %3" : "=s"(lo), "=s"(hi) : "i"((uint32_t)BITS), "i"((uint32_t)(BITS >> 32)));
+    return __hiloint2double((int)hi, (int)lo);
+}
+#define TRMC_DP_K(x) trmc_dp_scalar_const<__builtin_bit_cast(uint64_t, (double)(x))>()
+#else
+#define TRMC_DP_K(x) (x)
+#endif
+
 /* 2**(k/32) with the exponent of k added in: the double whose bits are  t + (ki << 47)  (glibc: `t += ki << 47`).  The
  * shifted term has no bits below 2**47, so the sum is an addition into the HIGH word alone; on the device that is ONE
  * 32-bit shift-add (the compiler makes a shift, a move and a 64-bit add of the plain form). */
@@ -140,10 +159,10 @@ TRMC_DP_FN double trmc_det_log2(float x, const uint64_t *tab)
     const double r = __builtin_fma(z, invc, -1.0);
     const double y0 = logc + (double)k;
     const double r2 = r * r;
-    double y = __builtin_fma(0x1.27616c9496e0bp-2, r, -0x1.71969a075c67ap-2);
-    const double p = __builtin_fma(0x1.ec70a6ca7baddp-2, r, -0x1.7154748bef6c8p-1);
+    double y = __builtin_fma(TRMC_DP_K(0x1.27616c9496e0bp-2), r, -0x1.71969a075c67ap-2);
+    const double p = __builtin_fma(TRMC_DP_K(0x1.ec70a6ca7baddp-2), r, -0x1.7154748bef6c8p-1);
     const double r4 = r2 * r2;
-    double q = __builtin_fma(0x1.71547652ab82bp0, r, y0);
+    double q = __builtin_fma(TRMC_DP_K(0x1.71547652ab82bp0), r, y0);
     q = __builtin_fma(p, r2, q);
     y = __builtin_fma(y, r4, q);
     return y;
@@ -153,19 +172,19 @@ TRMC_DP_FN double trmc_det_log2(float x, const uint64_t *tab)
 TRMC_DP_FN float trmc_det_powf_from_log(double L, float y, const uint64_t *tab)
 {
     const double ylogx = (double)y * L;
-    if (!(__builtin_fabs(ylogx) < 126.0)) { /* one test on the common path; the three cases of e_powf.c behind it */
+    if (!(__builtin_fabs(ylogx) < TRMC_DP_K(126.0))) { /* one test on the common path; the three cases of e_powf.c behind it */
         if (ylogx != ylogx) return trmc_sp_from_bits(0x7fc00000u);
-        if (ylogx > 0x1.fffffffd1d571p+6) return trmc_sp_from_bits(0x7f800000u); /* overflow */
-        if (ylogx <= -150.0) return 0.0f;                                        /* underflow */
+        if (ylogx > TRMC_DP_K(0x1.fffffffd1d571p+6)) return trmc_sp_from_bits(0x7f800000u); /* overflow */
+        if (ylogx <= TRMC_DP_K(-150.0)) return 0.0f;                                        /* underflow */
     }
-    double kd = ylogx + 0x1.8p+47;            /* round to a multiple of 1/32 */
+    double kd = ylogx + TRMC_DP_K(0x1.8p+47);            /* round to a multiple of 1/32 */
     const uint64_t ki = trmc_dp_bits(kd);
-    kd -= 0x1.8p+47;
+    kd -= TRMC_DP_K(0x1.8p+47);
     const double r = ylogx - kd;
     const double s = trmc_dp_exp2_scale(tab[32 + (ki & 31u)], ki);
-    const double z = __builtin_fma(0x1.c6af84b912394p-5, r, 0x1.ebfce50fac4f3p-3);
+    const double z = __builtin_fma(TRMC_DP_K(0x1.c6af84b912394p-5), r, 0x1.ebfce50fac4f3p-3);
     const double r2 = r * r;
-    double w = __builtin_fma(0x1.62e42ff0c52d6p-1, r, 1.0);
+    double w = __builtin_fma(TRMC_DP_K(0x1.62e42ff0c52d6p-1), r, 1.0);
     w = __builtin_fma(z, r2, w);
     w = w * s;
     return (float)w;
@@ -191,10 +210,10 @@ TRMC_DP_FN double trmc_det_log2_normal(float x, const uint64_t *tab)
     const double r = __builtin_fma(z, invc, -1.0);
     const double y0 = logc + (double)k;
     const double r2 = r * r;
-    double y = __builtin_fma(0x1.27616c9496e0bp-2, r, -0x1.71969a075c67ap-2);
-    const double p = __builtin_fma(0x1.ec70a6ca7baddp-2, r, -0x1.7154748bef6c8p-1);
+    double y = __builtin_fma(TRMC_DP_K(0x1.27616c9496e0bp-2), r, -0x1.71969a075c67ap-2);
+    const double p = __builtin_fma(TRMC_DP_K(0x1.ec70a6ca7baddp-2), r, -0x1.7154748bef6c8p-1);
     const double r4 = r2 * r2;
-    double q = __builtin_fma(0x1.71547652ab82bp0, r, y0);
+    double q = __builtin_fma(TRMC_DP_K(0x1.71547652ab82bp0), r, y0);
     q = __builtin_fma(p, r2, q);
     y = __builtin_fma(y, r4, q);
     return y;
@@ -202,14 +221,14 @@ TRMC_DP_FN double trmc_det_log2_normal(float x, const uint64_t *tab)
 TRMC_DP_FN float trmc_det_powf_from_log_inrange(double L, float y, const uint64_t *tab)
 {
     const double ylogx = (double)y * L;
-    double kd = ylogx + 0x1.8p+47;
+    double kd = ylogx + TRMC_DP_K(0x1.8p+47);
     const uint64_t ki = trmc_dp_bits(kd);
-    kd -= 0x1.8p+47;
+    kd -= TRMC_DP_K(0x1.8p+47);
     const double r = ylogx - kd;
     const double s = trmc_dp_exp2_scale(tab[32 + (ki & 31u)], ki);
-    const double z = __builtin_fma(0x1.c6af84b912394p-5, r, 0x1.ebfce50fac4f3p-3);
+    const double z = __builtin_fma(TRMC_DP_K(0x1.c6af84b912394p-5), r, 0x1.ebfce50fac4f3p-3);
     const double r2 = r * r;
-    double w = __builtin_fma(0x1.62e42ff0c52d6p-1, r, 1.0);
+    double w = __builtin_fma(TRMC_DP_K(0x1.62e42ff0c52d6p-1), r, 1.0);
     w = __builtin_fma(z, r2, w);
     w = w * s;
     return (float)w;
