@@ -236,8 +236,8 @@ int trmc_plan_create_opt(int64_t nseg, const int64_t *up_ptr, const int64_t *up_
 /* A STREAM OF WINDOWS on one plan (since ABI 18; csrc/stream.inc): the reference's run-set loop -- compute_nhd_routing_v02 per run
  * set, every call with that window's qlat_values (mc_reach.pyx:173,:723), new_q0 between them (AbstractNetwork.py:177-191; loop
  * nwm_routing/__main__.py:195-333) -- as ONE sequence of tile launches whose tile index runs on over the days.  assume_short_ts
- * only; the plan must be in cluster order (TRMC_PLAN_SHORT_TS on the level engine, cluster_rows >= 0), without reservoirs,
- * nudging tables or lagged rows.  Every launch routes every row through the next wide_k steps of ITS place in the stream (a row
+ * only; the plan must be in cluster order (TRMC_PLAN_SHORT_TS on the level engine, cluster_rows >= 0), without lagged rows
+ * (level-pool reservoirs and gages: see trmc_stream_set_gages below).  Every launch routes every row through the next wide_k steps of ITS place in the stream (a row
  * `lag` tiles behind the headwaters works on an earlier tile, possibly of the day before): nsteps / wide_k launches per day, no
  * launches that only part of the network has work in, nothing between two days.  Results are the bits of the same days routed
  * one by one.
@@ -264,6 +264,45 @@ int trmc_plan_create_opt(int64_t nseg, const int64_t *up_ptr, const int64_t *up_
 int trmc_stream_begin(trmc_plan *plan, int nsteps, int qts_subdivisions, int slots, int full_output, int output_stride);
 int trmc_stream_push(trmc_plan *plan, const void *qlat, int64_t nq, const void *boundary_q_dev, int32_t rowset, void *hyd_host,
                      void *q0_host, void *fvd_host);
+/* A stream on a plan with LEVEL-POOL RESERVOIRS and GAGES (additions within ABI 19; csrc/stream.inc).  trmc_set_reservoirs before
+ * trmc_stream_begin puts the plan's waterbodies into the stream: a reservoir row keeps its water elevation in the depth slot and
+ * hands it from day to day like any depth; TRMC_ESTATE while a stream is in progress.  A plan whose staged window has reservoir
+ * data-assimilation tables (trmc_set_reservoir_da, types 2-5) is refused by trmc_stream_begin: those are routed window by window.
+ *   trmc_stream_set_gages  the rows [ngage] whose flow the streams on this plan nudge (ngage = 0: none), declared ONCE, before
+ *                      trmc_stream_begin; no tables yet.  They stay until the next call (trmc_set_nudging's tables, which
+ *                      belong to one window, are not touched and not used by a stream).  One gage per row: the last listed
+ *                      wins; a gage on a reservoir or boundary row is TRMC_EINVAL; TRMC_ESTATE while a stream is in progress.
+ *   trmc_stream_push_day   trmc_stream_push with the day's tables: the members of trmc_stream_push by name, then
+ *                      da_mode / da_a / da_w [da_ngage][da_nsteps] -- what trmc_set_nudging takes for a window, resolved by the
+ *                      caller for THIS day (mode uint8; a, w in the plan's precision; host memory, page-locked or not; they must
+ *                      stay unchanged until the day has begun on the device) -- required when the stream has gage rows, with
+ *                      da_ngage / da_nsteps equal to the declared gages and the stream's nsteps (else TRMC_EINVAL); da_q0
+ *                      [da_ngage] (plan precision; NULL = none), the day's FIRST observations, usgs_values[:, 0]: where one is
+ *                      not NaN it replaces the flow the gage row starts the day from (mc_reach.pyx:404-411 -- what the drop-in
+ *                      writes into a window's initial state on the host; in a stream that state lives on the device); and two more
+ *                      products (either may be NULL): nudge_host [ngage][nsteps], the nudge applied at every gage and step, and
+ *                      res_inflow_host [res_nres][res_nsteps], the inflow of every reservoir at every step (the reference's
+ *                      upstream_array rows) -- page-locked host arrays, filled with the day's other products; trmc_stream_wait
+ *                      covers them.  Zero the struct first: members added later then keep their meaning. */
+typedef struct trmc_stream_day {
+    const void *qlat;
+    int64_t nq;
+    const void *boundary_q_dev;
+    int32_t rowset;
+    int32_t reserved0;
+    void *hyd_host, *q0_host, *fvd_host;
+    int64_t da_ngage;
+    int32_t da_nsteps, res_nsteps;
+    const uint8_t *da_mode;
+    const void *da_a, *da_w;
+    void *nudge_host;
+    int64_t res_nres;
+    void *res_inflow_host;
+    const void *da_q0;
+    int64_t reserved[3];
+} trmc_stream_day;
+int trmc_stream_set_gages(trmc_plan *plan, int64_t ngage, const int64_t *gage_rows);
+int trmc_stream_push_day(trmc_plan *plan, const trmc_stream_day *day);
 /* Multi-GPU streams (the trunk of a cut basin: rows fed by boundary rows, cluster_late_lag tiles behind).  trmc_stream_gather: the
  * flows of a row set over `day` [rows][nsteps] into DEVICE memory, queued on `stream` (NULL: the plan's) behind the launches
  * queued so far -- TRMC_ESTATE if the set's rows have not been queued through that day yet.  trmc_stream_boundary: the boundary

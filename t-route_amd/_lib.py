@@ -111,6 +111,8 @@ SIGNATURES = {
     "trmc_plan_set_sequence_mode": (_int, [_vp, _int]),
     "trmc_stream_begin": (_int, [_vp, _int, _int, _int, _int, _int]),
     "trmc_stream_push": (_int, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp]),
+    "trmc_stream_set_gages": (_int, [_vp, _i64, _vp]),
+    "trmc_stream_push_day": (_int, [_vp, _vp]),
     "trmc_stream_gather": (_int, [_vp, _i64, _i32, _vp, _vp]),
     "trmc_stream_boundary": (_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
     "trmc_stream_advance": (_int, [_vp, _int]),
@@ -205,6 +207,15 @@ SIGNATURES = {
     "trmc_event_record": (_int, [_int, _vp, _vp]),
     "trmc_stream_wait_event": (_int, [_int, _vp, _vp]),
 }
+
+class StreamDay(C.Structure):
+    """trmc_stream_day (include/trmc.h)"""
+    _fields_ = [("qlat", C.c_void_p), ("nq", C.c_int64), ("boundary_q_dev", C.c_void_p), ("rowset", C.c_int32), ("reserved0", C.c_int32),
+                ("hyd_host", C.c_void_p), ("q0_host", C.c_void_p), ("fvd_host", C.c_void_p), ("da_ngage", C.c_int64),
+                ("da_nsteps", C.c_int32), ("res_nsteps", C.c_int32), ("da_mode", C.c_void_p), ("da_a", C.c_void_p), ("da_w", C.c_void_p),
+                ("nudge_host", C.c_void_p), ("res_nres", C.c_int64), ("res_inflow_host", C.c_void_p), ("da_q0", C.c_void_p),
+                ("reserved", C.c_int64 * 3)]
+
 
 # include/trdw.h (the diffusive-wave mainstem solver, same shared library)
 SIGNATURES_DW = {

@@ -830,6 +830,7 @@ int trmc_set_reservoirs(trmc_plan *pl, int64_t nres, const int64_t *res_rows, co
 {
     if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
     if (nres < 0) return fail(TRMC_EINVAL, "nres < 0");
+    if (stream_active(pl)) return fail(TRMC_ESTATE, "a stream of windows is in progress: its reservoirs are set before trmc_stream_begin");
     pl->nres = 0;
     pl->res_da_on = false; // (the tables of trmc_set_reservoir_da belong to the reservoirs they were set for)
     if (nres == 0) return 0;

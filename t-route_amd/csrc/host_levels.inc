@@ -91,6 +91,7 @@ template <class T> StepArgs<T> step_args(trmc_plan *pl, int nsteps, int qts)
     a.hot_wave_rows = 64;
     a.seq_slots = a.seq_tpd = a.seq_day = a.seq_days = a.seq_day_min = 0;
     a.slot_tm = a.slot_qlat = a.slot_out = a.slot_dec = 0;
+    a.slot_res = a.slot_da = 0;
     a.up_ptr = (const int32_t *)pl->up_ptr.p;
     a.up_idx = (const int32_t *)pl->up_idx.p;
     a.up2 = (const int2 *)pl->up2.p;

@@ -180,7 +180,7 @@ __device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_
                 }
                 v_new = T(0);
                 d_new = H;
-                cold->res_inflow[(size_t)ri * (size_t)cold->nsteps + (size_t)(t - 1)] = qup;
+                cold->res_inflow[(size_t)slot * (size_t)cold->slot_res + (size_t)ri * (size_t)cold->nsteps + (size_t)(t - 1)] = qup; // (the day's own record)
                 it_last = 0;
             } else {
                 trmc::Inflow<T> f;
@@ -195,8 +195,8 @@ __device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_
                 it_last = r.iters;
                 over_last = r.over;
                 if (count_cost) it_acc += min(r.iters, 3) + (r.over ? 4 : 0);
-                if (gi >= 0) { // streamflow nudging (see k_mc_step)
-                    const size_t e = (size_t)gi * (size_t)cold->nsteps + (size_t)(t - 1);
+                if (gi >= 0) { // streamflow nudging (see k_mc_step); in a stream: the tables of the block's own day
+                    const size_t e = (size_t)slot * (size_t)cold->slot_da + (size_t)gi * (size_t)cold->nsteps + (size_t)(t - 1);
                     const T *const da_a = cold->da_a;
                     const uint8_t mode = cold->da_mode[e];
                     T nudge = T(0);

@@ -81,6 +81,10 @@ template <class T> struct StepArgs {
     int32_t seq_slots, seq_tpd, seq_day, seq_days; // slots; tiles per day; day of the launch's tile index; days pushed so far
     int32_t seq_day_min;                           // days before this one have been queued to their end (trmc_stream_flush)
     int64_t slot_tm, slot_qlat, slot_out, slot_dec;
+    // ... and, in a stream, the reservoirs' inflow record and the nudging tables of a row's day: res_inflow in slot s begins
+    // s * slot_res elements behind the pointer, da_mode / da_a / da_w / da_nudge s * slot_da (0 in a single window).  COLD: read
+    // inside the reservoir and gage branches only
+    int64_t slot_res, slot_da;
 };
 
 // which tile of which day a position `lag` tiles behind works on in a launch of the stream: false = none (before the first
@@ -516,7 +520,7 @@ __device__ __forceinline__ void mc_tile_rows(const StepArgs<T> &a, const int32_t
             }
             v_new = T(0);
             d_new = H;
-            cold->res_inflow[(size_t)ri * (size_t)cold->nsteps + (size_t)(t - 1)] = qup;
+            cold->res_inflow[(size_t)slot * (size_t)cold->slot_res + (size_t)ri * (size_t)cold->nsteps + (size_t)(t - 1)] = qup; // (the day's own record)
             it_last = 0;
         } else {
             trmc::Inflow<T> f;
@@ -531,8 +535,8 @@ __device__ __forceinline__ void mc_tile_rows(const StepArgs<T> &a, const int32_t
             it_last = r.iters;
             over_last = r.over;
             if (count_cost) it_acc += min(r.iters, 3) + (r.over ? 4 : 0);
-            if (gi >= 0) { // streamflow nudging (see k_mc_step)
-                const size_t e = (size_t)gi * (size_t)cold->nsteps + (size_t)(t - 1);
+            if (gi >= 0) { // streamflow nudging (see k_mc_step); in a stream: the tables of the row's own day
+                const size_t e = (size_t)slot * (size_t)cold->slot_da + (size_t)gi * (size_t)cold->nsteps + (size_t)(t - 1);
                 const T *const da_a = cold->da_a;
                 const uint8_t mode = cold->da_mode[e];
                 T nudge = T(0);

@@ -20,10 +20,19 @@
 //   trmc_stream_flush   queue the launches that bring every pushed day to its end (nothing new starts)
 //   trmc_stream_wait    block until a day's products are on the host
 //   trmc_stream_end     flush, wait for everything, leave the final state staged for whatever routes next
+//
+// LEVEL-POOL RESERVOIRS AND STREAMFLOW NUDGING ride along (SURVEY f2, f1).  A reservoir row keeps its water elevation in the depth
+// slot, so the end-of-day hand-off into the next slot's time row 0 carries it on like any depth.  What is per DAY lives in the
+// day's slot, as its forcing does: the reservoirs' inflow record [nres][nsteps] and, for the gage rows declared once with
+// trmc_stream_set_gages, the nudging tables (mode, a, w) and the nudge record [ngage][nsteps] -- a row finds them through its
+// slot (StepArgs::slot_res, slot_da).  The tables arrive with the day's push (trmc_stream_push_day) on the forcing's stream,
+// behind the slot's ev_free and in front of its ev_forcing -- never over a day whose rows still read them -- and the two records
+// leave on the copy stream with the day's other products.  Reservoir data assimilation (types 2-5) stays per window.
 extern "C++" {
 struct StreamProd {
     int64_t day = -1;
     void *hyd_host = nullptr, *q0_host = nullptr, *fvd_host = nullptr;
+    void *nudge_host = nullptr, *res_inflow_host = nullptr;
     int32_t rowset = -1;
     bool queued = false;          // the gathers and copies of this day are queued
     hipEvent_t ev_done = nullptr; // ... and this fires when they are through
@@ -38,6 +47,14 @@ struct StreamRun {
     int32_t dec_stride = 0, dec_keep = 0;
     int32_t rowset = -1;
     DevBuf tm, qlat, out, dec, hyd, q0;
+    // reservoirs and gages (see the head of this file): per-slot element counts, the per-slot buffers, and the gage rows of the
+    // streams on this plan (trmc_stream_set_gages: they outlive a stream, unlike the window's tables of trmc_set_nudging)
+    size_t slot_res = 0, slot_da = 0;
+    DevBuf res_inflow, da_mode, da_a, da_w, da_nudge;
+    DevBuf da_q0;                  // [slots][ngage] the days' first observations (NaN = none): the flow a gage row starts the day from
+    DevBuf gage_of_pos, gage_pos_dev; // [nseg_pad] gage of a position (-1: none); [ngage] position of a gage
+    std::vector<int32_t> gage_pos; // plan position of every declared gage
+    int64_t ngage = 0;
     std::vector<hipEvent_t> ev_slab;    // ring: "slab launch g is complete" (the cluster launch g + 1 waits for it)
     std::vector<hipEvent_t> ev_free;    // [slots] the day that used the slot has handed its products over
     std::vector<hipEvent_t> ev_ready;   // [slots] the gathers of that day are through (copy stream waits)
@@ -55,7 +72,8 @@ static void stream_release(trmc_plan *pl)
 {
     StreamRun *S = pl->seq;
     if (!S) return;
-    for (DevBuf *b : {&S->tm, &S->qlat, &S->out, &S->dec, &S->hyd, &S->q0}) b->release();
+    for (DevBuf *b : {&S->tm, &S->qlat, &S->out, &S->dec, &S->hyd, &S->q0, &S->res_inflow, &S->da_mode, &S->da_a, &S->da_w, &S->da_nudge, &S->da_q0, &S->gage_of_pos, &S->gage_pos_dev})
+        b->release();
     for (auto *v : {&S->ev_slab, &S->ev_free, &S->ev_ready, &S->ev_forcing, &S->ev_t0, &S->ev_t1})
         for (hipEvent_t e : *v)
             if (e) (void)hipEventDestroy(e);
@@ -96,6 +114,30 @@ k_stream_boundary_idx(const T *__restrict__ q_dev, int64_t src_stride, const int
     q_plane[(size_t)t * nseg_pad + b] = q_dev[(size_t)r * (size_t)src_stride + (size_t)(t - 1)];
 }
 
+// A gage row starts a day from the day's first observation where there is one (mc_reach.pyx:404-411: what the drop-in writes into
+// a window's initial state on the host; a stream's state lives on the device).  Queued in FRONT of launch g on the stream that
+// routes the positions [p0, p1): a gage row `lag` tiles behind begins day (g - lag) / tpd in that launch, and its time row 0 of the
+// day's slot was written by the launch before (the end-of-day hand-off; k_init_state for day 0).  The rows below it read that
+// row in later launches.  One thread per gage -- a kernel of its own, so that the tile kernels carry nothing for it.
+template <class T>
+__global__ void __launch_bounds__(kBlock)
+k_stream_first_obs(const int32_t *__restrict__ gage_pos, const int32_t *__restrict__ gage_of_pos, const int32_t *__restrict__ lagk,
+                   const T *__restrict__ da_q0, T *__restrict__ q_tm, int32_t ngage, int32_t p0, int32_t p1, int64_t g, int32_t tpd,
+                   int32_t slots, int64_t day_min, int64_t days, int64_t slot_tm)
+{
+    const int32_t gi = (int32_t)blockIdx.x * kBlock + (int32_t)threadIdx.x;
+    if (gi >= ngage) return;
+    const int32_t p = gage_pos[gi];
+    if (p < p0 || p >= p1 || gage_of_pos[p] != gi) return; // (two gages on one row: the last listed is the row's)
+    const int64_t i = g - lagk[p];
+    if (i < 0 || i % tpd != 0) return;
+    const int64_t day = i / tpd;
+    if (day < day_min || day >= days) return;
+    const int32_t slot = (int32_t)(day % slots);
+    const T v = da_q0[(size_t)slot * (size_t)ngage + (size_t)gi];
+    if (v == v) q_tm[(size_t)slot * (size_t)slot_tm + (size_t)p] = v;
+}
+
 // the stream on which the rows that run furthest behind are routed (a day's products go behind its launches)
 inline hipStream_t stream_last(const trmc_plan *pl, const StreamRun &S)
 {
@@ -122,6 +164,18 @@ template <class T> StepArgs<T> stream_args(trmc_plan *pl, const StreamRun &S, in
     a.slot_qlat = (int64_t)S.slot_qlat;
     a.slot_out = (int64_t)S.slot_out;
     a.slot_dec = (int64_t)S.slot_dec;
+    // the day's reservoir-inflow record and nudging tables: in the rows' slots (the window's own buffers are not used)
+    a.slot_res = (int64_t)S.slot_res;
+    a.slot_da = (int64_t)S.slot_da;
+    a.res_inflow = (T *)S.res_inflow.p;
+    a.res_da = nullptr;
+    a.gage_of_pos = S.ngage > 0 ? (const int32_t *)S.gage_of_pos.p : nullptr;
+    a.da_mode = (const uint8_t *)S.da_mode.p;
+    a.da_a = (const T *)S.da_a.p;
+    a.da_w = (const T *)S.da_w.p;
+    a.da_nudge = (T *)S.da_nudge.p;
+    a.raw_of_pos = nullptr;
+    a.da_raw = nullptr;
     if (S.dec_stride > 0) {
         a.dec = (T *)S.dec.p;
         a.dec_stride = S.dec_stride;
@@ -145,7 +199,8 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
     if (p.day != e) return fail(TRMC_ESTATE, "internal: the slot of a completed day holds another day");
     const T *q = (const T *)S.tm.p + (size_t)slot * S.slot_tm, *d = q + S.plane;
     const int64_t nrows = (p.hyd_host && p.rowset >= 0) ? pl->rowset_n[(size_t)p.rowset] : 0;
-    const bool any = nrows > 0 || p.q0_host || p.fvd_host;
+    const bool want_nudge = p.nudge_host && S.slot_da > 0, want_res = p.res_inflow_host && S.slot_res > 0;
+    const bool any = nrows > 0 || p.q0_host || p.fvd_host || want_nudge || want_res;
     if (nrows > 0) {
         hipLaunchKernelGGL((k_gather_rows<T>), dim3(blocks_for(nrows * S.nsteps)), dim3(kBlock), 0, pst, q,
                            (const int32_t *)pl->rowsets[(size_t)p.rowset].p, (T *)((char *)S.hyd.p + (size_t)slot * S.hyd_bytes), nrows,
@@ -176,6 +231,11 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
             HIP_TRY(hipMemcpyAsync(p.fvd_host, (const T *)S.out.p + (size_t)slot * S.slot_out, (size_t)pl->nseg * S.nsteps * 3 * sizeof(T),
                                    hipMemcpyDeviceToHost, pl->cstream));
     }
+    if (want_nudge)
+        HIP_TRY(hipMemcpyAsync(p.nudge_host, (const T *)S.da_nudge.p + (size_t)slot * S.slot_da, S.slot_da * sizeof(T), hipMemcpyDeviceToHost, pl->cstream));
+    if (want_res)
+        HIP_TRY(hipMemcpyAsync(p.res_inflow_host, (const T *)S.res_inflow.p + (size_t)slot * S.slot_res, S.slot_res * sizeof(T), hipMemcpyDeviceToHost,
+                               pl->cstream));
     HIP_TRY(hipEventRecord(S.ev_free[(size_t)slot], pl->cstream));
     HIP_TRY(hipEventRecord(p.ev_done, pl->cstream));
     p.queued = true;
@@ -198,7 +258,14 @@ template <class T> int stream_launch(trmc_plan *pl, StreamRun &S, int64_t g_from
     for (int64_t g = g_from + 1; g <= g_to; ++g) {
         StepArgs<T> a = stream_args<T>(pl, S, g, days);
         const int32_t tile = (int32_t)(g % S.tpd);
+        auto first_obs = [&](hipStream_t st, int32_t p0, int32_t p1) {
+            if (S.ngage > 0 && p1 > p0)
+                hipLaunchKernelGGL((k_stream_first_obs<T>), dim3(blocks_for(S.ngage)), dim3(kBlock), 0, st, (const int32_t *)S.gage_pos_dev.p,
+                                   (const int32_t *)S.gage_of_pos.p, a.level, (const T *)S.da_q0.p, (T *)S.tm.p, (int32_t)S.ngage, p0, p1, g, S.tpd,
+                                   S.slots, S.day_min, days, (int64_t)S.slot_tm);
+        };
         if (S.W > 0 && w1 > w0) {
+            first_obs(wst, w0, w1);
             StepArgs<T> as = a;
             if (pl->hot_list.p && a.cls_last) {
                 as.hot_list = (int32_t *)pl->hot_list.p;
@@ -215,6 +282,7 @@ template <class T> int stream_launch(trmc_plan *pl, StreamRun &S, int64_t g_from
         }
         if (ncblk > 0 || w2 > w1) {
             if (S.W > 0 && g >= 1) HIP_TRY(hipStreamWaitEvent(cst, S.ev_slab[(size_t)((g - 1) % kSlabEvents)], 0));
+            first_obs(cst, w1, (int32_t)pl->nseg_pad);
             if (w2 > w1) { // (the deeper slices: no hot rows here -- the lists belong to the tile stream's launches)
                 launch_tile<T>(cst, a, w1, w2, tile, S.K, tol);
                 ++S.launches;
@@ -273,6 +341,16 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
     if (S.dec_stride > 0)
         if (int rc = S.dec.ensure((size_t)S.slots * S.slot_dec * sizeof(T))) return rc;
     if (int rc = S.q0.ensure((size_t)S.slots * S.q0_bytes)) return rc;
+    S.slot_res = (size_t)pl->nres * (size_t)nsteps;
+    S.slot_da = (size_t)S.ngage * (size_t)nsteps;
+    if (S.slot_res > 0)
+        if (int rc = S.res_inflow.ensure((size_t)S.slots * S.slot_res * sizeof(T))) return rc;
+    if (S.slot_da > 0) {
+        if (int rc = S.da_mode.ensure((size_t)S.slots * S.slot_da)) return rc;
+        for (DevBuf *b : {&S.da_a, &S.da_w, &S.da_nudge})
+            if (int rc = b->ensure((size_t)S.slots * S.slot_da * sizeof(T))) return rc;
+        if (int rc = S.da_q0.ensure((size_t)S.slots * (size_t)S.ngage * sizeof(T))) return rc;
+    }
     if (int rc = ensure_copy_stream(pl)) return rc;
     if (!pl->wstream) {
         HIP_TRY(hipStreamCreateWithFlags(&pl->wstream, hipStreamNonBlocking));
@@ -361,10 +439,12 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
     return 0;
 }
 
-template <class T>
-int stream_push_t(trmc_plan *pl, const void *qlat, const void *boundary_q_dev, int32_t rowset, void *hyd_host, void *q0_host, void *fvd_host)
+template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
 {
     StreamRun &S = *pl->seq;
+    const void *const qlat = day.qlat, *const boundary_q_dev = day.boundary_q_dev;
+    const int32_t rowset = day.rowset;
+    void *const hyd_host = day.hyd_host, *const q0_host = day.q0_host, *const fvd_host = day.fvd_host;
     const trmc::Topology &tp = pl->topo;
     const int64_t d = S.days_pushed;
     const int32_t slot = (int32_t)(d % S.slots);
@@ -390,6 +470,8 @@ int stream_push_t(trmc_plan *pl, const void *qlat, const void *boundary_q_dev, i
     p.hyd_host = hyd_host;
     p.q0_host = q0_host;
     p.fvd_host = fvd_host;
+    p.nudge_host = day.nudge_host;
+    p.res_inflow_host = day.res_inflow_host;
     // the day's forcing: host -> staging area -> plan order in the slot, all on the copy stream of that direction
     const size_t bytes = (size_t)pl->nseg * S.nq * sizeof(T);
     if (int rc = pl->in_qlat.ensure(bytes)) return rc;
@@ -398,6 +480,20 @@ int stream_push_t(trmc_plan *pl, const void *qlat, const void *boundary_q_dev, i
         const int32_t n = (int32_t)pl->nseg;
         hipLaunchKernelGGL((k_prep_qlat<T>), dim3((n + 63) / 64, (unsigned)((S.nq + 31) / 32)), dim3(kBlock), 0, hst, (const T *)pl->in_qlat.p,
                            (const int32_t *)pl->row_of_pos.p, (T *)S.qlat.p + (size_t)slot * S.slot_qlat, n, pl->nseg_pad, (int32_t)S.nq);
+    }
+    if (S.slot_da > 0) {
+        // the day's nudging tables [ngage][nsteps] into the slot, beside its forcing: behind ev_free (the slot's last day has been
+        // read to its end), in front of ev_forcing (which this day's launches wait for).  The nudge record starts from zero: a gage
+        // that shares its row with a later one of the list is never visited (trmc_stream_set_gages).
+        const size_t n = S.slot_da, o = (size_t)slot * S.slot_da;
+        HIP_TRY(hipMemcpyAsync((uint8_t *)S.da_mode.p + o, day.da_mode, n, hipMemcpyHostToDevice, hst));
+        HIP_TRY(hipMemcpyAsync((T *)S.da_a.p + o, day.da_a, n * sizeof(T), hipMemcpyHostToDevice, hst));
+        HIP_TRY(hipMemcpyAsync((T *)S.da_w.p + o, day.da_w, n * sizeof(T), hipMemcpyHostToDevice, hst));
+        HIP_TRY(hipMemsetAsync((T *)S.da_nudge.p + o, 0, n * sizeof(T), hst));
+        // the day's first observations [ngage] (NaN = none; all bits set is a NaN in either precision)
+        T *const q0o = (T *)S.da_q0.p + (size_t)slot * (size_t)S.ngage;
+        if (day.da_q0) HIP_TRY(hipMemcpyAsync(q0o, day.da_q0, (size_t)S.ngage * sizeof(T), hipMemcpyHostToDevice, hst));
+        else HIP_TRY(hipMemsetAsync(q0o, 0xff, (size_t)S.ngage * sizeof(T), hst));
     }
     if (S.bnd_pending) { // (trmc_stream_boundary on a stream of the caller's: this day's launches go behind it)
         HIP_TRY(hipStreamWaitEvent(hst, S.ev_bnd, 0));
@@ -430,6 +526,19 @@ int stream_push_t(trmc_plan *pl, const void *qlat, const void *boundary_q_dev, i
 
 static bool stream_active(const trmc_plan *pl) { return pl && pl->seq && pl->seq->active; }
 
+// (the reservoir branch of the kernels ends a row's step before the nudging hook: trmc_set_nudging's rule)
+static int stream_gages_check(trmc_plan *pl, const std::vector<int32_t> &gage_pos)
+{
+    if (pl->nres == 0 || gage_pos.empty()) return 0;
+    if (int rc = use_device(pl)) return rc;
+    std::vector<int32_t> res_of_pos((size_t)pl->nseg_pad);
+    HIP_TRY(hipMemcpy(res_of_pos.data(), pl->res_of_pos.p, res_of_pos.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (const int32_t p : gage_pos)
+        if (res_of_pos[(size_t)p] >= 0)
+            return fail(TRMC_EINVAL, "a gage on a reservoir row is not supported (row " + std::to_string(pl->topo.row_of_pos[(size_t)p]) + ")");
+    return 0;
+}
+
 static int stream_check(trmc_plan *pl, bool want_active)
 {
     if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
@@ -449,7 +558,14 @@ int trmc_stream_begin(trmc_plan *pl, int nsteps, int qts_subdivisions, int slots
         return fail(TRMC_EINVAL, "a stream of windows needs a plan in cluster order (TRMC_PLAN_SHORT_TS on the level engine, "
                                  "trmc_plan_options.cluster_rows >= 0): every row is then routed in tiles");
     if (pl->maxlag > 0) return fail(TRMC_EINVAL, "rows with a lag (trmc_plan_set_lag) have no place in a stream of windows: every row has its tile lag");
-    if (pl->nres > 0 || pl->ngage > 0) return fail(TRMC_EINVAL, "reservoirs and nudging tables are per window: route such windows one by one");
+    if (pl->nres > 0 && pl->res_da_on)
+        return fail(TRMC_EINVAL, "reservoir data assimilation (reservoir types 2-5, trmc_set_reservoir_da) is routed window by window: "
+                                 "a stream of windows takes level-pool reservoirs only");
+    if (pl->ngage > 0 && !(pl->seq && pl->seq->ngage > 0))
+        return fail(TRMC_EINVAL, "the nudging tables of trmc_set_nudging belong to one window: declare a stream's gage rows with "
+                                 "trmc_stream_set_gages, its tables arrive with every day (trmc_stream_push_day)");
+    if (pl->seq && pl->seq->ngage > 0)
+        if (int rc = stream_gages_check(pl, pl->seq->gage_pos)) return rc;
     if (settle_deferred_state(pl)) return TRMC_ESTATE;
     if (pl->staged_nsteps < 0) return fail(TRMC_ESTATE, "trmc_upload_forcing (the state, and the shape of the forcing) must precede trmc_stream_begin");
     if (nsteps < 1 || qts_subdivisions < 1) return fail(TRMC_EINVAL, "nsteps and qts_subdivisions must be >= 1");
@@ -463,11 +579,54 @@ int trmc_stream_begin(trmc_plan *pl, int nsteps, int qts_subdivisions, int slots
     return rc;
 }
 
-int trmc_stream_push(trmc_plan *pl, const void *qlat, int64_t nq, const void *boundary_q_dev, int32_t rowset, void *hyd_host,
-                     void *q0_host, void *fvd_host)
+int trmc_stream_set_gages(trmc_plan *pl, int64_t ngage, const int64_t *gage_rows)
+{
+    if (int rc = stream_check(pl, false)) return rc;
+    if (pl->flow) return fail(TRMC_EINVAL, "a stream of windows runs on the level engine");
+    if (ngage < 0) return fail(TRMC_EINVAL, "ngage < 0");
+    if (ngage > 0 && !gage_rows) return fail(TRMC_EINVAL, "gage_rows is NULL");
+    if (!pl->seq) pl->seq = new StreamRun();
+    StreamRun &S = *pl->seq;
+    S.ngage = 0;
+    S.gage_pos.clear();
+    if (ngage == 0) return 0;
+    std::vector<int32_t> g_of_pos((size_t)pl->nseg_pad, -1), pos((size_t)ngage);
+    for (int64_t g = 0; g < ngage; ++g) {
+        const int64_t r = gage_rows[g];
+        if (r < 0 || r >= pl->nseg) return fail(TRMC_EINVAL, "gage row out of range");
+        if (pl->topo.level_of_row[r] < 0) return fail(TRMC_EINVAL, "gage on a boundary row");
+        pos[(size_t)g] = pl->topo.pos_of_row[r];
+        g_of_pos[(size_t)pos[(size_t)g]] = (int32_t)g; // one gage per segment: the last listed wins (trmc_set_nudging)
+    }
+    if (int rc = stream_gages_check(pl, pos)) return rc;
+    if (int rc = upload_i32(S.gage_of_pos, g_of_pos, 1)) return rc;
+    if (int rc = upload_i32(S.gage_pos_dev, pos, 1)) return rc;
+    S.gage_pos = std::move(pos);
+    S.ngage = ngage;
+    return 0;
+}
+
+int trmc_stream_push_day(trmc_plan *pl, const trmc_stream_day *day)
 {
     if (int rc = stream_check(pl, true)) return rc;
+    if (!day) return fail(TRMC_EINVAL, "day is NULL");
     StreamRun &S = *pl->seq;
+    const void *const qlat = day->qlat;
+    const int64_t nq = day->nq;
+    const int32_t rowset = day->rowset;
+    void *const hyd_host = day->hyd_host, *const fvd_host = day->fvd_host;
+    if (S.ngage > 0) {
+        if (!day->da_mode || !day->da_a || !day->da_w)
+            return fail(TRMC_EINVAL, "the stream has gage rows (trmc_stream_set_gages): every day must carry its nudging tables (mode, a, w)");
+        if (day->da_ngage != S.ngage || day->da_nsteps != S.nsteps)
+            return fail(TRMC_EINVAL, "nudging tables of a day must be [" + std::to_string(S.ngage) + "][" + std::to_string(S.nsteps) + "], got ["
+                                         + std::to_string(day->da_ngage) + "][" + std::to_string(day->da_nsteps) + "]");
+    } else if (day->da_mode || day->da_a || day->da_w || day->da_q0 || day->nudge_host) {
+        return fail(TRMC_EINVAL, "nudging tables for a stream without gage rows (trmc_stream_set_gages precedes trmc_stream_begin)");
+    }
+    if (day->res_inflow_host && (day->res_nres != pl->nres || day->res_nsteps != S.nsteps))
+        return fail(TRMC_EINVAL, "the reservoir-inflow record of a day is [" + std::to_string(pl->nres) + "][" + std::to_string(S.nsteps) + "], got ["
+                                     + std::to_string(day->res_nres) + "][" + std::to_string(day->res_nsteps) + "]");
     if (pl->nseg > 0 && !qlat) return fail(TRMC_EINVAL, "qlat is NULL");
     if (nq != S.nq) return fail(TRMC_EINVAL, "every day of a stream has the forcing columns of the first (" + std::to_string(S.nq) + ")");
     if (S.g_done > S.days_pushed * S.tpd - 1 && S.days_complete < S.days_pushed)
@@ -475,8 +634,21 @@ int trmc_stream_push(trmc_plan *pl, const void *qlat, int64_t nq, const void *bo
     if (hyd_host && (rowset < 0 || rowset >= (int32_t)pl->rowsets.size())) return fail(TRMC_EINVAL, "unknown row set");
     if (fvd_host && S.dec_stride == 0 && !S.want_out)
         return fail(TRMC_EINVAL, "the stream was begun without full_output / output_stride: there is no (q, v, d) block to hand over");
-    return pl->precision == 32 ? stream_push_t<float>(pl, qlat, boundary_q_dev, rowset, hyd_host, q0_host, fvd_host)
-                               : stream_push_t<double>(pl, qlat, boundary_q_dev, rowset, hyd_host, q0_host, fvd_host);
+    return pl->precision == 32 ? stream_push_t<float>(pl, *day) : stream_push_t<double>(pl, *day);
+}
+
+int trmc_stream_push(trmc_plan *pl, const void *qlat, int64_t nq, const void *boundary_q_dev, int32_t rowset, void *hyd_host,
+                     void *q0_host, void *fvd_host)
+{
+    trmc_stream_day day{};
+    day.qlat = qlat;
+    day.nq = nq;
+    day.boundary_q_dev = boundary_q_dev;
+    day.rowset = rowset;
+    day.hyd_host = hyd_host;
+    day.q0_host = q0_host;
+    day.fvd_host = fvd_host;
+    return trmc_stream_push_day(pl, &day);
 }
 
 int trmc_stream_boundary(trmc_plan *pl, int64_t day, const void *q_dev, int64_t src_row_stride, const int64_t *index_dev, void *stream)

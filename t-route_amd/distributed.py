@@ -43,7 +43,8 @@ class _EngineOf:
 
 class ShardedRouter:
     def __init__(self, to, params, rank=0, world=1, device=0, plan_factory=None, precision=32,
-                 partition=None, cost_hint=None, assume_short_ts=None, engine="auto", options=None, stream=False):
+                 partition=None, cost_hint=None, assume_short_ts=None, engine="auto", options=None, stream=False,
+                 reservoirs=None, gages=None):
         """cost_hint: optional uint8 [nseg] (global rows), the ``iteration_hint()`` of a router of the same network
         after a window -- every plan then groups its rows by that cost (RoutingPlan ``cost_hint``; results unchanged,
         the kernels' wavefronts become uniform in cost).  assume_short_ts / engine: passed to every RoutingPlan (the
@@ -52,7 +53,26 @@ class ShardedRouter:
         # stream=True: the router's windows follow each other as a STREAM (troute_amd.sequence.RouteStream, trmc_stream_*): its
         # plans are short-timestep plans of the level engine in cluster order, with as many levels in slices as are worth a
         # slice (in a stream they cost no launches)
+        # ... reservoirs=(rows, par [nres, 9], routing_period): level-pool waterbodies, gages=rows: the rows whose flow is nudged
+        # (both in global rows) -- applied to the plan ``stream_plan`` builds; a day's observations go to ``RouteStream.route``
         self._stream = bool(stream)
+        self._reservoirs = self._gages = None
+        if reservoirs is not None or gages is not None:
+            if not stream:
+                raise ValueError("reservoirs / gages are the stream's (ShardedRouter(..., stream=True)); a single window takes "
+                                 "them at plan level (RoutingPlan.set_reservoirs, set_nudging)")
+            if world > 1:
+                raise NotImplementedError("reservoirs and gages in a stream of several ranks (a waterbody's inflows and a gage's "
+                                          "tables would have to follow the partition)")
+            if reservoirs is not None:
+                rr, par, period = reservoirs
+                rr = np.ascontiguousarray(rr, dtype=np.int64)
+                par = np.asarray(par)
+                if par.shape != (rr.shape[0], 9):
+                    raise ValueError("reservoir parameters must be [nres, 9]")
+                self._reservoirs = (rr, par, float(period))
+            if gages is not None:
+                self._gages = np.ascontiguousarray(gages, dtype=np.int64)
         if stream:
             options = {"cluster_rows": 128, "wide_min_rows": 1024, "wide_levels": 32, **(options or {})}
             assume_short_ts, engine = True, "levels"
@@ -100,6 +120,7 @@ class ShardedRouter:
         g2l[self.rows0] = np.arange(self.rows0.shape[0])
         lp, li = restrict_csr(up_ptr, up_idx, self.rows0, g2l)
         self.plan0 = plan_factory(lp, li, params[self.rows0], None, precision, device, rows=self.rows0)
+        self._g2l0 = g2l if (self._reservoirs is not None or self._gages is not None) else None
         self._mk = {"factory": plan_factory, "precision": precision, "device": device, "params": params,
                     "csr0": (lp, li)}
         self.planM = None     # sub-basins + time-skewed trunk in one plan (short-timestep device path)
@@ -353,6 +374,11 @@ class ShardedRouter:
             P = mk["factory"](up_ptr, up_idx, mk["params"][rows], boundary, mk["precision"], mk["device"], rows=rows,
                               short=True, extra_options={"cluster_late_lag": int(late_lag)})
             out_local = np.concatenate([self.my_out0_local, n0 + self.my_out1_local]) if self.my_out1_global.size else self.my_out0_local
+        if self._reservoirs is not None:                    # (one rank: every row is a row of plan0)
+            rr, par, period = self._reservoirs
+            P.set_reservoirs(self._g2l0[rr], par, period)
+        if self._gages is not None:
+            P.stream_set_gages(self._g2l0[self._gages])
         self._planS, self._planS_lag = P, late_lag
         self._rsS_cut = P.rowset(self.my_cut_local)
         self._rsS_out = P.rowset(out_local)

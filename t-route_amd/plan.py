@@ -393,18 +393,65 @@ class RoutingPlan:
         self._nsteps = nsteps
         self._stream_keep = {}
 
-    def stream_push(self, qlat, boundary_q_ptr=None, rowset=None, hyd=None, q0=None, fvd=None):
+    def stream_set_gages(self, rows):
+        """The rows whose flow the streams on this plan nudge (trmc_stream_set_gages): declared once, before ``stream_begin``;
+        every ``stream_push`` then carries the day's tables.  ``None`` or an empty list: none."""
+        rows = np.ascontiguousarray([] if rows is None else rows, dtype=np.int64)
+        _lib.check(_lib.lib().trmc_stream_set_gages(self._h, rows.shape[0], _lib.ptr(rows)))
+        self._stream_ngage = int(rows.shape[0])
+
+    def stream_push(self, qlat, boundary_q_ptr=None, rowset=None, hyd=None, q0=None, fvd=None, nudging=None, nudge=None,
+                    reservoir_inflow=None):
         """The next day: ``qlat`` [nseg, nq] (page-locked: ``_lib.result_empty(..., always_pinned=True)``), where its products go
-        (page-locked arrays or None), the device pointer of its boundary rows' flows.  Returns the day's number in the stream."""
+        (page-locked arrays or None), the device pointer of its boundary rows' flows.  A plan with gage rows
+        (``stream_set_gages``): ``nudging=(mode, a, w)``, the day's tables [ngage, nsteps] as ``set_nudging`` takes them for a
+        window -- or ``(mode, a, w, first)`` with the day's first observations ``usgs_values[:, 0]`` [ngage]: where one is not NaN
+        the gage row starts the day from it (mc_reach.pyx:404-411; the drop-in writes it into a window's initial state); ``nudge`` [ngage, nsteps] and ``reservoir_inflow`` [nres, nsteps]: page-locked arrays for the day's nudge record
+        and the inflows of the plan's reservoirs.  Returns the day's number in the stream."""
         if qlat.dtype != self.dtype or not qlat.flags.c_contiguous or qlat.ndim != 2 or qlat.shape[0] != self.nseg:
             raise ValueError(f"qlat must be a C-contiguous {np.dtype(self.dtype).name} array of shape ({self.nseg}, nq)")
+        day_s = _lib.StreamDay()
+        tables = ()
+        if nudging is not None:
+            mode = np.ascontiguousarray(nudging[0], dtype=np.uint8)
+            a = np.ascontiguousarray(nudging[1], dtype=self.dtype)
+            w = np.ascontiguousarray(nudging[2], dtype=self.dtype)
+            if mode.ndim != 2 or a.shape != mode.shape or w.shape != mode.shape:
+                raise ValueError("nudging tables must be [ngage, nsteps]")
+            tables = (mode, a, w)
+            if len(nudging) > 3 and nudging[3] is not None:
+                first = np.ascontiguousarray(nudging[3], dtype=self.dtype)
+                if first.shape != (mode.shape[0],):
+                    raise ValueError("the day's first observations must be [ngage]")
+                tables += (first,)
+                day_s.da_q0 = first.ctypes.data
+            day_s.da_ngage, day_s.da_nsteps = mode.shape
+            day_s.da_mode, day_s.da_a, day_s.da_w = mode.ctypes.data, a.ctypes.data, w.ctypes.data
+        for name, arr in (("nudge", nudge), ("reservoir_inflow", reservoir_inflow)):
+            if arr is not None and (arr.dtype != self.dtype or not arr.flags.c_contiguous or arr.ndim != 2):
+                raise ValueError(f"{name} must be a C-contiguous {np.dtype(self.dtype).name} array [rows, nsteps]")
+        if nudge is not None:
+            if nudging is None or nudge.shape != tables[0].shape:
+                raise ValueError("nudge must have the shape of the day's nudging tables")
+            day_s.nudge_host = nudge.ctypes.data
+        if reservoir_inflow is not None:
+            day_s.res_nres, day_s.res_nsteps = reservoir_inflow.shape
+            day_s.res_inflow_host = reservoir_inflow.ctypes.data
         info = self.stream_info()
         day = info["days_pushed"]
-        self._stream_keep[day] = (qlat, hyd, q0, fvd)          # (alive while the copies may be in flight: a day's products are
-        for old in [k for k in self._stream_keep if isinstance(k, int) and k < day - max(8, info["slots"])]:   # queued up to `slots` days on)
+        # (alive while the copies may be in flight: a day's products are queued up to `slots` days on)
+        self._stream_keep[day] = (qlat, hyd, q0, fvd, tables, nudge, reservoir_inflow)
+        for old in [k for k in self._stream_keep if isinstance(k, int) and k < day - max(8, info["slots"])]:
             del self._stream_keep[old]
-        _lib.check(_lib.lib().trmc_stream_push(self._h, _lib.ptr(qlat), qlat.shape[1], C.c_void_p(boundary_q_ptr or 0),
-                                               -1 if rowset is None else int(rowset), _lib.ptr(hyd), _lib.ptr(q0), _lib.ptr(fvd)))
+        if nudging is None and reservoir_inflow is None:          # (the entry point every stream without tables has always used)
+            _lib.check(_lib.lib().trmc_stream_push(self._h, _lib.ptr(qlat), qlat.shape[1], C.c_void_p(boundary_q_ptr or 0),
+                                                   -1 if rowset is None else int(rowset), _lib.ptr(hyd), _lib.ptr(q0), _lib.ptr(fvd)))
+            return day
+        day_s.qlat, day_s.nq = qlat.ctypes.data, qlat.shape[1]
+        day_s.boundary_q_dev = boundary_q_ptr or None
+        day_s.rowset = -1 if rowset is None else int(rowset)
+        day_s.hyd_host, day_s.q0_host, day_s.fvd_host = (None if x is None else x.ctypes.data for x in (hyd, q0, fvd))
+        _lib.check(_lib.lib().trmc_stream_push_day(self._h, C.byref(day_s)))
         return day
 
     def stream_gather(self, day, rowset, device_ptr, stream=0):

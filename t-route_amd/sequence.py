@@ -409,11 +409,41 @@ class RouteStream:
         return {"el": el, "days_routed": total, "warmup": wu, "hyd": last[1], "final": last[2], "fvd": last[3] if len(last) > 3 else None,
                 "info": self.last_info, "push_ms": push_ms}
 
-    def route(self, forcings, state0=None, prepared=False):
+    def route(self, forcings, state0=None, prepared=False, observations=None, lastobs=None, da_parameters=None):
         """generator of (day, hydrographs, final_state[, fvd]) -- see the class.  prepared: the arrays hold this rank's rows only
-        (``prepare_days``)."""
+        (``prepare_days``).
+
+        A router with reservoirs or gages (``ShardedRouter(..., stream=True, reservoirs=..., gages=...)``): every tuple has one more
+        trailing element, a dict {"reservoir_inflow": [nres, nsteps] (the reference's upstream_array rows; None without
+        reservoirs), "nudge": [ngage, nsteps], "lastobs": (lastobs_times, lastobs_values) as the day left them (None, None without
+        gages)} -- arrays of the ring as well.  ``observations``: an iterable parallel to ``forcings``, a day's ``usgs_values``
+        [ngage, gage_maxtimestep] (NaN = missing) indexed by the day's own timestep, as ``simple_da.resolve_tables`` takes them;
+        ``lastobs`` = (lastobs_values_init, time_since_lastobs_init) of the first day (default: none known).  Every day's tables
+        are resolved on the host as the drop-in resolves a window's, a gage row starts a day from the day's first observation
+        (column 0, where it is not NaN: mc_reach.pyx:404-411), and the last observations go from day to day as between two
+        calls of the window path: the values as they are, the times less the day's length.  ``da_parameters``:
+        {"da_decay_coefficient": 120.0, "routing_period": the router's dt}."""
         r, nsteps, qts = self.r, self.nsteps, self.qts
         P = self.plan if self.plan is not None else self._setup()
+        res, gages = getattr(r, "_reservoirs", None), getattr(r, "_gages", None)
+        extras = res is not None or gages is not None
+        nres = 0 if res is None else res[0].shape[0]
+        ngage = 0 if gages is None else gages.shape[0]
+        if observations is not None and not ngage:
+            raise ValueError("observations need a router with gages (ShardedRouter(..., stream=True, gages=rows))")
+        if ngage:
+            from .routing.fast_reach import simple_da as _da
+            if observations is None:
+                raise ValueError("the router has gages: route(..., observations=...) must yield every day's usgs_values")
+            obs_it = iter(observations)
+            dap = {"da_decay_coefficient": 120.0, "routing_period": None, **(da_parameters or {})}
+            if dap["routing_period"] is None:
+                dap["routing_period"] = float(r._mk["params"][0, _lib.PARAM_COLS.index("dt")])
+            nan = np.full(ngage, np.nan, dtype=np.float32)
+            lv, lt = (nan, nan.copy()) if lastobs is None else (np.asarray(lastobs[0], dtype=np.float32), np.asarray(lastobs[1], dtype=np.float32))
+            if lv.shape != (ngage,) or lt.shape != (ngage,):
+                raise ValueError("lastobs must be (lastobs_values [ngage], time_since_lastobs [ngage])")
+            day_len = np.float32(nsteps * dap["routing_period"])
         world, multi = self.world, self.world > 1
         rows = self.rows
         local = multi or rows.shape[0] != r.nseg
@@ -455,6 +485,14 @@ class RouteStream:
         fins = [_lib.result_empty((nrows, 3), dtype, always_pinned=True) for _ in range(D)]
         fvds = [_lib.result_empty((nrows, keep, 3), dtype, always_pinned=True) if want_fvd else None for _ in range(D)]
         stage = [_lib.result_empty((nrows, nq), dtype, always_pinned=True) for _ in range(3)]
+        # reservoirs and gages: the records on the products' ring, the day's tables on a ring of their own (read by the copy that
+        # the push queues: alive until the day has begun on the device)
+        rinf = [_lib.result_empty((nres, nsteps), dtype, always_pinned=True) if nres else None for _ in range(D)]
+        nudg = [_lib.result_empty((ngage, nsteps), dtype, always_pinned=True) if ngage else None for _ in range(D)]
+        tabs = [(_lib.result_empty((ngage, nsteps), np.uint8, always_pinned=True), _lib.result_empty((ngage, nsteps), dtype, always_pinned=True),
+                 _lib.result_empty((ngage, nsteps), dtype, always_pinned=True), _lib.result_empty((ngage,), dtype, always_pinned=True))
+                if ngage else None for _ in range(3)]
+        lastobs_of = {}
         # when a day's products are waited for: a day after they were queued (the host then never waits for launches it has
         # just queued -- the device always holds a day of work); latency="low": right after the day's own push (flushed)
         low = self.latency == "low"
@@ -510,7 +548,10 @@ class RouteStream:
             else:
                 hyd = hyd[sel_own]
                 fin, fvd = fins[k], fvds[k]
-            return (day, hyd, fin, fvd) if want_fvd else (day, hyd, fin)
+            item = (day, hyd, fin, fvd) if want_fvd else (day, hyd, fin)
+            if extras:
+                item += ({"reservoir_inflow": rinf[k], "nudge": nudg[k], "lastobs": lastobs_of.pop(day, (None, None))},)
+            return item
 
         d, nxt, pending = 0, first, 0
         delivered = 0
@@ -520,7 +561,21 @@ class RouteStream:
                 buf = stage[d % 3]
                 buf[...] = q
                 q = buf
-            P.stream_push(q, rowset=r._rsS_out, hyd=hyds[d % D], q0=fins[d % D], fvd=fvds[d % D])
+            nudging = None
+            if ngage:
+                try:
+                    usgs = next(obs_it)
+                except StopIteration:
+                    raise ValueError(f"observations ended before the forcings (day {d})") from None
+                mode, a, w, lt_fin, lv_fin = _da.resolve_tables(nsteps, dap["routing_period"], dap["da_decay_coefficient"], usgs, lv, lt)
+                nudging = tabs[d % 3]
+                nudging[0][...], nudging[1][...], nudging[2][...] = mode, a, w
+                u = np.asarray(usgs, dtype=np.float32)
+                nudging[3][...] = u[:, 0] if (u.ndim == 2 and u.shape[1] > 0) else np.nan     # (mc_reach.pyx:404-411)
+                lastobs_of[d] = (lt_fin, lv_fin)
+                lv, lt = lv_fin, (lt_fin - day_len).astype(np.float32)       # (the next day counts from its own start)
+            more = {"nudging": nudging, "nudge": nudg[d % D], "reservoir_inflow": rinf[d % D]} if extras else {}
+            P.stream_push(q, rowset=r._rsS_out, hyd=hyds[d % D], q0=fins[d % D], fvd=fvds[d % D], **more)
             if low:
                 if multi:
                     raise ValueError("latency='low' is a one-GPU option")

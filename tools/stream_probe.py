@@ -1,6 +1,7 @@
 """A stream of windows (trmc_stream_*) against the same days routed one by one on the same plan: every day's final state of every
 row and the hydrographs of sampled rows bit for bit, and what a day costs either way.
-  python tools/stream_probe.py [--nseg N] [--days D] [--wide-min-rows R] [--hint] [--stride n] [--full]"""
+  python tools/stream_probe.py [--nseg N] [--days D] [--wide-min-rows R] [--hint] [--stride n] [--full]
+                               [--reservoirs N --gages M]   level-pool waterbodies and nudged gages scattered over the network"""
 import argparse
 import os
 import sys
@@ -27,6 +28,8 @@ ap.add_argument("--no-check", action="store_true")
 ap.add_argument("--slots", type=int, default=0)
 ap.add_argument("--velocity-on-demand", type=int, default=0)
 ap.add_argument("--later", type=int, default=0, help="hand a day over this many days later than its last row allows (and hold as many more slots)")
+ap.add_argument("--reservoirs", type=int, default=0, help="level-pool reservoirs scattered over the network (rows with an upstream row)")
+ap.add_argument("--gages", type=int, default=0, help="nudged gages scattered over the network (observations: 70 %% valid, lognormal)")
 a = ap.parse_args()
 _lib.single_hw_queue_per_priority("stream_probe")
 nnet = S.CONUS_NNET if a.nseg == S.CONUS_NSEG else max(1, a.nseg // 185)
@@ -45,6 +48,30 @@ for q in days:
 q0 = np.zeros((n, 3), np.float32)
 rng = np.random.default_rng(5)
 sample = np.sort(rng.choice(n, min(n, 3000), replace=False))
+# reservoirs and gages: synthetic level-pool parameters (oracle.LP_PAR order), every day's nudging tables resolved beforehand
+lakes = gages = par = None
+tabs = []
+if a.reservoirs or a.gages:
+    from troute_amd.routing.fast_reach import simple_da as DA          # noqa: E402
+    has_up = np.flatnonzero(np.diff(up_ptr) > 0)
+    lakes = np.sort(rng.choice(has_up, a.reservoirs, replace=False)) if a.reservoirs else np.zeros(0, np.int64)
+    rest = np.setdiff1d(np.arange(n), lakes)
+    gages = np.sort(rng.choice(rest, a.gages, replace=False)) if a.gages else np.zeros(0, np.int64)
+    nl = lakes.shape[0]
+    par = np.stack([rng.uniform(0.2, 5.0, nl), np.full(nl, 113.0), rng.uniform(0.5, 4.0, nl), np.full(nl, 0.1), np.full(nl, 100.0),
+                    np.full(nl, 0.4), np.full(nl, 110.0), rng.uniform(10.0, 60.0, nl), np.full(nl, 10.0)], 1).astype(np.float32)
+    q0[lakes, 2] = rng.uniform(104.0, 111.0, nl).astype(np.float32)     # the pools' elevations live in the depth slot
+    t0 = time.perf_counter()
+    for d in range(len(days) if a.gages else 0):
+        usgs = rng.lognormal(np.log(0.5), 1.0, (a.gages, nsteps + 1)).astype(np.float32)
+        usgs[rng.random(usgs.shape) < 0.3] = np.nan
+        nan = np.full(a.gages, np.nan, np.float32)
+        mode, ta, tw, _, _ = DA.resolve_tables(nsteps, 300.0, 120.0, usgs, nan, nan)
+        tabs.append(tuple(_lib.result_empty(x.shape, x.dtype, always_pinned=True) for x in (mode, ta, tw)))
+        for dst, src in zip(tabs[-1], (mode, ta, tw)):
+            dst[...] = src
+    if a.gages:
+        print(f"nudging tables of {a.gages} gages resolved on the host: {(time.perf_counter() - t0) / len(days):.2f} s per day", flush=True)
 opts = {"wide_min_rows": a.wide_min_rows, "wide_k": a.wide_k, "cluster_rows": 128, "wide_levels": a.wide_levels, "stream_split": a.split, "velocity_on_demand": a.velocity_on_demand}
 hint = None
 if a.hint:
@@ -59,15 +86,22 @@ if a.hint:
 with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="levels", cost_hint=hint, options=opts) as p:
     rs = p.rowset(sample)
     ref = []
+    if lakes is not None:
+        if lakes.size:
+            p.set_reservoirs(lakes, par, 300.0)
+        if gages.size:
+            p.stream_set_gages(gages)
     if not a.no_check:
         t0 = time.perf_counter()
         for d in range(a.days):
             p.upload_forcing(nsteps, days[d % len(days)], q0 if d == 0 else None)
+            if tabs:
+                p.set_nudging(nsteps, gages, *tabs[d % len(days)])
             st = p.route_device(nsteps, qts, True)
             fin = p.download_final_state()
             hyd = p.gather_flow_rows(sample)
             fvd = p.download_fvd(a.stride) if (a.stride or a.full) else None
-            ref.append((fin, hyd, fvd))
+            ref.append((fin, hyd, fvd, p.download_reservoir_inflow() if a.reservoirs else None, p.download_nudge() if tabs else None))
         print(f"one by one: {(time.perf_counter() - t0) / a.days * 1e3:.2f} ms per day (host loop, downloads included); window ms_main {st['ms_main']:.2f}", flush=True)
     # the stream
     p.upload_forcing(nsteps, days[0], q0)
@@ -79,6 +113,8 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
     fins = [_lib.result_empty((n, 3), np.float32, always_pinned=True) for _ in range(D)]
     keep = nsteps // a.stride if a.stride else nsteps
     fvds = [_lib.result_empty((n, keep, 3), np.float32, always_pinned=True) for _ in range(D)] if (a.stride or a.full) else [None] * D
+    rins = [_lib.result_empty((a.reservoirs, nsteps), np.float32, always_pinned=True) if a.reservoirs else None for _ in range(D)]
+    nuds = [_lib.result_empty((a.gages, nsteps), np.float32, always_pinned=True) if tabs else None for _ in range(D)]
     got = []
     behind = (info["lag_max"] + info["tiles_per_day"]) // info["tiles_per_day"] + a.later
     ok = True
@@ -90,7 +126,11 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
         marks.append(time.perf_counter())
         if a.no_check:
             return
-        fin, hyd, fvd = ref[e]
+        fin, hyd, fvd, rin, nud = ref[e]
+        for name, x, y in (("reservoir inflow", rin, rins[e % D]), ("nudge", nud, nuds[e % D])):
+            if x is not None and not np.array_equal(x.view(np.uint32), y.view(np.uint32)):
+                ok = False
+                print(f"   day {e}: {name} differs", flush=True)
         s1 = np.array_equal(fin.view(np.uint32), fins[e % D].view(np.uint32))
         s2 = np.array_equal(hyd.view(np.uint32), hyds[e % D].view(np.uint32))
         s3 = fvd is None or np.array_equal(np.ascontiguousarray(fvd).view(np.uint32), fvds[e % D].view(np.uint32))
@@ -99,7 +139,8 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
             print(f"   day {e}: final state {s1} hydrographs {s2} fvd {s3}", flush=True)
     t0 = time.perf_counter()
     for d in range(a.days):
-        p.stream_push(pinned[d % len(days)], rowset=rs, hyd=hyds[d % D], q0=fins[d % D], fvd=fvds[d % D])
+        p.stream_push(pinned[d % len(days)], rowset=rs, hyd=hyds[d % D], q0=fins[d % D], fvd=fvds[d % D],
+                      nudging=tabs[d % len(days)] if tabs else None, nudge=nuds[d % D], reservoir_inflow=rins[d % D])
         e = d - behind
         if e >= 0:
             take(e)
@@ -107,7 +148,10 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
     for e in range(max(0, a.days - behind), a.days):
         take(e)
     el = time.perf_counter() - t0
+    dev_ms = [p.stream_day_ms(e) for e in range(max(behind + 1, a.days - D + 1), a.days)]    # (days pushed into a full stream, still in the ring)
     p.stream_end()
+    if dev_ms:
+        print(f"   device time of a day's own launches on the slices' stream: median {np.median(dev_ms):.2f} ms over {len(dev_ms)} days {np.round(dev_ms, 2).tolist()}", flush=True)
     per = np.diff(marks) * 1e3
     print(f"stream: {el / a.days * 1e3:.2f} ms per day over {a.days} days (fill and drain included); between deliveries {np.round(per, 2).tolist()}", flush=True)
     print("   launches", p.stream_info()["launches"], " every day bit-identical to the days routed one by one:", ok if not a.no_check else "not checked", flush=True)
