@@ -267,7 +267,8 @@ int trmc_stream_push(trmc_plan *plan, const void *qlat, int64_t nq, const void *
 /* A stream on a plan with LEVEL-POOL RESERVOIRS and GAGES (additions within ABI 19; csrc/stream.inc).  trmc_set_reservoirs before
  * trmc_stream_begin puts the plan's waterbodies into the stream: a reservoir row keeps its water elevation in the depth slot and
  * hands it from day to day like any depth; TRMC_ESTATE while a stream is in progress.  A plan whose staged window has reservoir
- * data-assimilation tables (trmc_set_reservoir_da, types 2-5) is refused by trmc_stream_begin: those are routed window by window.
+ * data-assimilation tables (trmc_set_reservoir_da, types 2-5) is refused by trmc_stream_begin unless the plan's streams were told to
+ * carry them: trmc_stream_set_reservoir_da and trmc_stream_reservoir_da, below trmc_set_reservoir_da.
  *   trmc_stream_set_gages  the rows [ngage] whose flow the streams on this plan nudge (ngage = 0: none), declared ONCE, before
  *                      trmc_stream_begin; no tables yet.  They stay until the next call (trmc_set_nudging's tables, which
  *                      belong to one window, are not touched and not used by a stream).  One gage per row: the last listed
@@ -299,7 +300,8 @@ typedef struct trmc_stream_day {
     int64_t res_nres;
     void *res_inflow_host;
     const void *da_q0;
-    int64_t reserved[3];
+    const struct trmc_stream_reservoir_da *reservoir_da; /* (these three were reserved[3]: zero keeps today's meaning) */
+    void *res_da_state_host, *res_da_tsidx_host;
 } trmc_stream_day;
 int trmc_stream_set_gages(trmc_plan *plan, int64_t ngage, const int64_t *gage_rows);
 int trmc_stream_push_day(trmc_plan *plan, const trmc_stream_day *day);
@@ -479,6 +481,35 @@ int trmc_set_reservoir_da(trmc_plan *plan, int64_t nres, const int32_t *kind, co
  * reservoirs: [0] = update_time), timeseries_idx_out [nres].  Times are in seconds from the START of the window
  * (the loop's return shifts them by its length, mc_reach.pyx:820-837).  D2H. */
 int trmc_download_reservoir_da(trmc_plan *plan, float *state_out, int32_t *timeseries_idx_out);
+/*
+ * The same in a STREAM OF DAYS (additions within ABI 19; csrc/stream.inc).  trmc_stream_set_reservoir_da(plan, on != 0, ...) before
+ * trmc_stream_begin tells the streams on this plan to carry the reservoirs' data assimilation (until the next call; on = 0: a plan
+ * with tables is refused by trmc_stream_begin as before); precision 32, exact arithmetic only.  trmc_set_reservoir_da before
+ * trmc_stream_begin is then the stream's DECLARATION: kind and table_row of every reservoir and the tables' row counts n hold for
+ * the whole stream, and its state members (update_time, prev_persisted_outflow, persistence_index, persistence_update_time; RFC:
+ * update_time and timeseries_idx) are what day 0 starts from.  From there the state lives on the device: a reservoir row that ends
+ * a day takes float(nsteps) * float(routing_period) off update_time and persistence_update_time in fp32 (RFC: update_time), as the
+ * loop's return does (mc_reach.pyx:820-837), and starts the next day from that.
+ *   usgs_ncol, usace_ncol, rfc_ncol  the most columns a day's table of that kind may have (the ring's slots are sized by them);
+ *                      0, or less than the declared table's ncol: the declared table's ncol.
+ * Every day brings its own tables, trmc_stream_day::reservoir_da (required on such a stream, TRMC_EINVAL on any other): the three
+ * tables with the declaration's n and an ncol of the day's own, at most the capacity.  Of their members count
+ *   obs, time          the day's, times in seconds from the day's start
+ *   ipar               RFC: totalCounts use_forecast da_timestep rfc_persist_days are the day's; timeseries_idx only when
+ *                      rfc_reset_idx != 0 (the reference replaces the index when it reads a new forecast file,
+ *                      DataAssimilation.py:1978-1980), else the device's own is carried on
+ *   state              ignored (may be NULL)
+ * Host memory, page-locked or not; copied before trmc_stream_push_day returns.  Two more products of a day (either may be NULL):
+ * res_da_state_host [nres][4] float32 and res_da_tsidx_host [nres] int32, what trmc_download_reservoir_da hands over for a window
+ * but with the times ALREADY shifted to the next day's start -- tuple elements [4], [5], [7] of compute_network_structured; page-
+ * locked host arrays, filled with the day's other products, covered by trmc_stream_wait.
+ */
+typedef struct trmc_stream_reservoir_da {
+    trmc_reservoir_da_table usgs, usace, rfc;
+    int32_t rfc_reset_idx;
+    int32_t reserved0;
+} trmc_stream_reservoir_da;
+int trmc_stream_set_reservoir_da(trmc_plan *plan, int on, int64_t usgs_ncol, int64_t usace_ncol, int64_t rfc_ncol);
 /*
  * Batch of n independent data-assimilation steps on the device, through the device functions the step kernels call.
  *   TRMC_RESERVOIR_DA_HYBRID: obs [n][ncol], time [n][ncol],

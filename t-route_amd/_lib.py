@@ -97,6 +97,12 @@ class ReservoirDaTable(C.Structure):
                 ("ipar", C.c_void_p)]
 
 
+class StreamReservoirDa(C.Structure):
+    """trmc_stream_reservoir_da (include/trmc.h)"""
+    _fields_ = [("usgs", ReservoirDaTable), ("usace", ReservoirDaTable), ("rfc", ReservoirDaTable), ("rfc_reset_idx", C.c_int32),
+                ("reserved0", C.c_int32)]
+
+
 RESERVOIR_DA_HYBRID, RESERVOIR_DA_RFC = 2, 4
 _P = C.POINTER
 # name -> (restype, argtypes); must list every symbol include/trmc.h declares
@@ -113,6 +119,7 @@ SIGNATURES = {
     "trmc_stream_push": (_int, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp]),
     "trmc_stream_set_gages": (_int, [_vp, _i64, _vp]),
     "trmc_stream_push_day": (_int, [_vp, _vp]),
+    "trmc_stream_set_reservoir_da": (_int, [_vp, _int, _i64, _i64, _i64]),
     "trmc_stream_gather": (_int, [_vp, _i64, _i32, _vp, _vp]),
     "trmc_stream_boundary": (_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
     "trmc_stream_advance": (_int, [_vp, _int]),
@@ -214,7 +221,7 @@ class StreamDay(C.Structure):
                 ("hyd_host", C.c_void_p), ("q0_host", C.c_void_p), ("fvd_host", C.c_void_p), ("da_ngage", C.c_int64),
                 ("da_nsteps", C.c_int32), ("res_nsteps", C.c_int32), ("da_mode", C.c_void_p), ("da_a", C.c_void_p), ("da_w", C.c_void_p),
                 ("nudge_host", C.c_void_p), ("res_nres", C.c_int64), ("res_inflow_host", C.c_void_p), ("da_q0", C.c_void_p),
-                ("reserved", C.c_int64 * 3)]
+                ("reservoir_da", C.c_void_p), ("res_da_state_host", C.c_void_p), ("res_da_tsidx_host", C.c_void_p)]
 
 
 # include/trdw.h (the diffusive-wave mainstem solver, same shared library)

@@ -865,16 +865,24 @@ int trmc_download_reservoir_inflow(trmc_plan *pl, void *inflow_out)
     return 0;
 }
 
+// the plans that can have reservoir data-assimilation tables at all (trmc_set_reservoir_da; trmc_stream_set_reservoir_da, trmc_stream_begin)
+static int reservoir_da_plan_check(const trmc_plan *pl)
+{
+    if (pl->precision != 32 || pl->opt.tol)
+        return fail(TRMC_EINVAL, "reservoir data assimilation needs a precision 32 plan in the exact arithmetic");
+    return 0;
+}
+
 int trmc_set_reservoir_da(trmc_plan *pl, int64_t nres, const int32_t *kind, const int32_t *table_row,
                           const trmc_reservoir_da_table *usgs, const trmc_reservoir_da_table *usace, const trmc_reservoir_da_table *rfc)
 {
     if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
+    if (stream_active(pl)) return fail(TRMC_ESTATE, "a stream of windows is in progress: its reservoir tables arrive with every day (trmc_stream_push_day)");
     pl->res_da_on = false;
     if (nres == 0) return 0;
     if (nres != pl->nres) return fail(TRMC_ESTATE, "trmc_set_reservoirs (same nres) must precede trmc_set_reservoir_da");
     if (!kind || !table_row) return fail(TRMC_EINVAL, "kind/table_row is NULL");
-    if (pl->precision != 32 || pl->opt.tol)
-        return fail(TRMC_EINVAL, "reservoir data assimilation needs a precision 32 plan in the exact arithmetic");
+    if (int rc = reservoir_da_plan_check(pl)) return rc;
     if (pl->run.active) return fail(TRMC_ESTATE, "a routing window is in progress");
     const trmc_reservoir_da_table none{};
     const trmc_reservoir_da_table *tab[3] = {usgs ? usgs : &none, usace ? usace : &none, rfc ? rfc : &none};
@@ -923,19 +931,19 @@ int trmc_set_reservoir_da(trmc_plan *pl, int64_t nres, const int32_t *kind, cons
         r.time_off = time_off[k];
         if (k < 2) {
             const float *s = t.state + 4 * j;
-            r.update_time = s[0];
-            r.prev_persisted = s[1];
-            r.persistence_index = s[2];
-            r.persistence_update_time = s[3];
+            r.st.update_time = s[0];
+            r.st.prev_persisted = s[1];
+            r.st.persistence_index = s[2];
+            r.st.persistence_update_time = s[3];
         } else {
             const int32_t *p = t.ipar + 5 * j;
-            r.update_time = t.state[j];
-            r.timeseries_idx = p[0];
+            r.st.update_time = t.state[j];
+            r.st.timeseries_idx = p[0];
             r.total_counts = p[1];
             r.use_forecast = p[2];
             r.da_timestep = p[3];
             r.persist_days = p[4];
-            if (r.timeseries_idx < 0 || r.timeseries_idx >= r.ncol)
+            if (r.st.timeseries_idx < 0 || r.st.timeseries_idx >= r.ncol)
                 return fail(TRMC_EINVAL, "rfc table row " + std::to_string(j) + ": timeseries_idx outside the series");
         }
         rec[i] = r;
@@ -946,6 +954,12 @@ int trmc_set_reservoir_da(trmc_plan *pl, int64_t nres, const int32_t *kind, cons
     if (int rc = pl->res_da.ensure(host.size() * sizeof(float))) return rc;
     HIP_TRY(hipMemcpy(pl->res_da.p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
     pl->res_da_on = true;
+    pl->res_da_kind.assign(kind, kind + nres);
+    pl->res_da_trow.assign(table_row, table_row + nres);
+    for (int k = 0; k < 3; ++k) {
+        pl->res_da_n[k] = tab[k]->n;
+        pl->res_da_ncol[k] = tab[k]->n > 0 ? tab[k]->ncol : 0;
+    }
     pl->routed_nsteps = -1;
     return 0;
 }
@@ -960,11 +974,11 @@ int trmc_download_reservoir_da(trmc_plan *pl, float *state_out, int32_t *timeser
     std::vector<trmc::ResDaRec> rec((size_t)pl->nres);
     HIP_TRY(hipMemcpy(rec.data(), pl->res_da.p, rec.size() * sizeof(trmc::ResDaRec), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < rec.size(); ++i) {
-        state_out[4 * i + 0] = rec[i].update_time;
-        state_out[4 * i + 1] = rec[i].prev_persisted;
-        state_out[4 * i + 2] = rec[i].persistence_index;
-        state_out[4 * i + 3] = rec[i].persistence_update_time;
-        timeseries_idx_out[i] = rec[i].timeseries_idx;
+        state_out[4 * i + 0] = rec[i].st.update_time;
+        state_out[4 * i + 1] = rec[i].st.prev_persisted;
+        state_out[4 * i + 2] = rec[i].st.persistence_index;
+        state_out[4 * i + 3] = rec[i].st.persistence_update_time;
+        timeseries_idx_out[i] = rec[i].st.timeseries_idx;
     }
     return 0;
 }

@@ -92,6 +92,9 @@ template <class T> StepArgs<T> step_args(trmc_plan *pl, int nsteps, int qts)
     a.seq_slots = a.seq_tpd = a.seq_day = a.seq_days = a.seq_day_min = 0;
     a.slot_tm = a.slot_qlat = a.slot_out = a.slot_dec = 0;
     a.slot_res = a.slot_da = 0;
+    a.res_da_carry = nullptr; // (a stream of days with reservoir data assimilation: stream_args)
+    a.slot_rda = 0;
+    a.res_t_end = 0.0f;
     a.up_ptr = (const int32_t *)pl->up_ptr.p;
     a.up_idx = (const int32_t *)pl->up_idx.p;
     a.up2 = (const int2 *)pl->up2.p;
@@ -170,7 +173,7 @@ inline void launch_tile(hipStream_t st, const StepArgs<T> &a, int32_t p0, int32_
     const bool dec = a.dec != nullptr;
     const bool lazy = a.v_every != 0 && !a.out; // (velocity where it is handed on only: the LAZYV instances assemble no full result)
     if constexpr (sizeof(T) == 4) {
-        if (a.res_da) { // (never a stream's window, never the tolerance arithmetic: trmc_set_reservoir_da, stream_begin)
+        if (a.res_da) { // (never the tolerance arithmetic: trmc_set_reservoir_da)
             if (dec) hipLaunchKernelGGL((k_mc_tile_rda<true>), grid, block, 0, st, a, p0, p1, tile, K);
             else hipLaunchKernelGGL((k_mc_tile_rda<false>), grid, block, 0, st, a, p0, p1, tile, K);
             return;

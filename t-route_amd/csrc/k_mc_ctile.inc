@@ -174,7 +174,11 @@ __device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_
                 q_new = trmc::levelpool_step<T, M>(qup, T(0), cold->res_dt, H, lp, m);
                 if constexpr (RDA) { // (see k_mc_step)
                     void *const da = cold->res_da;
-                    const trmc::ResDaResult r = trmc::reservoir_da_row(da, ri, t, qup, d_prev, cold->res_dt, rp, q_new, H);
+                    trmc::ResDaState *const carry = (trmc::ResDaState *)cold->res_da_carry; // (a stream of days: the tables of the block's slot)
+                    const trmc::ResDaResult r =
+                        carry ? trmc::reservoir_da_row_day((char *)da + (size_t)slot * (size_t)cold->slot_rda, carry, ri, t, cold->nsteps,
+                                                           cold->res_t_end, qup, d_prev, cold->res_dt, rp, q_new, H)
+                              : trmc::reservoir_da_row(da, ri, t, qup, d_prev, cold->res_dt, rp, q_new, H);
                     q_new = r.outflow;
                     H = r.water_elevation;
                 }

@@ -85,6 +85,13 @@ template <class T> struct StepArgs {
     // s * slot_res elements behind the pointer, da_mode / da_a / da_w / da_nudge s * slot_da (0 in a single window).  COLD: read
     // inside the reservoir and gage branches only
     int64_t slot_res, slot_da;
+    // ... and the reservoir data-assimilation tables of a row's day (the _rda instances; reservoir_da.hpp reservoir_da_row_day):
+    // res_da in slot s begins s * slot_rda BYTES behind the pointer; the state lives outside the ring, res_da_carry [nres]
+    // (nullptr: one window, the state lives in its tables); res_t_end = float(nsteps) * float(dt), what a day's end takes off the
+    // times, rounded once on the host.  COLD
+    void *res_da_carry;
+    int64_t slot_rda;
+    float res_t_end;
 };
 
 // which tile of which day a position `lag` tiles behind works on in a launch of the stream: false = none (before the first
@@ -514,7 +521,11 @@ __device__ __forceinline__ void mc_tile_rows(const StepArgs<T> &a, const int32_t
             q_new = trmc::levelpool_step<T, M>(qup, T(0), cold->res_dt, H, lp, m);
             if constexpr (RDA) { // (see k_mc_step)
                 void *const da = cold->res_da;
-                const trmc::ResDaResult r = trmc::reservoir_da_row(da, ri, t, qup, d_prev, cold->res_dt, rp, q_new, H);
+                trmc::ResDaState *const carry = (trmc::ResDaState *)cold->res_da_carry; // (a stream of days: the tables of the row's slot)
+                const trmc::ResDaResult r =
+                    carry ? trmc::reservoir_da_row_day((char *)da + (size_t)slot * (size_t)cold->slot_rda, carry, ri, t, cold->nsteps, cold->res_t_end,
+                                                       qup, d_prev, cold->res_dt, rp, q_new, H)
+                          : trmc::reservoir_da_row(da, ri, t, qup, d_prev, cold->res_dt, rp, q_new, H);
                 q_new = r.outflow;
                 H = r.water_elevation;
             }

@@ -178,43 +178,56 @@ MC_HD RfcOut rfc_da_step(const float *series, int32_t ncol, const RfcIn &in)
 // One buffer: a record per level-pool reservoir of the plan (trmc_set_reservoirs order), then the float rows the records
 // point into.  The four (hybrid) or two (RFC) state values of a record are read and written by the one thread that owns
 // the reservoir's row at that step (mc_reach.pyx:624-636, :701-703).
+// What a reservoir carries from step to step -- and, between two windows or two days of a stream, from one to the next.
+struct ResDaState {
+    float update_time, prev_persisted, persistence_index, persistence_update_time; // (RFC: update_time only)
+    int32_t timeseries_idx;                                                         // (RFC only)
+};
 struct ResDaRec {
     int32_t kind;                // 0: level pool only; 2, 3: hybrid persistence; 4, 5: RFC series
     int32_t ncol;                // entries of the observation row (and of the time row)
     int64_t obs_off, time_off;   // where they begin, in floats from the start of the buffer
-    float update_time, prev_persisted, persistence_index, persistence_update_time;
-    int32_t timeseries_idx, total_counts, use_forecast, da_timestep, persist_days, pad_;
+    ResDaState st;               // a window: the state lives here; a day of a stream: what the day ended on (see reservoir_da_row_day)
+    int32_t total_counts, use_forecast, da_timestep, persist_days;
+    int32_t reset_idx;           // a day of a stream, RFC: != 0 = the day starts from st.timeseries_idx of THIS record (a new forecast file)
 };
 static_assert(sizeof(ResDaRec) == 64, "ResDaRec layout");
+
+// THE HAND-OVER between two windows: the loop returns update_time and persistence_update_time (RFC: update_time) less the
+// window's length, so that they count from the start of the next one (mc_reach.pyx:820-837); everything else passes unchanged.
+// t_end is float(nsteps) * float(dt) -- a C float product in the loop -- formed ONCE by the caller and handed over as a value,
+// so that no compiler can fuse the product into the subtraction: the difference is one fp32 operation on two fp32 values.
+MC_HD ResDaState reservoir_da_handover(int32_t kind, ResDaState s, float t_end)
+{
+    if (kind >= 2 && kind <= 5) s.update_time = s.update_time - t_end;
+    if (kind == 2 || kind == 3) s.persistence_update_time = s.persistence_update_time - t_end;
+    return s;
+}
 
 struct ResDaResult {
     float outflow, water_elevation;
 };
 
 #if defined(__HIPCC__)
-// The reservoir branch of the step kernels calls this right behind levelpool_step: reservoir `ri` at step t (1-based) of
+// The reservoir branch of the step kernels calls reservoir_da_row right behind levelpool_step: reservoir `ri` at step t (1-based) of
 // the window, inflow, the elevation before the level-pool step, the level-pool results.  par = the pool's nine
 // parameters (LevelPoolParams order).  Out of line on purpose: a handful of rows in ten thousand come here, and inlined
 // its fp64 arithmetic and loops would be allocated registers in every kernel that has the branch.
 // Consecutive launches of one window may overlap in time (k_mc_flow_lean hands a row's depth over through a granule): the
 // state written here is released before the caller publishes the step, and acquired behind the caller's wait for it.
-__device__ __noinline__ ResDaResult reservoir_da_row(void *tables, int32_t ri, int32_t t, float inflow, float h_before, float dt,
-                                                     const float *par, float lp_outflow, float lp_elevation)
+__device__ __forceinline__ ResDaResult reservoir_da_apply(const ResDaRec *rec, const float *base, ResDaState *st, int32_t t, float inflow,
+                                                          float h_before, float dt, const float *par, float lp_outflow, float lp_elevation)
 {
-    ResDaRec *const rec = (ResDaRec *)tables + ri;
-    ResDaResult r{lp_outflow, lp_elevation};
+    ResDaResult r;
     const int32_t kind = rec->kind;
-    if (kind == 0) return r;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    const float *const base = (const float *)tables;
     const float now = dt * (float)t;
     if (kind <= 3) {
         HybridIn in;
         in.now = now;
-        in.update_time = __hip_atomic_load(&rec->update_time, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        in.prev_persisted = __hip_atomic_load(&rec->prev_persisted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        in.persistence_index = __hip_atomic_load(&rec->persistence_index, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        in.persistence_update_time = __hip_atomic_load(&rec->persistence_update_time, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        in.update_time = __hip_atomic_load(&st->update_time, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        in.prev_persisted = __hip_atomic_load(&st->prev_persisted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        in.persistence_index = __hip_atomic_load(&st->persistence_index, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        in.persistence_update_time = __hip_atomic_load(&st->persistence_update_time, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         in.levelpool_outflow = lp_outflow;
         in.inflow = inflow;
         in.routing_period = dt;
@@ -223,17 +236,17 @@ __device__ __noinline__ ResDaResult reservoir_da_row(void *tables, int32_t ri, i
         in.orifice_elevation = par[4];
         in.initial_water_elevation = h_before;
         const HybridOut o = hybrid_da_step(base + rec->obs_off, base + rec->time_off, rec->ncol, in);
-        __hip_atomic_store(&rec->update_time, o.update_time, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&rec->prev_persisted, o.persisted_outflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&rec->persistence_index, o.persistence_index, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&rec->persistence_update_time, o.persistence_update_time, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&st->update_time, o.update_time, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&st->prev_persisted, o.persisted_outflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&st->persistence_index, o.persistence_index, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&st->persistence_update_time, o.persistence_update_time, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         r.outflow = o.outflow;
         r.water_elevation = o.water_elevation;
     } else {
         RfcIn in;
         in.now = now;
-        in.update_time = __hip_atomic_load(&rec->update_time, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        in.timeseries_idx = __hip_atomic_load(&rec->timeseries_idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        in.update_time = __hip_atomic_load(&st->update_time, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        in.timeseries_idx = __hip_atomic_load(&st->timeseries_idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         in.inflow = inflow;
         in.water_elevation = h_before;
         in.levelpool_outflow = lp_outflow;
@@ -247,10 +260,53 @@ __device__ __noinline__ ResDaResult reservoir_da_row(void *tables, int32_t ri, i
         in.persist_days = rec->persist_days;
         in.reservoir_type = kind;
         const RfcOut o = rfc_da_step(base + rec->obs_off, rec->ncol, in);
-        __hip_atomic_store(&rec->update_time, o.update_time, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&rec->timeseries_idx, o.timeseries_idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&st->update_time, o.update_time, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&st->timeseries_idx, o.timeseries_idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         r.outflow = o.outflow;
         r.water_elevation = o.water_elevation;
+    }
+    return r;
+}
+__device__ __noinline__ ResDaResult reservoir_da_row(void *tables, int32_t ri, int32_t t, float inflow, float h_before, float dt,
+                                                     const float *par, float lp_outflow, float lp_elevation)
+{
+    ResDaRec *const rec = (ResDaRec *)tables + ri;
+    if (rec->kind == 0) return ResDaResult{lp_outflow, lp_elevation};
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    const ResDaResult r = reservoir_da_apply(rec, (const float *)tables, &rec->st, t, inflow, h_before, dt, par, lp_outflow, lp_elevation);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    return r;
+}
+// The same in a STREAM OF DAYS (stream.inc).  `tables` are the tables of the row's DAY -- its slot of the ring, pushed with the
+// day's forcing: observations and times counted from the day's start, the RFC parameters of the day -- and the state lives in
+// `carry` [nres], outside the ring: a slot's tables arrive while rows further behind are still in the day before.  At the day's
+// first step an RFC row takes the day's timeseries_idx where the day says so (reset_idx: the reference replaces the index when
+// it reads a new forecast file, DataAssimilation.py:1978-1980).  At the day's last step the state is handed over
+// (reservoir_da_handover) -- into the carry, where the row finds it at step 1 of the next day, and into the day's own record,
+// the day's product.  One thread owns a reservoir row at any step, and a row's launches follow each other on one stream.
+__device__ __noinline__ ResDaResult reservoir_da_row_day(void *tables, ResDaState *carry, int32_t ri, int32_t t, int32_t nsteps, float t_end,
+                                                         float inflow, float h_before, float dt, const float *par, float lp_outflow,
+                                                         float lp_elevation)
+{
+    ResDaRec *const rec = (ResDaRec *)tables + ri;
+    const int32_t kind = rec->kind;
+    if (kind == 0) return ResDaResult{lp_outflow, lp_elevation};
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    ResDaState *const st = carry + ri;
+    if (t == 1 && kind >= 4 && rec->reset_idx != 0)
+        __hip_atomic_store(&st->timeseries_idx, rec->st.timeseries_idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const ResDaResult r = reservoir_da_apply(rec, (const float *)tables, st, t, inflow, h_before, dt, par, lp_outflow, lp_elevation);
+    if (t == nsteps) {
+        ResDaState s;
+        s.update_time = __hip_atomic_load(&st->update_time, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s.prev_persisted = __hip_atomic_load(&st->prev_persisted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s.persistence_index = __hip_atomic_load(&st->persistence_index, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s.persistence_update_time = __hip_atomic_load(&st->persistence_update_time, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s.timeseries_idx = __hip_atomic_load(&st->timeseries_idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s = reservoir_da_handover(kind, s, t_end);
+        __hip_atomic_store(&st->update_time, s.update_time, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&st->persistence_update_time, s.persistence_update_time, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        rec->st = s;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     return r;

@@ -27,12 +27,26 @@
 // trmc_stream_set_gages, the nudging tables (mode, a, w) and the nudge record [ngage][nsteps] -- a row finds them through its
 // slot (StepArgs::slot_res, slot_da).  The tables arrive with the day's push (trmc_stream_push_day) on the forcing's stream,
 // behind the slot's ev_free and in front of its ev_forcing -- never over a day whose rows still read them -- and the two records
-// leave on the copy stream with the day's other products.  Reservoir data assimilation (types 2-5) stays per window.
+// leave on the copy stream with the day's other products.
+//
+// RESERVOIR DATA ASSIMILATION (types 2-5: hybrid persistence, RFC series; reservoir_da.hpp) rides along too once the plan's streams
+// were told to carry it (trmc_stream_set_reservoir_da; without that trmc_stream_begin still refuses a plan that has such tables).
+// trmc_set_reservoir_da is the declaration: which reservoir is of which kind and on which row of which table, the tables' row
+// counts, and the state day 0 starts from.  Every day brings its own tables (trmc_stream_day::reservoir_da: observations and
+// times counted from the day's start, the RFC parameters of the day); they are laid out on the host as a window's are
+// (ResDaRec [nres], then the float rows, every table at its column CAPACITY so that a slot's size is fixed), copied into the
+// day's slot with its forcing, and a row reads them through its own slot (StepArgs::slot_rda).  The STATE does not live in the
+// ring -- a slot is filled while rows further behind are still in the day before -- but in a carry [nres] that the one thread
+// owning a reservoir row reads and writes; when that row ends a day it takes the day's length off the times (reservoir_da_handover,
+// mc_reach.pyx:820-837) and leaves the result both in the carry and in the day's record, from where the day's products
+// res_da_state_host / res_da_tsidx_host are gathered.  Such a stream forms every step's velocity: the _rda tile instances have no
+// LAZYV form (DESIGN.md 10).
 extern "C++" {
 struct StreamProd {
     int64_t day = -1;
     void *hyd_host = nullptr, *q0_host = nullptr, *fvd_host = nullptr;
     void *nudge_host = nullptr, *res_inflow_host = nullptr;
+    void *rda_state_host = nullptr, *rda_tsidx_host = nullptr;
     int32_t rowset = -1;
     bool queued = false;          // the gathers and copies of this day are queued
     hipEvent_t ev_done = nullptr; // ... and this fires when they are through
@@ -55,6 +69,16 @@ struct StreamRun {
     DevBuf gage_of_pos, gage_pos_dev; // [nseg_pad] gage of a position (-1: none); [ngage] position of a gage
     std::vector<int32_t> gage_pos; // plan position of every declared gage
     int64_t ngage = 0;
+    // reservoir data assimilation (see the head of this file).  rda_want / rda_cap_want: trmc_stream_set_reservoir_da, they outlive
+    // a stream as the gage rows do; the rest belongs to the stream in progress
+    bool rda_want = false, rda = false;
+    int64_t rda_cap_want[3] = {0, 0, 0}, rda_cap[3] = {0, 0, 0}; // columns a day's {usgs, usace, rfc} table may have
+    int64_t rda_off[3] = {0, 0, 0}, rda_time_off[3] = {0, 0, 0};  // where a slot's observation rows / time rows begin, in floats
+    size_t slot_rda = 0;           // bytes of a slot's tables
+    float t_end = 0.0f;            // float(nsteps) * float(routing period): what a day's end takes off the times
+    DevBuf rda_tab, rda_carry, rda_prod; // [slots][slot_rda]; ResDaState [nres]; [slots]{float [nres][4], int32 [nres]}
+    void *rda_stage = nullptr;     // page-locked host image of every slot's tables (the copy runs beside the launches)
+    size_t rda_stage_bytes = 0;
     std::vector<hipEvent_t> ev_slab;    // ring: "slab launch g is complete" (the cluster launch g + 1 waits for it)
     std::vector<hipEvent_t> ev_free;    // [slots] the day that used the slot has handed its products over
     std::vector<hipEvent_t> ev_ready;   // [slots] the gathers of that day are through (copy stream waits)
@@ -72,8 +96,10 @@ static void stream_release(trmc_plan *pl)
 {
     StreamRun *S = pl->seq;
     if (!S) return;
-    for (DevBuf *b : {&S->tm, &S->qlat, &S->out, &S->dec, &S->hyd, &S->q0, &S->res_inflow, &S->da_mode, &S->da_a, &S->da_w, &S->da_nudge, &S->da_q0, &S->gage_of_pos, &S->gage_pos_dev})
+    for (DevBuf *b : {&S->tm, &S->qlat, &S->out, &S->dec, &S->hyd, &S->q0, &S->res_inflow, &S->da_mode, &S->da_a, &S->da_w, &S->da_nudge, &S->da_q0, &S->gage_of_pos, &S->gage_pos_dev, &S->rda_tab,
+                       &S->rda_carry, &S->rda_prod})
         b->release();
+    if (S->rda_stage) (void)hipHostFree(S->rda_stage);
     for (auto *v : {&S->ev_slab, &S->ev_free, &S->ev_ready, &S->ev_forcing, &S->ev_t0, &S->ev_t1})
         for (hipEvent_t e : *v)
             if (e) (void)hipEventDestroy(e);
@@ -138,6 +164,56 @@ k_stream_first_obs(const int32_t *__restrict__ gage_pos, const int32_t *__restri
     if (v == v) q_tm[(size_t)slot * (size_t)slot_tm + (size_t)p] = v;
 }
 
+// a day's reservoir data-assimilation state for the host: the records its rows left in the slot's tables at their last step ->
+// state [nres][4], timeseries_idx [nres] (trmc_download_reservoir_da's layout)
+__global__ void __launch_bounds__(kBlock) k_stream_rda_state(const trmc::ResDaRec *__restrict__ rec, float *__restrict__ state,
+                                                             int32_t *__restrict__ tsidx, int32_t nres)
+{
+    const int32_t i = (int32_t)blockIdx.x * kBlock + (int32_t)threadIdx.x;
+    if (i >= nres) return;
+    const trmc::ResDaState s = rec[i].st;
+    state[4 * i + 0] = s.update_time;
+    state[4 * i + 1] = s.prev_persisted;
+    state[4 * i + 2] = s.persistence_index;
+    state[4 * i + 3] = s.persistence_update_time;
+    tsidx[i] = s.timeseries_idx;
+}
+
+// the tables of one day as a slot holds them (the head of this file), into `img` (slot_rda bytes, zeroed here)
+inline void stream_rda_image(const trmc_plan *pl, const StreamRun &S, const trmc_stream_reservoir_da &d, float *img)
+{
+    std::memset(img, 0, S.slot_rda);
+    const trmc_reservoir_da_table *tab[3] = {&d.usgs, &d.usace, &d.rfc};
+    for (int k = 0; k < 3; ++k) {
+        if (tab[k]->n <= 0) continue;
+        std::memcpy(img + S.rda_off[k], tab[k]->obs, (size_t)(tab[k]->n * tab[k]->ncol) * sizeof(float));
+        if (k < 2) std::memcpy(img + S.rda_time_off[k], tab[k]->time, (size_t)tab[k]->ncol * sizeof(float));
+    }
+    trmc::ResDaRec *rec = reinterpret_cast<trmc::ResDaRec *>(img);
+    for (int64_t i = 0; i < pl->nres; ++i) {
+        trmc::ResDaRec r{};
+        r.kind = pl->res_da_kind[(size_t)i];
+        if (r.kind != 0) {
+            const int k = r.kind == 2 ? 0 : (r.kind == 3 ? 1 : 2);
+            const trmc_reservoir_da_table &t = *tab[k];
+            const int64_t j = pl->res_da_trow[(size_t)i];
+            r.ncol = (int32_t)t.ncol;
+            r.obs_off = S.rda_off[k] + j * t.ncol;
+            r.time_off = S.rda_time_off[k];
+            if (k == 2) {
+                const int32_t *ip = t.ipar + 5 * j;
+                r.st.timeseries_idx = ip[0];
+                r.total_counts = ip[1];
+                r.use_forecast = ip[2];
+                r.da_timestep = ip[3];
+                r.persist_days = ip[4];
+                r.reset_idx = d.rfc_reset_idx != 0;
+            }
+        }
+        rec[i] = r;
+    }
+}
+
 // the stream on which the rows that run furthest behind are routed (a day's products go behind its launches)
 inline hipStream_t stream_last(const trmc_plan *pl, const StreamRun &S)
 {
@@ -168,7 +244,10 @@ template <class T> StepArgs<T> stream_args(trmc_plan *pl, const StreamRun &S, in
     a.slot_res = (int64_t)S.slot_res;
     a.slot_da = (int64_t)S.slot_da;
     a.res_inflow = (T *)S.res_inflow.p;
-    a.res_da = nullptr;
+    a.res_da = S.rda ? S.rda_tab.p : nullptr; // (the _rda instances: the tables of a row's day, the state in the carry)
+    a.res_da_carry = S.rda ? S.rda_carry.p : nullptr;
+    a.slot_rda = (int64_t)S.slot_rda;
+    a.res_t_end = S.t_end;
     a.gage_of_pos = S.ngage > 0 ? (const int32_t *)S.gage_of_pos.p : nullptr;
     a.da_mode = (const uint8_t *)S.da_mode.p;
     a.da_a = (const T *)S.da_a.p;
@@ -183,8 +262,8 @@ template <class T> StepArgs<T> stream_args(trmc_plan *pl, const StreamRun &S, in
     }
     // A stream that assembles no full result hands nobody a velocity but the kept steps' of output_stride -- or nobody at all
     // (hydrographs and final states are flows and depths): only those steps form it.  trmc_plan_options.velocity_on_demand < 0
-    // has every step form it anyway (A/B).
-    if (!S.want_out && pl->opt.velocity_on_demand >= 0) a.v_every = S.dec_stride > 0 ? S.dec_stride : -1;
+    // has every step form it anyway (A/B), and so does a stream with reservoir data assimilation (no LAZYV _rda instances).
+    if (!S.want_out && pl->opt.velocity_on_demand >= 0 && !S.rda) a.v_every = S.dec_stride > 0 ? S.dec_stride : -1;
     // the in-block partition and the hot rows: as in a window (route_advance_t); the buffers were made by trmc_stream_begin
     if (pl->cls_last.p) a.cls_last = (uint8_t *)pl->cls_last.p;
     return a;
@@ -200,7 +279,13 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
     const T *q = (const T *)S.tm.p + (size_t)slot * S.slot_tm, *d = q + S.plane;
     const int64_t nrows = (p.hyd_host && p.rowset >= 0) ? pl->rowset_n[(size_t)p.rowset] : 0;
     const bool want_nudge = p.nudge_host && S.slot_da > 0, want_res = p.res_inflow_host && S.slot_res > 0;
-    const bool any = nrows > 0 || p.q0_host || p.fvd_host || want_nudge || want_res;
+    const bool want_rda = S.rda && (p.rda_state_host || p.rda_tsidx_host);
+    const bool any = nrows > 0 || p.q0_host || p.fvd_host || want_nudge || want_res || want_rda;
+    float *const rda_state = (float *)S.rda_prod.p + (size_t)slot * (size_t)pl->nres * 5;
+    int32_t *const rda_tsidx = (int32_t *)(rda_state + (size_t)pl->nres * 4);
+    if (want_rda)
+        hipLaunchKernelGGL(k_stream_rda_state, dim3(blocks_for(pl->nres)), dim3(kBlock), 0, pst,
+                           (const trmc::ResDaRec *)((const char *)S.rda_tab.p + (size_t)slot * S.slot_rda), rda_state, rda_tsidx, (int32_t)pl->nres);
     if (nrows > 0) {
         hipLaunchKernelGGL((k_gather_rows<T>), dim3(blocks_for(nrows * S.nsteps)), dim3(kBlock), 0, pst, q,
                            (const int32_t *)pl->rowsets[(size_t)p.rowset].p, (T *)((char *)S.hyd.p + (size_t)slot * S.hyd_bytes), nrows,
@@ -236,6 +321,10 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
     if (want_res)
         HIP_TRY(hipMemcpyAsync(p.res_inflow_host, (const T *)S.res_inflow.p + (size_t)slot * S.slot_res, S.slot_res * sizeof(T), hipMemcpyDeviceToHost,
                                pl->cstream));
+    if (want_rda && p.rda_state_host)
+        HIP_TRY(hipMemcpyAsync(p.rda_state_host, rda_state, (size_t)pl->nres * 4 * sizeof(float), hipMemcpyDeviceToHost, pl->cstream));
+    if (want_rda && p.rda_tsidx_host)
+        HIP_TRY(hipMemcpyAsync(p.rda_tsidx_host, rda_tsidx, (size_t)pl->nres * sizeof(int32_t), hipMemcpyDeviceToHost, pl->cstream));
     HIP_TRY(hipEventRecord(S.ev_free[(size_t)slot], pl->cstream));
     HIP_TRY(hipEventRecord(p.ev_done, pl->cstream));
     p.queued = true;
@@ -351,6 +440,39 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
             if (int rc = b->ensure((size_t)S.slots * S.slot_da * sizeof(T))) return rc;
         if (int rc = S.da_q0.ensure((size_t)S.slots * (size_t)S.ngage * sizeof(T))) return rc;
     }
+    // reservoir data assimilation: the slots' tables at their capacity, the carry with the state trmc_set_reservoir_da supplied
+    // (or the plan's last window left in those tables), the days' state records
+    S.rda = pl->nres > 0 && pl->res_da_on && S.rda_want;
+    S.slot_rda = 0;
+    if (S.rda) {
+        int64_t floats = pl->nres * (int64_t)(sizeof(trmc::ResDaRec) / sizeof(float));
+        for (int k = 0; k < 3; ++k) {
+            const int64_t n = pl->res_da_n[k];
+            S.rda_cap[k] = n > 0 ? std::max(S.rda_cap_want[k], pl->res_da_ncol[k]) : 0;
+            S.rda_off[k] = floats;
+            floats += n * S.rda_cap[k];
+            S.rda_time_off[k] = floats;
+            if (k < 2) floats += S.rda_cap[k];
+        }
+        S.slot_rda = ((size_t)floats * sizeof(float) + 63) / 64 * 64;
+        S.t_end = (float)nsteps * (float)pl->res_dt;
+        if (int rc = S.rda_tab.ensure((size_t)S.slots * S.slot_rda)) return rc;
+        if (int rc = S.rda_carry.ensure((size_t)pl->nres * sizeof(trmc::ResDaState))) return rc;
+        if (int rc = S.rda_prod.ensure((size_t)S.slots * (size_t)pl->nres * 5 * sizeof(float))) return rc;
+        if (S.rda_stage_bytes < (size_t)S.slots * S.slot_rda) {
+            if (S.rda_stage) (void)hipHostFree(S.rda_stage);
+            S.rda_stage = nullptr;
+            S.rda_stage_bytes = 0;
+            HIP_TRY(hipHostMalloc(&S.rda_stage, (size_t)S.slots * S.slot_rda, hipHostMallocDefault));
+            S.rda_stage_bytes = (size_t)S.slots * S.slot_rda;
+        }
+        HIP_TRY(hipStreamSynchronize(pl->stream)); // (a window routed with these tables has left its state in them)
+        std::vector<trmc::ResDaRec> rec((size_t)pl->nres);
+        HIP_TRY(hipMemcpy(rec.data(), pl->res_da.p, rec.size() * sizeof(trmc::ResDaRec), hipMemcpyDeviceToHost));
+        std::vector<trmc::ResDaState> carry((size_t)pl->nres);
+        for (size_t i = 0; i < rec.size(); ++i) carry[i] = rec[i].st;
+        HIP_TRY(hipMemcpy(S.rda_carry.p, carry.data(), carry.size() * sizeof(trmc::ResDaState), hipMemcpyHostToDevice));
+    }
     if (int rc = ensure_copy_stream(pl)) return rc;
     if (!pl->wstream) {
         HIP_TRY(hipStreamCreateWithFlags(&pl->wstream, hipStreamNonBlocking));
@@ -453,6 +575,8 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
     if (d >= S.slots && S.days_complete <= d - S.slots)
         return fail(TRMC_ESTATE, "internal: the slot of the new day still belongs to a day that has not been queued to its end");
     StreamProd &p = S.prod[(size_t)slot];
+    // (the host image of the slot's reservoir tables is written below: the copy of the slot's last day must have read it)
+    if (S.rda && p.day >= 0) HIP_TRY(hipEventSynchronize(S.ev_forcing[(size_t)slot]));
     if (p.day >= 0 && p.queued) HIP_TRY(hipStreamWaitEvent(hst, S.ev_free[(size_t)slot], 0)); // (the slot's last day has handed its products over)
     if (hyd_host && rowset >= 0) {
         const size_t hb = (size_t)pl->rowset_n[(size_t)rowset] * S.nsteps * sizeof(T);
@@ -472,6 +596,8 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
     p.fvd_host = fvd_host;
     p.nudge_host = day.nudge_host;
     p.res_inflow_host = day.res_inflow_host;
+    p.rda_state_host = day.res_da_state_host;
+    p.rda_tsidx_host = day.res_da_tsidx_host;
     // the day's forcing: host -> staging area -> plan order in the slot, all on the copy stream of that direction
     const size_t bytes = (size_t)pl->nseg * S.nq * sizeof(T);
     if (int rc = pl->in_qlat.ensure(bytes)) return rc;
@@ -494,6 +620,12 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
         T *const q0o = (T *)S.da_q0.p + (size_t)slot * (size_t)S.ngage;
         if (day.da_q0) HIP_TRY(hipMemcpyAsync(q0o, day.da_q0, (size_t)S.ngage * sizeof(T), hipMemcpyHostToDevice, hst));
         else HIP_TRY(hipMemsetAsync(q0o, 0xff, (size_t)S.ngage * sizeof(T), hst));
+    }
+    if (S.rda) {
+        // the day's reservoir tables into the slot, as the nudging tables: behind ev_free, in front of ev_forcing
+        float *const img = (float *)((char *)S.rda_stage + (size_t)slot * S.slot_rda);
+        stream_rda_image(pl, S, *day.reservoir_da, img);
+        HIP_TRY(hipMemcpyAsync((char *)S.rda_tab.p + (size_t)slot * S.slot_rda, img, S.slot_rda, hipMemcpyHostToDevice, hst));
     }
     if (S.bnd_pending) { // (trmc_stream_boundary on a stream of the caller's: this day's launches go behind it)
         HIP_TRY(hipStreamWaitEvent(hst, S.ev_bnd, 0));
@@ -558,9 +690,12 @@ int trmc_stream_begin(trmc_plan *pl, int nsteps, int qts_subdivisions, int slots
         return fail(TRMC_EINVAL, "a stream of windows needs a plan in cluster order (TRMC_PLAN_SHORT_TS on the level engine, "
                                  "trmc_plan_options.cluster_rows >= 0): every row is then routed in tiles");
     if (pl->maxlag > 0) return fail(TRMC_EINVAL, "rows with a lag (trmc_plan_set_lag) have no place in a stream of windows: every row has its tile lag");
-    if (pl->nres > 0 && pl->res_da_on)
-        return fail(TRMC_EINVAL, "reservoir data assimilation (reservoir types 2-5, trmc_set_reservoir_da) is routed window by window: "
-                                 "a stream of windows takes level-pool reservoirs only");
+    if (pl->nres > 0 && pl->res_da_on) {
+        if (!(pl->seq && pl->seq->rda_want))
+            return fail(TRMC_EINVAL, "reservoir data assimilation (reservoir types 2-5, trmc_set_reservoir_da) is routed window by window "
+                                     "unless the plan's streams were told to carry it (trmc_stream_set_reservoir_da)");
+        if (int rc = reservoir_da_plan_check(pl)) return rc; // (trmc_set_reservoir_da let no other plan have tables)
+    }
     if (pl->ngage > 0 && !(pl->seq && pl->seq->ngage > 0))
         return fail(TRMC_EINVAL, "the nudging tables of trmc_set_nudging belong to one window: declare a stream's gage rows with "
                                  "trmc_stream_set_gages, its tables arrive with every day (trmc_stream_push_day)");
@@ -606,6 +741,59 @@ int trmc_stream_set_gages(trmc_plan *pl, int64_t ngage, const int64_t *gage_rows
     return 0;
 }
 
+int trmc_stream_set_reservoir_da(trmc_plan *pl, int on, int64_t usgs_ncol, int64_t usace_ncol, int64_t rfc_ncol)
+{
+    if (int rc = stream_check(pl, false)) return rc;
+    if (pl->flow) return fail(TRMC_EINVAL, "a stream of windows runs on the level engine");
+    if (usgs_ncol < 0 || usace_ncol < 0 || rfc_ncol < 0 || usgs_ncol > INT32_MAX || usace_ncol > INT32_MAX || rfc_ncol > INT32_MAX)
+        return fail(TRMC_EINVAL, "a table's column capacity must be >= 0 (0: as many as the declared table has)");
+    if (on)
+        if (int rc = reservoir_da_plan_check(pl)) return rc;
+    if (!pl->seq) pl->seq = new StreamRun();
+    StreamRun &S = *pl->seq;
+    S.rda_want = on != 0;
+    S.rda_cap_want[0] = usgs_ncol;
+    S.rda_cap_want[1] = usace_ncol;
+    S.rda_cap_want[2] = rfc_ncol;
+    return 0;
+}
+
+// the reservoir tables of a day against the declaration (trmc_set_reservoir_da) and the capacity fixed at trmc_stream_begin
+static int stream_rda_check(const trmc_plan *pl, const StreamRun &S, const trmc_stream_day &day)
+{
+    if (!S.rda) {
+        if (day.reservoir_da || day.res_da_state_host || day.res_da_tsidx_host)
+            return fail(TRMC_EINVAL, "reservoir data-assimilation tables for a stream without them (trmc_set_reservoir_da and "
+                                     "trmc_stream_set_reservoir_da precede trmc_stream_begin)");
+        return 0;
+    }
+    if (!day.reservoir_da)
+        return fail(TRMC_EINVAL, "the stream carries reservoir data assimilation: every day must bring its reservoir tables "
+                                 "(trmc_stream_day::reservoir_da)");
+    const trmc_reservoir_da_table *tab[3] = {&day.reservoir_da->usgs, &day.reservoir_da->usace, &day.reservoir_da->rfc};
+    const char *const tname[3] = {"usgs", "usace", "rfc"};
+    for (int k = 0; k < 3; ++k) {
+        const trmc_reservoir_da_table &t = *tab[k];
+        if (t.n != pl->res_da_n[k])
+            return fail(TRMC_EINVAL, std::string(tname[k]) + " table of a day: " + std::to_string(t.n) + " rows, the stream was declared with "
+                                         + std::to_string(pl->res_da_n[k]));
+        if (t.n == 0) continue;
+        if (t.ncol < 1) return fail(TRMC_EINVAL, std::string(tname[k]) + " table of a day: rows without columns");
+        if (t.ncol > S.rda_cap[k])
+            return fail(TRMC_EINVAL, std::string(tname[k]) + " table of a day: " + std::to_string(t.ncol) + " columns exceed the stream's capacity of "
+                                         + std::to_string(S.rda_cap[k]) + " (trmc_stream_set_reservoir_da)");
+        if (!t.obs || (k < 2 && !t.time) || (k == 2 && !t.ipar)) return fail(TRMC_EINVAL, std::string(tname[k]) + " table of a day: a pointer is NULL");
+    }
+    if (day.reservoir_da->rfc_reset_idx)
+        for (int64_t i = 0; i < pl->nres; ++i)
+            if (pl->res_da_kind[(size_t)i] >= 4) {
+                const int32_t idx = tab[2]->ipar[5 * pl->res_da_trow[(size_t)i]];
+                if (idx < 0 || idx >= tab[2]->ncol)
+                    return fail(TRMC_EINVAL, "rfc table row " + std::to_string(pl->res_da_trow[(size_t)i]) + ": timeseries_idx outside the series");
+            }
+    return 0;
+}
+
 int trmc_stream_push_day(trmc_plan *pl, const trmc_stream_day *day)
 {
     if (int rc = stream_check(pl, true)) return rc;
@@ -624,6 +812,7 @@ int trmc_stream_push_day(trmc_plan *pl, const trmc_stream_day *day)
     } else if (day->da_mode || day->da_a || day->da_w || day->da_q0 || day->nudge_host) {
         return fail(TRMC_EINVAL, "nudging tables for a stream without gage rows (trmc_stream_set_gages precedes trmc_stream_begin)");
     }
+    if (int rc = stream_rda_check(pl, S, *day)) return rc;
     if (day->res_inflow_host && (day->res_nres != pl->nres || day->res_nsteps != S.nsteps))
         return fail(TRMC_EINVAL, "the reservoir-inflow record of a day is [" + std::to_string(pl->nres) + "][" + std::to_string(S.nsteps) + "], got ["
                                      + std::to_string(day->res_nres) + "][" + std::to_string(day->res_nsteps) + "]");

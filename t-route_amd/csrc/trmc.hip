@@ -182,6 +182,8 @@ struct trmc_plan {
     double res_dt = 0.0;
     DevBuf res_da;                       // data-assimilation tables of those reservoirs for the staged window (reservoir_da.hpp)
     bool res_da_on = false;
+    std::vector<int32_t> res_da_kind, res_da_trow; // what trmc_set_reservoir_da declared, and its tables' shapes {usgs, usace, rfc}:
+    int64_t res_da_n[3] = {0, 0, 0}, res_da_ncol[3] = {0, 0, 0}; // fixed for a stream of days that carries them (stream.inc)
     int64_t ngage = 0;
     int64_t nraw = 0;                    // gages inside a reach whose successor reads the un-nudged flow (general mode)
     DevBuf raw_of_pos, da_raw;

@@ -44,7 +44,7 @@ class _EngineOf:
 class ShardedRouter:
     def __init__(self, to, params, rank=0, world=1, device=0, plan_factory=None, precision=32,
                  partition=None, cost_hint=None, assume_short_ts=None, engine="auto", options=None, stream=False,
-                 reservoirs=None, gages=None):
+                 reservoirs=None, gages=None, reservoir_da=None):
         """cost_hint: optional uint8 [nseg] (global rows), the ``iteration_hint()`` of a router of the same network
         after a window -- every plan then groups its rows by that cost (RoutingPlan ``cost_hint``; results unchanged,
         the kernels' wavefronts become uniform in cost).  assume_short_ts / engine: passed to every RoutingPlan (the
@@ -55,8 +55,17 @@ class ShardedRouter:
         # slice (in a stream they cost no launches)
         # ... reservoirs=(rows, par [nres, 9], routing_period): level-pool waterbodies, gages=rows: the rows whose flow is nudged
         # (both in global rows) -- applied to the plan ``stream_plan`` builds; a day's observations go to ``RouteStream.route``
+        # ... reservoir_da=(kind, table_row, usgs, usace, rfc[, ids]): the data assimilation of those reservoirs (types 2-5) as
+        # ``RoutingPlan.set_reservoir_da`` takes it -- the stream's declaration and the state its first day starts from; every
+        # day's tables go to ``RouteStream.route(reservoir_da=...)``.  ids = (usgs, usace, rfc) waterbody ids of the tables' rows:
+        # what the state tuples a day hands back begin with (default: the rows' numbers)
         self._stream = bool(stream)
-        self._reservoirs = self._gages = None
+        self._reservoirs = self._gages = self._reservoir_da = None
+        if reservoir_da is not None:
+            if reservoirs is None:
+                raise ValueError("reservoir_da needs the reservoirs it belongs to (reservoirs=(rows, par, routing_period))")
+            if len(reservoir_da) not in (5, 6):
+                raise ValueError("reservoir_da must be (kind, table_row, usgs, usace, rfc[, ids])")
         if reservoirs is not None or gages is not None:
             if not stream:
                 raise ValueError("reservoirs / gages are the stream's (ShardedRouter(..., stream=True)); a single window takes "
@@ -73,6 +82,11 @@ class ShardedRouter:
                 self._reservoirs = (rr, par, float(period))
             if gages is not None:
                 self._gages = np.ascontiguousarray(gages, dtype=np.int64)
+            if reservoir_da is not None:
+                kind = np.ascontiguousarray(reservoir_da[0], dtype=np.int32)
+                if kind.shape != self._reservoirs[0].shape or not np.isin(kind, (2, 3, 4, 5)).any():
+                    raise ValueError("reservoir_da: kind must be [nres] with a reservoir of type 2-5 among them")
+                self._reservoir_da = (kind,) + tuple(reservoir_da[1:])
         if stream:
             options = {"cluster_rows": 128, "wide_min_rows": 1024, "wide_levels": 32, **(options or {})}
             assume_short_ts, engine = True, "levels"
@@ -377,6 +391,8 @@ class ShardedRouter:
         if self._reservoirs is not None:                    # (one rank: every row is a row of plan0)
             rr, par, period = self._reservoirs
             P.set_reservoirs(self._g2l0[rr], par, period)
+            if self._reservoir_da is not None:
+                P.set_reservoir_da(*self._reservoir_da[:5])
         if self._gages is not None:
             P.stream_set_gages(self._g2l0[self._gages])
         self._planS, self._planS_lag = P, late_lag

@@ -270,26 +270,37 @@ class RoutingPlan:
         table_row = np.ascontiguousarray(table_row, dtype=np.int32)
         if kind.shape != (getattr(self, "_nres", 0),) or table_row.shape != kind.shape:
             raise ValueError("kind and table_row must be [nres] of set_reservoirs")
-        keep, tabs = [kind, table_row], []
+        tabs, _keep = self._reservoir_da_tables(usgs, usace, rfc)
+        _lib.check(_lib.lib().trmc_set_reservoir_da(self._h, kind.shape[0], _lib.ptr(kind), _lib.ptr(table_row),
+                                                    C.byref(tabs[0]), C.byref(tabs[1]), C.byref(tabs[2])))
+
+    @staticmethod
+    def _reservoir_da_tables(usgs, usace, rfc, with_state=True):
+        """the three trmc_reservoir_da_table of ``set_reservoir_da`` 's tuples and the arrays they point into; with_state=False
+        (a day of a stream, whose state the device carries): the hybrid tables' state may be missing or None, and is not passed"""
+        keep, tabs = [], []
         for t, hybrid in ((usgs, True), (usace, True), (rfc, False)):
             s = _lib.ReservoirDaTable()
             if t is not None and len(t[0]):
                 obs = np.ascontiguousarray(t[0], dtype=np.float32)
+                if obs.ndim != 2:
+                    raise ValueError("a reservoir data-assimilation table's observations must be [n, ncol]")
                 n, ncol = obs.shape
                 if hybrid:
-                    time, state, ipar = np.ascontiguousarray(t[1], dtype=np.float32), np.ascontiguousarray(t[2], dtype=np.float32), None
-                    if time.shape != (ncol,) or state.shape != (n, 4):
+                    time, ipar = np.ascontiguousarray(t[1], dtype=np.float32), None
+                    state = np.ascontiguousarray(t[2], dtype=np.float32) if with_state else None
+                    if time.shape != (ncol,) or (with_state and state.shape != (n, 4)):
                         raise ValueError("hybrid table: time must be [ncol], state [n, 4]")
                 else:
-                    time, state, ipar = None, np.ascontiguousarray(t[1], dtype=np.float32), np.ascontiguousarray(t[2], dtype=np.int32)
-                    if state.shape != (n,) or ipar.shape != (n, 5):
+                    time, ipar = None, np.ascontiguousarray(t[2], dtype=np.int32)
+                    state = np.ascontiguousarray(t[1], dtype=np.float32) if with_state else None
+                    if (with_state and state.shape != (n,)) or ipar.shape != (n, 5):
                         raise ValueError("rfc table: update_time must be [n], ipar [n, 5]")
                 keep += [obs, time, state, ipar]
                 s.n, s.ncol = n, ncol
                 s.obs, s.time, s.state, s.ipar = (None if a is None else a.ctypes.data for a in (obs, time, state, ipar))
             tabs.append(s)
-        _lib.check(_lib.lib().trmc_set_reservoir_da(self._h, kind.shape[0], _lib.ptr(kind), _lib.ptr(table_row),
-                                                    C.byref(tabs[0]), C.byref(tabs[1]), C.byref(tabs[2])))
+        return tabs, keep
 
     def download_reservoir_da(self):
         """(state [nres, 4] float32, timeseries_idx [nres] int32) the routed window left: include/trmc.h
@@ -386,8 +397,16 @@ class RoutingPlan:
         return self.stats()
 
     # -- a stream of windows (include/trmc.h, trmc_stream_*) ------------------------------------------------
-    def stream_begin(self, nsteps, qts_subdivisions, slots=0, full_output=False, output_stride=0):
-        """After ``upload_forcing`` (the state, the shape of the forcing): days are then ``stream_push``-ed one after the other."""
+    def stream_begin(self, nsteps, qts_subdivisions, slots=0, full_output=False, output_stride=0, reservoir_da=None):
+        """After ``upload_forcing`` (the state, the shape of the forcing): days are then ``stream_push``-ed one after the other.
+        ``reservoir_da``: True, or the most columns ``(usgs, usace, rfc)`` a day's tables may have (True: as many as the declared
+        ones) -- the stream carries the data assimilation of the reservoirs that ``set_reservoir_da`` declared (kind, table_row,
+        the tables' rows, the state day 0 starts from), and every ``stream_push`` brings the day's tables; None (default): a plan
+        with such tables is refused, as it always was (include/trmc.h trmc_stream_set_reservoir_da)."""
+        caps = (0, 0, 0) if reservoir_da in (None, False, True) else tuple(int(x) for x in reservoir_da)
+        if len(caps) != 3:
+            raise ValueError("reservoir_da: True or the three column capacities (usgs, usace, rfc)")
+        _lib.check(_lib.lib().trmc_stream_set_reservoir_da(self._h, int(reservoir_da not in (None, False)), *caps))
         _lib.check(_lib.lib().trmc_stream_begin(self._h, int(nsteps), int(qts_subdivisions), int(slots), int(bool(full_output)),
                                                 int(output_stride or 0)))
         self._nsteps = nsteps
@@ -401,13 +420,17 @@ class RoutingPlan:
         self._stream_ngage = int(rows.shape[0])
 
     def stream_push(self, qlat, boundary_q_ptr=None, rowset=None, hyd=None, q0=None, fvd=None, nudging=None, nudge=None,
-                    reservoir_inflow=None):
+                    reservoir_inflow=None, reservoir_da=None, reservoir_da_state=None):
         """The next day: ``qlat`` [nseg, nq] (page-locked: ``_lib.result_empty(..., always_pinned=True)``), where its products go
         (page-locked arrays or None), the device pointer of its boundary rows' flows.  A plan with gage rows
         (``stream_set_gages``): ``nudging=(mode, a, w)``, the day's tables [ngage, nsteps] as ``set_nudging`` takes them for a
         window -- or ``(mode, a, w, first)`` with the day's first observations ``usgs_values[:, 0]`` [ngage]: where one is not NaN
         the gage row starts the day from it (mc_reach.pyx:404-411; the drop-in writes it into a window's initial state); ``nudge`` [ngage, nsteps] and ``reservoir_inflow`` [nres, nsteps]: page-locked arrays for the day's nudge record
-        and the inflows of the plan's reservoirs.  Returns the day's number in the stream."""
+        and the inflows of the plan's reservoirs.  A stream begun with ``reservoir_da``: ``reservoir_da=(usgs, usace, rfc[,
+        rfc_reset_idx])``, the day's tables as ``set_reservoir_da`` takes them -- times from the day's start; the state members are
+        ignored and may be None, the device carries them; the RFC timeseries_idx counts only with ``rfc_reset_idx`` -- and
+        ``reservoir_da_state=(state [nres, 4] float32, timeseries_idx [nres] int32)``: page-locked arrays for the state the day
+        leaves, times already counted from the next day's start.  Returns the day's number in the stream."""
         if qlat.dtype != self.dtype or not qlat.flags.c_contiguous or qlat.ndim != 2 or qlat.shape[0] != self.nseg:
             raise ValueError(f"qlat must be a C-contiguous {np.dtype(self.dtype).name} array of shape ({self.nseg}, nq)")
         day_s = _lib.StreamDay()
@@ -437,13 +460,30 @@ class RoutingPlan:
         if reservoir_inflow is not None:
             day_s.res_nres, day_s.res_nsteps = reservoir_inflow.shape
             day_s.res_inflow_host = reservoir_inflow.ctypes.data
+        rda_s = None
+        if reservoir_da is not None:
+            if len(reservoir_da) not in (3, 4):
+                raise ValueError("reservoir_da must be (usgs, usace, rfc[, rfc_reset_idx])")
+            rtabs, rkeep = self._reservoir_da_tables(*reservoir_da[:3], with_state=False)
+            rda_s = _lib.StreamReservoirDa()
+            rda_s.usgs, rda_s.usace, rda_s.rfc = rtabs
+            rda_s.rfc_reset_idx = int(bool(reservoir_da[3])) if len(reservoir_da) == 4 else 0
+            tables += tuple(rkeep)
+            day_s.reservoir_da = C.addressof(rda_s)
+        if reservoir_da_state is not None:
+            st, ti = reservoir_da_state
+            nres = getattr(self, "_nres", 0)
+            if (st.dtype != np.float32 or ti.dtype != np.int32 or st.shape != (nres, 4) or ti.shape != (nres,)
+                    or not st.flags.c_contiguous or not ti.flags.c_contiguous):
+                raise ValueError(f"reservoir_da_state must be (float32 [{nres}, 4], int32 [{nres}]), C-contiguous")
+            day_s.res_da_state_host, day_s.res_da_tsidx_host = st.ctypes.data, ti.ctypes.data
         info = self.stream_info()
         day = info["days_pushed"]
         # (alive while the copies may be in flight: a day's products are queued up to `slots` days on)
-        self._stream_keep[day] = (qlat, hyd, q0, fvd, tables, nudge, reservoir_inflow)
+        self._stream_keep[day] = (qlat, hyd, q0, fvd, tables, nudge, reservoir_inflow, reservoir_da_state)
         for old in [k for k in self._stream_keep if isinstance(k, int) and k < day - max(8, info["slots"])]:
             del self._stream_keep[old]
-        if nudging is None and reservoir_inflow is None:          # (the entry point every stream without tables has always used)
+        if nudging is None and reservoir_inflow is None and reservoir_da is None and reservoir_da_state is None:  # (the entry point every stream without tables has always used)
             _lib.check(_lib.lib().trmc_stream_push(self._h, _lib.ptr(qlat), qlat.shape[1], C.c_void_p(boundary_q_ptr or 0),
                                                    -1 if rowset is None else int(rowset), _lib.ptr(hyd), _lib.ptr(q0), _lib.ptr(fvd)))
             return day

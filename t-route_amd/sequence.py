@@ -274,12 +274,15 @@ class RouteStream:
     """
 
     def __init__(self, router, nsteps, qts_subdivisions, output_stride=None, full_output=False, slots=0, latency="throughput",
-                 hydrographs_on_every_rank=False, comm=None, exchange=None):
+                 hydrographs_on_every_rank=False, comm=None, exchange=None, reservoir_da_ncol=None):
         """comm / exchange (several ranks): the communicator -- default: the one given to ``router.enable_device_exchange`` -- and
         how the daily cut-edge hydrographs travel: "device" (gather kernel -> all-gather on the exchange stream -> boundary rows,
         everything in HBM: RCCL over xGMI) or "host" (through ``comm.all_gather_rows_host``: any communicator with that method,
         ``all_reduce_max_host`` and ``barrier`` -- a transport without device collectives; the days of slack the trunk's lag gives
-        cover the round trip).  Default: "device" when the router has a device exchange, else "host"."""
+        cover the round trip).  Default: "device" when the router has a device exchange, else "host".
+        reservoir_da_ncol (a router with ``reservoir_da``): the most columns (usgs, usace, rfc) a day's tables may have; default:
+        as many as the declared tables."""
+        self._rda_ncol = reservoir_da_ncol
         if latency not in ("throughput", "low"):
             raise ValueError("latency must be 'throughput' or 'low'")
         self.r = router
@@ -409,7 +412,7 @@ class RouteStream:
         return {"el": el, "days_routed": total, "warmup": wu, "hyd": last[1], "final": last[2], "fvd": last[3] if len(last) > 3 else None,
                 "info": self.last_info, "push_ms": push_ms}
 
-    def route(self, forcings, state0=None, prepared=False, observations=None, lastobs=None, da_parameters=None):
+    def route(self, forcings, state0=None, prepared=False, observations=None, lastobs=None, da_parameters=None, reservoir_da=None):
         """generator of (day, hydrographs, final_state[, fvd]) -- see the class.  prepared: the arrays hold this rank's rows only
         (``prepare_days``).
 
@@ -422,13 +425,50 @@ class RouteStream:
         are resolved on the host as the drop-in resolves a window's, a gage row starts a day from the day's first observation
         (column 0, where it is not NaN: mc_reach.pyx:404-411), and the last observations go from day to day as between two
         calls of the window path: the values as they are, the times less the day's length.  ``da_parameters``:
-        {"da_decay_coefficient": 120.0, "routing_period": the router's dt}."""
+        {"da_decay_coefficient": 120.0, "routing_period": the router's dt}.
+
+        A router with ``reservoir_da`` (reservoir types 2-5): ``reservoir_da`` is an iterable parallel to ``forcings`` that yields
+        each day's tables ``(usgs, usace, rfc[, rfc_reset_idx])`` as ``RoutingPlan.stream_push`` takes them (times from the day's
+        start; the state is the device's), and the dict gains "reservoir_da": the three state tuples the day left, in the layout
+        of elements [4], [5], [7] of ``compute_network_structured`` 's result -- (ids, update_time, prev_persisted_flow,
+        persistence_index, persistence_update_time) for usgs and usace, (ids, update_time, timeseries_idx) for rfc, the times
+        counted from the next day's start -- which a caller writes back into its ``*_param_df`` as ``update_after_compute``
+        does.  Rows of a table that no reservoir of the router uses pass through as the loop passes them."""
         r, nsteps, qts = self.r, self.nsteps, self.qts
         P = self.plan if self.plan is not None else self._setup()
         res, gages = getattr(r, "_reservoirs", None), getattr(r, "_gages", None)
         extras = res is not None or gages is not None
         nres = 0 if res is None else res[0].shape[0]
         ngage = 0 if gages is None else gages.shape[0]
+        rda = getattr(r, "_reservoir_da", None)
+        if reservoir_da is not None and rda is None:
+            raise ValueError("reservoir_da needs a router with data-assimilation reservoirs (ShardedRouter(..., stream=True, "
+                             "reservoirs=..., reservoir_da=...))")
+        if rda is not None:
+            if reservoir_da is None:
+                raise ValueError("the router has data-assimilation reservoirs: route(..., reservoir_da=...) must yield every day's tables")
+            rda_it = iter(reservoir_da)
+            rda_kind, rda_trow = rda[0], np.asarray(rda[1], dtype=np.int64)
+            f32, i32 = (lambda a: np.array(a, dtype=np.float32)), (lambda a: np.array(a, dtype=np.int32))
+            n_of = [0 if t is None else len(t[0]) for t in rda[2:5]]
+            ids = rda[5] if len(rda) > 5 else [np.arange(n) for n in n_of]
+            # the state of every table row as the reference's loop hands it from run set to run set (mc_reach.pyx:820-837)
+            hyb = [[i32(ids[k])] + ([f32(rda[2 + k][2])[:, j] for j in range(4)] if n_of[k] else [f32([])] * 4) for k in (0, 1)]
+            rfc_state = [i32(ids[2]), f32(rda[4][1]) if n_of[2] else f32([]), i32(rda[4][2])[:, 0] if n_of[2] else i32([])]
+            rda_t_end = np.float32(np.float32(nsteps) * np.float32(res[2]))
+
+            def rda_tuples(state, tsidx):
+                for k in (0, 1):
+                    hyb[k][1], hyb[k][4] = hyb[k][1] - rda_t_end, hyb[k][4] - rda_t_end
+                    hyb[k][2], hyb[k][3] = hyb[k][2].copy(), hyb[k][3].copy()
+                rfc_state[1], rfc_state[2] = rfc_state[1] - rda_t_end, rfc_state[2].copy()
+                for i, (kd, tr) in enumerate(zip(rda_kind.tolist(), rda_trow.tolist())):
+                    if kd in (2, 3):
+                        for j in range(4):
+                            hyb[kd - 2][1 + j][tr] = state[i, j]
+                    elif kd in (4, 5):
+                        rfc_state[1][tr], rfc_state[2][tr] = state[i, 0], tsidx[i]
+                return tuple(hyb[0]), tuple(hyb[1]), tuple(rfc_state)
         if observations is not None and not ngage:
             raise ValueError("observations need a router with gages (ShardedRouter(..., stream=True, gages=rows))")
         if ngage:
@@ -476,7 +516,8 @@ class RouteStream:
             lmax_all = int(self.comm.all_reduce_max_host(np.array([lmax_mine], dtype=np.float64))[0])
             slots = max(slots, (-(-lmax_all // tpd0) if lmax_all else 0) + 3 + (1 if want_fvd else 0))
         P.stream_begin(nsteps, qts, slots=slots, full_output=self.full_output and not self.output_stride,
-                       output_stride=self.output_stride)
+                       output_stride=self.output_stride,
+                       **({} if rda is None else {"reservoir_da": True if self._rda_ncol is None else self._rda_ncol}))
         self.info = info = P.stream_info()
         D, tpd, lmax = info["slots"], info["tiles_per_day"], info["lag_max"]
         keep = nsteps // self.output_stride if self.output_stride else nsteps
@@ -492,6 +533,8 @@ class RouteStream:
         tabs = [(_lib.result_empty((ngage, nsteps), np.uint8, always_pinned=True), _lib.result_empty((ngage, nsteps), dtype, always_pinned=True),
                  _lib.result_empty((ngage, nsteps), dtype, always_pinned=True), _lib.result_empty((ngage,), dtype, always_pinned=True))
                 if ngage else None for _ in range(3)]
+        rdas = [(_lib.result_empty((nres, 4), np.float32, always_pinned=True), _lib.result_empty((nres,), np.int32, always_pinned=True))
+                if rda is not None else None for _ in range(D)]
         lastobs_of = {}
         # when a day's products are waited for: a day after they were queued (the host then never waits for launches it has
         # just queued -- the device always holds a day of work); latency="low": right after the day's own push (flushed)
@@ -551,6 +594,8 @@ class RouteStream:
             item = (day, hyd, fin, fvd) if want_fvd else (day, hyd, fin)
             if extras:
                 item += ({"reservoir_inflow": rinf[k], "nudge": nudg[k], "lastobs": lastobs_of.pop(day, (None, None))},)
+                if rda is not None:                     # (days are delivered in order: the host's copy of the state moves on with them)
+                    item[-1]["reservoir_da"] = rda_tuples(*rdas[k])
             return item
 
         d, nxt, pending = 0, first, 0
@@ -575,6 +620,12 @@ class RouteStream:
                 lastobs_of[d] = (lt_fin, lv_fin)
                 lv, lt = lv_fin, (lt_fin - day_len).astype(np.float32)       # (the next day counts from its own start)
             more = {"nudging": nudging, "nudge": nudg[d % D], "reservoir_inflow": rinf[d % D]} if extras else {}
+            if rda is not None:
+                try:
+                    more["reservoir_da"] = next(rda_it)
+                except StopIteration:
+                    raise ValueError(f"reservoir_da ended before the forcings (day {d})") from None
+                more["reservoir_da_state"] = rdas[d % D]
             P.stream_push(q, rowset=r._rsS_out, hyd=hyds[d % D], q0=fins[d % D], fvd=fvds[d % D], **more)
             if low:
                 if multi:

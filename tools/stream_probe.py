@@ -1,7 +1,9 @@
 """A stream of windows (trmc_stream_*) against the same days routed one by one on the same plan: every day's final state of every
 row and the hydrographs of sampled rows bit for bit, and what a day costs either way.
   python tools/stream_probe.py [--nseg N] [--days D] [--wide-min-rows R] [--hint] [--stride n] [--full]
-                               [--reservoirs N --gages M]   level-pool waterbodies and nudged gages scattered over the network"""
+                               [--reservoirs N --gages M]   level-pool waterbodies and nudged gages scattered over the network
+                               [--reservoir-da N]           N of those waterbodies are of types 2-5 (hybrid persistence, RFC series)
+                                                            with synthetic tables: their data assimilation rides in the stream"""
 import argparse
 import os
 import sys
@@ -29,8 +31,11 @@ ap.add_argument("--slots", type=int, default=0)
 ap.add_argument("--velocity-on-demand", type=int, default=0)
 ap.add_argument("--later", type=int, default=0, help="hand a day over this many days later than its last row allows (and hold as many more slots)")
 ap.add_argument("--reservoirs", type=int, default=0, help="level-pool reservoirs scattered over the network (rows with an upstream row)")
+ap.add_argument("--reservoir-da", type=int, default=0, help="so many of the --reservoirs are of types 2, 3, 4, 5 in turn, with synthetic tables")
 ap.add_argument("--gages", type=int, default=0, help="nudged gages scattered over the network (observations: 70 %% valid, lognormal)")
 a = ap.parse_args()
+if a.reservoir_da > a.reservoirs:
+    ap.error("--reservoir-da counts among the --reservoirs")
 _lib.single_hw_queue_per_priority("stream_probe")
 nnet = S.CONUS_NNET if a.nseg == S.CONUS_NSEG else max(1, a.nseg // 185)
 net = S.generate(a.nseg, nnet, cache_dir=os.environ.get("TRMC_SYNTH_CACHE", "/tmp"))
@@ -61,6 +66,40 @@ if a.reservoirs or a.gages:
     par = np.stack([rng.uniform(0.2, 5.0, nl), np.full(nl, 113.0), rng.uniform(0.5, 4.0, nl), np.full(nl, 0.1), np.full(nl, 100.0),
                     np.full(nl, 0.4), np.full(nl, 110.0), rng.uniform(10.0, 60.0, nl), np.full(nl, 10.0)], 1).astype(np.float32)
     q0[lakes, 2] = rng.uniform(104.0, 111.0, nl).astype(np.float32)     # the pools' elevations live in the depth slot
+    if a.reservoir_da:
+        # types 2, 3, 4, 5 in turn; the same observations every day (times from the day's start: 24 h back to 24 h on, every 15
+        # minutes), a forecast series of 48 hourly values
+        nda = a.reservoir_da
+        da_kind = np.zeros(nl, np.int32)
+        da_kind[np.sort(rng.choice(nl, nda, replace=False))] = 2 + np.arange(nda) % 4
+        da_trow = np.zeros(nl, np.int32)
+        da_n = [int(np.count_nonzero(da_kind == 2)), int(np.count_nonzero(da_kind == 3)), int(np.count_nonzero(da_kind >= 4))]
+        for sel in (da_kind == 2, da_kind == 3, da_kind >= 4):
+            da_trow[sel] = np.arange(np.count_nonzero(sel))
+        da_time = (np.arange(193, dtype=np.float32) - 96) * np.float32(900.0)
+        da_obs = []
+        for k in range(2):
+            o = rng.lognormal(np.log(2.0), 1.0, (da_n[k], 193)).astype(np.float32)
+            o[rng.random(o.shape) < 0.2] = np.nan
+            da_obs.append(o)
+        da_series = rng.lognormal(np.log(2.0), 1.0, (da_n[2], 48)).astype(np.float32)
+        da_t_end = np.float32(np.float32(nsteps) * np.float32(300.0))
+
+        def da_tables(state=None, tsidx=None):
+            """(usgs, usace, rfc) as set_reservoir_da takes them; state / tsidx [nres]: what the day before left (None: the start)"""
+            out = []
+            for k in range(2):
+                st = np.tile(np.array([0.0, 1.0, 0.0, 0.0], np.float32), (da_n[k], 1))
+                if state is not None:
+                    st[da_trow[da_kind == 2 + k]] = state[da_kind == 2 + k]
+                out.append((da_obs[k], da_time, st) if da_n[k] else None)
+            ut = np.zeros(da_n[2], np.float32)
+            ipar = np.tile(np.array([0, 47, 1, 3600, 10], np.int32), (da_n[2], 1))
+            if state is not None:
+                ut[da_trow[da_kind >= 4]] = state[da_kind >= 4, 0]
+                ipar[da_trow[da_kind >= 4], 0] = tsidx[da_kind >= 4]
+            out.append((da_series, ut, ipar) if da_n[2] else None)
+            return out
     t0 = time.perf_counter()
     for d in range(len(days) if a.gages else 0):
         usgs = rng.lognormal(np.log(0.5), 1.0, (a.gages, nsteps + 1)).astype(np.float32)
@@ -91,21 +130,32 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
             p.set_reservoirs(lakes, par, 300.0)
         if gages.size:
             p.stream_set_gages(gages)
+    da_state = da_tsidx = None
     if not a.no_check:
         t0 = time.perf_counter()
         for d in range(a.days):
-            p.upload_forcing(nsteps, days[d % len(days)], q0 if d == 0 else None)
+            if a.reservoir_da:              # (the state through the host, the times less the day's length: mc_reach.pyx:820-837)
+                p.set_reservoir_da(da_kind, da_trow, *da_tables(da_state, da_tsidx))
+            # (set_reservoir_da stages a new window: the state the last one left goes in again explicitly)
+            p.upload_forcing(nsteps, days[d % len(days)], q0 if d == 0 else (ref[-1][0] if a.reservoir_da else None))
             if tabs:
                 p.set_nudging(nsteps, gages, *tabs[d % len(days)])
             st = p.route_device(nsteps, qts, True)
             fin = p.download_final_state()
             hyd = p.gather_flow_rows(sample)
             fvd = p.download_fvd(a.stride) if (a.stride or a.full) else None
-            ref.append((fin, hyd, fvd, p.download_reservoir_inflow() if a.reservoirs else None, p.download_nudge() if tabs else None))
+            if a.reservoir_da:
+                da_state, da_tsidx = p.download_reservoir_da()
+                da_state[da_kind != 0, 0] -= da_t_end
+                da_state[(da_kind == 2) | (da_kind == 3), 3] -= da_t_end
+            ref.append((fin, hyd, fvd, p.download_reservoir_inflow() if a.reservoirs else None, p.download_nudge() if tabs else None,
+                        (da_state.copy(), da_tsidx.copy()) if a.reservoir_da else None))
         print(f"one by one: {(time.perf_counter() - t0) / a.days * 1e3:.2f} ms per day (host loop, downloads included); window ms_main {st['ms_main']:.2f}", flush=True)
     # the stream
+    if a.reservoir_da:
+        p.set_reservoir_da(da_kind, da_trow, *da_tables())
     p.upload_forcing(nsteps, days[0], q0)
-    p.stream_begin(nsteps, qts, slots=a.slots + a.later if a.slots else (a.later and 2 + -(-(int(p.lags()[0].max(initial=0)) + 1) // (nsteps // p.tile_steps)) + a.later), full_output=a.full and not a.stride, output_stride=a.stride)
+    p.stream_begin(nsteps, qts, reservoir_da=bool(a.reservoir_da) or None, slots=a.slots + a.later if a.slots else (a.later and 2 + -(-(int(p.lags()[0].max(initial=0)) + 1) // (nsteps // p.tile_steps)) + a.later), full_output=a.full and not a.stride, output_stride=a.stride)
     info = p.stream_info()
     print("stream:", info, flush=True)
     D = info["slots"]
@@ -115,6 +165,9 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
     fvds = [_lib.result_empty((n, keep, 3), np.float32, always_pinned=True) for _ in range(D)] if (a.stride or a.full) else [None] * D
     rins = [_lib.result_empty((a.reservoirs, nsteps), np.float32, always_pinned=True) if a.reservoirs else None for _ in range(D)]
     nuds = [_lib.result_empty((a.gages, nsteps), np.float32, always_pinned=True) if tabs else None for _ in range(D)]
+    rdas = [(_lib.result_empty((a.reservoirs, 4), np.float32, always_pinned=True), _lib.result_empty((a.reservoirs,), np.int32, always_pinned=True))
+            if a.reservoir_da else None for _ in range(D)]
+    da_day = da_tables() if a.reservoir_da else None
     got = []
     behind = (info["lag_max"] + info["tiles_per_day"]) // info["tiles_per_day"] + a.later
     ok = True
@@ -126,7 +179,10 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
         marks.append(time.perf_counter())
         if a.no_check:
             return
-        fin, hyd, fvd, rin, nud = ref[e]
+        fin, hyd, fvd, rin, nud, rda = ref[e]
+        if rda is not None and not (np.array_equal(rda[0].view(np.uint32), rdas[e % D][0].view(np.uint32)) and np.array_equal(rda[1], rdas[e % D][1])):
+            ok = False
+            print(f"   day {e}: reservoir data-assimilation state differs", flush=True)
         for name, x, y in (("reservoir inflow", rin, rins[e % D]), ("nudge", nud, nuds[e % D])):
             if x is not None and not np.array_equal(x.view(np.uint32), y.view(np.uint32)):
                 ok = False
@@ -140,7 +196,7 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
     t0 = time.perf_counter()
     for d in range(a.days):
         p.stream_push(pinned[d % len(days)], rowset=rs, hyd=hyds[d % D], q0=fins[d % D], fvd=fvds[d % D],
-                      nudging=tabs[d % len(days)] if tabs else None, nudge=nuds[d % D], reservoir_inflow=rins[d % D])
+                      nudging=tabs[d % len(days)] if tabs else None, nudge=nuds[d % D], reservoir_inflow=rins[d % D], reservoir_da=da_day, reservoir_da_state=rdas[d % D])
         e = d - behind
         if e >= 0:
             take(e)
