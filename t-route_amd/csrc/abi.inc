@@ -324,7 +324,7 @@ int trmc_plan_create_opt(int64_t nseg, const int64_t *up_ptr, const int64_t *up_
         for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreate(&pl->ev[i]);
         if (e != hipSuccess) return bail(fail(TRMC_EHIP, std::string("stream/event setup: ") + hipGetErrorString(e)));
     }
-    int rc = precision == 32 ? upload_params<float>(pl, params) : upload_params<double>(pl, params);
+    int rc = by_precision(pl, [&](auto t) { return upload_params<decltype(t)>(pl, params); });
     if (rc) return bail(rc);
     std::vector<int32_t> level_plan((size_t)pl->nseg_pad, 0);
     for (int64_t p = 0; p < nseg; ++p) level_plan[p] = pl->topo.level_of_row[pl->topo.row_of_pos[p]];
@@ -1135,7 +1135,6 @@ int trmc_route_device(trmc_plan *pl, int nsteps, int qts_subdivisions, int assum
     if (int rc = settle_deferred_state(pl)) return rc;
     if (int rc = route_check(pl, nsteps, qts_subdivisions, false)) return rc;
     if (int rc = lag_check(pl, assume_short_ts)) return rc;
-    const bool f = pl->precision == 32;
     const int t_last = nsteps + (assume_short_ts ? pl->maxlag : 0);
     int rc;
     if (pl->flow) {
@@ -1143,10 +1142,12 @@ int trmc_route_device(trmc_plan *pl, int nsteps, int qts_subdivisions, int assum
         if (!rc) rc = flow_route_advance(pl, t_last);
         if (!rc) rc = flow_route_end(pl);
     } else {
-        rc = f ? route_begin_t<float>(pl, nsteps, qts_subdivisions, assume_short_ts)
-               : route_begin_t<double>(pl, nsteps, qts_subdivisions, assume_short_ts);
-        if (!rc) rc = f ? route_advance_t<float>(pl, t_last) : route_advance_t<double>(pl, t_last);
-        if (!rc) rc = f ? route_end_t<float>(pl) : route_end_t<double>(pl);
+        rc = by_precision(pl, [&](auto t) {
+            using T = decltype(t);
+            int rc = route_begin_t<T>(pl, nsteps, qts_subdivisions, assume_short_ts);
+            if (!rc) rc = route_advance_t<T>(pl, t_last);
+            return rc ? rc : route_end_t<T>(pl);
+        });
     }
     if (rc) pl->run.active = false;
     return rc;
@@ -1158,8 +1159,7 @@ int trmc_route_begin(trmc_plan *pl, int nsteps, int qts_subdivisions, int assume
     if (int rc = route_check(pl, nsteps, qts_subdivisions, true)) return rc;
     if (int rc = lag_check(pl, assume_short_ts)) return rc;
     const int rc = pl->flow ? flow_route_begin(pl, nsteps, qts_subdivisions, assume_short_ts)
-                   : pl->precision == 32 ? route_begin_t<float>(pl, nsteps, qts_subdivisions, assume_short_ts)
-                                         : route_begin_t<double>(pl, nsteps, qts_subdivisions, assume_short_ts);
+                         : by_precision(pl, [&](auto t) { return route_begin_t<decltype(t)>(pl, nsteps, qts_subdivisions, assume_short_ts); });
     if (rc) pl->run.active = false;
     return rc;
 }
@@ -1179,7 +1179,7 @@ int trmc_route_advance(trmc_plan *pl, int t_end)
     if (t_end == pl->run.t_done) return 0;
     if (int rc = use_device(pl)) return rc;
     if (pl->flow) return flow_route_advance(pl, t_end);
-    return pl->precision == 32 ? route_advance_t<float>(pl, t_end) : route_advance_t<double>(pl, t_end);
+    return by_precision(pl, [&](auto t) { return route_advance_t<decltype(t)>(pl, t_end); });
 }
 
 int trmc_route_end(trmc_plan *pl)
@@ -1195,7 +1195,7 @@ int trmc_route_end(trmc_plan *pl)
         return fail(TRMC_ESTATE, "trmc_route_end before every timestep was queued; window abandoned");
     }
     if (int rc = use_device(pl)) return rc;
-    const int rc = pl->flow ? flow_route_end(pl) : pl->precision == 32 ? route_end_t<float>(pl) : route_end_t<double>(pl);
+    const int rc = pl->flow ? flow_route_end(pl) : by_precision(pl, [&](auto t) { return route_end_t<decltype(t)>(pl); });
     if (rc) pl->run.active = false;
     return rc;
 }
@@ -1545,7 +1545,7 @@ int trmc_fetch_begin_fvd(trmc_plan *pl, int32_t rowset, void *hyd_host, void *q0
     if (int rc = use_device(pl)) return rc;
     if (int rc = ensure_copy_stream(pl)) return rc;
     if (in_window) { // (the window's own end -- transposing launches, the clock's events -- first)
-        if (int rc = pl->precision == 32 ? route_end_queue<float>(pl) : route_end_queue<double>(pl)) return rc;
+        if (int rc = by_precision(pl, [&](auto t) { return route_end_queue<decltype(t)>(pl); })) return rc;
     }
     const int32_t T_ = in_window ? pl->run.nsteps : pl->routed_nsteps;
     const int64_t nrows = hyd_host ? pl->rowset_n[rowset] : 0;
@@ -1770,7 +1770,7 @@ int trmc_plan_chain_from(trmc_plan *dst, trmc_plan *src)
         || dst->topo.row_of_pos != src->topo.row_of_pos)
         return fail(TRMC_EINVAL, "the two plans must hold the same network in the same order (same inputs, same cost hint)");
     if (int rc = use_device(dst)) return rc;
-    return dst->precision == 32 ? chain_from_t<float>(dst, src, dst->staged_nsteps) : chain_from_t<double>(dst, src, dst->staged_nsteps);
+    return by_precision(dst, [&](auto t) { return chain_from_t<decltype(t)>(dst, src, dst->staged_nsteps); });
 }
 
 int trmc_selfcheck_fast_arith(int device, int what, int64_t n, uint64_t seed, int64_t *checked_out, int64_t *mismatches_out)

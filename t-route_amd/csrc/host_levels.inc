@@ -48,6 +48,21 @@ int use_device(const trmc_plan *pl)
     return 0;
 }
 
+// f(T()) with T the plan's element type
+template <class F> inline int by_precision(const trmc_plan *pl, F &&f) { return pl->precision == 32 ? f(float()) : f(double()); }
+
+// `v` grown to n events: ones that time (hipEventCreate) or ones that only order streams (hipEventDisableTiming)
+inline int ensure_events(std::vector<hipEvent_t> &v, size_t n, bool timing)
+{
+    while (v.size() < n) {
+        hipEvent_t e = nullptr;
+        if (timing) HIP_TRY(hipEventCreate(&e));
+        else HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        v.push_back(e);
+    }
+    return 0;
+}
+
 // a kernel that reads the result planes of the last window has just been queued on the plan's stream (outside a window)
 int note_gather(trmc_plan *pl, bool also_in_window = false)
 {
@@ -127,7 +142,7 @@ template <class T> StepArgs<T> step_args(trmc_plan *pl, int nsteps, int qts)
     a.out = (T *)pl->out.p;
     a.row_of_pos = (const int32_t *)pl->row_of_pos.p;
     a.out_vec = sizeof(T) == 4 && nsteps % 4 == 0 && pl->run.wide_k % 4 == 0;
-    a.cls_last = nullptr; // (route_advance_t switches the in-block partition on for its wide tiles)
+    a.cls_last = nullptr; // (tile_args switches the in-block partition on for the tiles of a window or a stream)
     return a;
 }
 
@@ -137,31 +152,96 @@ inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBl
 // 8-way CONUS partition, ms per day: 64: 2.70, 32: 2.82, 16: 3.03, 8: 2.86 -- more wavefronts of that cost, not a shorter chain)
 inline int32_t hot_wave_rows_of(const trmc_plan *pl) { return pl->opt.hot_wave_rows > 0 ? pl->opt.hot_wave_rows : 64; }
 
-template <class T, bool SHORT, bool TOL>
-inline void launch_step_m(hipStream_t st, const StepArgs<T> &a, int32_t s0, int32_t s1, int32_t d)
+// WHAT THE TILES OF A PLAN'S W WIDE LEVELS ARE LAUNCHED WITH, for a window (route_advance_t) and for a stream of days
+// (stream.inc) alike -- both use the plan's one set of buffers and hand it on to each other: the in-block partition (rows dealt to
+// the threads of every block of a tile by the cost class they showed in the tile before, k_mc_tile's prologue;
+// trmc_plan_options.tile_perm_group: > 0 on, 0 off, < 0 by the plan's kind) and, with it unless switched off, the hot rows
+// (trmc_plan_options.hot_rows).  tile_setup is idempotent: the buffers are made, and cleared, only where they are new (no history yet:
+// one class) or the tier is of another size (the lists start empty, the marks are cleared).
+// Hot rows measured on the CONUS sequence (ms per day, with / without): plan built from the topology alone 17.4 / 19.5; cost-ordered
+// plan on its own kind of days 16.22 / 16.34 -- once the list's blocks were made the FIRST of the launch: behind the others (the
+// costliest rows of all started last, every launch ended on them) it was 16.7 / 16.2 and 18.3 / 19.4.
+inline bool tile_partition_on(const trmc_plan *pl)
 {
-    const int64_t n = (int64_t)s1 - s0;
-    const dim3 grid((unsigned)((n + kStepBlock - 1) / kStepBlock)), block(kStepBlock);
-    if constexpr (sizeof(T) == 4 && !TOL) {
-        if (a.res_da) { // (trmc_set_reservoir_da: exact fp32 plans only)
-            if (SHORT && a.lag) hipLaunchKernelGGL((k_mc_step_rda<SHORT, SHORT>), grid, block, 0, st, a, s0, s1, d, (d - 1) / a.qts);
-            else hipLaunchKernelGGL((k_mc_step_rda<SHORT, false>), grid, block, 0, st, a, s0, s1, d, (d - 1) / a.qts);
-            return;
-        }
-    }
-    if (SHORT && a.lag)
-        hipLaunchKernelGGL((k_mc_step<T, SHORT, SHORT, TOL>), grid, block, 0, st, a, s0, s1, d, (d - 1) / a.qts);
-    else
-        hipLaunchKernelGGL((k_mc_step<T, SHORT, false, TOL>), grid, block, 0, st, a, s0, s1, d, (d - 1) / a.qts);
+    return pl->opt.tile_perm_group > 0 || (pl->opt.tile_perm_group < 0 && kTilePartitionDefault(pl->hinted));
 }
-// (tol: the plan's arithmetic is TRMC_ARITH_TOLERANCE -- precision-32 plans only, trmc_plan_create_opt sees to that)
+inline bool tile_hot_rows_on(const trmc_plan *pl, int32_t W) { return tile_partition_on(pl) && pl->opt.hot_rows != 0 && W > 0; }
+// ... the buffers (the only place that makes or clears them; what is queued goes to `st`) ...
+inline int tile_setup(trmc_plan *pl, hipStream_t st, int32_t W)
+{
+    if (!tile_partition_on(pl)) return 0;
+    const size_t np = (size_t)pl->nseg_pad;
+    const bool fresh = pl->cls_last.bytes < np;
+    if (int rc = pl->cls_last.ensure(np)) return rc;
+    if (fresh) HIP_TRY(hipMemsetAsync(pl->cls_last.p, 0, np, st));
+    if (!tile_hot_rows_on(pl, W)) return 0;
+    const int32_t rows = pl->topo.lvl_ptr[W] - pl->topo.lvl_ptr[0];
+    const int32_t cap = std::max<int32_t>(kTileBlock, (rows / 32 + kTileBlock - 1) / kTileBlock * kTileBlock);
+    if (pl->hot_cap != cap || !pl->hot_list.p) {
+        const size_t hl = ((size_t)3 * cap + 2 * np) * sizeof(int32_t); // (lists + the two mark columns, k_mc_tile)
+        if (int rc = pl->hot_list.ensure(hl)) return rc;
+        const bool first = !pl->hot_cnt.p;
+        if (int rc = pl->hot_cnt.ensure(4 * sizeof(int32_t))) return rc;
+        HIP_TRY(hipMemsetAsync(pl->hot_cnt.p, 0, (first ? 4 : 3) * sizeof(int32_t), st));
+        HIP_TRY(hipMemsetAsync(pl->hot_list.p, 0, hl, st)); // (no stamp equals a launch number: they start at 1)
+        pl->hot_cap = cap;
+    }
+    return 0;
+}
+// ... and the arguments of the launches behind a tile_setup for the same W (step_args left all of them switched off)
+template <class T> inline void tile_args(const trmc_plan *pl, int32_t W, StepArgs<T> &a)
+{
+    if (tile_partition_on(pl)) a.cls_last = (uint8_t *)pl->cls_last.p;
+    if (!tile_hot_rows_on(pl, W)) return;
+    a.hot_list = (int32_t *)pl->hot_list.p;
+    a.hot_cnt = (int32_t *)pl->hot_cnt.p;
+    a.hot_cap = pl->hot_cap;
+    a.hot_wave_rows = hot_wave_rows_of(pl);
+    a.hot_home = (a.hot_cap + a.hot_wave_rows * (kTileBlock / 64) - 1) / (a.hot_wave_rows * (kTileBlock / 64));
+}
+// the turn of one launch that carries the lists: its number among the plan's, and which of the three lists it reads
+template <class T> inline void tile_turn(trmc_plan *pl, StepArgs<T> &a)
+{
+    a.hot_seq = (int32_t)(pl->tile_seq & 0x3fffffff) + 1;
+    a.hot_cur = (int32_t)(pl->tile_seq++ % 3);
+}
+
+// THE INSTANCE OF A STEP OR TILE KERNEL is chosen here and nowhere else: every launch function below hands its kernel family a
+// set of std::integral_constant flags.  The rules: reservoir data assimilation (_rda) on exact fp32 plans only
+// (trmc_set_reservoir_da sees to that), the tolerance arithmetic on precision-32 plans only (trmc_plan_create_opt), never both.
+template <bool B> using flag = std::integral_constant<bool, B>;
+template <class T, class Go> inline void with_arithmetic(const StepArgs<T> &a, bool tol, Go &&go) // go(rda, tol)
+{
+    if constexpr (sizeof(T) == 4) {
+        if (a.res_da) return go(flag<true>{}, flag<false>{});
+        if (tol) return go(flag<false>{}, flag<true>{});
+    }
+    go(flag<false>{}, flag<false>{});
+}
+// ... and of k_mc_tile / k_mc_ctile: go(rda, tol, dec, lazy).  dec: the launch writes the kept steps of a decimated result; lazy:
+// velocity where it is handed on only -- the LAZYV instances assemble no full result, and the _rda instances have no LAZYV form
+template <class T, class Go> inline void with_tile_instance(const StepArgs<T> &a, bool tol, Go &&go)
+{
+    const bool dec = a.dec != nullptr, lazy = a.v_every != 0 && !a.out;
+    with_arithmetic(a, tol, [&](auto rda, auto tl) {
+        auto by_dec = [&](auto lz) { dec ? go(rda, tl, flag<true>{}, lz) : go(rda, tl, flag<false>{}, lz); };
+        if constexpr (rda()) by_dec(flag<false>{});
+        else lazy ? by_dec(flag<true>{}) : by_dec(flag<false>{});
+    });
+}
+
 template <class T, bool SHORT>
 inline void launch_step(hipStream_t st, const StepArgs<T> &a, int32_t s0, int32_t s1, int32_t d, bool tol)
 {
-    if constexpr (sizeof(T) == 4) {
-        if (tol) return launch_step_m<T, SHORT, true>(st, a, s0, s1, d);
-    }
-    launch_step_m<T, SHORT, false>(st, a, s0, s1, d);
+    const int64_t n = (int64_t)s1 - s0;
+    const dim3 grid((unsigned)((n + kStepBlock - 1) / kStepBlock)), block(kStepBlock);
+    with_arithmetic(a, tol, [&](auto rda, auto tl) {
+        auto go = [&](auto lag) {
+            if constexpr (rda()) hipLaunchKernelGGL((k_mc_step_rda<SHORT, lag()>), grid, block, 0, st, a, s0, s1, d, (d - 1) / a.qts);
+            else hipLaunchKernelGGL((k_mc_step<T, SHORT, lag(), tl()>), grid, block, 0, st, a, s0, s1, d, (d - 1) / a.qts);
+        };
+        (SHORT && a.lag) ? go(flag<SHORT>{}) : go(flag<false>{});
+    });
 }
 // one launch of k_mc_tile: positions [p0, p1), `tile` = launch index + the first level of the tier, K steps
 template <class T>
@@ -170,62 +250,21 @@ inline void launch_tile(hipStream_t st, const StepArgs<T> &a, int32_t p0, int32_
     // (with hot rows: the first a.hot_home blocks take the list, the blocks behind them positions)
     const unsigned home = (unsigned)((p1 - p0 + kTileBlock - 1) / kTileBlock);
     const dim3 grid(home + (a.hot_list ? (unsigned)a.hot_home : 0u)), block(kTileBlock);
-    const bool dec = a.dec != nullptr;
-    const bool lazy = a.v_every != 0 && !a.out; // (velocity where it is handed on only: the LAZYV instances assemble no full result)
-    if constexpr (sizeof(T) == 4) {
-        if (a.res_da) { // (never the tolerance arithmetic: trmc_set_reservoir_da)
-            if (dec) hipLaunchKernelGGL((k_mc_tile_rda<true>), grid, block, 0, st, a, p0, p1, tile, K);
-            else hipLaunchKernelGGL((k_mc_tile_rda<false>), grid, block, 0, st, a, p0, p1, tile, K);
-            return;
-        }
-        if (tol) {
-            if (lazy) {
-                if (dec) hipLaunchKernelGGL((k_mc_tile<T, true, true, true>), grid, block, 0, st, a, p0, p1, tile, K);
-                else hipLaunchKernelGGL((k_mc_tile<T, true, false, true>), grid, block, 0, st, a, p0, p1, tile, K);
-            } else if (dec) hipLaunchKernelGGL((k_mc_tile<T, true, true>), grid, block, 0, st, a, p0, p1, tile, K);
-            else hipLaunchKernelGGL((k_mc_tile<T, true, false>), grid, block, 0, st, a, p0, p1, tile, K);
-            return;
-        }
-    }
-    if (lazy) {
-        if (dec) hipLaunchKernelGGL((k_mc_tile<T, false, true, true>), grid, block, 0, st, a, p0, p1, tile, K);
-        else hipLaunchKernelGGL((k_mc_tile<T, false, false, true>), grid, block, 0, st, a, p0, p1, tile, K);
-        return;
-    }
-    if (dec) hipLaunchKernelGGL((k_mc_tile<T, false, true>), grid, block, 0, st, a, p0, p1, tile, K);
-    else hipLaunchKernelGGL((k_mc_tile<T, false, false>), grid, block, 0, st, a, p0, p1, tile, K);
+    with_tile_instance(a, tol, [&](auto rda, auto tl, auto dec, auto lazy) {
+        if constexpr (rda()) hipLaunchKernelGGL((k_mc_tile_rda<dec()>), grid, block, 0, st, a, p0, p1, tile, K);
+        else hipLaunchKernelGGL((k_mc_tile<T, tl(), dec(), lazy()>), grid, block, 0, st, a, p0, p1, tile, K);
+    });
 }
-
 // one launch of k_mc_ctile: the cluster blocks [b0, b1) of the plan at tile index `tile`
 template <class T>
 inline void launch_ctile(hipStream_t st, const StepArgs<T> &a, const int32_t *cblk_ptr, int32_t b0, int32_t b1, int32_t tile, int32_t K,
                          bool tol)
 {
     const dim3 grid((unsigned)(b1 - b0)), block(kCtileBlock);
-    const bool dec = a.dec != nullptr;
-    const bool lazy = a.v_every != 0 && !a.out;
-    if constexpr (sizeof(T) == 4) {
-        if (a.res_da) { // (see launch_tile)
-            if (dec) hipLaunchKernelGGL((k_mc_ctile_rda<true>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);
-            else hipLaunchKernelGGL((k_mc_ctile_rda<false>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);
-            return;
-        }
-        if (tol) {
-            if (lazy) {
-                if (dec) hipLaunchKernelGGL((k_mc_ctile<T, true, true, true>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);
-                else hipLaunchKernelGGL((k_mc_ctile<T, true, false, true>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);
-            } else if (dec) hipLaunchKernelGGL((k_mc_ctile<T, true, true>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);
-            else hipLaunchKernelGGL((k_mc_ctile<T, true, false>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);
-            return;
-        }
-    }
-    if (lazy) {
-        if (dec) hipLaunchKernelGGL((k_mc_ctile<T, false, true, true>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);
-        else hipLaunchKernelGGL((k_mc_ctile<T, false, false, true>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);
-        return;
-    }
-    if (dec) hipLaunchKernelGGL((k_mc_ctile<T, false, true>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);
-    else hipLaunchKernelGGL((k_mc_ctile<T, false, false>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);
+    with_tile_instance(a, tol, [&](auto rda, auto tl, auto dec, auto lazy) {
+        if constexpr (rda()) hipLaunchKernelGGL((k_mc_ctile_rda<dec()>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);
+        else hipLaunchKernelGGL((k_mc_ctile<T, tl(), dec(), lazy()>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);
+    });
 }
 
 // A routing window runs in three parts so that a caller can interleave other device work (the multi-GPU
@@ -290,11 +329,7 @@ template <class T> int route_begin_t(trmc_plan *pl, int nsteps, int qts, int sho
     const int32_t *row_of_pos = (const int32_t *)pl->row_of_pos.p;
     constexpr int32_t kTile = TRMC_EMIT_TILE;
     const int32_t ntiles = (nsteps + kTile - 1) / kTile;
-    while ((int32_t)pl->tile_ev.size() < ntiles) {
-        hipEvent_t e = nullptr;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        pl->tile_ev.push_back(e);
-    }
+    if (int rc = ensure_events(pl->tile_ev, (size_t)std::max(0, ntiles), false)) return rc;
 
     for (int i = 0; i < 2; ++i) // a receiver of this plan's last window (trmc_plan_chain_from) has read what this window overwrites
         if (pl->released_pending[i]) {
@@ -417,13 +452,8 @@ template <class T> int route_begin_t(trmc_plan *pl, int nsteps, int qts, int sho
             }
             HIP_TRY(hipStreamWaitEvent(pl->wstream, pl->ev[1], 0)); // the tiles start behind the window's set-up
             const size_t ntile = (size_t)std::max(1, (nsteps + r.wide_k - 1) / r.wide_k + W - 1);
-            while (pl->wide_t0.size() < ntile) { // (t0: only the first is used -- a tile starts where the one before it ended)
-                hipEvent_t e0 = nullptr, e1 = nullptr;
-                HIP_TRY(hipEventCreate(&e0));
-                HIP_TRY(hipEventCreate(&e1));
-                pl->wide_t0.push_back(e0);
-                pl->wide_t1.push_back(e1);
-            }
+            if (int rc = ensure_events(pl->wide_t0, ntile, true)) return rc; // (only the first is used: a tile starts where the one before it ended)
+            if (int rc = ensure_events(pl->wide_t1, ntile, true)) return rc;
         }
     }
     HIP_TRY(hipGetLastError());
@@ -482,58 +512,27 @@ template <class T> int route_advance_t(trmc_plan *pl, int t_end)
             // device once the runtime's pool of dependency signals is in use -- and the tail, the critical path, waited
             // 1.2 ms for them.)  One event per tile: it ends the tile for the clock (a tile starts where the one before it
             // ended; the first has a start event of its own) and it is what the tail waits for.
-            // what the tiles of this window are launched with: the in-block partition, the hot rows, the decimated output
-            // (idempotent: the buffers are made and cleared on the first call only)
+            // what the tiles of this window are launched with: the in-block partition and the hot rows (tile_setup: made and
+            // cleared on the first call only), the decimated output
             StepArgs<T> at = a;
             if (r.cl) at.level = (const int32_t *)pl->lagk.p; // (tiles every position runs behind: the level in the slices)
-            {
-                // rows dealt to the threads of every block of a tile by the cost class they showed in the tile before (k_mc_tile's
-                // prologue; trmc_plan_options.tile_perm_group: > 0 on, 0 off, < 0 the default below).
-                const bool use_perm = pl->opt.tile_perm_group > 0 || (pl->opt.tile_perm_group < 0 && kTilePartitionDefault(pl->hinted));
-                if (pl->out_stride > 0 && nsteps / pl->out_stride >= 1) {
-                    r.dec_stride = pl->out_stride;
-                    r.dec_keep = nsteps / pl->out_stride;
-                    if (int rc = pl->dec.ensure((size_t)pl->nseg * r.dec_keep * 3 * sizeof(T))) return rc;
-                    at.dec = (T *)pl->dec.p;
-                    at.dec_stride = r.dec_stride;
-                    at.dec_keep = r.dec_keep;
-                    r.dec_lo = w0;
-                    r.dec_hi = r.cl ? s1 : m1;
-                }
-                if (use_perm) {
-                    const bool fresh = pl->cls_last.bytes < (size_t)pl->nseg_pad;
-                    if (int rc = pl->cls_last.ensure((size_t)pl->nseg_pad)) return rc;
-                    if (fresh) HIP_TRY(hipMemsetAsync(pl->cls_last.p, 0, (size_t)pl->nseg_pad, ws)); // (no history yet: one class)
-                    at.cls_last = (uint8_t *)pl->cls_last.p;
-                    // hot rows (trmc_plan_options.hot_rows): with the partition unless switched off.  Measured on the CONUS sequence
-                    // (ms per day, with / without): plan built from the topology alone 17.4 / 19.5; cost-ordered plan on its own
-                    // kind of days 16.22 / 16.34 -- once the list's blocks were made the FIRST of the launch: behind the others
-                    // (the costliest rows of all started last, every launch ended on them) it was 16.7 / 16.2 and 18.3 / 19.4.
-                    if (pl->opt.hot_rows != 0 && W > 0) {
-                        const int32_t cap = std::max<int32_t>(kTileBlock, ((w1 - w0) / 32 + kTileBlock - 1) / kTileBlock * kTileBlock);
-                        if (pl->hot_cap != cap || !pl->hot_list.p) { // (a tier of another size: the lists start empty, the marks are cleared)
-                            const size_t hl = ((size_t)3 * cap + (size_t)2 * pl->nseg_pad) * sizeof(int32_t); // (lists + the two mark columns)
-                            if (int rc = pl->hot_list.ensure(hl)) return rc;
-                            const bool first = !pl->hot_cnt.p;
-                            if (int rc = pl->hot_cnt.ensure(4 * sizeof(int32_t))) return rc;
-                            HIP_TRY(hipMemsetAsync(pl->hot_cnt.p, 0, (first ? 4 : 3) * sizeof(int32_t), ws));
-                            HIP_TRY(hipMemsetAsync(pl->hot_list.p, 0, hl, ws)); // (no stamp equals a launch number: they start at 1)
-                            pl->hot_cap = cap;
-                        }
-                        at.hot_list = (int32_t *)pl->hot_list.p;
-                        at.hot_cnt = (int32_t *)pl->hot_cnt.p;
-                        at.hot_cap = cap;
-                        at.hot_wave_rows = hot_wave_rows_of(pl);
-                        at.hot_home = (cap + at.hot_wave_rows * (kTileBlock / 64) - 1) / (at.hot_wave_rows * (kTileBlock / 64));
-                    }
-                }
+            if (pl->out_stride > 0 && nsteps / pl->out_stride >= 1) {
+                r.dec_stride = pl->out_stride;
+                r.dec_keep = nsteps / pl->out_stride;
+                if (int rc = pl->dec.ensure((size_t)pl->nseg * r.dec_keep * 3 * sizeof(T))) return rc;
+                at.dec = (T *)pl->dec.p;
+                at.dec_stride = r.dec_stride;
+                at.dec_keep = r.dec_keep;
+                r.dec_lo = w0;
+                r.dec_hi = r.cl ? s1 : m1;
             }
+            if (int rc = tile_setup(pl, ws, W)) return rc;
+            tile_args(pl, W, at);
             if (r.wide_next == 0 && W > 0) {
                 stamp(pl, ws, 0);
                 HIP_TRY(hipEventRecord(pl->wide_t0[0], ws));
                 for (int32_t j = 0; j < ntile; ++j) {
-                    at.hot_seq = (int32_t)(pl->tile_seq & 0x3fffffff) + 1;
-                    at.hot_cur = (int32_t)(pl->tile_seq++ % 3);
+                    tile_turn(pl, at);
                     launch_tile<T>(ws, at, w0, w1, j, K, tol);
                     HIP_TRY(hipEventRecord(pl->wide_t1[(size_t)j], ws));
                     ++r.launches;

@@ -221,7 +221,8 @@ inline hipStream_t stream_last(const trmc_plan *pl, const StreamRun &S)
     return (S.C > 0 || split) ? pl->stream : pl->wstream;
 }
 
-template <class T> StepArgs<T> stream_args(trmc_plan *pl, const StreamRun &S, int64_t g, int64_t days)
+// what every launch of a stream with `days` days pushed is given (but its day, seq_day, and the tiles' set-up: stream_launch)
+template <class T> StepArgs<T> stream_args(trmc_plan *pl, const StreamRun &S, int64_t days)
 {
     StepArgs<T> a = step_args<T>(pl, S.nsteps, S.qts);
     a.q_tm = (T *)S.tm.p;
@@ -233,7 +234,6 @@ template <class T> StepArgs<T> stream_args(trmc_plan *pl, const StreamRun &S, in
     a.level = pl->topo.ncl > 0 ? (const int32_t *)pl->lagk.p : (const int32_t *)pl->level.p;
     a.seq_slots = S.slots;
     a.seq_tpd = S.tpd;
-    a.seq_day = (int32_t)(g / S.tpd);
     a.seq_days = (int32_t)days;
     a.seq_day_min = (int32_t)S.day_min;
     a.slot_tm = (int64_t)S.slot_tm;
@@ -264,8 +264,6 @@ template <class T> StepArgs<T> stream_args(trmc_plan *pl, const StreamRun &S, in
     // (hydrographs and final states are flows and depths): only those steps form it.  trmc_plan_options.velocity_on_demand < 0
     // has every step form it anyway (A/B), and so does a stream with reservoir data assimilation (no LAZYV _rda instances).
     if (!S.want_out && pl->opt.velocity_on_demand >= 0 && !S.rda) a.v_every = S.dec_stride > 0 ? S.dec_stride : -1;
-    // the in-block partition and the hot rows: as in a window (route_advance_t); the buffers were made by trmc_stream_begin
-    if (pl->cls_last.p) a.cls_last = (uint8_t *)pl->cls_last.p;
     return a;
 }
 
@@ -344,8 +342,15 @@ template <class T> int stream_launch(trmc_plan *pl, StreamRun &S, int64_t g_from
     hipStream_t wst = pl->wstream, cst = pl->stream;
     hipStream_t pst = stream_last(pl, S);
     const int32_t ncblk = S.C > 0 ? (int32_t)tp.cblk_ptr.size() - 1 : 0;
+    // the slices on the tile stream carry the partition and the hot rows as a window's do (tile_args: trmc_stream_begin has made
+    // and cleared the buffers); the deeper slices and the clusters the partition alone -- the lists belong to the tile stream's
+    // launches
+    StepArgs<T> as = stream_args<T>(pl, S, days);
+    tile_args(pl, S.W, as);
+    StepArgs<T> a = as;
+    a.hot_list = a.hot_cnt = nullptr;
     for (int64_t g = g_from + 1; g <= g_to; ++g) {
-        StepArgs<T> a = stream_args<T>(pl, S, g, days);
+        a.seq_day = as.seq_day = (int32_t)(g / S.tpd);
         const int32_t tile = (int32_t)(g % S.tpd);
         auto first_obs = [&](hipStream_t st, int32_t p0, int32_t p1) {
             if (S.ngage > 0 && p1 > p0)
@@ -355,16 +360,7 @@ template <class T> int stream_launch(trmc_plan *pl, StreamRun &S, int64_t g_from
         };
         if (S.W > 0 && w1 > w0) {
             first_obs(wst, w0, w1);
-            StepArgs<T> as = a;
-            if (pl->hot_list.p && a.cls_last) {
-                as.hot_list = (int32_t *)pl->hot_list.p;
-                as.hot_cnt = (int32_t *)pl->hot_cnt.p;
-                as.hot_cap = pl->hot_cap;
-                as.hot_wave_rows = hot_wave_rows_of(pl);
-                as.hot_home = (pl->hot_cap + as.hot_wave_rows * (kTileBlock / 64) - 1) / (as.hot_wave_rows * (kTileBlock / 64));
-                as.hot_seq = (int32_t)(pl->tile_seq & 0x3fffffff) + 1;
-                as.hot_cur = (int32_t)(pl->tile_seq++ % 3);
-            }
+            if (as.hot_list) tile_turn(pl, as);
             launch_tile<T>(wst, as, w0, w1, tile, S.K, tol);
             HIP_TRY(hipEventRecord(S.ev_slab[(size_t)(g % kSlabEvents)], wst));
             ++S.launches;
@@ -372,7 +368,7 @@ template <class T> int stream_launch(trmc_plan *pl, StreamRun &S, int64_t g_from
         if (ncblk > 0 || w2 > w1) {
             if (S.W > 0 && g >= 1) HIP_TRY(hipStreamWaitEvent(cst, S.ev_slab[(size_t)((g - 1) % kSlabEvents)], 0));
             first_obs(cst, w1, (int32_t)pl->nseg_pad);
-            if (w2 > w1) { // (the deeper slices: no hot rows here -- the lists belong to the tile stream's launches)
+            if (w2 > w1) { // (the deeper slices)
                 launch_tile<T>(cst, a, w1, w2, tile, S.K, tol);
                 ++S.launches;
             }
@@ -478,24 +474,11 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
         HIP_TRY(hipStreamCreateWithFlags(&pl->wstream, hipStreamNonBlocking));
         HIP_TRY(hipEventCreateWithFlags(&pl->ev_tail, hipEventDisableTiming));
     }
-    auto events = [&](std::vector<hipEvent_t> &v, size_t n) -> int {
-        while (v.size() < n) {
-            hipEvent_t e = nullptr;
-            HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            v.push_back(e);
-        }
-        return 0;
-    };
-    if (int rc = events(S.ev_slab, kSlabEvents)) return rc;
-    if (int rc = events(S.ev_free, (size_t)S.slots)) return rc;
-    if (int rc = events(S.ev_ready, (size_t)S.slots)) return rc;
-    if (int rc = events(S.ev_forcing, (size_t)S.slots)) return rc;
+    if (int rc = ensure_events(S.ev_slab, kSlabEvents, false)) return rc;
+    for (auto *v : {&S.ev_free, &S.ev_ready, &S.ev_forcing})
+        if (int rc = ensure_events(*v, (size_t)S.slots, false)) return rc;
     for (auto *v : {&S.ev_t0, &S.ev_t1})
-        while (v->size() < (size_t)S.slots) {
-            hipEvent_t e = nullptr;
-            HIP_TRY(hipEventCreate(&e));
-            v->push_back(e);
-        }
+        if (int rc = ensure_events(*v, (size_t)S.slots, true)) return rc;
     S.prod.resize((size_t)S.slots);
     for (StreamProd &p : S.prod) {
         if (!p.ev_done) HIP_TRY(hipEventCreateWithFlags(&p.ev_done, hipEventDisableTiming));
@@ -527,28 +510,10 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
                            (const int32_t *)pl->row_of_pos.p, q, q + S.plane /* (the velocity of the state is not an input) */,
                            q + S.plane, (int32_t)pl->nseg);
     }
-    // the in-block partition and the hot rows of the tiles (route_advance_t's set-up, once per stream)
-    const bool use_perm = pl->opt.tile_perm_group > 0 || (pl->opt.tile_perm_group < 0 && kTilePartitionDefault(pl->hinted));
-    if (use_perm) {
-        const bool fresh = pl->cls_last.bytes < np;
-        if (int rc = pl->cls_last.ensure(np)) return rc;
-        if (fresh) HIP_TRY(hipMemsetAsync(pl->cls_last.p, 0, np, st));
-        if (pl->opt.hot_rows != 0 && S.W > 0) {
-            const int32_t w = tp.lvl_ptr[S.W] - tp.lvl_ptr[0];
-            const int32_t cap = std::max<int32_t>(kTileBlock, (w / 32 + kTileBlock - 1) / kTileBlock * kTileBlock);
-            if (pl->hot_cap != cap || !pl->hot_list.p) {
-                const size_t hl = ((size_t)3 * cap + (size_t)2 * np) * sizeof(int32_t); // (lists + the two mark columns, k_mc_tile)
-                if (int rc = pl->hot_list.ensure(hl)) return rc;
-                const bool first = !pl->hot_cnt.p;
-                if (int rc = pl->hot_cnt.ensure(4 * sizeof(int32_t))) return rc;
-                HIP_TRY(hipMemsetAsync(pl->hot_cnt.p, 0, (first ? 4 : 3) * sizeof(int32_t), st));
-                HIP_TRY(hipMemsetAsync(pl->hot_list.p, 0, hl, st));
-                pl->hot_cap = cap;
-            }
-        }
-    } else {
-        pl->cls_last.release();
-    }
+    // the in-block partition and the hot rows of the slices: made and cleared here, in front of ev_begin (the launches' arguments:
+    // tile_args, stream_launch).  A stream leaves no history behind where the partition is off.
+    if (int rc = tile_setup(pl, st, S.W)) return rc;
+    if (!tile_partition_on(pl)) pl->cls_last.release();
     HIP_TRY(hipEventRecord(S.ev_begin, st));
     HIP_TRY(hipStreamWaitEvent(pl->wstream, S.ev_begin, 0));
     if (!S.fst) HIP_TRY(hipStreamCreateWithFlags(&S.fst, hipStreamNonBlocking));
@@ -708,8 +673,7 @@ int trmc_stream_begin(trmc_plan *pl, int nsteps, int qts_subdivisions, int slots
         return fail(TRMC_EINVAL, "Number of columns (timesteps) in Qlat is incorrect: need " + std::to_string((nsteps - 1) / qts_subdivisions + 1)
                                      + ", got " + std::to_string(pl->nq));
     if (output_stride < 0 || slots < 0) return fail(TRMC_EINVAL, "slots and output_stride must be >= 0");
-    const int rc = pl->precision == 32 ? stream_begin_t<float>(pl, nsteps, qts_subdivisions, slots, full_output, output_stride)
-                                       : stream_begin_t<double>(pl, nsteps, qts_subdivisions, slots, full_output, output_stride);
+    const int rc = by_precision(pl, [&](auto t) { return stream_begin_t<decltype(t)>(pl, nsteps, qts_subdivisions, slots, full_output, output_stride); });
     if (rc && pl->seq) pl->seq->active = false;
     return rc;
 }
@@ -823,7 +787,7 @@ int trmc_stream_push_day(trmc_plan *pl, const trmc_stream_day *day)
     if (hyd_host && (rowset < 0 || rowset >= (int32_t)pl->rowsets.size())) return fail(TRMC_EINVAL, "unknown row set");
     if (fvd_host && S.dec_stride == 0 && !S.want_out)
         return fail(TRMC_EINVAL, "the stream was begun without full_output / output_stride: there is no (q, v, d) block to hand over");
-    return pl->precision == 32 ? stream_push_t<float>(pl, *day) : stream_push_t<double>(pl, *day);
+    return by_precision(pl, [&](auto t) { return stream_push_t<decltype(t)>(pl, *day); });
 }
 
 int trmc_stream_push(trmc_plan *pl, const void *qlat, int64_t nq, const void *boundary_q_dev, int32_t rowset, void *hyd_host,
@@ -853,8 +817,8 @@ int trmc_stream_boundary(trmc_plan *pl, int64_t day, const void *q_dev, int64_t 
     hipStream_t st = stream ? (hipStream_t)stream : S.fst;
     const size_t np = (size_t)pl->nseg_pad;
     const int32_t slot = (int32_t)(day % S.slots);
-    auto go = [&](auto zero) -> int {
-        using T = decltype(zero);
+    const int rc = by_precision(pl, [&](auto t) -> int {
+        using T = decltype(t);
         T *q = (T *)S.tm.p + (size_t)slot * S.slot_tm;
         if (day > 0) { // time row 0: where the boundary rows' day before ended (filled by the call for that day, in order)
             const T *qp = (const T *)S.tm.p + (size_t)((day - 1) % S.slots) * S.slot_tm + (size_t)S.nsteps * np;
@@ -864,8 +828,8 @@ int trmc_stream_boundary(trmc_plan *pl, int64_t day, const void *q_dev, int64_t 
                            src_row_stride, index_dev, q, (int32_t)tp.nboundary, S.nsteps, pl->nseg_pad);
         HIP_TRY(hipGetLastError());
         return 0;
-    };
-    if (int rc = pl->precision == 32 ? go(0.0f) : go(0.0)) return rc;
+    });
+    if (rc) return rc;
     HIP_TRY(hipEventRecord(S.ev_bnd, st));
     S.bnd_pending = true;
     return 0;
@@ -897,14 +861,13 @@ int trmc_stream_gather(trmc_plan *pl, int64_t day, int32_t rowset, void *dst_dev
         HIP_TRY(hipStreamWaitEvent(st, S.ev_gat, 0));
     }
     const int32_t slot = (int32_t)(day % S.slots);
-    if (pl->precision == 32)
-        hipLaunchKernelGGL((k_gather_rows<float>), dim3(blocks_for(nrows * S.nsteps)), dim3(kBlock), 0, st, (const float *)S.tm.p + (size_t)slot * S.slot_tm,
-                           (const int32_t *)pl->rowsets[(size_t)rowset].p, (float *)dst_dev, nrows, pl->nseg_pad, S.nsteps, 1);
-    else
-        hipLaunchKernelGGL((k_gather_rows<double>), dim3(blocks_for(nrows * S.nsteps)), dim3(kBlock), 0, st, (const double *)S.tm.p + (size_t)slot * S.slot_tm,
-                           (const int32_t *)pl->rowsets[(size_t)rowset].p, (double *)dst_dev, nrows, pl->nseg_pad, S.nsteps, 1);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return by_precision(pl, [&](auto t) -> int {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_gather_rows<T>), dim3(blocks_for(nrows * S.nsteps)), dim3(kBlock), 0, st, (const T *)S.tm.p + (size_t)slot * S.slot_tm,
+                           (const int32_t *)pl->rowsets[(size_t)rowset].p, (T *)dst_dev, nrows, pl->nseg_pad, S.nsteps, 1);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    });
 }
 
 int trmc_stream_advance(trmc_plan *pl, int ntiles)
@@ -922,7 +885,7 @@ int trmc_stream_advance(trmc_plan *pl, int ntiles)
             HIP_TRY(hipStreamWaitEvent(pl->stream, S.ev_bnd, 0));
             S.bnd_pending = false;
         }
-        rc = pl->precision == 32 ? stream_launch<float>(pl, S, g_from, g_to, S.days_pushed) : stream_launch<double>(pl, S, g_from, g_to, S.days_pushed);
+        rc = by_precision(pl, [&](auto t) { return stream_launch<decltype(t)>(pl, S, g_from, g_to, S.days_pushed); });
     }
     if (!rc && S.days_complete >= S.days_pushed) S.day_min = S.days_pushed; // (what follows starts with a new day; the rows' tiles of earlier days are done)
     return rc;
@@ -984,16 +947,15 @@ int trmc_stream_end(trmc_plan *pl)
         const int32_t slot = (int32_t)((S.days_pushed - 1) % S.slots);
         if (int rc = pl->in_q0.ensure((size_t)pl->nseg * 3 * pl->esz)) return rc;
         hipStream_t pst = stream_last(pl, S);
-        if (pl->precision == 32) {
-            const float *q = (const float *)S.tm.p + (size_t)slot * S.slot_tm;
-            hipLaunchKernelGGL((k_final_state<float>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, q, q + S.plane, (const int32_t *)pl->row_of_pos.p,
-                               (float *)pl->in_q0.p, (int32_t)pl->nseg, pl->nseg_pad, S.nsteps, 1, S.nsteps);
-        } else {
-            const double *q = (const double *)S.tm.p + (size_t)slot * S.slot_tm;
-            hipLaunchKernelGGL((k_final_state<double>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, q, q + S.plane, (const int32_t *)pl->row_of_pos.p,
-                               (double *)pl->in_q0.p, (int32_t)pl->nseg, pl->nseg_pad, S.nsteps, 1, S.nsteps);
-        }
-        HIP_TRY(hipGetLastError());
+        const int rc = by_precision(pl, [&](auto t) -> int {
+            using T = decltype(t);
+            const T *q = (const T *)S.tm.p + (size_t)slot * S.slot_tm;
+            hipLaunchKernelGGL((k_final_state<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, q, q + S.plane, (const int32_t *)pl->row_of_pos.p,
+                               (T *)pl->in_q0.p, (int32_t)pl->nseg, pl->nseg_pad, S.nsteps, 1, S.nsteps);
+            HIP_TRY(hipGetLastError());
+            return 0;
+        });
+        if (rc) return rc;
         pl->q0_staged = true;
         pl->state_missing = false;
     }

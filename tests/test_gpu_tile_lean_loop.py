@@ -7,9 +7,9 @@ of three and of four rows in the slices and in the tail (the CSR walk behind the
 qts = 4, as a stream WITHOUT full_output: every row's hydrograph and the final states of both days against the oracle and
 against the same days through the full_output instances; then with output_stride = 4 (kept steps carry velocities).
 
-A stream takes no reservoir or nudging tables (trmc_stream_begin refuses a plan that has them: they are per window), so the
-level-pool row and the nudged gage -- the other two rare branches of the loop -- are routed the way the library routes them:
-the same network, one window at plan level, full result against the oracle's level pool and simple_da.
+The level-pool row and the nudged gage -- the other two rare branches of the loop -- are routed here as one window at plan
+level: the same network, full result against the oracle's level pool and simple_da.  (A stream of days carries reservoirs and
+nudging too, its tables arriving with every day: test_gpu_stream_reservoirs_nudging, test_gpu_stream_reservoir_da.)
 
 The hot-list boundaries: one wide level of 130 rows (a full block and a block of two rows) and one of 64 + 1."""
 import functools
