@@ -113,6 +113,8 @@ __device__ __forceinline__ bool seq_locate(const StepArgs<T> &a, int32_t tile, i
     return true;
 }
 
+#include "k_tile_row.inc"
+
 // One launch = one timestep (SHORT) or one wavefront diagonal (!SHORT) over the plan
 // positions [s_begin, s_end); thread w of the launch takes position s_begin + w.
 //
@@ -186,26 +188,8 @@ __device__ __forceinline__ void mc_step_rows(const StepArgs<T> &a, const int32_t
         const T *const q_curr = a.q_tm + row_c;
 
         trmc::ChannelParams<T> p;
-        p.dt = a.dt_col ? at(a.dt_col, ob) : a.dt;
-        // (the zero-extension of the offset has to be visible in the basic block of the loads for the
-        // SGPR-base addressing form to be selected: re-introduce it after every branch)
-        asm volatile("" : "+v"(ob));
-        p.dx = at(a.dx, ob);
-        p.bw = at(a.bw, ob);
-        p.twcc = at(a.twcc, ob);
-        p.n = at(a.n, ob);
-        p.ncc = at(a.ncc, ob);
-        p.s0 = at(a.s0, ob);
-        p.tw = p.cs = T(0); // only enter the constants below
         trmc::ChannelConst<T> c;
-        c.z = at(a.z, ob);
-        c.bfd = at(a.bfd, ob);
-        c.sqrt_s0 = at(a.sqrt_s0, ob);
-        c.sq1pz2 = at(a.sq1pz2, ob);
-        c.s0_n = at(a.s0_n, ob);
-        c.s0_ncc = at(a.s0_ncc, ob);
-        c.inv_n = at(a.inv_n, ob);
-        trmc::derive_const(c, p);
+        load_row_params(a, ob, p, c);
 
         trmc::Inflow<T> f;
         f.qdp = at(q_prev, ob);
@@ -444,24 +428,8 @@ __device__ __forceinline__ void mc_tile_rows(const StepArgs<T> &a, const int32_t
     uint32_t ob = su * (uint32_t)sizeof(T);
     const size_t np = (size_t)a.nseg_pad;
     trmc::ChannelParams<T> p;
-    p.dt = a.dt_col ? at(a.dt_col, ob) : a.dt;
-    asm volatile("" : "+v"(ob));
-    p.dx = at(a.dx, ob);
-    p.bw = at(a.bw, ob);
-    p.twcc = at(a.twcc, ob);
-    p.n = at(a.n, ob);
-    p.ncc = at(a.ncc, ob);
-    p.s0 = at(a.s0, ob);
-    p.tw = p.cs = T(0);
     trmc::ChannelConst<T> c;
-    c.z = at(a.z, ob);
-    c.bfd = at(a.bfd, ob);
-    c.sqrt_s0 = at(a.sqrt_s0, ob);
-    c.sq1pz2 = at(a.sq1pz2, ob);
-    c.s0_n = at(a.s0_n, ob);
-    c.s0_ncc = at(a.s0_ncc, ob);
-    c.inv_n = at(a.inv_n, ob);
-    trmc::derive_const(c, p);
+    load_row_params(a, ob, p, c);
     const int2 u = a.up2[su];
     const int32_t ri = a.res_of_pos ? a.res_of_pos[s] : -1;
     const int32_t gi = a.gage_of_pos ? a.gage_of_pos[s] : -1;
@@ -515,23 +483,7 @@ __device__ __forceinline__ void mc_tile_rows(const StepArgs<T> &a, const int32_t
         }
         T q_new, v_new, d_new;
         if (ri >= 0) { // level-pool reservoir row (see k_mc_step)
-            const T *rp = cold->res_par + (size_t)ri * 9;
-            const trmc::LevelPoolParams<T> lp{rp[0], rp[1], rp[2], rp[3], rp[4], rp[5], rp[6], rp[7], rp[8]};
-            T H = d_prev;
-            q_new = trmc::levelpool_step<T, M>(qup, T(0), cold->res_dt, H, lp, m);
-            if constexpr (RDA) { // (see k_mc_step)
-                void *const da = cold->res_da;
-                trmc::ResDaState *const carry = (trmc::ResDaState *)cold->res_da_carry; // (a stream of days: the tables of the row's slot)
-                const trmc::ResDaResult r =
-                    carry ? trmc::reservoir_da_row_day((char *)da + (size_t)slot * (size_t)cold->slot_rda, carry, ri, t, cold->nsteps, cold->res_t_end,
-                                                       qup, d_prev, cold->res_dt, rp, q_new, H)
-                          : trmc::reservoir_da_row(da, ri, t, qup, d_prev, cold->res_dt, rp, q_new, H);
-                q_new = r.outflow;
-                H = r.water_elevation;
-            }
-            v_new = T(0);
-            d_new = H;
-            cold->res_inflow[(size_t)slot * (size_t)cold->slot_res + (size_t)ri * (size_t)cold->nsteps + (size_t)(t - 1)] = qup; // (the day's own record)
+            reservoir_row<T, M, RDA>(cold, m, slot, ri, t, qup, d_prev, q_new, v_new, d_new);
             it_last = 0;
         } else {
             trmc::Inflow<T> f;
@@ -546,30 +498,11 @@ __device__ __forceinline__ void mc_tile_rows(const StepArgs<T> &a, const int32_t
             it_last = r.iters;
             over_last = r.over;
             if (count_cost) it_acc += min(r.iters, 3) + (r.over ? 4 : 0);
-            if (gi >= 0) { // streamflow nudging (see k_mc_step); in a stream: the tables of the row's own day
-                const size_t e = (size_t)slot * (size_t)cold->slot_da + (size_t)gi * (size_t)cold->nsteps + (size_t)(t - 1);
-                const T *const da_a = cold->da_a;
-                const uint8_t mode = cold->da_mode[e];
-                T nudge = T(0);
-                if (mode == 1) {
-                    nudge = da_a[e] - q_new;
-                    q_new = da_a[e];
-                } else if (mode == 2) {
-                    nudge = (da_a[e] - q_new) * cold->da_w[e];
-                    q_new = q_new + nudge;
-                }
-                cold->da_nudge[e] = nudge;
-            }
+            if (gi >= 0) nudge_row<T>(cold, slot, gi, t, q_new);
         }
         asm volatile("" : "+v"(ob));
         at(q_up + np, ob) = q_new;
-        if (t == t_hi) {
-            at(cold->d_tm + (size_t)slot * (size_t)cold->slot_tm + (size_t)t * np, ob) = d_new;
-            if (cold->seq_slots > 1 && t == cold->nsteps) { // the day ends: the next one starts from here (its slot's time row 0)
-                at(cold->q_tm + (size_t)slot_next * (size_t)cold->slot_tm, ob) = q_new;
-                at(cold->d_tm + (size_t)slot_next * (size_t)cold->slot_tm, ob) = d_new;
-            }
-        }
+        hand_on_row<T>(cold, slot, slot_next, ob, np, t, t_hi, q_new, d_new);
         q_prev = q_new;
         d_prev = d_new;
         // (LAZYV: the velocity of a kept step, from the depth the step ended on -- what mc_segment_step forms; 0 where the step

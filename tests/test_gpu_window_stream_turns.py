@@ -15,7 +15,10 @@ k_mc_ctile <double, false, false, false>), a window that decimates as it goes (D
 one (DEC and LAZYV).
 
 The step kernels of rows with a lag (trmc_plan_set_lag) in the other arithmetics -- k_mc_step <float, SHORT, LAG, TOL>,
-<double, SHORT, LAG> and k_mc_step_rda <SHORT, LAG> -- on the lagged chain of test_gpu_window_api."""
+<double, SHORT, LAG> and k_mc_step_rda <SHORT, LAG> -- on the lagged chain of test_gpu_window_api.
+
+Tiles that are no whole number of stages (K = 12: runs of 8 + 4 steps, a last tile of 4 or 6): what both tile kernels stage, write
+as runs and keep of a window, in the float4 and in the scalar form."""
 import functools
 
 import numpy as np
@@ -234,3 +237,40 @@ def test_lagged_rows_in_the_other_arithmetics_equal_two_phase_routing(variant):
     assert np.all(np.isfinite(want)) and np.all(want[:, -1, 0] > 0)
     assert np.array_equal(bits(got[:n]), bits(want[:n]))
     assert np.array_equal(bits(got[n + 1:]), bits(want[n:]))
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_window(nsteps, qts):
+    """one window of nsteps steps from the lean-loop test's first day (its first nsteps / qts forcing columns): [n, nsteps, 3]"""
+    up_ptr, up_idx, level, params, days, q0 = LL.inputs()
+    ql = np.ascontiguousarray(days[0][:, :nsteps // qts])
+    w = O.network_by_segment(nsteps, qts, up_ptr, up_idx, level, params, q0, ql, True, det=True)[:, 1:, :]
+    w.setflags(write=False)
+    return ql, w
+
+
+@pytest.mark.parametrize("stride", [0, 5], ids=["full", "stride5"])
+@pytest.mark.parametrize("nsteps,qts", [(28, 4), (30, 5)], ids=["float4_runs", "scalar_runs"])
+def test_tiles_that_are_no_whole_number_of_stages(nsteps, qts, stride):
+    """K = 12 against stages of 8 steps: a tile is staged and written as a run of 8 steps and one of 4, the window's last tile
+    (4 steps of 28; 6 of 30) as one short run.  28 steps, qts = 4: nsteps and K are multiples of 4, every run goes out as
+    16-byte pieces; 30 steps, qts = 5: the scalar form, and a last run of 6 steps -- no multiple of 4.  With output_stride = 5
+    the kept steps 5, 10 | 15, 20 | 25 (, 30) lie in the first and in the second run of a tile and in every tile: the block
+    kept aside is those steps of the full result.  Slices (k_mc_tile) and clusters (k_mc_ctile), bit for bit against the oracle."""
+    up_ptr, up_idx, level, params, days, q0 = LL.inputs()
+    ql, want = oracle_window(nsteps, qts)
+    n = params.shape[0]
+    with RoutingPlan(up_ptr, up_idx, params, assume_short_ts=True, engine="levels", options={**LL.OPTS, "wide_k": 12}) as plan:
+        LL.check_paths(plan)
+        plan.set_output_stride(stride)
+        plan.upload_forcing(nsteps, ql, q0)
+        stats = plan.route_device(nsteps, qts, True)
+        assert stats["wide_levels"] == 3 and stats["wide_segment_steps"] == n * nsteps, stats
+        got = plan.download_fvd()
+        assert got.shape == want.shape and np.array_equal(bits(got), bits(want))
+        if stride:
+            plan.fetch_begin(plan.rowset(np.arange(n)), True, stride)
+            kept = np.ascontiguousarray(want[:, stride - 1::stride])
+            blk = plan.fetch_wait()[2]
+            assert kept.shape == (n, nsteps // stride, 3) and np.any(kept[:, :, 1] != 0)
+            assert blk.shape == kept.shape and np.array_equal(bits(blk), bits(kept))

@@ -81,8 +81,8 @@ def kind_of(kinds, f, ln):
     for kf, (a, b), k in kinds:
         if f == kf and a <= ln <= b:
             return k
-    if f in ("kernels_levels.inc", "k_mc_ctile.inc"):
-        return "frame"
+    if f in ("kernels_levels.inc", "k_mc_ctile.inc", "k_tile_row.inc"):
+        return "frame"  # (k_tile_row.inc: load_row_params, reservoir_row, nudge_row, hand_on_row -- text of the two loops, as before)
     return None  # (dev_math.inc, compiler headers: whatever surrounds them)
 
 
