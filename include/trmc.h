@@ -305,6 +305,30 @@ typedef struct trmc_stream_day {
 } trmc_stream_day;
 int trmc_stream_set_gages(trmc_plan *plan, int64_t ngage, const int64_t *gage_rows);
 int trmc_stream_push_day(trmc_plan *plan, const trmc_stream_day *day);
+/* A PER-ROW SUMMARY of every day (additions within ABI 19; csrc/stream.inc): how high every row got, when, and how much water
+ * passed -- 3 x [nseg] per day instead of the hourly block or the full result.  It is formed from ALL nsteps flows of the day
+ * (not from every output_stride-th one) where the day is handed over, by one reduction over the slot's flow plane; the tile
+ * kernels carry nothing for it, and a stream without a summary allocates and launches nothing.  The flows are those of the day's
+ * result, out[row][step][0]: after nudging at gage rows, the outflow at reservoir rows, the prescribed flow at boundary rows.
+ *   peak_flow [nseg] (plan precision), peak_step [nseg] (int32, 1-based step of the day): peak = q[1], step = 1, then for
+ *                      t = 2 .. nsteps in order `if (q[t] > peak) { peak = q[t]; step = t; }` -- the first of equal peaks wins, a
+ *                      NaN never replaces a number and a NaN at step 1 stays.
+ *   mean_flow [nseg] (plan precision): ((q[1] + q[2]) + ... + q[nsteps]) / nsteps, summed in that order in the plan's
+ *                      precision (numpy: np.cumsum(q, axis=1, dtype=T)[:, -1] / T(nsteps)).
+ *   trmc_stream_set_summary   what: a mask of TRMC_SUMMARY_PEAK (flow and step) and TRMC_SUMMARY_MEAN, 0 = none (the default).
+ *                      Before trmc_stream_begin; it stays until the next call, as trmc_stream_set_gages does; TRMC_ESTATE while
+ *                      a stream is in progress.  Works with full_output, output_stride or neither, with reservoirs, gages and
+ *                      reservoir data assimilation, in both arithmetics and precisions.
+ *   trmc_stream_summary_dest  page-locked host arrays [nseg] for the summary of the NEXT day pushed (any may be NULL): the next
+ *                      trmc_stream_push / trmc_stream_push_day that is accepted consumes them, a day pushed without this call
+ *                      has no summary.  They are filled with the day's other products; trmc_stream_wait covers them.
+ *                      TRMC_ESTATE if the stream in progress was begun without a summary, TRMC_EINVAL for an array whose part
+ *                      of the mask is off.
+ * A maximum over several days is the caller's: the larger of the days' peak_flow, the time from the winning day's peak_step.
+ * Depths and velocities have no summary (the planes hold depths at tile ends only and no velocity). */
+enum { TRMC_SUMMARY_PEAK = 1, TRMC_SUMMARY_MEAN = 2 };
+int trmc_stream_set_summary(trmc_plan *plan, int what);
+int trmc_stream_summary_dest(trmc_plan *plan, void *peak_flow_host, int32_t *peak_step_host, void *mean_flow_host);
 /* Multi-GPU streams (the trunk of a cut basin: rows fed by boundary rows, cluster_late_lag tiles behind).  trmc_stream_gather: the
  * flows of a row set over `day` [rows][nsteps] into DEVICE memory, queued on `stream` (NULL: the plan's) behind the launches
  * queued so far -- TRMC_ESTATE if the set's rows have not been queued through that day yet.  trmc_stream_boundary: the boundary

@@ -104,6 +104,7 @@ class StreamReservoirDa(C.Structure):
 
 
 RESERVOIR_DA_HYBRID, RESERVOIR_DA_RFC = 2, 4
+SUMMARY_PEAK, SUMMARY_MEAN = 1, 2   # trmc_stream_set_summary's mask (include/trmc.h)
 _P = C.POINTER
 # name -> (restype, argtypes); must list every symbol include/trmc.h declares
 SIGNATURES = {
@@ -120,6 +121,8 @@ SIGNATURES = {
     "trmc_stream_set_gages": (_int, [_vp, _i64, _vp]),
     "trmc_stream_push_day": (_int, [_vp, _vp]),
     "trmc_stream_set_reservoir_da": (_int, [_vp, _int, _i64, _i64, _i64]),
+    "trmc_stream_set_summary": (_int, [_vp, _int]),
+    "trmc_stream_summary_dest": (_int, [_vp, _vp, _vp, _vp]),
     "trmc_stream_gather": (_int, [_vp, _i64, _i32, _vp, _vp]),
     "trmc_stream_boundary": (_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
     "trmc_stream_advance": (_int, [_vp, _int]),

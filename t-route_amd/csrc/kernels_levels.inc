@@ -773,6 +773,52 @@ k_final_state(const T *__restrict__ q_tm, const T *__restrict__ d_tm, const int3
     q0_out[r + 2] = d_tm[(size_t)d_row * nseg_pad + p];
 }
 
+// A day's per-row summary from its slot's time-major flow plane (csrc/stream.inc: launched where the day is handed over, beside
+// k_final_state): peak flow and the 1-based step it was first reached at, and the mean flow, written in ROW order.  One thread
+// per plan position walks the time rows 1..nsteps, so a wavefront reads 64 consecutive flows of a time row per load.  The
+// compares and the adds are a dependent chain in time order -- `>` keeps the first of equal peaks and never lets a NaN replace a
+// number, the sum is the left-to-right one in T (np.cumsum) -- but the loads are independent: kSummaryUnroll of them are issued
+// before the first is used.  `peak` (with `step`) or `mean` may be NULL.
+constexpr int kSummaryUnroll = 8;
+template <class T>
+__global__ void __launch_bounds__(kBlock)
+k_stream_summary(const T *__restrict__ q_tm, const int32_t *__restrict__ row_of_pos, T *__restrict__ peak, int32_t *__restrict__ step,
+                 T *__restrict__ mean, int32_t nseg, int64_t nseg_pad, int32_t nsteps)
+{
+    const int32_t p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= nseg) return;
+    const T *q = q_tm + (size_t)nseg_pad + p; // (time row 1)
+    T pk = q[0], s = pk;
+    int32_t at = 1, t = 2;
+    for (; t + kSummaryUnroll - 1 <= nsteps; t += kSummaryUnroll) {
+        T v[kSummaryUnroll];
+#pragma unroll
+        for (int j = 0; j < kSummaryUnroll; ++j) v[j] = q[(size_t)(t - 1 + j) * (size_t)nseg_pad];
+#pragma unroll
+        for (int j = 0; j < kSummaryUnroll; ++j) {
+            if (v[j] > pk) {
+                pk = v[j];
+                at = t + j;
+            }
+            s += v[j];
+        }
+    }
+    for (; t <= nsteps; ++t) {
+        const T v = q[(size_t)(t - 1) * (size_t)nseg_pad];
+        if (v > pk) {
+            pk = v;
+            at = t;
+        }
+        s += v;
+    }
+    const size_t r = (size_t)row_of_pos[p];
+    if (peak) {
+        peak[r] = pk;
+        step[r] = at;
+    }
+    if (mean) mean[r] = s / T(nsteps);
+}
+
 template <class T>
 __global__ void __launch_bounds__(kBlock)
 k_gather_rows(const T *__restrict__ q_tm, const int32_t *__restrict__ pos, T *__restrict__ out, int64_t nrows,

@@ -41,12 +41,20 @@
 // mc_reach.pyx:820-837) and leaves the result both in the carry and in the day's record, from where the day's products
 // res_da_state_host / res_da_tsidx_host are gathered.  Such a stream forms every step's velocity: the _rda tile instances have no
 // LAZYV form (DESIGN.md 10).
+//
+// A PER-ROW SUMMARY OF THE DAY (trmc_stream_set_summary: peak flow, the step of the peak, mean flow) is one more product, for the
+// caller who asks about every reach but wants neither the hourly block nor the full result.  The tile kernels carry nothing for
+// it: they already leave every step's flow of every row in the slot's flow plane (the rows below read it there), so when a day is
+// handed over one column reduction over that plane (k_stream_summary, beside k_final_state) forms the three arrays [nseg] in row
+// order in the slot's summary buffers, and they leave on the copy stream with the day's other products.  Off (the default): no
+// buffer, no launch.
 extern "C++" {
 struct StreamProd {
     int64_t day = -1;
     void *hyd_host = nullptr, *q0_host = nullptr, *fvd_host = nullptr;
     void *nudge_host = nullptr, *res_inflow_host = nullptr;
     void *rda_state_host = nullptr, *rda_tsidx_host = nullptr;
+    void *peak_host = nullptr, *step_host = nullptr, *mean_host = nullptr; // the day's summary (trmc_stream_summary_dest)
     int32_t rowset = -1;
     bool queued = false;          // the gathers and copies of this day are queued
     hipEvent_t ev_done = nullptr; // ... and this fires when they are through
@@ -79,6 +87,11 @@ struct StreamRun {
     DevBuf rda_tab, rda_carry, rda_prod; // [slots][slot_rda]; ResDaState [nres]; [slots]{float [nres][4], int32 [nres]}
     void *rda_stage = nullptr;     // page-locked host image of every slot's tables (the copy runs beside the launches)
     size_t rda_stage_bytes = 0;
+    // the per-row summary of a day (see the head of this file).  sum_want: trmc_stream_set_summary, it outlives a stream as the gage
+    // rows do; sum: the mask of the stream in progress; next_*: where the summary of the NEXT day pushed goes
+    int32_t sum_want = 0, sum = 0;
+    DevBuf sum_peak, sum_step, sum_mean; // [slots][nseg] each, in row order (only what the mask asks for)
+    void *next_peak = nullptr, *next_step = nullptr, *next_mean = nullptr;
     std::vector<hipEvent_t> ev_slab;    // ring: "slab launch g is complete" (the cluster launch g + 1 waits for it)
     std::vector<hipEvent_t> ev_free;    // [slots] the day that used the slot has handed its products over
     std::vector<hipEvent_t> ev_ready;   // [slots] the gathers of that day are through (copy stream waits)
@@ -97,7 +110,7 @@ static void stream_release(trmc_plan *pl)
     StreamRun *S = pl->seq;
     if (!S) return;
     for (DevBuf *b : {&S->tm, &S->qlat, &S->out, &S->dec, &S->hyd, &S->q0, &S->res_inflow, &S->da_mode, &S->da_a, &S->da_w, &S->da_nudge, &S->da_q0, &S->gage_of_pos, &S->gage_pos_dev, &S->rda_tab,
-                       &S->rda_carry, &S->rda_prod})
+                       &S->rda_carry, &S->rda_prod, &S->sum_peak, &S->sum_step, &S->sum_mean})
         b->release();
     if (S->rda_stage) (void)hipHostFree(S->rda_stage);
     for (auto *v : {&S->ev_slab, &S->ev_free, &S->ev_ready, &S->ev_forcing, &S->ev_t0, &S->ev_t1})
@@ -278,7 +291,9 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
     const int64_t nrows = (p.hyd_host && p.rowset >= 0) ? pl->rowset_n[(size_t)p.rowset] : 0;
     const bool want_nudge = p.nudge_host && S.slot_da > 0, want_res = p.res_inflow_host && S.slot_res > 0;
     const bool want_rda = S.rda && (p.rda_state_host || p.rda_tsidx_host);
-    const bool any = nrows > 0 || p.q0_host || p.fvd_host || want_nudge || want_res || want_rda;
+    const bool want_peak = (S.sum & TRMC_SUMMARY_PEAK) && (p.peak_host || p.step_host) && pl->nseg > 0;
+    const bool want_mean = (S.sum & TRMC_SUMMARY_MEAN) && p.mean_host && pl->nseg > 0;
+    const bool any = nrows > 0 || p.q0_host || p.fvd_host || want_nudge || want_res || want_rda || want_peak || want_mean;
     float *const rda_state = (float *)S.rda_prod.p + (size_t)slot * (size_t)pl->nres * 5;
     int32_t *const rda_tsidx = (int32_t *)(rda_state + (size_t)pl->nres * 4);
     if (want_rda)
@@ -292,6 +307,12 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
     if (p.q0_host && pl->nseg > 0)
         hipLaunchKernelGGL((k_final_state<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, q, d, (const int32_t *)pl->row_of_pos.p,
                            (T *)((char *)S.q0.p + (size_t)slot * S.q0_bytes), (int32_t)pl->nseg, pl->nseg_pad, S.nsteps, 1, S.nsteps);
+    T *const sum_peak = want_peak ? (T *)S.sum_peak.p + (size_t)slot * (size_t)pl->nseg : nullptr;
+    int32_t *const sum_step = want_peak ? (int32_t *)S.sum_step.p + (size_t)slot * (size_t)pl->nseg : nullptr;
+    T *const sum_mean = want_mean ? (T *)S.sum_mean.p + (size_t)slot * (size_t)pl->nseg : nullptr;
+    if (want_peak || want_mean)
+        hipLaunchKernelGGL((k_stream_summary<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, q, (const int32_t *)pl->row_of_pos.p, sum_peak,
+                           sum_step, sum_mean, (int32_t)pl->nseg, pl->nseg_pad, S.nsteps);
     HIP_TRY(hipGetLastError());
     if (!any) {
         HIP_TRY(hipEventRecord(S.ev_free[(size_t)slot], pst));
@@ -323,6 +344,12 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
         HIP_TRY(hipMemcpyAsync(p.rda_state_host, rda_state, (size_t)pl->nres * 4 * sizeof(float), hipMemcpyDeviceToHost, pl->cstream));
     if (want_rda && p.rda_tsidx_host)
         HIP_TRY(hipMemcpyAsync(p.rda_tsidx_host, rda_tsidx, (size_t)pl->nres * sizeof(int32_t), hipMemcpyDeviceToHost, pl->cstream));
+    if (want_peak && p.peak_host)
+        HIP_TRY(hipMemcpyAsync(p.peak_host, sum_peak, (size_t)pl->nseg * sizeof(T), hipMemcpyDeviceToHost, pl->cstream));
+    if (want_peak && p.step_host)
+        HIP_TRY(hipMemcpyAsync(p.step_host, sum_step, (size_t)pl->nseg * sizeof(int32_t), hipMemcpyDeviceToHost, pl->cstream));
+    if (want_mean)
+        HIP_TRY(hipMemcpyAsync(p.mean_host, sum_mean, (size_t)pl->nseg * sizeof(T), hipMemcpyDeviceToHost, pl->cstream));
     HIP_TRY(hipEventRecord(S.ev_free[(size_t)slot], pl->cstream));
     HIP_TRY(hipEventRecord(p.ev_done, pl->cstream));
     p.queued = true;
@@ -436,6 +463,20 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
             if (int rc = b->ensure((size_t)S.slots * S.slot_da * sizeof(T))) return rc;
         if (int rc = S.da_q0.ensure((size_t)S.slots * (size_t)S.ngage * sizeof(T))) return rc;
     }
+    // the days' summaries: only what the mask asks for (a stream without one holds no such buffer)
+    S.sum = S.sum_want;
+    S.next_peak = S.next_step = S.next_mean = nullptr;
+    if (!(S.sum & TRMC_SUMMARY_PEAK)) {
+        S.sum_peak.release();
+        S.sum_step.release();
+    }
+    if (!(S.sum & TRMC_SUMMARY_MEAN)) S.sum_mean.release();
+    if (S.sum & TRMC_SUMMARY_PEAK) {
+        if (int rc = S.sum_peak.ensure((size_t)S.slots * (size_t)pl->nseg * sizeof(T))) return rc;
+        if (int rc = S.sum_step.ensure((size_t)S.slots * (size_t)pl->nseg * sizeof(int32_t))) return rc;
+    }
+    if (S.sum & TRMC_SUMMARY_MEAN)
+        if (int rc = S.sum_mean.ensure((size_t)S.slots * (size_t)pl->nseg * sizeof(T))) return rc;
     // reservoir data assimilation: the slots' tables at their capacity, the carry with the state trmc_set_reservoir_da supplied
     // (or the plan's last window left in those tables), the days' state records
     S.rda = pl->nres > 0 && pl->res_da_on && S.rda_want;
@@ -563,6 +604,10 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
     p.res_inflow_host = day.res_inflow_host;
     p.rda_state_host = day.res_da_state_host;
     p.rda_tsidx_host = day.res_da_tsidx_host;
+    p.peak_host = S.next_peak; // (trmc_stream_summary_dest: this push consumes them)
+    p.step_host = S.next_step;
+    p.mean_host = S.next_mean;
+    S.next_peak = S.next_step = S.next_mean = nullptr;
     // the day's forcing: host -> staging area -> plan order in the slot, all on the copy stream of that direction
     const size_t bytes = (size_t)pl->nseg * S.nq * sizeof(T);
     if (int rc = pl->in_qlat.ensure(bytes)) return rc;
@@ -719,6 +764,30 @@ int trmc_stream_set_reservoir_da(trmc_plan *pl, int on, int64_t usgs_ncol, int64
     S.rda_cap_want[0] = usgs_ncol;
     S.rda_cap_want[1] = usace_ncol;
     S.rda_cap_want[2] = rfc_ncol;
+    return 0;
+}
+
+int trmc_stream_set_summary(trmc_plan *pl, int what)
+{
+    if (int rc = stream_check(pl, false)) return rc;
+    if (pl->flow) return fail(TRMC_EINVAL, "a stream of windows runs on the level engine");
+    if (what & ~(TRMC_SUMMARY_PEAK | TRMC_SUMMARY_MEAN)) return fail(TRMC_EINVAL, "what: a mask of TRMC_SUMMARY_PEAK and TRMC_SUMMARY_MEAN (0: no summary)");
+    if (!pl->seq) pl->seq = new StreamRun();
+    pl->seq->sum_want = what;
+    return 0;
+}
+
+int trmc_stream_summary_dest(trmc_plan *pl, void *peak_flow_host, int32_t *peak_step_host, void *mean_flow_host)
+{
+    if (int rc = stream_check(pl, true)) return rc;
+    StreamRun &S = *pl->seq;
+    if (S.sum == 0) return fail(TRMC_ESTATE, "the stream was begun without a summary (trmc_stream_set_summary precedes trmc_stream_begin)");
+    if ((peak_flow_host || peak_step_host) && !(S.sum & TRMC_SUMMARY_PEAK))
+        return fail(TRMC_EINVAL, "a peak array for a stream whose summary has no TRMC_SUMMARY_PEAK");
+    if (mean_flow_host && !(S.sum & TRMC_SUMMARY_MEAN)) return fail(TRMC_EINVAL, "a mean array for a stream whose summary has no TRMC_SUMMARY_MEAN");
+    S.next_peak = peak_flow_host;
+    S.next_step = peak_step_host;
+    S.next_mean = mean_flow_host;
     return 0;
 }
 
@@ -965,6 +1034,7 @@ int trmc_stream_end(trmc_plan *pl)
     if (S.fst) HIP_TRY(hipStreamSynchronize(S.fst));
     HIP_TRY(hipStreamSynchronize(pl->cstream));
     if (pl->collect_cost) pl->cost_nsteps = (int32_t)std::min<int64_t>(S.days_pushed * S.nsteps, 1 << 30);
+    S.next_peak = S.next_step = S.next_mean = nullptr;
     S.active = false;
     return 0;
 }

@@ -419,8 +419,24 @@ class RoutingPlan:
         _lib.check(_lib.lib().trmc_stream_set_gages(self._h, rows.shape[0], _lib.ptr(rows)))
         self._stream_ngage = int(rows.shape[0])
 
+    def stream_set_summary(self, what):
+        """The per-row summary the streams on this plan form of every day (trmc_stream_set_summary): an iterable of ``"peak"`` (peak
+        flow and the 1-based step of the peak) and ``"mean"`` (mean flow), or ``None`` for none.  Declared before
+        ``stream_begin``; it stays until the next call.  Every ``stream_push`` then says where the day's arrays go
+        (``summary=``)."""
+        names = {"peak": _lib.SUMMARY_PEAK, "mean": _lib.SUMMARY_MEAN}
+        if isinstance(what, str):
+            what = (what,)
+        mask = 0
+        for w in (what or ()):
+            if w not in names:
+                raise ValueError(f"summary: 'peak' and / or 'mean', got {w!r}")
+            mask |= names[w]
+        _lib.check(_lib.lib().trmc_stream_set_summary(self._h, mask))
+        self._stream_summary = mask
+
     def stream_push(self, qlat, boundary_q_ptr=None, rowset=None, hyd=None, q0=None, fvd=None, nudging=None, nudge=None,
-                    reservoir_inflow=None, reservoir_da=None, reservoir_da_state=None):
+                    reservoir_inflow=None, reservoir_da=None, reservoir_da_state=None, summary=None):
         """The next day: ``qlat`` [nseg, nq] (page-locked: ``_lib.result_empty(..., always_pinned=True)``), where its products go
         (page-locked arrays or None), the device pointer of its boundary rows' flows.  A plan with gage rows
         (``stream_set_gages``): ``nudging=(mode, a, w)``, the day's tables [ngage, nsteps] as ``set_nudging`` takes them for a
@@ -430,7 +446,10 @@ class RoutingPlan:
         rfc_reset_idx])``, the day's tables as ``set_reservoir_da`` takes them -- times from the day's start; the state members are
         ignored and may be None, the device carries them; the RFC timeseries_idx counts only with ``rfc_reset_idx`` -- and
         ``reservoir_da_state=(state [nres, 4] float32, timeseries_idx [nres] int32)``: page-locked arrays for the state the day
-        leaves, times already counted from the next day's start.  Returns the day's number in the stream."""
+        leaves, times already counted from the next day's start.  A plan whose streams form a summary (``stream_set_summary``):
+        ``summary=(peak_flow, peak_step, mean_flow)``, page-locked [nseg] arrays (plan precision, int32, plan precision; any may
+        be None) for the day's peak flow, the 1-based step of the peak and the mean flow.  Returns the day's number in the
+        stream."""
         if qlat.dtype != self.dtype or not qlat.flags.c_contiguous or qlat.ndim != 2 or qlat.shape[0] != self.nseg:
             raise ValueError(f"qlat must be a C-contiguous {np.dtype(self.dtype).name} array of shape ({self.nseg}, nq)")
         day_s = _lib.StreamDay()
@@ -477,22 +496,36 @@ class RoutingPlan:
                     or not st.flags.c_contiguous or not ti.flags.c_contiguous):
                 raise ValueError(f"reservoir_da_state must be (float32 [{nres}, 4], int32 [{nres}]), C-contiguous")
             day_s.res_da_state_host, day_s.res_da_tsidx_host = st.ctypes.data, ti.ctypes.data
+        if summary is not None:
+            if len(summary) != 3:
+                raise ValueError("summary must be (peak_flow, peak_step, mean_flow); any may be None")
+            for name, arr, dt in zip(("peak_flow", "peak_step", "mean_flow"), summary, (self.dtype, np.int32, self.dtype)):
+                if arr is not None and (not isinstance(arr, np.ndarray) or arr.dtype != dt or arr.shape != (self.nseg,)
+                                        or not arr.flags.c_contiguous):
+                    raise ValueError(f"summary: {name} must be a C-contiguous {np.dtype(dt).name} array of shape ({self.nseg},)")
         info = self.stream_info()
         day = info["days_pushed"]
         # (alive while the copies may be in flight: a day's products are queued up to `slots` days on)
-        self._stream_keep[day] = (qlat, hyd, q0, fvd, tables, nudge, reservoir_inflow, reservoir_da_state)
+        self._stream_keep[day] = (qlat, hyd, q0, fvd, tables, nudge, reservoir_inflow, reservoir_da_state, summary)
         for old in [k for k in self._stream_keep if isinstance(k, int) and k < day - max(8, info["slots"])]:
             del self._stream_keep[old]
-        if nudging is None and reservoir_inflow is None and reservoir_da is None and reservoir_da_state is None:  # (the entry point every stream without tables has always used)
-            _lib.check(_lib.lib().trmc_stream_push(self._h, _lib.ptr(qlat), qlat.shape[1], C.c_void_p(boundary_q_ptr or 0),
-                                                   -1 if rowset is None else int(rowset), _lib.ptr(hyd), _lib.ptr(q0), _lib.ptr(fvd)))
+        if summary is not None:  # (where the NEXT day's summary goes: the push below consumes it)
+            _lib.check(_lib.lib().trmc_stream_summary_dest(self._h, *(_lib.ptr(x) for x in summary)))
+        try:
+            if nudging is None and reservoir_inflow is None and reservoir_da is None and reservoir_da_state is None:  # (the entry point every stream without tables has always used)
+                _lib.check(_lib.lib().trmc_stream_push(self._h, _lib.ptr(qlat), qlat.shape[1], C.c_void_p(boundary_q_ptr or 0),
+                                                       -1 if rowset is None else int(rowset), _lib.ptr(hyd), _lib.ptr(q0), _lib.ptr(fvd)))
+                return day
+            day_s.qlat, day_s.nq = qlat.ctypes.data, qlat.shape[1]
+            day_s.boundary_q_dev = boundary_q_ptr or None
+            day_s.rowset = -1 if rowset is None else int(rowset)
+            day_s.hyd_host, day_s.q0_host, day_s.fvd_host = (None if x is None else x.ctypes.data for x in (hyd, q0, fvd))
+            _lib.check(_lib.lib().trmc_stream_push_day(self._h, C.byref(day_s)))
             return day
-        day_s.qlat, day_s.nq = qlat.ctypes.data, qlat.shape[1]
-        day_s.boundary_q_dev = boundary_q_ptr or None
-        day_s.rowset = -1 if rowset is None else int(rowset)
-        day_s.hyd_host, day_s.q0_host, day_s.fvd_host = (None if x is None else x.ctypes.data for x in (hyd, q0, fvd))
-        _lib.check(_lib.lib().trmc_stream_push_day(self._h, C.byref(day_s)))
-        return day
+        except Exception:
+            if summary is not None:  # (a refused push has not consumed the arrays: they must not wait for another day)
+                _lib.lib().trmc_stream_summary_dest(self._h, None, None, None)
+            raise
 
     def stream_gather(self, day, rowset, device_ptr, stream=0):
         """Flows of a row set over `day` [rows, nsteps] into device memory (trmc_stream_gather)."""

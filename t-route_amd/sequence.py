@@ -261,6 +261,13 @@ class RouteStream:
     of its ``rows``), with ``output_stride=n`` also every n-th step of (q, v, d) of those rows.  The arrays belong to a ring:
     copy what is kept beyond the next few days.
 
+    ``summary=("peak", "mean")`` (or one of them): every tuple ends in a dict with ``"peak_flow"``, ``"peak_step"`` (int32, the
+    1-based step of the day at which the peak was first reached) and ``"mean_flow"`` -- [rows] ring arrays over this rank's
+    ``rows`` in the order of the final state, formed on the device from ALL nsteps flows of the day (include/trmc.h,
+    trmc_stream_set_summary; None for what was not asked).  A router with reservoirs or gages: its trailing dict gains these
+    keys.  The maximum of a forecast of several days is ``np.maximum`` over the days' ``peak_flow``, its time the winning
+    day's ``peak_step``.
+
     Underneath is ONE stream of tile launches (include/trmc.h, trmc_stream_*): the tile index runs on over the days, every
     launch routes every row through the next K steps of its own place in the stream -- a row deep in the network works on an
     earlier tile than the headwaters, possibly of an earlier day -- so a day costs nsteps / K launches and nothing else, and a
@@ -274,7 +281,7 @@ class RouteStream:
     """
 
     def __init__(self, router, nsteps, qts_subdivisions, output_stride=None, full_output=False, slots=0, latency="throughput",
-                 hydrographs_on_every_rank=False, comm=None, exchange=None, reservoir_da_ncol=None):
+                 hydrographs_on_every_rank=False, comm=None, exchange=None, reservoir_da_ncol=None, summary=None):
         """comm / exchange (several ranks): the communicator -- default: the one given to ``router.enable_device_exchange`` -- and
         how the daily cut-edge hydrographs travel: "device" (gather kernel -> all-gather on the exchange stream -> boundary rows,
         everything in HBM: RCCL over xGMI) or "host" (through ``comm.all_gather_rows_host``: any communicator with that method,
@@ -283,6 +290,10 @@ class RouteStream:
         reservoir_da_ncol (a router with ``reservoir_da``): the most columns (usgs, usace, rfc) a day's tables may have; default:
         as many as the declared tables."""
         self._rda_ncol = reservoir_da_ncol
+        summary = (summary,) if isinstance(summary, str) else tuple(summary or ())
+        if any(w not in ("peak", "mean") for w in summary):
+            raise ValueError("summary: an iterable of 'peak' and / or 'mean', or None")
+        self.summary = summary
         if latency not in ("throughput", "low"):
             raise ValueError("latency must be 'throughput' or 'low'")
         self.r = router
@@ -409,11 +420,11 @@ class RouteStream:
         el = marks["t1"] - marks["t0"]
         if multi:
             el = float(self.comm.all_reduce_max_host(np.array([el], dtype=np.float64))[0])
-        return {"el": el, "days_routed": total, "warmup": wu, "hyd": last[1], "final": last[2], "fvd": last[3] if len(last) > 3 else None,
-                "info": self.last_info, "push_ms": push_ms}
+        return {"el": el, "days_routed": total, "warmup": wu, "hyd": last[1], "final": last[2],
+                "fvd": last[3] if len(last) > 3 and not isinstance(last[3], dict) else None, "info": self.last_info, "push_ms": push_ms}
 
     def route(self, forcings, state0=None, prepared=False, observations=None, lastobs=None, da_parameters=None, reservoir_da=None):
-        """generator of (day, hydrographs, final_state[, fvd]) -- see the class.  prepared: the arrays hold this rank's rows only
+        """generator of (day, hydrographs, final_state[, fvd][, dict]) -- see the class (``summary``) and below.  prepared: the arrays hold this rank's rows only
         (``prepare_days``).
 
         A router with reservoirs or gages (``ShardedRouter(..., stream=True, reservoirs=..., gages=...)``): every tuple has one more
@@ -515,6 +526,8 @@ class RouteStream:
             # has it: a rank's ring must hold its days that long
             lmax_all = int(self.comm.all_reduce_max_host(np.array([lmax_mine], dtype=np.float64))[0])
             slots = max(slots, (-(-lmax_all // tpd0) if lmax_all else 0) + 3 + (1 if want_fvd else 0))
+        if self.summary or getattr(P, "_stream_summary", 0):   # (the declaration outlives a stream: an earlier one's is withdrawn)
+            P.stream_set_summary(self.summary)
         P.stream_begin(nsteps, qts, slots=slots, full_output=self.full_output and not self.output_stride,
                        output_stride=self.output_stride,
                        **({} if rda is None else {"reservoir_da": True if self._rda_ncol is None else self._rda_ncol}))
@@ -535,6 +548,10 @@ class RouteStream:
                 if ngage else None for _ in range(3)]
         rdas = [(_lib.result_empty((nres, 4), np.float32, always_pinned=True), _lib.result_empty((nres,), np.int32, always_pinned=True))
                 if rda is not None else None for _ in range(D)]
+        want_peak, want_mean = "peak" in self.summary, "mean" in self.summary
+        pkf = [_lib.result_empty((nrows,), dtype, always_pinned=True) if want_peak else None for _ in range(D)]
+        pks = [_lib.result_empty((nrows,), np.int32, always_pinned=True) if want_peak else None for _ in range(D)]
+        mnf = [_lib.result_empty((nrows,), dtype, always_pinned=True) if want_mean else None for _ in range(D)]
         lastobs_of = {}
         # when a day's products are waited for: a day after they were queued (the host then never waits for launches it has
         # just queued -- the device always holds a day of work); latency="low": right after the day's own push (flushed)
@@ -596,6 +613,12 @@ class RouteStream:
                 item += ({"reservoir_inflow": rinf[k], "nudge": nudg[k], "lastobs": lastobs_of.pop(day, (None, None))},)
                 if rda is not None:                     # (days are delivered in order: the host's copy of the state moves on with them)
                     item[-1]["reservoir_da"] = rda_tuples(*rdas[k])
+            if self.summary:
+                sm = {"peak_flow": pkf[k], "peak_step": pks[k], "mean_flow": mnf[k]}
+                if extras:
+                    item[-1].update(sm)
+                else:
+                    item += (sm,)
             return item
 
         d, nxt, pending = 0, first, 0
@@ -626,6 +649,8 @@ class RouteStream:
                 except StopIteration:
                     raise ValueError(f"reservoir_da ended before the forcings (day {d})") from None
                 more["reservoir_da_state"] = rdas[d % D]
+            if self.summary:
+                more["summary"] = (pkf[d % D], pks[d % D], mnf[d % D])
             P.stream_push(q, rowset=r._rsS_out, hyd=hyds[d % D], q0=fins[d % D], fvd=fvds[d % D], **more)
             if low:
                 if multi:

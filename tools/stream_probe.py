@@ -3,7 +3,10 @@ row and the hydrographs of sampled rows bit for bit, and what a day costs either
   python tools/stream_probe.py [--nseg N] [--days D] [--wide-min-rows R] [--hint] [--stride n] [--full]
                                [--reservoirs N --gages M]   level-pool waterbodies and nudged gages scattered over the network
                                [--reservoir-da N]           N of those waterbodies are of types 2-5 (hybrid persistence, RFC series)
-                                                            with synthetic tables: their data assimilation rides in the stream"""
+                                                            with synthetic tables: their data assimilation rides in the stream
+                               [--summary]                  every day's per-row peak flow, step of the peak and mean flow as stream
+                                                            products (trmc_stream_set_summary); checked against the host's reduction
+                                                            of the one-by-one day's full result where that fits (nseg * 288 <= 2^26)"""
 import argparse
 import os
 import sys
@@ -32,6 +35,7 @@ ap.add_argument("--velocity-on-demand", type=int, default=0)
 ap.add_argument("--later", type=int, default=0, help="hand a day over this many days later than its last row allows (and hold as many more slots)")
 ap.add_argument("--reservoirs", type=int, default=0, help="level-pool reservoirs scattered over the network (rows with an upstream row)")
 ap.add_argument("--reservoir-da", type=int, default=0, help="so many of the --reservoirs are of types 2, 3, 4, 5 in turn, with synthetic tables")
+ap.add_argument("--summary", action="store_true", help="per-row peak flow, step of the peak and mean flow of every day as stream products")
 ap.add_argument("--gages", type=int, default=0, help="nudged gages scattered over the network (observations: 70 %% valid, lognormal)")
 a = ap.parse_args()
 if a.reservoir_da > a.reservoirs:
@@ -111,6 +115,20 @@ if a.reservoirs or a.gages:
             dst[...] = src
     if a.gages:
         print(f"nudging tables of {a.gages} gages resolved on the host: {(time.perf_counter() - t0) / len(days):.2f} s per day", flush=True)
+
+
+def summary_of(q):
+    """(peak_flow, peak_step, mean_flow) of flows q [rows, nsteps] as include/trmc.h defines them"""
+    peak, step = q[:, 0].copy(), np.ones(q.shape[0], np.int32)
+    for t in range(1, q.shape[1]):
+        m = q[:, t] > peak
+        peak[m] = q[m, t]
+        step[m] = t + 1
+    return peak, step, np.cumsum(q, axis=1, dtype=q.dtype)[:, -1] / q.dtype.type(q.shape[1])
+
+
+check_summary = a.summary and not a.no_check and n * nsteps <= 1 << 26
+ref_sum = []
 opts = {"wide_min_rows": a.wide_min_rows, "wide_k": a.wide_k, "cluster_rows": 128, "wide_levels": a.wide_levels, "stream_split": a.split, "velocity_on_demand": a.velocity_on_demand}
 hint = None
 if a.hint:
@@ -144,6 +162,8 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
             fin = p.download_final_state()
             hyd = p.gather_flow_rows(sample)
             fvd = p.download_fvd(a.stride) if (a.stride or a.full) else None
+            if check_summary:
+                ref_sum.append(summary_of(np.ascontiguousarray((fvd if (a.full and not a.stride) else p.download_fvd())[:, :, 0])))
             if a.reservoir_da:
                 da_state, da_tsidx = p.download_reservoir_da()
                 da_state[da_kind != 0, 0] -= da_t_end
@@ -155,6 +175,7 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
     if a.reservoir_da:
         p.set_reservoir_da(da_kind, da_trow, *da_tables())
     p.upload_forcing(nsteps, days[0], q0)
+    p.stream_set_summary(("peak", "mean") if a.summary else None)
     p.stream_begin(nsteps, qts, reservoir_da=bool(a.reservoir_da) or None, slots=a.slots + a.later if a.slots else (a.later and 2 + -(-(int(p.lags()[0].max(initial=0)) + 1) // (nsteps // p.tile_steps)) + a.later), full_output=a.full and not a.stride, output_stride=a.stride)
     info = p.stream_info()
     print("stream:", info, flush=True)
@@ -167,6 +188,8 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
     nuds = [_lib.result_empty((a.gages, nsteps), np.float32, always_pinned=True) if tabs else None for _ in range(D)]
     rdas = [(_lib.result_empty((a.reservoirs, 4), np.float32, always_pinned=True), _lib.result_empty((a.reservoirs,), np.int32, always_pinned=True))
             if a.reservoir_da else None for _ in range(D)]
+    sums = [(_lib.result_empty((n,), np.float32, always_pinned=True), _lib.result_empty((n,), np.int32, always_pinned=True),
+             _lib.result_empty((n,), np.float32, always_pinned=True)) if a.summary else None for _ in range(D)]
     da_day = da_tables() if a.reservoir_da else None
     got = []
     behind = (info["lag_max"] + info["tiles_per_day"]) // info["tiles_per_day"] + a.later
@@ -187,6 +210,9 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
             if x is not None and not np.array_equal(x.view(np.uint32), y.view(np.uint32)):
                 ok = False
                 print(f"   day {e}: {name} differs", flush=True)
+        if check_summary and not all(np.array_equal(x.view(np.uint32), y.view(np.uint32)) for x, y in zip(ref_sum[e], sums[e % D])):
+            ok = False
+            print(f"   day {e}: summary differs", flush=True)
         s1 = np.array_equal(fin.view(np.uint32), fins[e % D].view(np.uint32))
         s2 = np.array_equal(hyd.view(np.uint32), hyds[e % D].view(np.uint32))
         s3 = fvd is None or np.array_equal(np.ascontiguousarray(fvd).view(np.uint32), fvds[e % D].view(np.uint32))
@@ -196,7 +222,7 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
     t0 = time.perf_counter()
     for d in range(a.days):
         p.stream_push(pinned[d % len(days)], rowset=rs, hyd=hyds[d % D], q0=fins[d % D], fvd=fvds[d % D],
-                      nudging=tabs[d % len(days)] if tabs else None, nudge=nuds[d % D], reservoir_inflow=rins[d % D], reservoir_da=da_day, reservoir_da_state=rdas[d % D])
+                      nudging=tabs[d % len(days)] if tabs else None, nudge=nuds[d % D], reservoir_inflow=rins[d % D], reservoir_da=da_day, reservoir_da_state=rdas[d % D], summary=sums[d % D])
         e = d - behind
         if e >= 0:
             take(e)
@@ -210,4 +236,7 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
         print(f"   device time of a day's own launches on the slices' stream: median {np.median(dev_ms):.2f} ms over {len(dev_ms)} days {np.round(dev_ms, 2).tolist()}", flush=True)
     per = np.diff(marks) * 1e3
     print(f"stream: {el / a.days * 1e3:.2f} ms per day over {a.days} days (fill and drain included); between deliveries {np.round(per, 2).tolist()}", flush=True)
+    if a.summary:
+        print("   summary (peak flow, step of the peak, mean flow of every row):",
+              "checked against the host's reduction of every day's full result" if check_summary else "not checked (no check asked for, or too large for a host reduction)", flush=True)
     print("   launches", p.stream_info()["launches"], " every day bit-identical to the days routed one by one:", ok if not a.no_check else "not checked", flush=True)
