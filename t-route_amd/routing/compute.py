@@ -22,8 +22,11 @@ Level-pool waterbodies (``waterbodies_df``, reservoir type 1) are routed and gag
 (``usgs_df`` / ``lastobs_df``, streamflow nudging) are prepared as the reference prepares them
 (``_prep_da_dataframes``, ``_prep_da_positions_byreach``), and so are the reservoir data-assimilation DataFrames of
 hybrid-persistence (USGS, USACE) and RFC reservoirs (``_prep_reservoir_da_dataframes``: tables and state per call, reservoir
-types demoted to level pool where a table is empty).  NotImplementedError: ``great_lakes_df``; a reservoir observation
-table that arrives without its ``*_param_df``; what the kernel callable refuses (mc_reach.py).
+types demoted to level pool where a table is empty; a type-5 waterbody with a row in the RFC frames gets its series like a type-4
+one).  The waterbody frames are read on every call -- the run-set loop updates them in place -- while what follows from the
+topology and the parameter table is kept by the identity of the caller's objects (``_NETWORKS``).  NotImplementedError:
+``great_lakes_df``; a reservoir observation table that arrives without its ``*_param_df``; what the kernel callable refuses
+(mc_reach.py).
 """
 from collections import defaultdict
 
@@ -215,20 +218,22 @@ def compute_nhd_routing_v02(
     import os
     ckey = None
     if os.environ.get("TRMC_CALL_CACHE", "1") != "0":
-        ckey = (id(reaches_bytw), id(independent_networks), id(param_df), id(waterbodies_df), id(waterbody_types_df), float(dt),
+        ckey = (id(reaches_bytw), id(independent_networks), id(param_df), float(dt),
                 len(reaches_bytw), len(independent_networks), tuple(param_df.shape), tuple(offnetwork_upstreams),
                 param_df.iloc[:: max(1, len(param_df) // 257)].values.astype("float64").sum(axis=0).tobytes() if len(param_df) else b"")
     net = _NETWORKS.get(ckey) if ckey is not None else None
     if net is None:
-        net = _network_of_call(reaches_bytw, independent_networks, param_df, dt, waterbodies_df, waterbody_types_df, offnetwork_upstreams)
+        net = _network_of_call(reaches_bytw, independent_networks, param_df, dt, offnetwork_upstreams)
         if ckey is not None:
-            net["refs"] = (reaches_bytw, independent_networks, param_df, waterbodies_df, waterbody_types_df)   # (ids stay taken)
+            net["refs"] = (reaches_bytw, independent_networks, param_df)   # (ids stay taken)
             _NETWORKS[ckey] = net
             while len(_NETWORKS) > 2:
                 _NETWORKS.pop(next(iter(_NETWORKS)))
     tws, reaches_wTypes, reach_owner, upstream_connections = net["tws"], net["reaches_wTypes"], net["reach_owner"], net["upstream_connections"]
-    lake_segs, waterbodies_sub, types_sub, table_index, table_cols, table_values = (
-        net["lake_segs"], net["waterbodies_sub"], net["types_sub"], net["index"], net["columns"], net["values"])
+    lake_segs, table_index, table_cols, table_values = net["lake_segs"], net["index"], net["columns"], net["values"]
+    # ---- the waterbody tables are the CALL's: the run-set loop writes every run set's outflows and pool elevations into the same
+    # waterbodies_df in place (update_waterbody_water_elevation, AbstractNetwork.py:198), so nothing of them is kept with the network
+    waterbodies_sub, types_sub = _waterbodies_of_call(net, waterbodies_df, waterbody_types_df)
     ids = net["ids"]
     nseg = ids.shape[0]
 
@@ -278,10 +283,17 @@ def compute_nhd_routing_v02(
     if len(lake_segs) and not _is_empty(waterbody_types_df):
         edf = pd.DataFrame()
         types_df_sub = waterbody_types_df.loc[lake_segs, ["reservoir_type"]].copy()
+        # a type-5 waterbody that has a row in the RFC tables is prepared like a type-4 one: the kernel callable looks both up there
+        # (mc_reach.py), the reference's helper selects type 4 only and leaves a type-5 waterbody without its series
+        as_rfc = np.zeros(len(lake_segs), dtype=bool)
+        if not _is_empty(reservoir_rfc_df) and not from_files:
+            as_rfc = (types_df_sub["reservoir_type"].values == 5) & types_df_sub.index.isin(reservoir_rfc_df.index)
+            types_df_sub.loc[as_rfc, "reservoir_type"] = 4
         p = _prep_reservoir_da_dataframes(
             edf if _is_empty(reservoir_usgs_df) else reservoir_usgs_df, reservoir_usgs_param_df,
             edf if _is_empty(reservoir_usace_df) else reservoir_usace_df, reservoir_usace_param_df,
             edf if _is_empty(reservoir_rfc_df) else reservoir_rfc_df, reservoir_rfc_param_df, types_df_sub, t0, from_files)
+        p[20].loc[as_rfc, "reservoir_type"] = 5
         types_sub = p[20].values.astype("int32")
         f32a, i32a = (lambda a: np.asarray(a).astype("float32")), (lambda a: np.asarray(a).astype("int32"))
         res_da_args = (
@@ -355,10 +367,39 @@ def compute_nhd_routing_v02(
 _NETWORKS = {}
 
 
-def _network_of_call(reaches_bytw, independent_networks, param_df, dt, waterbodies_df, waterbody_types_df, offnetwork_upstreams):
+_WB_COLS = ["LkArea", "LkMxE", "OrificeA", "OrificeC", "OrificeE", "WeirC", "WeirE", "WeirL", "ifd", "qd0", "h0"]
+
+
+def _waterbodies_of_call(net, waterbodies_df, waterbody_types_df):
+    """The waterbody table [lakes, 11] (compute.py:1421-1436: parameters, ``qd0``, ``h0``) and the reservoir types of the network's
+    waterbodies as the caller's frames hold them NOW -- one ``.loc`` over the lake rows per call.  They are state, not network:
+    between two run sets the reference writes the pools' last outflows and elevations into the same ``waterbodies_df`` object in
+    place (AbstractNetwork.py:198) and may demote reservoir types; a copy kept with the cached network would restart every pool
+    from the first run set."""
+    import pandas as pd
+    lake_segs, off_lakes = net["lake_segs"], net["off_lakes"]
+    if not lake_segs:
+        return np.zeros((0, 0), dtype="float64"), np.zeros((0, 0), dtype="int32")
+    if net["have_wb"] and _is_empty(waterbodies_df):
+        raise ValueError("reaches contain waterbody nodes but waterbodies_df is empty")
+    if off_lakes and (_is_empty(waterbodies_df) or len(pd.Index(off_lakes).difference(waterbodies_df.index))):
+        raise ValueError(f"flowveldepth_interorder key {off_lakes[0]} is neither a segment of param_df nor a waterbody")
+    missing = pd.Index(lake_segs).difference(waterbodies_df.index)
+    if len(missing):
+        raise ValueError(f"element {missing[0]} not found in {list(waterbodies_df.index)}")
+    waterbodies_sub = waterbodies_df.loc[lake_segs, _WB_COLS].values.astype("float64")               # compute.py:1421-1436
+    if not _is_empty(waterbody_types_df):
+        types_sub = waterbody_types_df.loc[lake_segs, ["reservoir_type"]].values.astype("int32")
+    else:
+        types_sub = np.zeros((0, 1) if net["have_wb"] else (0, 0), dtype="int32")
+    return waterbodies_sub, types_sub
+
+
+def _network_of_call(reaches_bytw, independent_networks, param_df, dt, offnetwork_upstreams):
     """Everything compute_nhd_routing_v02 derives from the network alone: the reach list with its types, the merged upstream
-    dictionary, the parameter table of the call (compute.py:548-549, :1399-1467: one table for every network of the call instead
-    of one per tailwater), which tailwater owns every row, and the order that groups the rows by tailwater."""
+    dictionary, the waterbodies' ids, the parameter table of the call (compute.py:548-549, :1399-1467: one table for every network
+    of the call instead of one per tailwater), which tailwater owns every row, and the order that groups the rows by tailwater.
+    Nothing of the waterbody frames: _waterbodies_of_call reads them on every call."""
     # compute.py:548-549
     param_df = param_df.copy()
     param_df["dt"] = dt
@@ -379,34 +420,9 @@ def _network_of_call(reaches_bytw, independent_networks, param_df, dt, waterbodi
             reach_owner.append(k)
             (lake_ids if is_wb else seg_ids).extend(reach)
     have_wb = bool(lake_ids)
-    if have_wb and _is_empty(waterbodies_df):
-        raise ValueError("reaches contain waterbody nodes but waterbodies_df is empty")
-    lake_segs = sorted(lake_ids)
-    if have_wb:
-        missing = [l for l in lake_segs if l not in waterbodies_df.index]
-        if missing:
-            raise ValueError(f"element {missing[0]} not found in {list(waterbodies_df.index)}")
-        wb_cols = ["LkArea", "LkMxE", "OrificeA", "OrificeC", "OrificeE", "WeirC", "WeirE", "WeirL", "ifd", "qd0", "h0"]
-        waterbodies_sub = waterbodies_df.loc[lake_segs, wb_cols].values.astype("float64")       # compute.py:1421-1436
-        if not _is_empty(waterbody_types_df):
-            types_sub = waterbody_types_df.loc[lake_segs, ["reservoir_type"]].values.astype("int32")
-        else:
-            types_sub = np.zeros((0, 1), dtype="int32")
-    else:
-        waterbodies_sub = np.zeros((0, 0), dtype="float64")
-        types_sub = np.zeros((0, 0), dtype="int32")
-
     off_segs = [u for u in offnetwork_upstreams if u in param_ids]      # compute.py:1586-1589: joined to the table
     off_lakes = [u for u in offnetwork_upstreams if u not in param_ids]
-    if off_lakes:
-        if _is_empty(waterbodies_df) or any(l not in waterbodies_df.index for l in off_lakes):
-            raise ValueError(f"flowveldepth_interorder key {off_lakes[0]} is neither a segment of param_df nor a waterbody")
-        if not have_wb:
-            wb_cols = ["LkArea", "LkMxE", "OrificeA", "OrificeC", "OrificeE", "WeirC", "WeirE", "WeirL", "ifd", "qd0", "h0"]
-        lake_segs = sorted(set(lake_segs) | set(off_lakes))
-        waterbodies_sub = waterbodies_df.loc[lake_segs, wb_cols].values.astype("float64")
-        if not _is_empty(waterbody_types_df):
-            types_sub = waterbody_types_df.loc[lake_segs, ["reservoir_type"]].values.astype("int32")
+    lake_segs = sorted(set(lake_ids) | set(off_lakes)) if off_lakes else sorted(lake_ids)
     seg_all = sorted(set(seg_ids) | set(off_segs))
     table = param_df.loc[seg_all, cols].reindex(seg_all + lake_segs).sort_index()                   # :1447-1465
     ids = np.ascontiguousarray(table.index.values.astype("int64"))
@@ -419,10 +435,9 @@ def _network_of_call(reaches_bytw, independent_networks, param_df, dt, waterbodi
     order = np.argsort(owner, kind="stable")
     bounds = np.searchsorted(owner[order], np.arange(len(tws) + 1))
     return {"tws": tws, "reaches_wTypes": reaches_wTypes, "reach_owner": reach_owner, "upstream_connections": upstream_connections,
-            "lake_segs": lake_segs, "waterbodies_sub": waterbodies_sub, "types_sub": types_sub, "index": table.index,
+            "lake_segs": lake_segs, "have_wb": have_wb, "off_lakes": off_lakes, "index": table.index,
             "columns": table.columns.values, "values": np.ascontiguousarray(table.values.astype("float32")), "ids": ids,
             "owner": owner, "order": order, "bounds": bounds}
-
 
 
 def compute_diffusive_routing(results, diffusive_network_data, cpu_pool, t0, dt, nts, q0, qlats, qts_subdivisions, usgs_df,
