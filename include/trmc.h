@@ -53,7 +53,8 @@ typedef enum trmc_status {
     TRMC_ENODEVICE = -3, /* no usable HIP device           -> RuntimeError   */
     TRMC_EHIP = -4,      /* HIP runtime error              -> RuntimeError   */
     TRMC_ENOMEM = -5,    /* allocation failed              -> MemoryError    */
-    TRMC_ESTATE = -6     /* call order violated (e.g. download before route) */
+    TRMC_ESTATE = -6,    /* call order violated (e.g. download before route) */
+    TRMC_EUNSUPPORTED = -7 /* a combination that is not built  -> NotImplementedError */
 } trmc_status;
 
 /* Parameter column order of `params` (9 columns, row-major [nseg][9]): the
@@ -315,20 +316,46 @@ int trmc_stream_push_day(trmc_plan *plan, const trmc_stream_day *day);
  *                      NaN never replaces a number and a NaN at step 1 stays.
  *   mean_flow [nseg] (plan precision): ((q[1] + q[2]) + ... + q[nsteps]) / nsteps, summed in that order in the plan's
  *                      precision (numpy: np.cumsum(q, axis=1, dtype=T)[:, -1] / T(nsteps)).
- *   trmc_stream_set_summary   what: a mask of TRMC_SUMMARY_PEAK (flow and step) and TRMC_SUMMARY_MEAN, 0 = none (the default).
+ *   peak_depth [nseg] (plan precision), peak_depth_step [nseg] (int32, 1-based): the same rule over the day's depths
+ *                      d[t] = out[row][step][2] -- the channel depth, the pool's water elevation at a reservoir row, 0 at a step
+ *                      without flow; nudging changes flows only.  The planes hold the depth of a tile's last step only, so this
+ *                      part is carried by the tile kernels (instances of their own, k_mc_tile_pkd / k_mc_ctile_pkd: a stream
+ *                      without the part launches what it always launched); a stream with full_output reduces its full result
+ *                      instead, to the same bits.  A boundary row is routed by nobody and has no depth: (0, 1) -- what the
+ *                      reduction of the rank's own full result gives there (such a stream's full result holds zeros at boundary
+ *                      rows).  TRMC_EUNSUPPORTED from trmc_stream_begin in a stream with reservoir data assimilation
+ *                      (trmc_stream_set_reservoir_da), and without full_output on a plan with velocity_on_demand < 0.
+ *   trmc_stream_set_summary   what: a mask of TRMC_SUMMARY_PEAK (flow and step), TRMC_SUMMARY_MEAN, TRMC_SUMMARY_PEAK_DEPTH (depth
+ *                      and step) and TRMC_SUMMARY_TOTAL (below; with at least one of the others), 0 = none (the default).
  *                      Before trmc_stream_begin; it stays until the next call, as trmc_stream_set_gages does; TRMC_ESTATE while
  *                      a stream is in progress.  Works with full_output, output_stride or neither, with reservoirs, gages and
- *                      reservoir data assimilation, in both arithmetics and precisions.
+ *                      (but the peak depth) reservoir data assimilation, in both arithmetics and precisions.
  *   trmc_stream_summary_dest  page-locked host arrays [nseg] for the summary of the NEXT day pushed (any may be NULL): the next
  *                      trmc_stream_push / trmc_stream_push_day that is accepted consumes them, a day pushed without this call
  *                      has no summary.  They are filled with the day's other products; trmc_stream_wait covers them.
  *                      TRMC_ESTATE if the stream in progress was begun without a summary, TRMC_EINVAL for an array whose part
  *                      of the mask is off.
- * A maximum over several days is the caller's: the larger of the days' peak_flow, the time from the winning day's peak_step.
- * Depths and velocities have no summary (the planes hold depths at tile ends only and no velocity). */
-enum { TRMC_SUMMARY_PEAK = 1, TRMC_SUMMARY_MEAN = 2 };
+ *   trmc_stream_summary_depth_dest  the same for peak_depth and peak_depth_step of the NEXT day pushed, with the same rules:
+ *                      TRMC_ESTATE if the stream in progress was begun without TRMC_SUMMARY_PEAK_DEPTH.
+ * THE TOTALS OVER THE DAYS (TRMC_SUMMARY_TOTAL): running values over all days handed over since trmc_stream_begin, [nseg] arrays in
+ * row order that live on the device outside the ring; every day's summary is folded into them in day order where the day is
+ * handed over, whether or not the day's own arrays go to the host (no trmc_stream_summary_dest: nothing of the summary crosses
+ * to the host but the totals).  All of them fold the per-day products:
+ *   peak_flow, peak_step (int64, 1-based from the stream's first step): day 0's values; then for day D >= 1 (0-based)
+ *                      `if (pk_D > pk) { pk = pk_D; step = D * nsteps + st_D; }`
+ *   peak_depth, peak_depth_step (int64): the same fold, with TRMC_SUMMARY_PEAK_DEPTH
+ *   mean_flow          (((m_0 + m_1) + m_2) + ...) / T(ndays) in the plan's precision, left to right
+ *   trmc_stream_summary_total  HOST arrays [nseg] (any may be NULL); synchronous: returns when the totals of all days handed over
+ *                      so far are on the host and writes that number of days to days_out.  TRMC_ESTATE when no stream is in
+ *                      progress, when it was begun without TRMC_SUMMARY_TOTAL or when no day is complete yet; TRMC_EINVAL for an
+ *                      array whose part of the mask is off.
+ * Velocities have no summary (a stream that assembles no full result forms no velocity). */
+enum { TRMC_SUMMARY_PEAK = 1, TRMC_SUMMARY_MEAN = 2, TRMC_SUMMARY_PEAK_DEPTH = 4, TRMC_SUMMARY_TOTAL = 8 };
 int trmc_stream_set_summary(trmc_plan *plan, int what);
 int trmc_stream_summary_dest(trmc_plan *plan, void *peak_flow_host, int32_t *peak_step_host, void *mean_flow_host);
+int trmc_stream_summary_depth_dest(trmc_plan *plan, void *peak_depth_host, int32_t *peak_depth_step_host);
+int trmc_stream_summary_total(trmc_plan *plan, void *peak_flow, int64_t *peak_step, void *mean_flow, void *peak_depth,
+                              int64_t *peak_depth_step, int64_t *days_out);
 /* Multi-GPU streams (the trunk of a cut basin: rows fed by boundary rows, cluster_late_lag tiles behind).  trmc_stream_gather: the
  * flows of a row set over `day` [rows][nsteps] into DEVICE memory, queued on `stream` (NULL: the plan's) behind the launches
  * queued so far -- TRMC_ESTATE if the set's rows have not been queued through that day yet.  trmc_stream_boundary: the boundary

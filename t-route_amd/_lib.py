@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TRMC_LIB_PATH") or os.path.join(_HERE, "libtrmc.so")
 
 TRMC_OK, TRMC_EINVAL, TRMC_ECYCLE, TRMC_ENODEVICE, TRMC_EHIP, TRMC_ENOMEM, TRMC_ESTATE = 0, -1, -2, -3, -4, -5, -6
+TRMC_EUNSUPPORTED = -7
 ENGINE_AUTO, ENGINE_LEVELS, ENGINE_FLOW, PLAN_SHORT_TS, PLAN_FULL_TS = 0, 1, 2, 4, 8   # trmc.h plan flags
 NPARAM = 9
 PARAM_COLS = ("dt", "dx", "bw", "tw", "twcc", "n", "ncc", "cs", "s0")  # trmc.h TRMC_P_*
@@ -105,6 +106,8 @@ class StreamReservoirDa(C.Structure):
 
 RESERVOIR_DA_HYBRID, RESERVOIR_DA_RFC = 2, 4
 SUMMARY_PEAK, SUMMARY_MEAN = 1, 2   # trmc_stream_set_summary's mask (include/trmc.h)
+SUMMARY_PEAK_DEPTH, SUMMARY_TOTAL = 4, 8
+SUMMARY_NAMES = {"peak": SUMMARY_PEAK, "mean": SUMMARY_MEAN, "peak_depth": SUMMARY_PEAK_DEPTH, "total": SUMMARY_TOTAL}
 _P = C.POINTER
 # name -> (restype, argtypes); must list every symbol include/trmc.h declares
 SIGNATURES = {
@@ -123,6 +126,8 @@ SIGNATURES = {
     "trmc_stream_set_reservoir_da": (_int, [_vp, _int, _i64, _i64, _i64]),
     "trmc_stream_set_summary": (_int, [_vp, _int]),
     "trmc_stream_summary_dest": (_int, [_vp, _vp, _vp, _vp]),
+    "trmc_stream_summary_depth_dest": (_int, [_vp, _vp, _vp]),
+    "trmc_stream_summary_total": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "trmc_stream_gather": (_int, [_vp, _i64, _i32, _vp, _vp]),
     "trmc_stream_boundary": (_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
     "trmc_stream_advance": (_int, [_vp, _int]),
@@ -294,6 +299,8 @@ def check(rc):
         raise ValueError(msg)
     if rc == TRMC_ENOMEM:
         raise MemoryError(msg)
+    if rc == TRMC_EUNSUPPORTED:
+        raise NotImplementedError(msg)
     raise RuntimeError(f"trmc error {rc}: {msg}")
 
 

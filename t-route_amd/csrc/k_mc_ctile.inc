@@ -37,8 +37,9 @@ constexpr int kClusterRowsMax = 128; // the most rows of a cluster (trmc_plan_op
 static_assert(kCtileBlock % 64 == 0 && kCtileBlock >= kClusterRowsMax && kCtileBlock <= 1024,
               "TRMC_CTILE_BLOCK: whole wavefronts, at least one cluster, at most one workgroup");
 constexpr int kCtileStage = kCtileBlock > 512 ? kTileStage / 2 : kTileStage; // (steps staged per run: fp64 rows of 1024 threads within a CU's LDS)
-template <class T, bool TOL, bool DEC, bool LAZYV, bool RDA> // (see mc_step_rows)
-__device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_t *__restrict__ cblk_ptr, int32_t cb0, int32_t tile, int32_t K);
+template <class T, bool TOL, bool DEC, bool LAZYV, bool RDA, bool PKD = false> // (see mc_step_rows; PKD: see k_mc_tile_pkd)
+__device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_t *__restrict__ cblk_ptr, int32_t cb0, int32_t tile, int32_t K,
+                                              T *pk_d = nullptr, int32_t *pk_at = nullptr);
 template <class T, bool TOL = false, bool DEC = false, bool LAZYV = false>
 __global__ void __launch_bounds__(kCtileBlock, sizeof(T) == 4 ? (LAZYV ? TRMC_TILE_WAVES_LAZY : TRMC_TILE_WAVES) : 1)
 k_mc_ctile(const StepArgs<T> a, const int32_t *__restrict__ cblk_ptr, const int32_t cb0, const int32_t tile, const int32_t K)
@@ -51,9 +52,17 @@ k_mc_ctile_rda(const StepArgs<float> a, const int32_t *__restrict__ cblk_ptr, co
 {
     mc_ctile_rows<float, false, DEC, false, true>(a, cblk_ptr, cb0, tile, K);
 }
-template <class T, bool TOL, bool DEC, bool LAZYV, bool RDA>
+// (the cluster rows' peak depth of the day: k_mc_tile_pkd)
+template <class T, bool TOL = false, bool DEC = false>
+__global__ void __launch_bounds__(kCtileBlock, sizeof(T) == 4 ? TRMC_TILE_WAVES_LAZY : 1)
+k_mc_ctile_pkd(const StepArgs<T> a, const int32_t *__restrict__ cblk_ptr, const int32_t cb0, const int32_t tile, const int32_t K,
+               T *const pk_d, int32_t *const pk_at)
+{
+    mc_ctile_rows<T, TOL, DEC, true, false, true>(a, cblk_ptr, cb0, tile, K, pk_d, pk_at);
+}
+template <class T, bool TOL, bool DEC, bool LAZYV, bool RDA, bool PKD>
 __device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_t *__restrict__ cblk_ptr, const int32_t cb0,
-                                              const int32_t tile, const int32_t K)
+                                              const int32_t tile, const int32_t K, T *const pk_d, int32_t *const pk_at)
 {
     using M = typename DevMath<T, TOL>::type;
     const ColdArgs<StepArgs<T>> cold = cold_args<StepArgs<T>>();
@@ -121,6 +130,15 @@ __device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_
     T *q_up = q_tm + (size_t)(t_lo - 1) * np;
     const int32_t v_every = (LAZYV && DEC) ? cold->v_every : 0; // (see StepArgs and k_mc_tile)
     int32_t v_left = v_every > 0 ? (v_every - 1) - ((t_lo - 1) % v_every) : 0;
+    T dmax = T(0);
+    int32_t dmax_at = 1;
+    if constexpr (PKD) {
+        if (t_lo != 1) { // (as k_mc_tile; a lane without a row reads the block's first row's and writes nothing)
+            const size_t col = (size_t)slot * np + (size_t)su;
+            dmax = pk_d[col];
+            dmax_at = pk_at[col];
+        }
+    }
     for (int32_t t = t_lo; t <= t_hi; ++t, q_up += np) {
         bool want_v = false;
         if constexpr (LAZYV && DEC) {
@@ -175,6 +193,12 @@ __device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_
             hand_on_row<T>(cold, slot, slot_next, ob, np, t, t_hi, q_new, d_new);
             q_prev = q_new;
             d_prev = d_new;
+            if constexpr (PKD) {
+                if (t == 1 || d_new > dmax) {
+                    dmax = d_new;
+                    dmax_at = t;
+                }
+            }
             if (LAZYV && want_v && it_last > 0) v_new = trmc::step_velocity<T, M>(p, c, d_new, m); // (as k_mc_tile)
             if (DEC || (!LAZYV && a.out)) { // stage (q, v, d) of step t; a run ends when kCtileStage steps are staged and at the tile's last step
                 // (a.out == nullptr: a stream of windows whose callers take products only -- nothing of the full result is assembled)
@@ -217,6 +241,11 @@ __device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_
         __syncthreads(); // step t's flows are in s_x[t & 1] for step t + 1; slot (t - 1) & 1 is free again
     }
     if (!active) return;
+    if constexpr (PKD) {
+        const size_t col = (size_t)slot * np + (size_t)su;
+        pk_d[col] = dmax;
+        pk_at[col] = dmax_at;
+    }
     if (t_hi == cold->nsteps) cold->it_prev[su] = (uint8_t)min(it_last, 255);
     if (uint8_t *const cls = cold->cls_last) cls[su] = (uint8_t)(min(it_last, 3) + (over_last ? 4 : 0));
     if (uint16_t *const it_sum = cold->it_sum) it_sum[su] = (uint16_t)min(65535, (int)it_sum[su] + it_acc);

@@ -332,8 +332,9 @@ constexpr int64_t kMidDefaultRowsPerCu = 0; // default threshold of the second t
 // sequence, ms per day on the cost-ordered / the unordered plan: 6: 16.06 / 17.55, 16: 16.07 / 17.33, 40: 16.06 / 17.36
 #define TRMC_HOT_WAVE_MAX 16
 #endif
-template <class T, bool TOL, bool DEC, bool LAZYV, bool RDA> // (see mc_step_rows)
-__device__ __forceinline__ void mc_tile_rows(const StepArgs<T> &a, int32_t s_begin, int32_t s_end, int32_t tile, int32_t K);
+template <class T, bool TOL, bool DEC, bool LAZYV, bool RDA, bool PKD = false> // (see mc_step_rows; PKD: see k_mc_tile_pkd)
+__device__ __forceinline__ void mc_tile_rows(const StepArgs<T> &a, int32_t s_begin, int32_t s_end, int32_t tile, int32_t K,
+                                             T *pk_d = nullptr, int32_t *pk_at = nullptr);
 template <class T, bool TOL = false, bool DEC = false, bool LAZYV = false> // (LAZYV: StepArgs::v_every != 0)
 __global__ void __launch_bounds__(kTileBlock, sizeof(T) == 4 ? (LAZYV ? TRMC_TILE_WAVES_LAZY : TRMC_TILE_WAVES) : 1)
 k_mc_tile(const StepArgs<T> a, const int32_t s_begin, const int32_t s_end, const int32_t tile, const int32_t K)
@@ -346,9 +347,23 @@ k_mc_tile_rda(const StepArgs<float> a, const int32_t s_begin, const int32_t s_en
 {
     mc_tile_rows<float, false, DEC, false, true>(a, s_begin, s_end, tile, K);
 }
-template <class T, bool TOL, bool DEC, bool LAZYV, bool RDA>
+// PKD: THE ROW'S PEAK DEPTH OF THE DAY rides along (trmc_stream_set_summary, TRMC_SUMMARY_PEAK_DEPTH).  Every step's depth is in a
+// register here and nowhere else -- the planes hold the depth of a tile's last step only -- so the row keeps (dmax, at) through
+// its K steps: `peak = d[1], step = 1`, then `if (d[t] > peak) { peak = d[t]; step = t; }`, peak_flow's rule.  Between the tiles
+// of a day they live in two columns of the row's slot, pk_d / pk_at [slots][nseg_pad] in plan order: read at the tile's start
+// unless the tile begins the day (a slot's last occupant leaves nothing behind), written at its end; where the day is handed
+// over k_stream_peak_depth puts them into row order.  Instances of their own (the LAZYV forms: a stream that assembles no full
+// result; one that does reduces out[row][step][2]), so that every other instance compiles as it did.
+template <class T, bool TOL = false, bool DEC = false>
+__global__ void __launch_bounds__(kTileBlock, sizeof(T) == 4 ? TRMC_TILE_WAVES_LAZY : 1)
+k_mc_tile_pkd(const StepArgs<T> a, const int32_t s_begin, const int32_t s_end, const int32_t tile, const int32_t K, T *const pk_d,
+              int32_t *const pk_at)
+{
+    mc_tile_rows<T, TOL, DEC, true, false, true>(a, s_begin, s_end, tile, K, pk_d, pk_at);
+}
+template <class T, bool TOL, bool DEC, bool LAZYV, bool RDA, bool PKD>
 __device__ __forceinline__ void mc_tile_rows(const StepArgs<T> &a, const int32_t s_begin, const int32_t s_end, const int32_t tile,
-                                             const int32_t K)
+                                             const int32_t K, T *const pk_d, int32_t *const pk_at)
 {
     using M = typename DevMath<T, TOL>::type;
     const ColdArgs<StepArgs<T>> cold = cold_args<StepArgs<T>>(); // (see cold_args: what the loop rarely needs is not kept in registers)
@@ -457,6 +472,15 @@ __device__ __forceinline__ void mc_tile_rows(const StepArgs<T> &a, const int32_t
     // step's stores, and only at the steps whose velocity is kept (DEC); without DEC nothing is staged and none of it is compiled.
     const int32_t v_every = (LAZYV && DEC) ? cold->v_every : 0;
     int32_t v_left = v_every > 0 ? (v_every - 1) - ((t_lo - 1) % v_every) : 0; // steps before the next one whose velocity is wanted
+    T dmax = T(0);
+    int32_t dmax_at = 1;
+    if constexpr (PKD) {
+        if (t_lo != 1) { // (the day's earlier tiles of this row; step 1 starts the day's peak over)
+            const size_t col = (size_t)slot * np + (size_t)su;
+            dmax = pk_d[col];
+            dmax_at = pk_at[col];
+        }
+    }
     for (int32_t t = t_lo; t <= t_hi; ++t, q_up += np) {
         bool want_v = false;
         if constexpr (LAZYV && DEC) {
@@ -505,6 +529,12 @@ __device__ __forceinline__ void mc_tile_rows(const StepArgs<T> &a, const int32_t
         hand_on_row<T>(cold, slot, slot_next, ob, np, t, t_hi, q_new, d_new);
         q_prev = q_new;
         d_prev = d_new;
+        if constexpr (PKD) {
+            if (t == 1 || d_new > dmax) { // (the first of equal peaks wins; a NaN never replaces a number)
+                dmax = d_new;
+                dmax_at = t;
+            }
+        }
         // (LAZYV: the velocity of a kept step, from the depth the step ended on -- what mc_segment_step forms; 0 where the step
         // had no flow, iters == 0, as there.  Nudging changes the flow only.)
         if (LAZYV && want_v && it_last > 0) v_new = trmc::step_velocity<T, M>(p, c, d_new, m);
@@ -546,6 +576,11 @@ __device__ __forceinline__ void mc_tile_rows(const StepArgs<T> &a, const int32_t
                 staged = 0;
             }
         }
+    }
+    if constexpr (PKD) {
+        const size_t col = (size_t)slot * np + (size_t)su;
+        pk_d[col] = dmax;
+        pk_at[col] = dmax_at;
     }
     if (t_hi == cold->nsteps) cold->it_prev[su] = (uint8_t)min(it_last, 255);
     if (uint8_t *const cls = cold->cls_last) {
@@ -817,6 +852,71 @@ k_stream_summary(const T *__restrict__ q_tm, const int32_t *__restrict__ row_of_
         step[r] = at;
     }
     if (mean) mean[r] = s / T(nsteps);
+}
+
+// A day's peak depth and its step in ROW order, beside k_stream_summary.  From the slot's two carry columns (k_mc_tile_pkd: plan
+// order, one thread per position): boundary rows are routed by nobody and have no depth -- (0, 1), what the reduction below gives
+// there, a full result holding zeros at those rows ...
+template <class T>
+__global__ void __launch_bounds__(kBlock)
+k_stream_peak_depth(const T *__restrict__ pk_d, const int32_t *__restrict__ pk_at, const int32_t *__restrict__ row_of_pos,
+                    T *__restrict__ peak, int32_t *__restrict__ step, int32_t nseg, int32_t nboundary)
+{
+    const int32_t p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= nseg) return;
+    const size_t r = (size_t)row_of_pos[p];
+    peak[r] = p < nboundary ? T(0) : pk_d[p];
+    step[r] = p < nboundary ? 1 : pk_at[p];
+}
+// ... or, in a stream that assembles the full result, from out[row][step][2] of the day (one thread per row; the same compares in
+// the same order on the same depths: the same bits)
+template <class T>
+__global__ void __launch_bounds__(kBlock)
+k_stream_peak_depth_out(const T *__restrict__ out, T *__restrict__ peak, int32_t *__restrict__ step, int32_t nseg, int32_t nsteps)
+{
+    const int32_t r = blockIdx.x * kBlock + threadIdx.x;
+    if (r >= nseg) return;
+    const T *d = out + (size_t)r * (size_t)nsteps * 3 + 2;
+    T pk = d[0];
+    int32_t at = 1;
+    for (int32_t t = 2; t <= nsteps; ++t) {
+        const T v = d[(size_t)(t - 1) * 3];
+        if (v > pk) {
+            pk = v;
+            at = t;
+        }
+    }
+    peak[r] = pk;
+    step[r] = at;
+}
+
+// The totals over the days of a stream (TRMC_SUMMARY_TOTAL): day `day`'s summary folded into the running values, [nseg] in row
+// order, one thread per row.  Day 0 starts them; then `if (pk_D > pk) { pk = pk_D; step = D * nsteps + st_D; }` for the flow and
+// for the depth, and the days' means summed left to right in T (the fetch divides by the number of days).  Any part may be NULL.
+template <class T>
+__global__ void __launch_bounds__(kBlock)
+k_stream_total(const T *__restrict__ pk_day, const int32_t *__restrict__ st_day, const T *__restrict__ mean_day,
+               const T *__restrict__ pd_day, const int32_t *__restrict__ pds_day, T *__restrict__ pk, int64_t *__restrict__ st,
+               T *__restrict__ mean_sum, T *__restrict__ pd, int64_t *__restrict__ pds, int32_t nseg, int64_t day, int32_t nsteps)
+{
+    const int32_t r = blockIdx.x * kBlock + threadIdx.x;
+    if (r >= nseg) return;
+    const int64_t t0 = day * (int64_t)nsteps;
+    if (pk_day) {
+        const T v = pk_day[r];
+        if (day == 0 || v > pk[r]) {
+            pk[r] = v;
+            st[r] = t0 + st_day[r];
+        }
+    }
+    if (pd_day) {
+        const T v = pd_day[r];
+        if (day == 0 || v > pd[r]) {
+            pd[r] = v;
+            pds[r] = t0 + pds_day[r];
+        }
+    }
+    if (mean_day) mean_sum[r] = day == 0 ? mean_day[r] : mean_sum[r] + mean_day[r];
 }
 
 template <class T>

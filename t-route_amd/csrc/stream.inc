@@ -48,6 +48,15 @@
 // handed over one column reduction over that plane (k_stream_summary, beside k_final_state) forms the three arrays [nseg] in row
 // order in the slot's summary buffers, and they leave on the copy stream with the day's other products.  Off (the default): no
 // buffer, no launch.
+// THE PEAK DEPTH of the day (TRMC_SUMMARY_PEAK_DEPTH) is the one part the planes cannot give -- they hold the depth of a tile's last
+// step only -- so the tile kernels carry it, in instances of their own (k_mc_tile_pkd, k_mc_ctile_pkd: two registers through a
+// tile's steps, two columns [slots][nseg_pad] between the tiles), and k_stream_peak_depth puts the slot's columns into row order
+// where the day is handed over.  A stream with full_output runs the instances it always ran and reduces the day's
+// out[row][step][2] instead (k_stream_peak_depth_out): the same bits.  Every row of a stream is routed by one of the two tile
+// kernels (stream_launch), the hot-list blocks of k_mc_tile included; boundary rows by nobody: (0, 1).
+// THE TOTALS over the days of the stream (TRMC_SUMMARY_TOTAL) live outside the ring: [nseg] arrays in row order into which
+// k_stream_total folds every day's summary, in day order, right behind the kernels that formed it; trmc_stream_summary_total
+// fetches them.
 extern "C++" {
 struct StreamProd {
     int64_t day = -1;
@@ -55,6 +64,7 @@ struct StreamProd {
     void *nudge_host = nullptr, *res_inflow_host = nullptr;
     void *rda_state_host = nullptr, *rda_tsidx_host = nullptr;
     void *peak_host = nullptr, *step_host = nullptr, *mean_host = nullptr; // the day's summary (trmc_stream_summary_dest)
+    void *pd_host = nullptr, *pds_host = nullptr;                           // ... its peak depth (trmc_stream_summary_depth_dest)
     int32_t rowset = -1;
     bool queued = false;          // the gathers and copies of this day are queued
     hipEvent_t ev_done = nullptr; // ... and this fires when they are through
@@ -92,6 +102,15 @@ struct StreamRun {
     int32_t sum_want = 0, sum = 0;
     DevBuf sum_peak, sum_step, sum_mean; // [slots][nseg] each, in row order (only what the mask asks for)
     void *next_peak = nullptr, *next_step = nullptr, *next_mean = nullptr;
+    // the peak depth: carry = the tile launches carry it in pkd_d / pkd_at [slots][nseg_pad] (plan order; otherwise the full result
+    // is reduced); sum_pd / sum_pds [slots][nseg] in row order; next_*: as above (trmc_stream_summary_depth_dest)
+    bool carry = false;
+    DevBuf pkd_d, pkd_at, sum_pd, sum_pds;
+    void *next_pd = nullptr, *next_pds = nullptr;
+    // the totals over the days (TRMC_SUMMARY_TOTAL): [nseg] in row order, outside the ring; tot_days days are folded in (queued)
+    DevBuf tot_pk, tot_st, tot_mean, tot_pd, tot_pds;
+    int64_t tot_days = 0;
+    hipEvent_t ev_total = nullptr; // the last fold queued is through
     std::vector<hipEvent_t> ev_slab;    // ring: "slab launch g is complete" (the cluster launch g + 1 waits for it)
     std::vector<hipEvent_t> ev_free;    // [slots] the day that used the slot has handed its products over
     std::vector<hipEvent_t> ev_ready;   // [slots] the gathers of that day are through (copy stream waits)
@@ -110,7 +129,8 @@ static void stream_release(trmc_plan *pl)
     StreamRun *S = pl->seq;
     if (!S) return;
     for (DevBuf *b : {&S->tm, &S->qlat, &S->out, &S->dec, &S->hyd, &S->q0, &S->res_inflow, &S->da_mode, &S->da_a, &S->da_w, &S->da_nudge, &S->da_q0, &S->gage_of_pos, &S->gage_pos_dev, &S->rda_tab,
-                       &S->rda_carry, &S->rda_prod, &S->sum_peak, &S->sum_step, &S->sum_mean})
+                       &S->rda_carry, &S->rda_prod, &S->sum_peak, &S->sum_step, &S->sum_mean, &S->pkd_d, &S->pkd_at, &S->sum_pd, &S->sum_pds,
+                       &S->tot_pk, &S->tot_st, &S->tot_mean, &S->tot_pd, &S->tot_pds})
         b->release();
     if (S->rda_stage) (void)hipHostFree(S->rda_stage);
     for (auto *v : {&S->ev_slab, &S->ev_free, &S->ev_ready, &S->ev_forcing, &S->ev_t0, &S->ev_t1})
@@ -118,7 +138,7 @@ static void stream_release(trmc_plan *pl)
             if (e) (void)hipEventDestroy(e);
     for (StreamProd &p : S->prod)
         if (p.ev_done) (void)hipEventDestroy(p.ev_done);
-    for (hipEvent_t e : {S->ev_begin, S->ev_bnd, S->ev_gat})
+    for (hipEvent_t e : {S->ev_begin, S->ev_bnd, S->ev_gat, S->ev_total})
         if (e) (void)hipEventDestroy(e);
     if (S->fst) (void)hipStreamDestroy(S->fst);
     delete S;
@@ -291,9 +311,13 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
     const int64_t nrows = (p.hyd_host && p.rowset >= 0) ? pl->rowset_n[(size_t)p.rowset] : 0;
     const bool want_nudge = p.nudge_host && S.slot_da > 0, want_res = p.res_inflow_host && S.slot_res > 0;
     const bool want_rda = S.rda && (p.rda_state_host || p.rda_tsidx_host);
-    const bool want_peak = (S.sum & TRMC_SUMMARY_PEAK) && (p.peak_host || p.step_host) && pl->nseg > 0;
-    const bool want_mean = (S.sum & TRMC_SUMMARY_MEAN) && p.mean_host && pl->nseg > 0;
-    const bool any = nrows > 0 || p.q0_host || p.fvd_host || want_nudge || want_res || want_rda || want_peak || want_mean;
+    // (the totals fold every day's summary: with them a part is formed whether or not the day's own arrays go to the host)
+    const bool total = (S.sum & TRMC_SUMMARY_TOTAL) && pl->nseg > 0;
+    const bool want_peak = (S.sum & TRMC_SUMMARY_PEAK) && (p.peak_host || p.step_host || total) && pl->nseg > 0;
+    const bool want_mean = (S.sum & TRMC_SUMMARY_MEAN) && (p.mean_host || total) && pl->nseg > 0;
+    const bool want_pd = (S.sum & TRMC_SUMMARY_PEAK_DEPTH) && (p.pd_host || p.pds_host || total) && pl->nseg > 0;
+    const bool any = nrows > 0 || p.q0_host || p.fvd_host || want_nudge || want_res || want_rda || (want_peak && (p.peak_host || p.step_host))
+                     || (want_mean && p.mean_host) || (want_pd && (p.pd_host || p.pds_host)); // (what the copy stream has to carry)
     float *const rda_state = (float *)S.rda_prod.p + (size_t)slot * (size_t)pl->nres * 5;
     int32_t *const rda_tsidx = (int32_t *)(rda_state + (size_t)pl->nres * 4);
     if (want_rda)
@@ -313,6 +337,22 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
     if (want_peak || want_mean)
         hipLaunchKernelGGL((k_stream_summary<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, q, (const int32_t *)pl->row_of_pos.p, sum_peak,
                            sum_step, sum_mean, (int32_t)pl->nseg, pl->nseg_pad, S.nsteps);
+    T *const sum_pd = want_pd ? (T *)S.sum_pd.p + (size_t)slot * (size_t)pl->nseg : nullptr;
+    int32_t *const sum_pds = want_pd ? (int32_t *)S.sum_pds.p + (size_t)slot * (size_t)pl->nseg : nullptr;
+    if (want_pd && S.carry)
+        hipLaunchKernelGGL((k_stream_peak_depth<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, (const T *)S.pkd_d.p + (size_t)slot * (size_t)pl->nseg_pad,
+                           (const int32_t *)S.pkd_at.p + (size_t)slot * (size_t)pl->nseg_pad, (const int32_t *)pl->row_of_pos.p, sum_pd, sum_pds,
+                           (int32_t)pl->nseg, (int32_t)pl->topo.nboundary);
+    else if (want_pd)
+        hipLaunchKernelGGL((k_stream_peak_depth_out<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, (const T *)S.out.p + (size_t)slot * S.slot_out,
+                           sum_pd, sum_pds, (int32_t)pl->nseg, S.nsteps);
+    if (total) {
+        hipLaunchKernelGGL((k_stream_total<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, (const T *)sum_peak, (const int32_t *)sum_step,
+                           (const T *)sum_mean, (const T *)sum_pd, (const int32_t *)sum_pds, (T *)S.tot_pk.p, (int64_t *)S.tot_st.p, (T *)S.tot_mean.p,
+                           (T *)S.tot_pd.p, (int64_t *)S.tot_pds.p, (int32_t)pl->nseg, e, S.nsteps);
+        HIP_TRY(hipEventRecord(S.ev_total, pst));
+        S.tot_days = e + 1;
+    }
     HIP_TRY(hipGetLastError());
     if (!any) {
         HIP_TRY(hipEventRecord(S.ev_free[(size_t)slot], pst));
@@ -344,11 +384,14 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
         HIP_TRY(hipMemcpyAsync(p.rda_state_host, rda_state, (size_t)pl->nres * 4 * sizeof(float), hipMemcpyDeviceToHost, pl->cstream));
     if (want_rda && p.rda_tsidx_host)
         HIP_TRY(hipMemcpyAsync(p.rda_tsidx_host, rda_tsidx, (size_t)pl->nres * sizeof(int32_t), hipMemcpyDeviceToHost, pl->cstream));
+    if (want_pd && p.pd_host) HIP_TRY(hipMemcpyAsync(p.pd_host, sum_pd, (size_t)pl->nseg * sizeof(T), hipMemcpyDeviceToHost, pl->cstream));
+    if (want_pd && p.pds_host)
+        HIP_TRY(hipMemcpyAsync(p.pds_host, sum_pds, (size_t)pl->nseg * sizeof(int32_t), hipMemcpyDeviceToHost, pl->cstream));
     if (want_peak && p.peak_host)
         HIP_TRY(hipMemcpyAsync(p.peak_host, sum_peak, (size_t)pl->nseg * sizeof(T), hipMemcpyDeviceToHost, pl->cstream));
     if (want_peak && p.step_host)
         HIP_TRY(hipMemcpyAsync(p.step_host, sum_step, (size_t)pl->nseg * sizeof(int32_t), hipMemcpyDeviceToHost, pl->cstream));
-    if (want_mean)
+    if (want_mean && p.mean_host)
         HIP_TRY(hipMemcpyAsync(p.mean_host, sum_mean, (size_t)pl->nseg * sizeof(T), hipMemcpyDeviceToHost, pl->cstream));
     HIP_TRY(hipEventRecord(S.ev_free[(size_t)slot], pl->cstream));
     HIP_TRY(hipEventRecord(p.ev_done, pl->cstream));
@@ -376,6 +419,9 @@ template <class T> int stream_launch(trmc_plan *pl, StreamRun &S, int64_t g_from
     tile_args(pl, S.W, as);
     StepArgs<T> a = as;
     a.hot_list = a.hot_cnt = nullptr;
+    // (the rows' peak depth of the day rides in these launches: the slots' two columns -- NULL: the instances of a stream without it)
+    T *const pk_d = S.carry ? (T *)S.pkd_d.p : nullptr;
+    int32_t *const pk_at = S.carry ? (int32_t *)S.pkd_at.p : nullptr;
     for (int64_t g = g_from + 1; g <= g_to; ++g) {
         a.seq_day = as.seq_day = (int32_t)(g / S.tpd);
         const int32_t tile = (int32_t)(g % S.tpd);
@@ -388,7 +434,7 @@ template <class T> int stream_launch(trmc_plan *pl, StreamRun &S, int64_t g_from
         if (S.W > 0 && w1 > w0) {
             first_obs(wst, w0, w1);
             if (as.hot_list) tile_turn(pl, as);
-            launch_tile<T>(wst, as, w0, w1, tile, S.K, tol);
+            launch_tile<T>(wst, as, w0, w1, tile, S.K, tol, pk_d, pk_at);
             HIP_TRY(hipEventRecord(S.ev_slab[(size_t)(g % kSlabEvents)], wst));
             ++S.launches;
         }
@@ -396,11 +442,11 @@ template <class T> int stream_launch(trmc_plan *pl, StreamRun &S, int64_t g_from
             if (S.W > 0 && g >= 1) HIP_TRY(hipStreamWaitEvent(cst, S.ev_slab[(size_t)((g - 1) % kSlabEvents)], 0));
             first_obs(cst, w1, (int32_t)pl->nseg_pad);
             if (w2 > w1) { // (the deeper slices)
-                launch_tile<T>(cst, a, w1, w2, tile, S.K, tol);
+                launch_tile<T>(cst, a, w1, w2, tile, S.K, tol, pk_d, pk_at);
                 ++S.launches;
             }
             if (ncblk > 0) {
-                launch_ctile<T>(cst, a, (const int32_t *)pl->cblk_ptr.p, 0, ncblk, tile, S.K, tol);
+                launch_ctile<T>(cst, a, (const int32_t *)pl->cblk_ptr.p, 0, ncblk, tile, S.K, tol, pk_d, pk_at);
                 ++S.launches;
             }
         }
@@ -477,9 +523,52 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
     }
     if (S.sum & TRMC_SUMMARY_MEAN)
         if (int rc = S.sum_mean.ensure((size_t)S.slots * (size_t)pl->nseg * sizeof(T))) return rc;
+    // ... the peak depth: carried by the tile launches unless the stream assembles the full result, which is reduced then
+    S.next_pd = S.next_pds = nullptr;
+    S.carry = (S.sum & TRMC_SUMMARY_PEAK_DEPTH) && !S.want_out;
+    if (S.carry && pl->opt.velocity_on_demand < 0)
+        return fail(TRMC_EUNSUPPORTED, "the peak depth of a stream without full_output is carried by the tile kernels' on-demand-velocity instances: "
+                                       "not with trmc_plan_options.velocity_on_demand < 0");
+    for (DevBuf *b : {&S.pkd_d, &S.pkd_at})
+        if (!S.carry) b->release();
+    for (DevBuf *b : {&S.sum_pd, &S.sum_pds})
+        if (!(S.sum & TRMC_SUMMARY_PEAK_DEPTH)) b->release();
+    if (S.carry) {
+        if (int rc = S.pkd_d.ensure((size_t)S.slots * np * sizeof(T))) return rc;
+        if (int rc = S.pkd_at.ensure((size_t)S.slots * np * sizeof(int32_t))) return rc;
+    }
+    if (S.sum & TRMC_SUMMARY_PEAK_DEPTH) {
+        if (int rc = S.sum_pd.ensure((size_t)S.slots * (size_t)pl->nseg * sizeof(T))) return rc;
+        if (int rc = S.sum_pds.ensure((size_t)S.slots * (size_t)pl->nseg * sizeof(int32_t))) return rc;
+        // (boundary rows of the full result are written by nobody: zeros, so that their reduction is the (0, 1) the carry gives)
+        if (S.want_out && tp.nboundary > 0) HIP_TRY(hipMemsetAsync(S.out.p, 0, (size_t)S.slots * S.slot_out * sizeof(T), pl->stream));
+    }
+    // ... the totals over the days: only the parts the mask asks for
+    S.tot_days = 0;
+    const bool tot = (S.sum & TRMC_SUMMARY_TOTAL) != 0;
+    if (!(tot && (S.sum & TRMC_SUMMARY_PEAK))) {
+        S.tot_pk.release();
+        S.tot_st.release();
+    } else {
+        if (int rc = S.tot_pk.ensure((size_t)pl->nseg * sizeof(T))) return rc;
+        if (int rc = S.tot_st.ensure((size_t)pl->nseg * sizeof(int64_t))) return rc;
+    }
+    if (!(tot && (S.sum & TRMC_SUMMARY_MEAN))) S.tot_mean.release();
+    else if (int rc = S.tot_mean.ensure((size_t)pl->nseg * sizeof(T))) return rc;
+    if (!(tot && (S.sum & TRMC_SUMMARY_PEAK_DEPTH))) {
+        S.tot_pd.release();
+        S.tot_pds.release();
+    } else {
+        if (int rc = S.tot_pd.ensure((size_t)pl->nseg * sizeof(T))) return rc;
+        if (int rc = S.tot_pds.ensure((size_t)pl->nseg * sizeof(int64_t))) return rc;
+    }
+    if (tot && !S.ev_total) HIP_TRY(hipEventCreateWithFlags(&S.ev_total, hipEventDisableTiming));
     // reservoir data assimilation: the slots' tables at their capacity, the carry with the state trmc_set_reservoir_da supplied
     // (or the plan's last window left in those tables), the days' state records
     S.rda = pl->nres > 0 && pl->res_da_on && S.rda_want;
+    if (S.rda && (S.sum & TRMC_SUMMARY_PEAK_DEPTH))
+        return fail(TRMC_EUNSUPPORTED, "the peak depth of the day (TRMC_SUMMARY_PEAK_DEPTH) is not supported in a stream with reservoir data "
+                                       "assimilation: the _rda tile instances do not carry it");
     S.slot_rda = 0;
     if (S.rda) {
         int64_t floats = pl->nres * (int64_t)(sizeof(trmc::ResDaRec) / sizeof(float));
@@ -607,7 +696,9 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
     p.peak_host = S.next_peak; // (trmc_stream_summary_dest: this push consumes them)
     p.step_host = S.next_step;
     p.mean_host = S.next_mean;
-    S.next_peak = S.next_step = S.next_mean = nullptr;
+    p.pd_host = S.next_pd; // (trmc_stream_summary_depth_dest)
+    p.pds_host = S.next_pds;
+    S.next_peak = S.next_step = S.next_mean = S.next_pd = S.next_pds = nullptr;
     // the day's forcing: host -> staging area -> plan order in the slot, all on the copy stream of that direction
     const size_t bytes = (size_t)pl->nseg * S.nq * sizeof(T);
     if (int rc = pl->in_qlat.ensure(bytes)) return rc;
@@ -771,7 +862,11 @@ int trmc_stream_set_summary(trmc_plan *pl, int what)
 {
     if (int rc = stream_check(pl, false)) return rc;
     if (pl->flow) return fail(TRMC_EINVAL, "a stream of windows runs on the level engine");
-    if (what & ~(TRMC_SUMMARY_PEAK | TRMC_SUMMARY_MEAN)) return fail(TRMC_EINVAL, "what: a mask of TRMC_SUMMARY_PEAK and TRMC_SUMMARY_MEAN (0: no summary)");
+    constexpr int parts = TRMC_SUMMARY_PEAK | TRMC_SUMMARY_MEAN | TRMC_SUMMARY_PEAK_DEPTH;
+    if (what & ~(parts | TRMC_SUMMARY_TOTAL))
+        return fail(TRMC_EINVAL, "what: a mask of TRMC_SUMMARY_PEAK, TRMC_SUMMARY_MEAN, TRMC_SUMMARY_PEAK_DEPTH and TRMC_SUMMARY_TOTAL (0: no summary)");
+    if ((what & TRMC_SUMMARY_TOTAL) && !(what & parts))
+        return fail(TRMC_EINVAL, "TRMC_SUMMARY_TOTAL needs at least one of the parts it totals (TRMC_SUMMARY_PEAK, TRMC_SUMMARY_MEAN, TRMC_SUMMARY_PEAK_DEPTH)");
     if (!pl->seq) pl->seq = new StreamRun();
     pl->seq->sum_want = what;
     return 0;
@@ -788,6 +883,53 @@ int trmc_stream_summary_dest(trmc_plan *pl, void *peak_flow_host, int32_t *peak_
     S.next_peak = peak_flow_host;
     S.next_step = peak_step_host;
     S.next_mean = mean_flow_host;
+    return 0;
+}
+
+int trmc_stream_summary_depth_dest(trmc_plan *pl, void *peak_depth_host, int32_t *peak_depth_step_host)
+{
+    if (int rc = stream_check(pl, true)) return rc;
+    StreamRun &S = *pl->seq;
+    if (!(S.sum & TRMC_SUMMARY_PEAK_DEPTH))
+        return fail(TRMC_ESTATE, "the stream was begun without TRMC_SUMMARY_PEAK_DEPTH (trmc_stream_set_summary precedes trmc_stream_begin)");
+    S.next_pd = peak_depth_host;
+    S.next_pds = peak_depth_step_host;
+    return 0;
+}
+
+int trmc_stream_summary_total(trmc_plan *pl, void *peak_flow, int64_t *peak_step, void *mean_flow, void *peak_depth, int64_t *peak_depth_step,
+                              int64_t *days_out)
+{
+    if (int rc = stream_check(pl, true)) return rc;
+    StreamRun &S = *pl->seq;
+    if (!(S.sum & TRMC_SUMMARY_TOTAL)) return fail(TRMC_ESTATE, "the stream was begun without TRMC_SUMMARY_TOTAL (trmc_stream_set_summary precedes trmc_stream_begin)");
+    if (S.tot_days < 1)
+        return fail(TRMC_ESTATE, "no day of the stream is complete yet: its last rows run " + std::to_string(S.lmax)
+                                     + " tiles behind its first -- push further days or trmc_stream_flush");
+    if ((peak_flow || peak_step) && !(S.sum & TRMC_SUMMARY_PEAK)) return fail(TRMC_EINVAL, "a peak array for a stream whose summary has no TRMC_SUMMARY_PEAK");
+    if (mean_flow && !(S.sum & TRMC_SUMMARY_MEAN)) return fail(TRMC_EINVAL, "a mean array for a stream whose summary has no TRMC_SUMMARY_MEAN");
+    if ((peak_depth || peak_depth_step) && !(S.sum & TRMC_SUMMARY_PEAK_DEPTH))
+        return fail(TRMC_EINVAL, "a peak-depth array for a stream whose summary has no TRMC_SUMMARY_PEAK_DEPTH");
+    const int64_t days = S.tot_days;
+    const size_t n = (size_t)pl->nseg, esz = (size_t)pl->esz;
+    // behind the last fold queued (nothing is queued meanwhile: the calls of a plan come from one thread)
+    HIP_TRY(hipStreamWaitEvent(pl->cstream, S.ev_total, 0));
+    if (peak_flow && n) HIP_TRY(hipMemcpyAsync(peak_flow, S.tot_pk.p, n * esz, hipMemcpyDeviceToHost, pl->cstream));
+    if (peak_step && n) HIP_TRY(hipMemcpyAsync(peak_step, S.tot_st.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, pl->cstream));
+    if (mean_flow && n) HIP_TRY(hipMemcpyAsync(mean_flow, S.tot_mean.p, n * esz, hipMemcpyDeviceToHost, pl->cstream));
+    if (peak_depth && n) HIP_TRY(hipMemcpyAsync(peak_depth, S.tot_pd.p, n * esz, hipMemcpyDeviceToHost, pl->cstream));
+    if (peak_depth_step && n) HIP_TRY(hipMemcpyAsync(peak_depth_step, S.tot_pds.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, pl->cstream));
+    HIP_TRY(hipStreamSynchronize(pl->cstream));
+    if (mean_flow) { // (((m_0 + m_1) + ...) was summed on the device; the division in the plan's precision)
+        if (esz == 4) {
+            float *m = (float *)mean_flow;
+            for (size_t i = 0; i < n; ++i) m[i] = m[i] / (float)days;
+        } else {
+            double *m = (double *)mean_flow;
+            for (size_t i = 0; i < n; ++i) m[i] = m[i] / (double)days;
+        }
+    }
+    if (days_out) *days_out = days;
     return 0;
 }
 
@@ -1034,7 +1176,7 @@ int trmc_stream_end(trmc_plan *pl)
     if (S.fst) HIP_TRY(hipStreamSynchronize(S.fst));
     HIP_TRY(hipStreamSynchronize(pl->cstream));
     if (pl->collect_cost) pl->cost_nsteps = (int32_t)std::min<int64_t>(S.days_pushed * S.nsteps, 1 << 30);
-    S.next_peak = S.next_step = S.next_mean = nullptr;
+    S.next_peak = S.next_step = S.next_mean = S.next_pd = S.next_pds = nullptr;
     S.active = false;
     return 0;
 }

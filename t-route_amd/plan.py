@@ -421,16 +421,18 @@ class RoutingPlan:
 
     def stream_set_summary(self, what):
         """The per-row summary the streams on this plan form of every day (trmc_stream_set_summary): an iterable of ``"peak"`` (peak
-        flow and the 1-based step of the peak) and ``"mean"`` (mean flow), or ``None`` for none.  Declared before
-        ``stream_begin``; it stays until the next call.  Every ``stream_push`` then says where the day's arrays go
-        (``summary=``)."""
-        names = {"peak": _lib.SUMMARY_PEAK, "mean": _lib.SUMMARY_MEAN}
+        flow and the 1-based step of the peak), ``"mean"`` (mean flow), ``"peak_depth"`` (peak depth and its step; carried by the
+        tile kernels, refused by ``stream_begin`` with NotImplementedError in a stream with reservoir data assimilation) and
+        ``"total"`` (running totals of the other parts over the days of the stream: ``stream_summary_total``), or ``None`` for
+        none.  Declared before ``stream_begin``; it stays until the next call.  Every ``stream_push`` then says where the day's
+        arrays go (``summary=``)."""
+        names = _lib.SUMMARY_NAMES
         if isinstance(what, str):
             what = (what,)
         mask = 0
         for w in (what or ()):
             if w not in names:
-                raise ValueError(f"summary: 'peak' and / or 'mean', got {w!r}")
+                raise ValueError(f"summary: 'peak' and / or 'mean', 'peak_depth', 'total', got {w!r}")
             mask |= names[w]
         _lib.check(_lib.lib().trmc_stream_set_summary(self._h, mask))
         self._stream_summary = mask
@@ -448,8 +450,8 @@ class RoutingPlan:
         ``reservoir_da_state=(state [nres, 4] float32, timeseries_idx [nres] int32)``: page-locked arrays for the state the day
         leaves, times already counted from the next day's start.  A plan whose streams form a summary (``stream_set_summary``):
         ``summary=(peak_flow, peak_step, mean_flow)``, page-locked [nseg] arrays (plan precision, int32, plan precision; any may
-        be None) for the day's peak flow, the 1-based step of the peak and the mean flow.  Returns the day's number in the
-        stream."""
+        be None) for the day's peak flow, the 1-based step of the peak and the mean flow -- with ``"peak_depth"`` two more,
+        ``(..., peak_depth, peak_depth_step)`` (plan precision, int32).  Returns the day's number in the stream."""
         if qlat.dtype != self.dtype or not qlat.flags.c_contiguous or qlat.ndim != 2 or qlat.shape[0] != self.nseg:
             raise ValueError(f"qlat must be a C-contiguous {np.dtype(self.dtype).name} array of shape ({self.nseg}, nq)")
         day_s = _lib.StreamDay()
@@ -497,9 +499,10 @@ class RoutingPlan:
                 raise ValueError(f"reservoir_da_state must be (float32 [{nres}, 4], int32 [{nres}]), C-contiguous")
             day_s.res_da_state_host, day_s.res_da_tsidx_host = st.ctypes.data, ti.ctypes.data
         if summary is not None:
-            if len(summary) != 3:
-                raise ValueError("summary must be (peak_flow, peak_step, mean_flow); any may be None")
-            for name, arr, dt in zip(("peak_flow", "peak_step", "mean_flow"), summary, (self.dtype, np.int32, self.dtype)):
+            if len(summary) not in (3, 5):
+                raise ValueError("summary must be (peak_flow, peak_step, mean_flow[, peak_depth, peak_depth_step]); any may be None")
+            for name, arr, dt in zip(("peak_flow", "peak_step", "mean_flow", "peak_depth", "peak_depth_step"), summary,
+                                     (self.dtype, np.int32, self.dtype, self.dtype, np.int32)):
                 if arr is not None and (not isinstance(arr, np.ndarray) or arr.dtype != dt or arr.shape != (self.nseg,)
                                         or not arr.flags.c_contiguous):
                     raise ValueError(f"summary: {name} must be a C-contiguous {np.dtype(dt).name} array of shape ({self.nseg},)")
@@ -509,9 +512,12 @@ class RoutingPlan:
         self._stream_keep[day] = (qlat, hyd, q0, fvd, tables, nudge, reservoir_inflow, reservoir_da_state, summary)
         for old in [k for k in self._stream_keep if isinstance(k, int) and k < day - max(8, info["slots"])]:
             del self._stream_keep[old]
+        depth = summary is not None and len(summary) == 5 and (summary[3] is not None or summary[4] is not None)
         if summary is not None:  # (where the NEXT day's summary goes: the push below consumes it)
-            _lib.check(_lib.lib().trmc_stream_summary_dest(self._h, *(_lib.ptr(x) for x in summary)))
+            _lib.check(_lib.lib().trmc_stream_summary_dest(self._h, *(_lib.ptr(x) for x in summary[:3])))
         try:
+            if depth:
+                _lib.check(_lib.lib().trmc_stream_summary_depth_dest(self._h, _lib.ptr(summary[3]), _lib.ptr(summary[4])))
             if nudging is None and reservoir_inflow is None and reservoir_da is None and reservoir_da_state is None:  # (the entry point every stream without tables has always used)
                 _lib.check(_lib.lib().trmc_stream_push(self._h, _lib.ptr(qlat), qlat.shape[1], C.c_void_p(boundary_q_ptr or 0),
                                                        -1 if rowset is None else int(rowset), _lib.ptr(hyd), _lib.ptr(q0), _lib.ptr(fvd)))
@@ -525,7 +531,29 @@ class RoutingPlan:
         except Exception:
             if summary is not None:  # (a refused push has not consumed the arrays: they must not wait for another day)
                 _lib.lib().trmc_stream_summary_dest(self._h, None, None, None)
+            if depth:
+                _lib.lib().trmc_stream_summary_depth_dest(self._h, None, None)
             raise
+
+    def stream_summary_total(self):
+        """The totals over all days of the stream in progress that have been handed over so far (a stream whose summary has
+        ``"total"``; trmc_stream_summary_total, synchronous): a dict with ``"days"`` and, for the parts of the summary,
+        ``"peak_flow"`` / ``"peak_step"`` (int64, 1-based from the stream's first step), ``"mean_flow"``, ``"peak_depth"`` /
+        ``"peak_depth_step"`` (int64) -- [nseg] arrays in row order, the folds of the days' arrays that include/trmc.h defines."""
+        mask = getattr(self, "_stream_summary", 0)
+        n = self.nseg
+        out = {}
+        if mask & _lib.SUMMARY_PEAK:
+            out["peak_flow"], out["peak_step"] = np.empty(n, self.dtype), np.empty(n, np.int64)
+        if mask & _lib.SUMMARY_MEAN:
+            out["mean_flow"] = np.empty(n, self.dtype)
+        if mask & _lib.SUMMARY_PEAK_DEPTH:
+            out["peak_depth"], out["peak_depth_step"] = np.empty(n, self.dtype), np.empty(n, np.int64)
+        days = C.c_int64(0)
+        _lib.check(_lib.lib().trmc_stream_summary_total(self._h, *(_lib.ptr(out.get(k)) for k in (
+            "peak_flow", "peak_step", "mean_flow", "peak_depth", "peak_depth_step")), C.byref(days)))
+        out["days"] = int(days.value)
+        return out
 
     def stream_gather(self, day, rowset, device_ptr, stream=0):
         """Flows of a row set over `day` [rows, nsteps] into device memory (trmc_stream_gather)."""

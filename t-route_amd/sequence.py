@@ -265,8 +265,14 @@ class RouteStream:
     1-based step of the day at which the peak was first reached) and ``"mean_flow"`` -- [rows] ring arrays over this rank's
     ``rows`` in the order of the final state, formed on the device from ALL nsteps flows of the day (include/trmc.h,
     trmc_stream_set_summary; None for what was not asked).  A router with reservoirs or gages: its trailing dict gains these
-    keys.  The maximum of a forecast of several days is ``np.maximum`` over the days' ``peak_flow``, its time the winning
-    day's ``peak_step``.
+    keys.  ``"peak_depth"`` adds ``"peak_depth"`` and ``"peak_depth_step"`` (int32) to that dict: the highest depth of the day
+    -- the pool's water elevation at a reservoir row, (0, 1) at a rank's boundary copies, which nobody routes -- and the step
+    it was first reached at, carried by the tile kernels through every step (a router with ``reservoir_da``: NotImplementedError).
+    ``"total"`` (with at least one of the others) keeps the maximum and the mean of the whole forecast on the device:
+    ``rs.total`` holds ``RoutingPlan.stream_summary_total()`` -- ``"days"``, ``"peak_flow"``, ``"peak_step"`` (int64, 1-based from
+    the stream's first step), ``"mean_flow"``, ``"peak_depth"``, ``"peak_depth_step"`` over this rank's ``rows`` -- once
+    ``route()`` has yielded its last day; ``daily_summary=False`` then leaves the per-day dict out (the tuples of
+    ``summary=None``) and no per-day summary array crosses to the host.
 
     Underneath is ONE stream of tile launches (include/trmc.h, trmc_stream_*): the tile index runs on over the days, every
     launch routes every row through the next K steps of its own place in the stream -- a row deep in the network works on an
@@ -281,7 +287,8 @@ class RouteStream:
     """
 
     def __init__(self, router, nsteps, qts_subdivisions, output_stride=None, full_output=False, slots=0, latency="throughput",
-                 hydrographs_on_every_rank=False, comm=None, exchange=None, reservoir_da_ncol=None, summary=None):
+                 hydrographs_on_every_rank=False, comm=None, exchange=None, reservoir_da_ncol=None, summary=None,
+                 daily_summary=True):
         """comm / exchange (several ranks): the communicator -- default: the one given to ``router.enable_device_exchange`` -- and
         how the daily cut-edge hydrographs travel: "device" (gather kernel -> all-gather on the exchange stream -> boundary rows,
         everything in HBM: RCCL over xGMI) or "host" (through ``comm.all_gather_rows_host``: any communicator with that method,
@@ -291,9 +298,15 @@ class RouteStream:
         as many as the declared tables."""
         self._rda_ncol = reservoir_da_ncol
         summary = (summary,) if isinstance(summary, str) else tuple(summary or ())
-        if any(w not in ("peak", "mean") for w in summary):
-            raise ValueError("summary: an iterable of 'peak' and / or 'mean', or None")
+        if any(w not in _lib.SUMMARY_NAMES for w in summary):
+            raise ValueError("summary: an iterable of 'peak' and / or 'mean', 'peak_depth', 'total', or None")
+        if "total" in summary and len(set(summary)) < 2:
+            raise ValueError("summary: 'total' needs at least one of 'peak', 'mean', 'peak_depth'")
+        if not daily_summary and "total" not in summary:
+            raise ValueError("daily_summary=False leaves nothing of a summary without 'total'")
         self.summary = summary
+        self.daily_summary = bool(daily_summary)
+        self.total = None
         if latency not in ("throughput", "low"):
             raise ValueError("latency must be 'throughput' or 'low'")
         self.r = router
@@ -538,17 +551,19 @@ class RouteStream:
         hyds = [_lib.result_empty((max(nout, 1), nsteps), dtype, always_pinned=True) for _ in range(D)]
         fins = [_lib.result_empty((nrows, 3), dtype, always_pinned=True) for _ in range(D)]
         fvds = [_lib.result_empty((nrows, keep, 3), dtype, always_pinned=True) if want_fvd else None for _ in range(D)]
-        stage = [_lib.result_empty((nrows, nq), dtype, always_pinned=True) for _ in range(3)]
+        stage = {}                                  # (page-locked staging buffers of the forcing: made when a day needs one, see `ring`)
         # reservoirs and gages: the records on the products' ring, the day's tables on a ring of their own (read by the copy that
         # the push queues: alive until the day has begun on the device)
         rinf = [_lib.result_empty((nres, nsteps), dtype, always_pinned=True) if nres else None for _ in range(D)]
         nudg = [_lib.result_empty((ngage, nsteps), dtype, always_pinned=True) if ngage else None for _ in range(D)]
-        tabs = [(_lib.result_empty((ngage, nsteps), np.uint8, always_pinned=True), _lib.result_empty((ngage, nsteps), dtype, always_pinned=True),
-                 _lib.result_empty((ngage, nsteps), dtype, always_pinned=True), _lib.result_empty((ngage,), dtype, always_pinned=True))
-                if ngage else None for _ in range(3)]
+        tabs = {}                                   # (the day's nudging tables, page-locked: on the same ring)
         rdas = [(_lib.result_empty((nres, 4), np.float32, always_pinned=True), _lib.result_empty((nres,), np.int32, always_pinned=True))
                 if rda is not None else None for _ in range(D)]
-        want_peak, want_mean = "peak" in self.summary, "mean" in self.summary
+        daily = bool(self.summary) and self.daily_summary
+        want_peak, want_mean, want_pd = (daily and w in self.summary for w in ("peak", "mean", "peak_depth"))
+        pkd = [_lib.result_empty((nrows,), dtype, always_pinned=True) if want_pd else None for _ in range(D)]
+        pds = [_lib.result_empty((nrows,), np.int32, always_pinned=True) if want_pd else None for _ in range(D)]
+        self.total = None
         pkf = [_lib.result_empty((nrows,), dtype, always_pinned=True) if want_peak else None for _ in range(D)]
         pks = [_lib.result_empty((nrows,), np.int32, always_pinned=True) if want_peak else None for _ in range(D)]
         mnf = [_lib.result_empty((nrows,), dtype, always_pinned=True) if want_mean else None for _ in range(D)]
@@ -570,6 +585,12 @@ class RouteStream:
                 sc = r._sc
             behind = (-(-lmax_all // tpd) if lmax_all else 0) + 1 + (1 if want_fvd else 0)   # (every rank hands a day over in the same iteration)
             order = None
+        # A staging buffer is read by the copy that the day's push queues, and nothing makes the host wait for that copy but the
+        # delivery of a day: before day d is staged the days up to d - 1 - behind have been delivered, so their forcing (which
+        # their launches waited for) has been read.  The ring that the host writes the forcing and the tables of a day into
+        # must therefore be behind + 1 days deep -- with three, a host that ran ahead of the device (several ranks whose first
+        # exchange and first delivery come days after the first push) overwrote the forcing of a day that had not been copied yet.
+        ring = max(3, behind + 1)
         self._out_rows = np.sort(r._outS_global) if not multi else None
         sel_own = np.argsort(r._outS_global, kind="stable")
 
@@ -613,8 +634,10 @@ class RouteStream:
                 item += ({"reservoir_inflow": rinf[k], "nudge": nudg[k], "lastobs": lastobs_of.pop(day, (None, None))},)
                 if rda is not None:                     # (days are delivered in order: the host's copy of the state moves on with them)
                     item[-1]["reservoir_da"] = rda_tuples(*rdas[k])
-            if self.summary:
+            if daily:
                 sm = {"peak_flow": pkf[k], "peak_step": pks[k], "mean_flow": mnf[k]}
+                if "peak_depth" in self.summary:
+                    sm.update({"peak_depth": pkd[k], "peak_depth_step": pds[k]})
                 if extras:
                     item[-1].update(sm)
                 else:
@@ -626,7 +649,9 @@ class RouteStream:
         while nxt is not None:
             q = take(nxt)
             if not (_lib.is_pinned(q) and q.dtype == dtype and q.flags.c_contiguous):
-                buf = stage[d % 3]
+                buf = stage.get(d % ring)
+                if buf is None:
+                    buf = stage[d % ring] = _lib.result_empty((nrows, nq), dtype, always_pinned=True)
                 buf[...] = q
                 q = buf
             nudging = None
@@ -636,7 +661,12 @@ class RouteStream:
                 except StopIteration:
                     raise ValueError(f"observations ended before the forcings (day {d})") from None
                 mode, a, w, lt_fin, lv_fin = _da.resolve_tables(nsteps, dap["routing_period"], dap["da_decay_coefficient"], usgs, lv, lt)
-                nudging = tabs[d % 3]
+                nudging = tabs.get(d % ring)
+                if nudging is None:
+                    nudging = tabs[d % ring] = (_lib.result_empty((ngage, nsteps), np.uint8, always_pinned=True),
+                                                _lib.result_empty((ngage, nsteps), dtype, always_pinned=True),
+                                                _lib.result_empty((ngage, nsteps), dtype, always_pinned=True),
+                                                _lib.result_empty((ngage,), dtype, always_pinned=True))
                 nudging[0][...], nudging[1][...], nudging[2][...] = mode, a, w
                 u = np.asarray(usgs, dtype=np.float32)
                 nudging[3][...] = u[:, 0] if (u.ndim == 2 and u.shape[1] > 0) else np.nan     # (mc_reach.pyx:404-411)
@@ -649,8 +679,8 @@ class RouteStream:
                 except StopIteration:
                     raise ValueError(f"reservoir_da ended before the forcings (day {d})") from None
                 more["reservoir_da_state"] = rdas[d % D]
-            if self.summary:
-                more["summary"] = (pkf[d % D], pks[d % D], mnf[d % D])
+            if daily:
+                more["summary"] = (pkf[d % D], pks[d % D], mnf[d % D]) + ((pkd[d % D], pds[d % D]) if want_pd else ())
             P.stream_push(q, rowset=r._rsS_out, hyd=hyds[d % D], q0=fins[d % D], fvd=fvds[d % D], **more)
             if low:
                 if multi:
@@ -675,6 +705,8 @@ class RouteStream:
                 P.stream_advance(tpd)
                 exchange(total + k - self._dc)
         P.stream_flush()
+        if "total" in self.summary:     # (every day has been handed over on the device: the totals of the whole stream)
+            self.total = P.stream_summary_total()
         while delivered < total:
             yield deliver(delivered)
             delivered += 1

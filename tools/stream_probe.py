@@ -6,7 +6,10 @@ row and the hydrographs of sampled rows bit for bit, and what a day costs either
                                                             with synthetic tables: their data assimilation rides in the stream
                                [--summary]                  every day's per-row peak flow, step of the peak and mean flow as stream
                                                             products (trmc_stream_set_summary); checked against the host's reduction
-                                                            of the one-by-one day's full result where that fits (nseg * 288 <= 2^26)"""
+                                                            of the one-by-one day's full result where that fits (nseg * 288 <= 2^26)
+                               [--summary-depth]            ... and the peak depth with its step (carried by the tile kernels)
+                               [--summary-total]            the totals over the days on the device, fetched once at the end; the
+                                                            days' own summary arrays then stay on the device"""
 import argparse
 import os
 import sys
@@ -36,10 +39,14 @@ ap.add_argument("--later", type=int, default=0, help="hand a day over this many 
 ap.add_argument("--reservoirs", type=int, default=0, help="level-pool reservoirs scattered over the network (rows with an upstream row)")
 ap.add_argument("--reservoir-da", type=int, default=0, help="so many of the --reservoirs are of types 2, 3, 4, 5 in turn, with synthetic tables")
 ap.add_argument("--summary", action="store_true", help="per-row peak flow, step of the peak and mean flow of every day as stream products")
+ap.add_argument("--summary-depth", action="store_true", help="the day's peak depth and its step as well (with or without --summary)")
+ap.add_argument("--summary-total", action="store_true", help="the totals over the days of the stream; no per-day summary array crosses to the host")
 ap.add_argument("--gages", type=int, default=0, help="nudged gages scattered over the network (observations: 70 %% valid, lognormal)")
 a = ap.parse_args()
 if a.reservoir_da > a.reservoirs:
     ap.error("--reservoir-da counts among the --reservoirs")
+if a.summary_total and not (a.summary or a.summary_depth):
+    ap.error("--summary-total totals --summary and / or --summary-depth")
 _lib.single_hw_queue_per_priority("stream_probe")
 nnet = S.CONUS_NNET if a.nseg == S.CONUS_NSEG else max(1, a.nseg // 185)
 net = S.generate(a.nseg, nnet, cache_dir=os.environ.get("TRMC_SYNTH_CACHE", "/tmp"))
@@ -119,15 +126,22 @@ if a.reservoirs or a.gages:
 
 def summary_of(q):
     """(peak_flow, peak_step, mean_flow) of flows q [rows, nsteps] as include/trmc.h defines them"""
+    peak, step = peak_of(q)
+    return peak, step, np.cumsum(q, axis=1, dtype=q.dtype)[:, -1] / q.dtype.type(q.shape[1])
+
+
+def peak_of(q):
     peak, step = q[:, 0].copy(), np.ones(q.shape[0], np.int32)
     for t in range(1, q.shape[1]):
         m = q[:, t] > peak
         peak[m] = q[m, t]
         step[m] = t + 1
-    return peak, step, np.cumsum(q, axis=1, dtype=q.dtype)[:, -1] / q.dtype.type(q.shape[1])
+    return peak, step
 
 
-check_summary = a.summary and not a.no_check and n * nsteps <= 1 << 26
+any_summary = a.summary or a.summary_depth
+daily = any_summary and not a.summary_total
+check_summary = any_summary and not a.no_check and n * nsteps <= 1 << 26
 ref_sum = []
 opts = {"wide_min_rows": a.wide_min_rows, "wide_k": a.wide_k, "cluster_rows": 128, "wide_levels": a.wide_levels, "stream_split": a.split, "velocity_on_demand": a.velocity_on_demand}
 hint = None
@@ -163,7 +177,8 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
             hyd = p.gather_flow_rows(sample)
             fvd = p.download_fvd(a.stride) if (a.stride or a.full) else None
             if check_summary:
-                ref_sum.append(summary_of(np.ascontiguousarray((fvd if (a.full and not a.stride) else p.download_fvd())[:, :, 0])))
+                full = fvd if (a.full and not a.stride) else p.download_fvd()
+                ref_sum.append(summary_of(np.ascontiguousarray(full[:, :, 0])) + peak_of(np.ascontiguousarray(full[:, :, 2])))
             if a.reservoir_da:
                 da_state, da_tsidx = p.download_reservoir_da()
                 da_state[da_kind != 0, 0] -= da_t_end
@@ -175,7 +190,8 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
     if a.reservoir_da:
         p.set_reservoir_da(da_kind, da_trow, *da_tables())
     p.upload_forcing(nsteps, days[0], q0)
-    p.stream_set_summary(("peak", "mean") if a.summary else None)
+    p.stream_set_summary((("peak", "mean") if a.summary else ()) + (("peak_depth",) if a.summary_depth else ())
+                         + (("total",) if a.summary_total else ()) or None)
     p.stream_begin(nsteps, qts, reservoir_da=bool(a.reservoir_da) or None, slots=a.slots + a.later if a.slots else (a.later and 2 + -(-(int(p.lags()[0].max(initial=0)) + 1) // (nsteps // p.tile_steps)) + a.later), full_output=a.full and not a.stride, output_stride=a.stride)
     info = p.stream_info()
     print("stream:", info, flush=True)
@@ -189,7 +205,10 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
     rdas = [(_lib.result_empty((a.reservoirs, 4), np.float32, always_pinned=True), _lib.result_empty((a.reservoirs,), np.int32, always_pinned=True))
             if a.reservoir_da else None for _ in range(D)]
     sums = [(_lib.result_empty((n,), np.float32, always_pinned=True), _lib.result_empty((n,), np.int32, always_pinned=True),
-             _lib.result_empty((n,), np.float32, always_pinned=True)) if a.summary else None for _ in range(D)]
+             _lib.result_empty((n,), np.float32, always_pinned=True)) if (a.summary and daily) else ((None, None, None) if daily else None)
+            for _ in range(D)]
+    if daily and a.summary_depth:
+        sums = [s + (_lib.result_empty((n,), np.float32, always_pinned=True), _lib.result_empty((n,), np.int32, always_pinned=True)) for s in sums]
     da_day = da_tables() if a.reservoir_da else None
     got = []
     behind = (info["lag_max"] + info["tiles_per_day"]) // info["tiles_per_day"] + a.later
@@ -210,7 +229,7 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
             if x is not None and not np.array_equal(x.view(np.uint32), y.view(np.uint32)):
                 ok = False
                 print(f"   day {e}: {name} differs", flush=True)
-        if check_summary and not all(np.array_equal(x.view(np.uint32), y.view(np.uint32)) for x, y in zip(ref_sum[e], sums[e % D])):
+        if check_summary and daily and not all(y is None or np.array_equal(x.view(np.uint32), y.view(np.uint32)) for x, y in zip(ref_sum[e], sums[e % D])):
             ok = False
             print(f"   day {e}: summary differs", flush=True)
         s1 = np.array_equal(fin.view(np.uint32), fins[e % D].view(np.uint32))
@@ -230,13 +249,34 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
     for e in range(max(0, a.days - behind), a.days):
         take(e)
     el = time.perf_counter() - t0
+    if a.summary_total:
+        tot = p.stream_summary_total()
+        print(f"   totals over {tot['days']} days fetched in {(time.perf_counter() - t0 - el) * 1e3:.2f} ms: {sorted(k for k in tot if k != 'days')}", flush=True)
+        if check_summary:
+            for kf, ks, i in (("peak_flow", "peak_step", 0), ("peak_depth", "peak_depth_step", 3)):
+                if kf in tot:
+                    pk, st = ref_sum[0][i].copy(), ref_sum[0][i + 1].astype(np.int64)
+                    for e in range(1, a.days):
+                        m = ref_sum[e][i] > pk
+                        pk[m], st[m] = ref_sum[e][i][m], e * nsteps + ref_sum[e][i + 1][m]
+                    if not (np.array_equal(pk.view(np.uint32), tot[kf].view(np.uint32)) and np.array_equal(st, tot[ks])):
+                        ok = False
+                        print(f"   totals: {kf} differs", flush=True)
+            if "mean_flow" in tot:
+                m = ref_sum[0][2].copy()
+                for e in range(1, a.days):
+                    m = m + ref_sum[e][2]
+                if not np.array_equal((m / np.float32(a.days)).view(np.uint32), tot["mean_flow"].view(np.uint32)):
+                    ok = False
+                    print("   totals: mean_flow differs", flush=True)
     dev_ms = [p.stream_day_ms(e) for e in range(max(behind + 1, a.days - D + 1), a.days)]    # (days pushed into a full stream, still in the ring)
     p.stream_end()
     if dev_ms:
         print(f"   device time of a day's own launches on the slices' stream: median {np.median(dev_ms):.2f} ms over {len(dev_ms)} days {np.round(dev_ms, 2).tolist()}", flush=True)
     per = np.diff(marks) * 1e3
     print(f"stream: {el / a.days * 1e3:.2f} ms per day over {a.days} days (fill and drain included); between deliveries {np.round(per, 2).tolist()}", flush=True)
-    if a.summary:
-        print("   summary (peak flow, step of the peak, mean flow of every row):",
+    if any_summary:
+        print("   summary (" + ", ".join((["peak flow, step of the peak, mean flow"] if a.summary else []) + (["peak depth and its step"] if a.summary_depth else []))
+              + " of every row" + ("; totals only" if a.summary_total else "") + "):",
               "checked against the host's reduction of every day's full result" if check_summary else "not checked (no check asked for, or too large for a host reduction)", flush=True)
     print("   launches", p.stream_info()["launches"], " every day bit-identical to the days routed one by one:", ok if not a.no_check else "not checked", flush=True)
