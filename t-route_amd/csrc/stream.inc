@@ -13,7 +13,8 @@
 // and depth planes, the forcing in plan order, optionally the full result and the decimated one); a row that ends a day leaves
 // its state in time row 0 of the next slot.  A day's products (outlet hydrographs, final state, decimated result) are gathered
 // from its slot when its LAST row has been queued through it -- `lag_max` launches into the following days -- and copied to
-// the caller's page-locked arrays beside the launches that follow; the slot is reused `slots` days later.
+// the caller's page-locked arrays beside the launches that follow; the slot is reused `slots` days later.  What a day can hand
+// over is ONE TABLE (P_*, StreamRun::tab below): every product named further down is a row of it, and nothing else lists them.
 //
 //   trmc_stream_begin   the state: what trmc_upload_forcing staged (or the state the plan's last window left)
 //   trmc_stream_push    one more day: its forcing (host, page-locked for an asynchronous copy), where its products go
@@ -58,13 +59,37 @@
 // k_stream_total folds every day's summary, in day order, right behind the kernels that formed it; trmc_stream_summary_total
 // fetches them.
 extern "C++" {
+// THE PRODUCTS A DAY CAN HAND TO THE HOST, one row of StreamRun::tab each.  trmc_stream_begin fills the row (stream_begin_t: whether
+// the stream carries the product, a slot's bytes, where a slot's bytes begin on the device), a push names the day's destinations
+// (StreamProd::host), and everything else -- the buffers' life, "has the copy stream anything to carry", the copies, the
+// destinations named in front of a push -- is a loop over the rows.  A new product: an enumerator, its row in stream_begin_t, the
+// kernel that forms it in stream_complete_day (and, unless it is a summary part, its member of trmc_stream_day in stream_push_t).
+enum : int {
+    P_HYD,      // outlet hydrographs [rows of the day's set][nsteps]: a slot is sized by the stream's first push
+    P_Q0,       // final state [nseg][3]
+    P_FVD,      // the (q, v, d) block: no buffer of its own, a slot of `dec` (output_stride) or of `out` (full_output)
+    P_NUDGE,    // nudge record [ngage][nsteps]: the slot's record itself, which the gage rows write (StepArgs::da_nudge)
+    P_RES,      // reservoir inflow [nres][nsteps]: likewise (StepArgs::res_inflow)
+    P_RDA,      // reservoir-DA state float [nres][4] ...
+    P_RDA_IDX,  // ... and timeseries_idx int32 [nres] behind it in the same slot
+    P_PEAK,     // the summary parts [nseg] in row order, the totals' order (tot[k - P_PEAK]): peak flow,
+    P_STEP,     // its step,
+    P_MEAN,     // mean flow,
+    P_PD,       // peak depth,
+    P_PDS,      // its step
+    P_N
+};
+struct StreamProdRow {
+    bool on = false;      // the stream in progress carries the product
+    size_t bytes = 0;     // what a day's copy takes (P_HYD: of the day's row set, stream_prod_bytes)
+    size_t stride = 0;    // a slot's bytes on the device: slot s begins at base + s * stride
+    char *base = nullptr;
+    DevBuf buf;           // [slots][stride], where the product has a buffer of its own
+    void *next = nullptr; // (summary parts) where the part of the NEXT day pushed goes: trmc_stream_summary_dest, _depth_dest
+};
 struct StreamProd {
     int64_t day = -1;
-    void *hyd_host = nullptr, *q0_host = nullptr, *fvd_host = nullptr;
-    void *nudge_host = nullptr, *res_inflow_host = nullptr;
-    void *rda_state_host = nullptr, *rda_tsidx_host = nullptr;
-    void *peak_host = nullptr, *step_host = nullptr, *mean_host = nullptr; // the day's summary (trmc_stream_summary_dest)
-    void *pd_host = nullptr, *pds_host = nullptr;                           // ... its peak depth (trmc_stream_summary_depth_dest)
+    void *host[P_N] = {};         // the day's destinations (NULL: not asked for)
     int32_t rowset = -1;
     bool queued = false;          // the gathers and copies of this day are queued
     hipEvent_t ev_done = nullptr; // ... and this fires when they are through
@@ -74,15 +99,16 @@ struct StreamRun {
     int32_t nsteps = 0, qts = 1, K = 0, tpd = 0, slots = 0, W = 0, C = 0, lmax = 0;
     int64_t nq = 0;
     int64_t days_pushed = 0, day_min = 0, days_complete = 0, g_done = -1, launches = 0;
-    size_t plane = 0, slot_tm = 0, slot_qlat = 0, slot_out = 0, slot_dec = 0, hyd_bytes = 0, q0_bytes = 0;
+    size_t plane = 0, slot_tm = 0, slot_qlat = 0, slot_out = 0, slot_dec = 0;
     bool want_out = false;
     int32_t dec_stride = 0, dec_keep = 0;
     int32_t rowset = -1;
-    DevBuf tm, qlat, out, dec, hyd, q0;
-    // reservoirs and gages (see the head of this file): per-slot element counts, the per-slot buffers, and the gage rows of the
+    DevBuf tm, qlat, out, dec;
+    StreamProdRow tab[P_N];        // the day's products (above)
+    // reservoirs and gages (see the head of this file): per-slot element counts, the per-slot tables, and the gage rows of the
     // streams on this plan (trmc_stream_set_gages: they outlive a stream, unlike the window's tables of trmc_set_nudging)
     size_t slot_res = 0, slot_da = 0;
-    DevBuf res_inflow, da_mode, da_a, da_w, da_nudge;
+    DevBuf da_mode, da_a, da_w;
     DevBuf da_q0;                  // [slots][ngage] the days' first observations (NaN = none): the flow a gage row starts the day from
     DevBuf gage_of_pos, gage_pos_dev; // [nseg_pad] gage of a position (-1: none); [ngage] position of a gage
     std::vector<int32_t> gage_pos; // plan position of every declared gage
@@ -94,21 +120,19 @@ struct StreamRun {
     int64_t rda_off[3] = {0, 0, 0}, rda_time_off[3] = {0, 0, 0};  // where a slot's observation rows / time rows begin, in floats
     size_t slot_rda = 0;           // bytes of a slot's tables
     float t_end = 0.0f;            // float(nsteps) * float(routing period): what a day's end takes off the times
-    DevBuf rda_tab, rda_carry, rda_prod; // [slots][slot_rda]; ResDaState [nres]; [slots]{float [nres][4], int32 [nres]}
+    DevBuf rda_tab, rda_carry;     // [slots][slot_rda]; ResDaState [nres]
     void *rda_stage = nullptr;     // page-locked host image of every slot's tables (the copy runs beside the launches)
     size_t rda_stage_bytes = 0;
     // the per-row summary of a day (see the head of this file).  sum_want: trmc_stream_set_summary, it outlives a stream as the gage
-    // rows do; sum: the mask of the stream in progress; next_*: where the summary of the NEXT day pushed goes
+    // rows do; sum: the mask of the stream in progress
     int32_t sum_want = 0, sum = 0;
-    DevBuf sum_peak, sum_step, sum_mean; // [slots][nseg] each, in row order (only what the mask asks for)
-    void *next_peak = nullptr, *next_step = nullptr, *next_mean = nullptr;
     // the peak depth: carry = the tile launches carry it in pkd_d / pkd_at [slots][nseg_pad] (plan order; otherwise the full result
-    // is reduced); sum_pd / sum_pds [slots][nseg] in row order; next_*: as above (trmc_stream_summary_depth_dest)
+    // is reduced)
     bool carry = false;
-    DevBuf pkd_d, pkd_at, sum_pd, sum_pds;
-    void *next_pd = nullptr, *next_pds = nullptr;
-    // the totals over the days (TRMC_SUMMARY_TOTAL): [nseg] in row order, outside the ring; tot_days days are folded in (queued)
-    DevBuf tot_pk, tot_st, tot_mean, tot_pd, tot_pds;
+    DevBuf pkd_d, pkd_at;
+    // the totals over the days (TRMC_SUMMARY_TOTAL): [nseg] in row order, outside the ring, one per summary part (tot[k - P_PEAK]:
+    // the steps are int64 here); tot_days days are folded in (queued)
+    DevBuf tot[P_N - P_PEAK];
     int64_t tot_days = 0;
     hipEvent_t ev_total = nullptr; // the last fold queued is through
     std::vector<hipEvent_t> ev_slab;    // ring: "slab launch g is complete" (the cluster launch g + 1 waits for it)
@@ -128,10 +152,11 @@ static void stream_release(trmc_plan *pl)
 {
     StreamRun *S = pl->seq;
     if (!S) return;
-    for (DevBuf *b : {&S->tm, &S->qlat, &S->out, &S->dec, &S->hyd, &S->q0, &S->res_inflow, &S->da_mode, &S->da_a, &S->da_w, &S->da_nudge, &S->da_q0, &S->gage_of_pos, &S->gage_pos_dev, &S->rda_tab,
-                       &S->rda_carry, &S->rda_prod, &S->sum_peak, &S->sum_step, &S->sum_mean, &S->pkd_d, &S->pkd_at, &S->sum_pd, &S->sum_pds,
-                       &S->tot_pk, &S->tot_st, &S->tot_mean, &S->tot_pd, &S->tot_pds})
+    for (DevBuf *b : {&S->tm, &S->qlat, &S->out, &S->dec, &S->da_mode, &S->da_a, &S->da_w, &S->da_q0, &S->gage_of_pos, &S->gage_pos_dev, &S->rda_tab,
+                       &S->rda_carry, &S->pkd_d, &S->pkd_at})
         b->release();
+    for (StreamProdRow &t : S->tab) t.buf.release();
+    for (DevBuf &b : S->tot) b.release();
     if (S->rda_stage) (void)hipHostFree(S->rda_stage);
     for (auto *v : {&S->ev_slab, &S->ev_free, &S->ev_ready, &S->ev_forcing, &S->ev_t0, &S->ev_t1})
         for (hipEvent_t e : *v)
@@ -276,8 +301,8 @@ template <class T> StepArgs<T> stream_args(trmc_plan *pl, const StreamRun &S, in
     // the day's reservoir-inflow record and nudging tables: in the rows' slots (the window's own buffers are not used)
     a.slot_res = (int64_t)S.slot_res;
     a.slot_da = (int64_t)S.slot_da;
-    a.res_inflow = (T *)S.res_inflow.p;
-    a.res_da = S.rda ? S.rda_tab.p : nullptr; // (the _rda instances: the tables of a row's day, the state in the carry)
+    a.res_inflow = (T *)S.tab[P_RES].base;
+    a.res_da =S.rda ? S.rda_tab.p : nullptr; // (the _rda instances: the tables of a row's day, the state in the carry)
     a.res_da_carry = S.rda ? S.rda_carry.p : nullptr;
     a.slot_rda = (int64_t)S.slot_rda;
     a.res_t_end = S.t_end;
@@ -285,7 +310,7 @@ template <class T> StepArgs<T> stream_args(trmc_plan *pl, const StreamRun &S, in
     a.da_mode = (const uint8_t *)S.da_mode.p;
     a.da_a = (const T *)S.da_a.p;
     a.da_w = (const T *)S.da_w.p;
-    a.da_nudge = (T *)S.da_nudge.p;
+    a.da_nudge = (T *)S.tab[P_NUDGE].base;
     a.raw_of_pos = nullptr;
     a.da_raw = nullptr;
     if (S.dec_stride > 0) {
@@ -300,6 +325,15 @@ template <class T> StepArgs<T> stream_args(trmc_plan *pl, const StreamRun &S, in
     return a;
 }
 
+// bytes of product k that the day of `p` hands to the host (0: not carried by the stream, not asked for, or empty)
+inline size_t stream_prod_bytes(const trmc_plan *pl, const StreamRun &S, const StreamProd &p, int k)
+{
+    const StreamProdRow &t = S.tab[k];
+    if (!t.on || !p.host[k]) return 0;
+    if (k == P_HYD) return p.rowset >= 0 ? (size_t)pl->rowset_n[(size_t)p.rowset] * (size_t)S.nsteps * (size_t)pl->esz : 0;
+    return t.bytes;
+}
+
 // the gathers and copies that hand day `e` over (its last row has just been queued through it on `pst`)
 template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t e, hipStream_t pst)
 {
@@ -308,37 +342,32 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
     S.days_complete = e + 1;
     if (p.day != e) return fail(TRMC_ESTATE, "internal: the slot of a completed day holds another day");
     const T *q = (const T *)S.tm.p + (size_t)slot * S.slot_tm, *d = q + S.plane;
-    const int64_t nrows = (p.hyd_host && p.rowset >= 0) ? pl->rowset_n[(size_t)p.rowset] : 0;
-    const bool want_nudge = p.nudge_host && S.slot_da > 0, want_res = p.res_inflow_host && S.slot_res > 0;
-    const bool want_rda = S.rda && (p.rda_state_host || p.rda_tsidx_host);
+    size_t bytes[P_N]; // what the copy stream has to carry of every product
+    bool any = false;
+    for (int k = 0; k < P_N; ++k) any |= (bytes[k] = stream_prod_bytes(pl, S, p, k)) > 0;
+    auto at = [&](int k, bool want = true) { return want ? S.tab[k].base + (size_t)slot * S.tab[k].stride : nullptr; }; // (the product's slot)
     // (the totals fold every day's summary: with them a part is formed whether or not the day's own arrays go to the host)
     const bool total = (S.sum & TRMC_SUMMARY_TOTAL) && pl->nseg > 0;
-    const bool want_peak = (S.sum & TRMC_SUMMARY_PEAK) && (p.peak_host || p.step_host || total) && pl->nseg > 0;
-    const bool want_mean = (S.sum & TRMC_SUMMARY_MEAN) && (p.mean_host || total) && pl->nseg > 0;
-    const bool want_pd = (S.sum & TRMC_SUMMARY_PEAK_DEPTH) && (p.pd_host || p.pds_host || total) && pl->nseg > 0;
-    const bool any = nrows > 0 || p.q0_host || p.fvd_host || want_nudge || want_res || want_rda || (want_peak && (p.peak_host || p.step_host))
-                     || (want_mean && p.mean_host) || (want_pd && (p.pd_host || p.pds_host)); // (what the copy stream has to carry)
-    float *const rda_state = (float *)S.rda_prod.p + (size_t)slot * (size_t)pl->nres * 5;
-    int32_t *const rda_tsidx = (int32_t *)(rda_state + (size_t)pl->nres * 4);
-    if (want_rda)
+    const bool want_peak = S.tab[P_PEAK].on && (bytes[P_PEAK] || bytes[P_STEP] || total);
+    const bool want_mean = S.tab[P_MEAN].on && (bytes[P_MEAN] || total);
+    const bool want_pd = S.tab[P_PD].on && (bytes[P_PD] || bytes[P_PDS] || total);
+    if (bytes[P_RDA] || bytes[P_RDA_IDX])
         hipLaunchKernelGGL(k_stream_rda_state, dim3(blocks_for(pl->nres)), dim3(kBlock), 0, pst,
-                           (const trmc::ResDaRec *)((const char *)S.rda_tab.p + (size_t)slot * S.slot_rda), rda_state, rda_tsidx, (int32_t)pl->nres);
-    if (nrows > 0) {
+                           (const trmc::ResDaRec *)((const char *)S.rda_tab.p + (size_t)slot * S.slot_rda), (float *)at(P_RDA), (int32_t *)at(P_RDA_IDX),
+                           (int32_t)pl->nres);
+    if (bytes[P_HYD]) {
+        const int64_t nrows = pl->rowset_n[(size_t)p.rowset];
         hipLaunchKernelGGL((k_gather_rows<T>), dim3(blocks_for(nrows * S.nsteps)), dim3(kBlock), 0, pst, q,
-                           (const int32_t *)pl->rowsets[(size_t)p.rowset].p, (T *)((char *)S.hyd.p + (size_t)slot * S.hyd_bytes), nrows,
-                           pl->nseg_pad, S.nsteps, 1);
+                           (const int32_t *)pl->rowsets[(size_t)p.rowset].p, (T *)at(P_HYD), nrows, pl->nseg_pad, S.nsteps, 1);
     }
-    if (p.q0_host && pl->nseg > 0)
+    if (bytes[P_Q0])
         hipLaunchKernelGGL((k_final_state<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, q, d, (const int32_t *)pl->row_of_pos.p,
-                           (T *)((char *)S.q0.p + (size_t)slot * S.q0_bytes), (int32_t)pl->nseg, pl->nseg_pad, S.nsteps, 1, S.nsteps);
-    T *const sum_peak = want_peak ? (T *)S.sum_peak.p + (size_t)slot * (size_t)pl->nseg : nullptr;
-    int32_t *const sum_step = want_peak ? (int32_t *)S.sum_step.p + (size_t)slot * (size_t)pl->nseg : nullptr;
-    T *const sum_mean = want_mean ? (T *)S.sum_mean.p + (size_t)slot * (size_t)pl->nseg : nullptr;
+                           (T *)at(P_Q0), (int32_t)pl->nseg, pl->nseg_pad, S.nsteps, 1, S.nsteps);
+    T *const sum_peak = (T *)at(P_PEAK, want_peak), *const sum_mean = (T *)at(P_MEAN, want_mean), *const sum_pd = (T *)at(P_PD, want_pd);
+    int32_t *const sum_step = (int32_t *)at(P_STEP, want_peak), *const sum_pds = (int32_t *)at(P_PDS, want_pd);
     if (want_peak || want_mean)
         hipLaunchKernelGGL((k_stream_summary<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, q, (const int32_t *)pl->row_of_pos.p, sum_peak,
                            sum_step, sum_mean, (int32_t)pl->nseg, pl->nseg_pad, S.nsteps);
-    T *const sum_pd = want_pd ? (T *)S.sum_pd.p + (size_t)slot * (size_t)pl->nseg : nullptr;
-    int32_t *const sum_pds = want_pd ? (int32_t *)S.sum_pds.p + (size_t)slot * (size_t)pl->nseg : nullptr;
     if (want_pd && S.carry)
         hipLaunchKernelGGL((k_stream_peak_depth<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, (const T *)S.pkd_d.p + (size_t)slot * (size_t)pl->nseg_pad,
                            (const int32_t *)S.pkd_at.p + (size_t)slot * (size_t)pl->nseg_pad, (const int32_t *)pl->row_of_pos.p, sum_pd, sum_pds,
@@ -348,8 +377,8 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
                            sum_pd, sum_pds, (int32_t)pl->nseg, S.nsteps);
     if (total) {
         hipLaunchKernelGGL((k_stream_total<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, (const T *)sum_peak, (const int32_t *)sum_step,
-                           (const T *)sum_mean, (const T *)sum_pd, (const int32_t *)sum_pds, (T *)S.tot_pk.p, (int64_t *)S.tot_st.p, (T *)S.tot_mean.p,
-                           (T *)S.tot_pd.p, (int64_t *)S.tot_pds.p, (int32_t)pl->nseg, e, S.nsteps);
+                           (const T *)sum_mean, (const T *)sum_pd, (const int32_t *)sum_pds, (T *)S.tot[0].p, (int64_t *)S.tot[1].p, (T *)S.tot[2].p,
+                           (T *)S.tot[3].p, (int64_t *)S.tot[4].p, (int32_t)pl->nseg, e, S.nsteps);
         HIP_TRY(hipEventRecord(S.ev_total, pst));
         S.tot_days = e + 1;
     }
@@ -362,37 +391,8 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
     }
     HIP_TRY(hipEventRecord(S.ev_ready[(size_t)slot], pst));
     HIP_TRY(hipStreamWaitEvent(pl->cstream, S.ev_ready[(size_t)slot], 0));
-    if (nrows > 0)
-        HIP_TRY(hipMemcpyAsync(p.hyd_host, (char *)S.hyd.p + (size_t)slot * S.hyd_bytes, (size_t)nrows * S.nsteps * sizeof(T),
-                               hipMemcpyDeviceToHost, pl->cstream));
-    if (p.q0_host && pl->nseg > 0)
-        HIP_TRY(hipMemcpyAsync(p.q0_host, (char *)S.q0.p + (size_t)slot * S.q0_bytes, S.q0_bytes, hipMemcpyDeviceToHost, pl->cstream));
-    if (p.fvd_host && pl->nseg > 0) {
-        if (S.dec_stride > 0)
-            HIP_TRY(hipMemcpyAsync(p.fvd_host, (const T *)S.dec.p + (size_t)slot * S.slot_dec, (size_t)pl->nseg * S.dec_keep * 3 * sizeof(T),
-                                   hipMemcpyDeviceToHost, pl->cstream));
-        else
-            HIP_TRY(hipMemcpyAsync(p.fvd_host, (const T *)S.out.p + (size_t)slot * S.slot_out, (size_t)pl->nseg * S.nsteps * 3 * sizeof(T),
-                                   hipMemcpyDeviceToHost, pl->cstream));
-    }
-    if (want_nudge)
-        HIP_TRY(hipMemcpyAsync(p.nudge_host, (const T *)S.da_nudge.p + (size_t)slot * S.slot_da, S.slot_da * sizeof(T), hipMemcpyDeviceToHost, pl->cstream));
-    if (want_res)
-        HIP_TRY(hipMemcpyAsync(p.res_inflow_host, (const T *)S.res_inflow.p + (size_t)slot * S.slot_res, S.slot_res * sizeof(T), hipMemcpyDeviceToHost,
-                               pl->cstream));
-    if (want_rda && p.rda_state_host)
-        HIP_TRY(hipMemcpyAsync(p.rda_state_host, rda_state, (size_t)pl->nres * 4 * sizeof(float), hipMemcpyDeviceToHost, pl->cstream));
-    if (want_rda && p.rda_tsidx_host)
-        HIP_TRY(hipMemcpyAsync(p.rda_tsidx_host, rda_tsidx, (size_t)pl->nres * sizeof(int32_t), hipMemcpyDeviceToHost, pl->cstream));
-    if (want_pd && p.pd_host) HIP_TRY(hipMemcpyAsync(p.pd_host, sum_pd, (size_t)pl->nseg * sizeof(T), hipMemcpyDeviceToHost, pl->cstream));
-    if (want_pd && p.pds_host)
-        HIP_TRY(hipMemcpyAsync(p.pds_host, sum_pds, (size_t)pl->nseg * sizeof(int32_t), hipMemcpyDeviceToHost, pl->cstream));
-    if (want_peak && p.peak_host)
-        HIP_TRY(hipMemcpyAsync(p.peak_host, sum_peak, (size_t)pl->nseg * sizeof(T), hipMemcpyDeviceToHost, pl->cstream));
-    if (want_peak && p.step_host)
-        HIP_TRY(hipMemcpyAsync(p.step_host, sum_step, (size_t)pl->nseg * sizeof(int32_t), hipMemcpyDeviceToHost, pl->cstream));
-    if (want_mean && p.mean_host)
-        HIP_TRY(hipMemcpyAsync(p.mean_host, sum_mean, (size_t)pl->nseg * sizeof(T), hipMemcpyDeviceToHost, pl->cstream));
+    for (int k = 0; k < P_N; ++k)
+        if (bytes[k]) HIP_TRY(hipMemcpyAsync(p.host[k], at(k), bytes[k], hipMemcpyDeviceToHost, pl->cstream));
     HIP_TRY(hipEventRecord(S.ev_free[(size_t)slot], pl->cstream));
     HIP_TRY(hipEventRecord(p.ev_done, pl->cstream));
     p.queued = true;
@@ -490,85 +490,84 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
     S.dec_keep = S.dec_stride > 0 ? nsteps / S.dec_stride : 0;
     if (S.dec_stride > 0 && S.dec_keep < 1) return fail(TRMC_EINVAL, "output_stride exceeds nsteps");
     S.slot_dec = (size_t)pl->nseg * S.dec_keep * 3;
-    S.q0_bytes = (size_t)pl->nseg * 3 * sizeof(T);
-    S.hyd_bytes = 0; // (sized by the first push of THIS stream, for this stream's number of slots)
     if (int rc = S.tm.ensure((size_t)S.slots * S.slot_tm * sizeof(T))) return rc;
     if (int rc = S.qlat.ensure((size_t)S.slots * S.slot_qlat * sizeof(T))) return rc;
     if (S.want_out)
         if (int rc = S.out.ensure((size_t)S.slots * S.slot_out * sizeof(T))) return rc;
     if (S.dec_stride > 0)
         if (int rc = S.dec.ensure((size_t)S.slots * S.slot_dec * sizeof(T))) return rc;
-    if (int rc = S.q0.ensure((size_t)S.slots * S.q0_bytes)) return rc;
     S.slot_res = (size_t)pl->nres * (size_t)nsteps;
     S.slot_da = (size_t)S.ngage * (size_t)nsteps;
-    if (S.slot_res > 0)
-        if (int rc = S.res_inflow.ensure((size_t)S.slots * S.slot_res * sizeof(T))) return rc;
     if (S.slot_da > 0) {
         if (int rc = S.da_mode.ensure((size_t)S.slots * S.slot_da)) return rc;
-        for (DevBuf *b : {&S.da_a, &S.da_w, &S.da_nudge})
+        for (DevBuf *b : {&S.da_a, &S.da_w})
             if (int rc = b->ensure((size_t)S.slots * S.slot_da * sizeof(T))) return rc;
         if (int rc = S.da_q0.ensure((size_t)S.slots * (size_t)S.ngage * sizeof(T))) return rc;
     }
-    // the days' summaries: only what the mask asks for (a stream without one holds no such buffer)
+    // the peak depth of the day: carried by the tile launches unless the stream assembles the full result, which is reduced then
     S.sum = S.sum_want;
-    S.next_peak = S.next_step = S.next_mean = nullptr;
-    if (!(S.sum & TRMC_SUMMARY_PEAK)) {
-        S.sum_peak.release();
-        S.sum_step.release();
-    }
-    if (!(S.sum & TRMC_SUMMARY_MEAN)) S.sum_mean.release();
-    if (S.sum & TRMC_SUMMARY_PEAK) {
-        if (int rc = S.sum_peak.ensure((size_t)S.slots * (size_t)pl->nseg * sizeof(T))) return rc;
-        if (int rc = S.sum_step.ensure((size_t)S.slots * (size_t)pl->nseg * sizeof(int32_t))) return rc;
-    }
-    if (S.sum & TRMC_SUMMARY_MEAN)
-        if (int rc = S.sum_mean.ensure((size_t)S.slots * (size_t)pl->nseg * sizeof(T))) return rc;
-    // ... the peak depth: carried by the tile launches unless the stream assembles the full result, which is reduced then
-    S.next_pd = S.next_pds = nullptr;
-    S.carry = (S.sum & TRMC_SUMMARY_PEAK_DEPTH) && !S.want_out;
+    const bool pd = (S.sum & TRMC_SUMMARY_PEAK_DEPTH) != 0;
+    S.carry = pd && !S.want_out;
     if (S.carry && pl->opt.velocity_on_demand < 0)
         return fail(TRMC_EUNSUPPORTED, "the peak depth of a stream without full_output is carried by the tile kernels' on-demand-velocity instances: "
                                        "not with trmc_plan_options.velocity_on_demand < 0");
+    S.rda = pl->nres > 0 && pl->res_da_on && S.rda_want;
+    if (S.rda && pd)
+        return fail(TRMC_EUNSUPPORTED, "the peak depth of the day (TRMC_SUMMARY_PEAK_DEPTH) is not supported in a stream with reservoir data "
+                                       "assimilation: the _rda tile instances do not carry it");
     for (DevBuf *b : {&S.pkd_d, &S.pkd_at})
         if (!S.carry) b->release();
-    for (DevBuf *b : {&S.sum_pd, &S.sum_pds})
-        if (!(S.sum & TRMC_SUMMARY_PEAK_DEPTH)) b->release();
     if (S.carry) {
         if (int rc = S.pkd_d.ensure((size_t)S.slots * np * sizeof(T))) return rc;
         if (int rc = S.pkd_at.ensure((size_t)S.slots * np * sizeof(int32_t))) return rc;
     }
-    if (S.sum & TRMC_SUMMARY_PEAK_DEPTH) {
-        if (int rc = S.sum_pd.ensure((size_t)S.slots * (size_t)pl->nseg * sizeof(T))) return rc;
-        if (int rc = S.sum_pds.ensure((size_t)S.slots * (size_t)pl->nseg * sizeof(int32_t))) return rc;
-        // (boundary rows of the full result are written by nobody: zeros, so that their reduction is the (0, 1) the carry gives)
-        if (S.want_out && tp.nboundary > 0) HIP_TRY(hipMemsetAsync(S.out.p, 0, (size_t)S.slots * S.slot_out * sizeof(T), pl->stream));
-    }
-    // ... the totals over the days: only the parts the mask asks for
-    S.tot_days = 0;
+    // (boundary rows of the full result are written by nobody: zeros, so that their reduction is the (0, 1) the carry gives)
+    if (pd && S.want_out && tp.nboundary > 0) HIP_TRY(hipMemsetAsync(S.out.p, 0, (size_t)S.slots * S.slot_out * sizeof(T), pl->stream));
+    // THE TABLE OF THE DAY'S PRODUCTS (the head of StreamRun), in the enumeration's order: {carried, bytes of a day's copy, bytes of a
+    // slot, has a buffer of its own, bytes of its total over the days}.  A summary part that the mask does not ask for holds no
+    // buffer; the other buffers are kept between streams.
+    const size_t row = (size_t)pl->nseg * sizeof(T), irow = (size_t)pl->nseg * sizeof(int32_t), lrow = (size_t)pl->nseg * sizeof(int64_t);
+    const size_t fvd = (S.dec_stride > 0 ? S.slot_dec : S.slot_out) * sizeof(T), da = S.slot_da * sizeof(T), res = S.slot_res * sizeof(T);
+    const size_t rda4 = (size_t)pl->nres * 4 * sizeof(float), rda1 = (size_t)pl->nres * sizeof(int32_t);
+    const bool peak = (S.sum & TRMC_SUMMARY_PEAK) != 0, mean = (S.sum & TRMC_SUMMARY_MEAN) != 0;
+    const struct { bool on; size_t bytes, stride; bool own; size_t total; } rows[] = {
+        /* P_HYD     */ {true, 0, 0, true, 0}, // (bytes: of the day's row set; a slot is sized by the first push of THIS stream)
+        /* P_Q0      */ {true, 3 * row, 3 * row, true, 0},
+        /* P_FVD     */ {S.dec_stride > 0 || S.want_out, fvd, fvd, false, 0}, // (in a slot of dec or of out: below)
+        /* P_NUDGE   */ {S.slot_da > 0, da, da, true, 0},
+        /* P_RES     */ {S.slot_res > 0, res, res, true, 0},
+        /* P_RDA     */ {S.rda, rda4, rda4 + rda1, true, 0},
+        /* P_RDA_IDX */ {S.rda, rda1, rda4 + rda1, false, 0}, // (behind the state in P_RDA's slot: below)
+        /* P_PEAK    */ {peak, row, row, true, row},
+        /* P_STEP    */ {peak, irow, irow, true, lrow},
+        /* P_MEAN    */ {mean, row, row, true, row},
+        /* P_PD      */ {pd, row, row, true, row},
+        /* P_PDS     */ {pd, irow, irow, true, lrow},
+    };
+    static_assert(sizeof(rows) / sizeof(rows[0]) == P_N, "one row per product, in the enumeration's order");
     const bool tot = (S.sum & TRMC_SUMMARY_TOTAL) != 0;
-    if (!(tot && (S.sum & TRMC_SUMMARY_PEAK))) {
-        S.tot_pk.release();
-        S.tot_st.release();
-    } else {
-        if (int rc = S.tot_pk.ensure((size_t)pl->nseg * sizeof(T))) return rc;
-        if (int rc = S.tot_st.ensure((size_t)pl->nseg * sizeof(int64_t))) return rc;
+    S.tot_days = 0;
+    for (int k = 0; k < P_N; ++k) {
+        StreamProdRow &t = S.tab[k];
+        t.on = rows[k].on;
+        t.bytes = rows[k].bytes;
+        t.stride = rows[k].stride;
+        t.next = nullptr;
+        if (k >= P_PEAK && !t.on) t.buf.release();
+        if (rows[k].own && t.on)
+            if (int rc = t.buf.ensure((size_t)S.slots * t.stride)) return rc;
+        t.base = (char *)t.buf.p;
+        if (k < P_PEAK) continue;
+        // ... and the part's total over the days, outside the ring (the steps count on over the days: int64)
+        DevBuf &b = S.tot[k - P_PEAK];
+        if (!(tot && t.on)) b.release();
+        else if (int rc = b.ensure(rows[k].total)) return rc;
     }
-    if (!(tot && (S.sum & TRMC_SUMMARY_MEAN))) S.tot_mean.release();
-    else if (int rc = S.tot_mean.ensure((size_t)pl->nseg * sizeof(T))) return rc;
-    if (!(tot && (S.sum & TRMC_SUMMARY_PEAK_DEPTH))) {
-        S.tot_pd.release();
-        S.tot_pds.release();
-    } else {
-        if (int rc = S.tot_pd.ensure((size_t)pl->nseg * sizeof(T))) return rc;
-        if (int rc = S.tot_pds.ensure((size_t)pl->nseg * sizeof(int64_t))) return rc;
-    }
+    S.tab[P_FVD].base = (char *)(S.dec_stride > 0 ? S.dec.p : S.out.p);
+    if (S.rda) S.tab[P_RDA_IDX].base = S.tab[P_RDA].base + rda4;
     if (tot && !S.ev_total) HIP_TRY(hipEventCreateWithFlags(&S.ev_total, hipEventDisableTiming));
     // reservoir data assimilation: the slots' tables at their capacity, the carry with the state trmc_set_reservoir_da supplied
-    // (or the plan's last window left in those tables), the days' state records
-    S.rda = pl->nres > 0 && pl->res_da_on && S.rda_want;
-    if (S.rda && (S.sum & TRMC_SUMMARY_PEAK_DEPTH))
-        return fail(TRMC_EUNSUPPORTED, "the peak depth of the day (TRMC_SUMMARY_PEAK_DEPTH) is not supported in a stream with reservoir data "
-                                       "assimilation: the _rda tile instances do not carry it");
+    // (or the plan's last window left in those tables); the days' state records are products (P_RDA)
     S.slot_rda = 0;
     if (S.rda) {
         int64_t floats = pl->nres * (int64_t)(sizeof(trmc::ResDaRec) / sizeof(float));
@@ -584,7 +583,6 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
         S.t_end = (float)nsteps * (float)pl->res_dt;
         if (int rc = S.rda_tab.ensure((size_t)S.slots * S.slot_rda)) return rc;
         if (int rc = S.rda_carry.ensure((size_t)pl->nres * sizeof(trmc::ResDaState))) return rc;
-        if (int rc = S.rda_prod.ensure((size_t)S.slots * (size_t)pl->nres * 5 * sizeof(float))) return rc;
         if (S.rda_stage_bytes < (size_t)S.slots * S.slot_rda) {
             if (S.rda_stage) (void)hipHostFree(S.rda_stage);
             S.rda_stage = nullptr;
@@ -661,7 +659,6 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
     StreamRun &S = *pl->seq;
     const void *const qlat = day.qlat, *const boundary_q_dev = day.boundary_q_dev;
     const int32_t rowset = day.rowset;
-    void *const hyd_host = day.hyd_host, *const q0_host = day.q0_host, *const fvd_host = day.fvd_host;
     const trmc::Topology &tp = pl->topo;
     const int64_t d = S.days_pushed;
     const int32_t slot = (int32_t)(d % S.slots);
@@ -673,32 +670,28 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
     // (the host image of the slot's reservoir tables is written below: the copy of the slot's last day must have read it)
     if (S.rda && p.day >= 0) HIP_TRY(hipEventSynchronize(S.ev_forcing[(size_t)slot]));
     if (p.day >= 0 && p.queued) HIP_TRY(hipStreamWaitEvent(hst, S.ev_free[(size_t)slot], 0)); // (the slot's last day has handed its products over)
-    if (hyd_host && rowset >= 0) {
+    if (day.hyd_host && rowset >= 0) { // (the hydrographs' slot is sized by the stream's first push)
+        StreamProdRow &h = S.tab[P_HYD];
         const size_t hb = (size_t)pl->rowset_n[(size_t)rowset] * S.nsteps * sizeof(T);
-        if (hb > S.hyd_bytes) {
+        if (hb > h.stride) {
             if (d > S.day_min || S.days_complete < d) {
-                if (S.hyd_bytes > 0) return fail(TRMC_ESTATE, "a larger row set than the stream's first one: begin a new stream");
+                if (h.stride > 0) return fail(TRMC_ESTATE, "a larger row set than the stream's first one: begin a new stream");
             }
-            S.hyd_bytes = hb;
-            if (int rc = S.hyd.ensure((size_t)S.slots * hb)) return rc;
+            h.stride = hb;
+            if (int rc = h.buf.ensure((size_t)S.slots * hb)) return rc;
+            h.base = (char *)h.buf.p;
         }
     }
     p.day = d;
     p.queued = false;
     p.rowset = rowset;
-    p.hyd_host = hyd_host;
-    p.q0_host = q0_host;
-    p.fvd_host = fvd_host;
-    p.nudge_host = day.nudge_host;
-    p.res_inflow_host = day.res_inflow_host;
-    p.rda_state_host = day.res_da_state_host;
-    p.rda_tsidx_host = day.res_da_tsidx_host;
-    p.peak_host = S.next_peak; // (trmc_stream_summary_dest: this push consumes them)
-    p.step_host = S.next_step;
-    p.mean_host = S.next_mean;
-    p.pd_host = S.next_pd; // (trmc_stream_summary_depth_dest)
-    p.pds_host = S.next_pds;
-    S.next_peak = S.next_step = S.next_mean = S.next_pd = S.next_pds = nullptr;
+    // the day's destinations: from the day, the summary parts' from the calls in front of this push, which consumes them
+    void *const from_day[P_PEAK] = {day.hyd_host, day.q0_host, day.fvd_host, day.nudge_host, day.res_inflow_host, day.res_da_state_host,
+                                    day.res_da_tsidx_host};
+    for (int k = 0; k < P_N; ++k) {
+        p.host[k] = k < P_PEAK ? from_day[k] : S.tab[k].next;
+        S.tab[k].next = nullptr;
+    }
     // the day's forcing: host -> staging area -> plan order in the slot, all on the copy stream of that direction
     const size_t bytes = (size_t)pl->nseg * S.nq * sizeof(T);
     if (int rc = pl->in_qlat.ensure(bytes)) return rc;
@@ -716,7 +709,7 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
         HIP_TRY(hipMemcpyAsync((uint8_t *)S.da_mode.p + o, day.da_mode, n, hipMemcpyHostToDevice, hst));
         HIP_TRY(hipMemcpyAsync((T *)S.da_a.p + o, day.da_a, n * sizeof(T), hipMemcpyHostToDevice, hst));
         HIP_TRY(hipMemcpyAsync((T *)S.da_w.p + o, day.da_w, n * sizeof(T), hipMemcpyHostToDevice, hst));
-        HIP_TRY(hipMemsetAsync((T *)S.da_nudge.p + o, 0, n * sizeof(T), hst));
+        HIP_TRY(hipMemsetAsync((T *)S.tab[P_NUDGE].base + o, 0, n * sizeof(T), hst));
         // the day's first observations [ngage] (NaN = none; all bits set is a NaN in either precision)
         T *const q0o = (T *)S.da_q0.p + (size_t)slot * (size_t)S.ngage;
         if (day.da_q0) HIP_TRY(hipMemcpyAsync(q0o, day.da_q0, (size_t)S.ngage * sizeof(T), hipMemcpyHostToDevice, hst));
@@ -880,9 +873,9 @@ int trmc_stream_summary_dest(trmc_plan *pl, void *peak_flow_host, int32_t *peak_
     if ((peak_flow_host || peak_step_host) && !(S.sum & TRMC_SUMMARY_PEAK))
         return fail(TRMC_EINVAL, "a peak array for a stream whose summary has no TRMC_SUMMARY_PEAK");
     if (mean_flow_host && !(S.sum & TRMC_SUMMARY_MEAN)) return fail(TRMC_EINVAL, "a mean array for a stream whose summary has no TRMC_SUMMARY_MEAN");
-    S.next_peak = peak_flow_host;
-    S.next_step = peak_step_host;
-    S.next_mean = mean_flow_host;
+    S.tab[P_PEAK].next = peak_flow_host;
+    S.tab[P_STEP].next = peak_step_host;
+    S.tab[P_MEAN].next = mean_flow_host;
     return 0;
 }
 
@@ -892,8 +885,8 @@ int trmc_stream_summary_depth_dest(trmc_plan *pl, void *peak_depth_host, int32_t
     StreamRun &S = *pl->seq;
     if (!(S.sum & TRMC_SUMMARY_PEAK_DEPTH))
         return fail(TRMC_ESTATE, "the stream was begun without TRMC_SUMMARY_PEAK_DEPTH (trmc_stream_set_summary precedes trmc_stream_begin)");
-    S.next_pd = peak_depth_host;
-    S.next_pds = peak_depth_step_host;
+    S.tab[P_PD].next = peak_depth_host;
+    S.tab[P_PDS].next = peak_depth_step_host;
     return 0;
 }
 
@@ -914,11 +907,11 @@ int trmc_stream_summary_total(trmc_plan *pl, void *peak_flow, int64_t *peak_step
     const size_t n = (size_t)pl->nseg, esz = (size_t)pl->esz;
     // behind the last fold queued (nothing is queued meanwhile: the calls of a plan come from one thread)
     HIP_TRY(hipStreamWaitEvent(pl->cstream, S.ev_total, 0));
-    if (peak_flow && n) HIP_TRY(hipMemcpyAsync(peak_flow, S.tot_pk.p, n * esz, hipMemcpyDeviceToHost, pl->cstream));
-    if (peak_step && n) HIP_TRY(hipMemcpyAsync(peak_step, S.tot_st.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, pl->cstream));
-    if (mean_flow && n) HIP_TRY(hipMemcpyAsync(mean_flow, S.tot_mean.p, n * esz, hipMemcpyDeviceToHost, pl->cstream));
-    if (peak_depth && n) HIP_TRY(hipMemcpyAsync(peak_depth, S.tot_pd.p, n * esz, hipMemcpyDeviceToHost, pl->cstream));
-    if (peak_depth_step && n) HIP_TRY(hipMemcpyAsync(peak_depth_step, S.tot_pds.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, pl->cstream));
+    void *const dst[P_N - P_PEAK] = {peak_flow, peak_step, mean_flow, peak_depth, peak_depth_step}; // (the parts' order: S.tot)
+    for (int i = 0; i < P_N - P_PEAK; ++i) {
+        const bool step = i == P_STEP - P_PEAK || i == P_PDS - P_PEAK;
+        if (dst[i] && n) HIP_TRY(hipMemcpyAsync(dst[i], S.tot[i].p, n * (step ? sizeof(int64_t) : esz), hipMemcpyDeviceToHost, pl->cstream));
+    }
     HIP_TRY(hipStreamSynchronize(pl->cstream));
     if (mean_flow) { // (((m_0 + m_1) + ...) was summed on the device; the division in the plan's precision)
         if (esz == 4) {
@@ -1176,7 +1169,7 @@ int trmc_stream_end(trmc_plan *pl)
     if (S.fst) HIP_TRY(hipStreamSynchronize(S.fst));
     HIP_TRY(hipStreamSynchronize(pl->cstream));
     if (pl->collect_cost) pl->cost_nsteps = (int32_t)std::min<int64_t>(S.days_pushed * S.nsteps, 1 << 30);
-    S.next_peak = S.next_step = S.next_mean = S.next_pd = S.next_pds = nullptr;
+    for (StreamProdRow &t : S.tab) t.next = nullptr;
     S.active = false;
     return 0;
 }

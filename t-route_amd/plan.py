@@ -471,16 +471,27 @@ class RoutingPlan:
                 day_s.da_q0 = first.ctypes.data
             day_s.da_ngage, day_s.da_nsteps = mode.shape
             day_s.da_mode, day_s.da_a, day_s.da_w = mode.ctypes.data, a.ctypes.data, w.ctypes.data
-        for name, arr in (("nudge", nudge), ("reservoir_inflow", reservoir_inflow)):
-            if arr is not None and (arr.dtype != self.dtype or not arr.flags.c_contiguous or arr.ndim != 2):
-                raise ValueError(f"{name} must be a C-contiguous {np.dtype(self.dtype).name} array [rows, nsteps]")
-        if nudge is not None:
-            if nudging is None or nudge.shape != tables[0].shape:
-                raise ValueError("nudge must have the shape of the day's nudging tables")
-            day_s.nudge_host = nudge.ctypes.data
+        # the day's destinations: (what a wrong one is told, array, dtype, shape -- None: any extent); None = not asked for
+        dn, nres = np.dtype(self.dtype).name, getattr(self, "_nres", 0)
+        st, ti = (None, None) if reservoir_da_state is None else reservoir_da_state
+        if summary is not None and len(summary) not in (3, 5):
+            raise ValueError("summary must be (peak_flow, peak_step, mean_flow[, peak_depth, peak_depth_step]); any may be None")
+        rda_msg = f"reservoir_da_state must be (float32 [{nres}, 4], int32 [{nres}]), C-contiguous"
+        dests = [(f"nudge must be a C-contiguous {dn} array [rows, nsteps]", nudge, self.dtype, (None, None)),
+                 ("nudge must have the shape of the day's nudging tables", nudge, self.dtype, tables[0].shape if tables else ()),
+                 (f"reservoir_inflow must be a C-contiguous {dn} array [rows, nsteps]", reservoir_inflow, self.dtype, (None, None)),
+                 (rda_msg, st, np.float32, (nres, 4)), (rda_msg, ti, np.int32, (nres,))]
+        dests += [(f"summary: {name} must be a C-contiguous {np.dtype(dt).name} array of shape ({self.nseg},)", arr, dt, (self.nseg,))
+                  for name, arr, dt in zip(("peak_flow", "peak_step", "mean_flow", "peak_depth", "peak_depth_step"), summary or (),
+                                           (self.dtype, np.int32, self.dtype, self.dtype, np.int32))]
+        for msg, arr, dt, shape in dests:
+            if arr is not None and not (isinstance(arr, np.ndarray) and arr.dtype == dt and arr.flags.c_contiguous and arr.ndim == len(shape)
+                                        and all(n in (None, m) for n, m in zip(shape, arr.shape))):
+                raise ValueError(msg)
         if reservoir_inflow is not None:
             day_s.res_nres, day_s.res_nsteps = reservoir_inflow.shape
-            day_s.res_inflow_host = reservoir_inflow.ctypes.data
+        day_s.nudge_host, day_s.res_inflow_host, day_s.res_da_state_host, day_s.res_da_tsidx_host = (
+            None if x is None else x.ctypes.data for x in (nudge, reservoir_inflow, st, ti))
         rda_s = None
         if reservoir_da is not None:
             if len(reservoir_da) not in (3, 4):
@@ -491,25 +502,10 @@ class RoutingPlan:
             rda_s.rfc_reset_idx = int(bool(reservoir_da[3])) if len(reservoir_da) == 4 else 0
             tables += tuple(rkeep)
             day_s.reservoir_da = C.addressof(rda_s)
-        if reservoir_da_state is not None:
-            st, ti = reservoir_da_state
-            nres = getattr(self, "_nres", 0)
-            if (st.dtype != np.float32 or ti.dtype != np.int32 or st.shape != (nres, 4) or ti.shape != (nres,)
-                    or not st.flags.c_contiguous or not ti.flags.c_contiguous):
-                raise ValueError(f"reservoir_da_state must be (float32 [{nres}, 4], int32 [{nres}]), C-contiguous")
-            day_s.res_da_state_host, day_s.res_da_tsidx_host = st.ctypes.data, ti.ctypes.data
-        if summary is not None:
-            if len(summary) not in (3, 5):
-                raise ValueError("summary must be (peak_flow, peak_step, mean_flow[, peak_depth, peak_depth_step]); any may be None")
-            for name, arr, dt in zip(("peak_flow", "peak_step", "mean_flow", "peak_depth", "peak_depth_step"), summary,
-                                     (self.dtype, np.int32, self.dtype, self.dtype, np.int32)):
-                if arr is not None and (not isinstance(arr, np.ndarray) or arr.dtype != dt or arr.shape != (self.nseg,)
-                                        or not arr.flags.c_contiguous):
-                    raise ValueError(f"summary: {name} must be a C-contiguous {np.dtype(dt).name} array of shape ({self.nseg},)")
         info = self.stream_info()
         day = info["days_pushed"]
         # (alive while the copies may be in flight: a day's products are queued up to `slots` days on)
-        self._stream_keep[day] = (qlat, hyd, q0, fvd, tables, nudge, reservoir_inflow, reservoir_da_state, summary)
+        self._stream_keep[day] = {"qlat": qlat, "tables": tables, "dests": [hyd, q0, fvd] + [d[1] for d in dests]}
         for old in [k for k in self._stream_keep if isinstance(k, int) and k < day - max(8, info["slots"])]:
             del self._stream_keep[old]
         depth = summary is not None and len(summary) == 5 and (summary[3] is not None or summary[4] is not None)

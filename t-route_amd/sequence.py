@@ -548,25 +548,27 @@ class RouteStream:
         D, tpd, lmax = info["slots"], info["tiles_per_day"], info["lag_max"]
         keep = nsteps // self.output_stride if self.output_stride else nsteps
         nout = r._outS_global.shape[0]
-        hyds = [_lib.result_empty((max(nout, 1), nsteps), dtype, always_pinned=True) for _ in range(D)]
-        fins = [_lib.result_empty((nrows, 3), dtype, always_pinned=True) for _ in range(D)]
-        fvds = [_lib.result_empty((nrows, keep, 3), dtype, always_pinned=True) if want_fvd else None for _ in range(D)]
-        stage = {}                                  # (page-locked staging buffers of the forcing: made when a day needs one, see `ring`)
-        # reservoirs and gages: the records on the products' ring, the day's tables on a ring of their own (read by the copy that
-        # the push queues: alive until the day has begun on the device)
-        rinf = [_lib.result_empty((nres, nsteps), dtype, always_pinned=True) if nres else None for _ in range(D)]
-        nudg = [_lib.result_empty((ngage, nsteps), dtype, always_pinned=True) if ngage else None for _ in range(D)]
-        tabs = {}                                   # (the day's nudging tables, page-locked: on the same ring)
-        rdas = [(_lib.result_empty((nres, 4), np.float32, always_pinned=True), _lib.result_empty((nres,), np.int32, always_pinned=True))
-                if rda is not None else None for _ in range(D)]
         daily = bool(self.summary) and self.daily_summary
         want_peak, want_mean, want_pd = (daily and w in self.summary for w in ("peak", "mean", "peak_depth"))
-        pkd = [_lib.result_empty((nrows,), dtype, always_pinned=True) if want_pd else None for _ in range(D)]
-        pds = [_lib.result_empty((nrows,), np.int32, always_pinned=True) if want_pd else None for _ in range(D)]
+
+        def products():
+            """a day's page-locked destinations under the names ``RoutingPlan.stream_push`` takes them by: only what the stream
+            hands over is allocated (None: not asked for)"""
+            def new(on, shape, t=dtype):
+                return _lib.result_empty(shape, t, always_pinned=True) if on else None
+            rec = {"hyd": new(True, (max(nout, 1), nsteps)), "q0": new(True, (nrows, 3)), "fvd": new(want_fvd, (nrows, keep, 3))}
+            if extras:                              # (reservoirs and gages: the day's records)
+                rec.update(nudge=new(ngage, (ngage, nsteps)), reservoir_inflow=new(nres, (nres, nsteps)))
+            if rda is not None:
+                rec["reservoir_da_state"] = (new(True, (nres, 4), np.float32), new(True, (nres,), np.int32))
+            if daily:
+                rec["summary"] = (new(want_peak, (nrows,)), new(want_peak, (nrows,), np.int32), new(want_mean, (nrows,))) + (
+                    (new(True, (nrows,)), new(True, (nrows,), np.int32)) if want_pd else ())
+            return rec
+        prods = [products() for _ in range(D)]      # the ring of the days' products: day d hands over into prods[d % D]
+        stage = {}                                  # (page-locked staging buffers of the forcing: made when a day needs one, see `ring`)
+        tabs = {}                                   # (the day's nudging tables, page-locked: on the same ring as the forcing)
         self.total = None
-        pkf = [_lib.result_empty((nrows,), dtype, always_pinned=True) if want_peak else None for _ in range(D)]
-        pks = [_lib.result_empty((nrows,), np.int32, always_pinned=True) if want_peak else None for _ in range(D)]
-        mnf = [_lib.result_empty((nrows,), dtype, always_pinned=True) if want_mean else None for _ in range(D)]
         lastobs_of = {}
         # when a day's products are waited for: a day after they were queued (the host then never waits for launches it has
         # just queued -- the device always holds a day of work); latency="low": right after the day's own push (flushed)
@@ -615,8 +617,8 @@ class RouteStream:
         def deliver(day):
             nonlocal order
             P.stream_wait(day)
-            k = day % D
-            hyd = hyds[k][:nout]
+            rec = prods[day % D]
+            hyd = rec["hyd"][:nout]
             if multi:
                 parts = comm.all_gather_rows_host(np.ascontiguousarray(hyd))
                 if order is None:
@@ -624,20 +626,18 @@ class RouteStream:
                     order = np.argsort(rows_all, kind="stable")
                     self._out_rows = rows_all[order]
                 hyd = np.concatenate(parts, 0)[order] if (self.rank == 0 or self._hyd_everywhere) else None
-                fin = [fins[k]]
-                fvd = [fvds[k]] if want_fvd else None
+                fin = [rec["q0"]]
+                fvd = [rec["fvd"]] if want_fvd else None
             else:
                 hyd = hyd[sel_own]
-                fin, fvd = fins[k], fvds[k]
+                fin, fvd = rec["q0"], rec["fvd"]
             item = (day, hyd, fin, fvd) if want_fvd else (day, hyd, fin)
             if extras:
-                item += ({"reservoir_inflow": rinf[k], "nudge": nudg[k], "lastobs": lastobs_of.pop(day, (None, None))},)
+                item += ({"reservoir_inflow": rec["reservoir_inflow"], "nudge": rec["nudge"], "lastobs": lastobs_of.pop(day, (None, None))},)
                 if rda is not None:                     # (days are delivered in order: the host's copy of the state moves on with them)
-                    item[-1]["reservoir_da"] = rda_tuples(*rdas[k])
-            if daily:
-                sm = {"peak_flow": pkf[k], "peak_step": pks[k], "mean_flow": mnf[k]}
-                if "peak_depth" in self.summary:
-                    sm.update({"peak_depth": pkd[k], "peak_depth_step": pds[k]})
+                    item[-1]["reservoir_da"] = rda_tuples(*rec["reservoir_da_state"])
+            if daily:                                   # (three parts, five with "peak_depth")
+                sm = dict(zip(("peak_flow", "peak_step", "mean_flow", "peak_depth", "peak_depth_step"), rec["summary"]))
                 if extras:
                     item[-1].update(sm)
                 else:
@@ -672,16 +672,13 @@ class RouteStream:
                 nudging[3][...] = u[:, 0] if (u.ndim == 2 and u.shape[1] > 0) else np.nan     # (mc_reach.pyx:404-411)
                 lastobs_of[d] = (lt_fin, lv_fin)
                 lv, lt = lv_fin, (lt_fin - day_len).astype(np.float32)       # (the next day counts from its own start)
-            more = {"nudging": nudging, "nudge": nudg[d % D], "reservoir_inflow": rinf[d % D]} if extras else {}
+            more = {"nudging": nudging} if extras else {}
             if rda is not None:
                 try:
                     more["reservoir_da"] = next(rda_it)
                 except StopIteration:
                     raise ValueError(f"reservoir_da ended before the forcings (day {d})") from None
-                more["reservoir_da_state"] = rdas[d % D]
-            if daily:
-                more["summary"] = (pkf[d % D], pks[d % D], mnf[d % D]) + ((pkd[d % D], pds[d % D]) if want_pd else ())
-            P.stream_push(q, rowset=r._rsS_out, hyd=hyds[d % D], q0=fins[d % D], fvd=fvds[d % D], **more)
+            P.stream_push(q, rowset=r._rsS_out, **prods[d % D], **more)
             if low:
                 if multi:
                     raise ValueError("latency='low' is a one-GPU option")
