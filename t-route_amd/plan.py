@@ -11,6 +11,7 @@ import os
 import numpy as np
 
 from . import _lib
+from . import stream_products as SP
 
 
 def csr_from_lists(lists):
@@ -449,9 +450,9 @@ class RoutingPlan:
         ignored and may be None, the device carries them; the RFC timeseries_idx counts only with ``rfc_reset_idx`` -- and
         ``reservoir_da_state=(state [nres, 4] float32, timeseries_idx [nres] int32)``: page-locked arrays for the state the day
         leaves, times already counted from the next day's start.  A plan whose streams form a summary (``stream_set_summary``):
-        ``summary=(peak_flow, peak_step, mean_flow)``, page-locked [nseg] arrays (plan precision, int32, plan precision; any may
-        be None) for the day's peak flow, the 1-based step of the peak and the mean flow -- with ``"peak_depth"`` two more,
-        ``(..., peak_depth, peak_depth_step)`` (plan precision, int32).  Returns the day's number in the stream."""
+        ``summary=`` a tuple of page-locked [nseg] arrays (any may be None) for the day's peak flow, the 1-based step of the peak
+        and the mean flow -- with ``"peak_depth"`` two more, the peak depth and its step: the rows of ``stream_products.SUMMARY``
+        with their types.  Returns the day's number in the stream."""
         if qlat.dtype != self.dtype or not qlat.flags.c_contiguous or qlat.ndim != 2 or qlat.shape[0] != self.nseg:
             raise ValueError(f"qlat must be a C-contiguous {np.dtype(self.dtype).name} array of shape ({self.nseg}, nq)")
         day_s = _lib.StreamDay()
@@ -471,27 +472,21 @@ class RoutingPlan:
                 day_s.da_q0 = first.ctypes.data
             day_s.da_ngage, day_s.da_nsteps = mode.shape
             day_s.da_mode, day_s.da_a, day_s.da_w = mode.ctypes.data, a.ctypes.data, w.ctypes.data
-        # the day's destinations: (what a wrong one is told, array, dtype, shape -- None: any extent); None = not asked for
-        dn, nres = np.dtype(self.dtype).name, getattr(self, "_nres", 0)
-        st, ti = (None, None) if reservoir_da_state is None else reservoir_da_state
-        if summary is not None and len(summary) not in (3, 5):
-            raise ValueError("summary must be (peak_flow, peak_step, mean_flow[, peak_depth, peak_depth_step]); any may be None")
-        rda_msg = f"reservoir_da_state must be (float32 [{nres}, 4], int32 [{nres}]), C-contiguous"
-        dests = [(f"nudge must be a C-contiguous {dn} array [rows, nsteps]", nudge, self.dtype, (None, None)),
-                 ("nudge must have the shape of the day's nudging tables", nudge, self.dtype, tables[0].shape if tables else ()),
-                 (f"reservoir_inflow must be a C-contiguous {dn} array [rows, nsteps]", reservoir_inflow, self.dtype, (None, None)),
-                 (rda_msg, st, np.float32, (nres, 4)), (rda_msg, ti, np.int32, (nres,))]
-        dests += [(f"summary: {name} must be a C-contiguous {np.dtype(dt).name} array of shape ({self.nseg},)", arr, dt, (self.nseg,))
-                  for name, arr, dt in zip(("peak_flow", "peak_step", "mean_flow", "peak_depth", "peak_depth_step"), summary or (),
-                                           (self.dtype, np.int32, self.dtype, self.dtype, np.int32))]
-        for msg, arr, dt, shape in dests:
-            if arr is not None and not (isinstance(arr, np.ndarray) and arr.dtype == dt and arr.flags.c_contiguous and arr.ndim == len(shape)
-                                        and all(n in (None, m) for n, m in zip(shape, arr.shape))):
-                raise ValueError(msg)
+        # the day's destinations, each checked against its row of the table (None = not asked for)
+        if summary is not None and len(summary) not in SP.SUMMARY_LENGTHS:
+            raise ValueError(SP.SUMMARY_WRONG)
+        dims = {"rows": self.nseg, "nres": getattr(self, "_nres", 0)}
+        dest = {p.name: SP.given(p, {"hyd": hyd, "q0": q0, "fvd": fvd, "nudge": nudge, "reservoir_inflow": reservoir_inflow,
+                                     "reservoir_da_state": reservoir_da_state, "summary": summary}) for p in SP.PRODUCTS}
+        for p in SP.PRODUCTS:
+            if p.wrong and dest[p.name] is not None and not SP.fits(p, dest[p.name], self.dtype, dims):
+                raise ValueError(SP.wrong(p, self.dtype, dims))
+        if nudge is not None and nudge.shape != (tables[0].shape if tables else ()):
+            raise ValueError("nudge must have the shape of the day's nudging tables")
         if reservoir_inflow is not None:
             day_s.res_nres, day_s.res_nsteps = reservoir_inflow.shape
         day_s.nudge_host, day_s.res_inflow_host, day_s.res_da_state_host, day_s.res_da_tsidx_host = (
-            None if x is None else x.ctypes.data for x in (nudge, reservoir_inflow, st, ti))
+            None if x is None else x.ctypes.data for x in (nudge, reservoir_inflow, dest["reservoir_da_state"], dest["reservoir_da_tsidx"]))
         rda_s = None
         if reservoir_da is not None:
             if len(reservoir_da) not in (3, 4):
@@ -505,15 +500,16 @@ class RoutingPlan:
         info = self.stream_info()
         day = info["days_pushed"]
         # (alive while the copies may be in flight: a day's products are queued up to `slots` days on)
-        self._stream_keep[day] = {"qlat": qlat, "tables": tables, "dests": [hyd, q0, fvd] + [d[1] for d in dests]}
+        self._stream_keep[day] = {"qlat": qlat, "tables": tables, "dests": list(dest.values())}
         for old in [k for k in self._stream_keep if isinstance(k, int) and k < day - max(8, info["slots"])]:
             del self._stream_keep[old]
-        depth = summary is not None and len(summary) == 5 and (summary[3] is not None or summary[4] is not None)
+        parts = [dest[p.name] for p in SP.SUMMARY]
+        depth = any(x is not None for x in parts[3:])
         if summary is not None:  # (where the NEXT day's summary goes: the push below consumes it)
-            _lib.check(_lib.lib().trmc_stream_summary_dest(self._h, *(_lib.ptr(x) for x in summary[:3])))
+            _lib.check(_lib.lib().trmc_stream_summary_dest(self._h, *(_lib.ptr(x) for x in parts[:3])))
         try:
             if depth:
-                _lib.check(_lib.lib().trmc_stream_summary_depth_dest(self._h, _lib.ptr(summary[3]), _lib.ptr(summary[4])))
+                _lib.check(_lib.lib().trmc_stream_summary_depth_dest(self._h, *(_lib.ptr(x) for x in parts[3:])))
             if nudging is None and reservoir_inflow is None and reservoir_da is None and reservoir_da_state is None:  # (the entry point every stream without tables has always used)
                 _lib.check(_lib.lib().trmc_stream_push(self._h, _lib.ptr(qlat), qlat.shape[1], C.c_void_p(boundary_q_ptr or 0),
                                                        -1 if rowset is None else int(rowset), _lib.ptr(hyd), _lib.ptr(q0), _lib.ptr(fvd)))
@@ -533,21 +529,13 @@ class RoutingPlan:
 
     def stream_summary_total(self):
         """The totals over all days of the stream in progress that have been handed over so far (a stream whose summary has
-        ``"total"``; trmc_stream_summary_total, synchronous): a dict with ``"days"`` and, for the parts of the summary,
-        ``"peak_flow"`` / ``"peak_step"`` (int64, 1-based from the stream's first step), ``"mean_flow"``, ``"peak_depth"`` /
-        ``"peak_depth_step"`` (int64) -- [nseg] arrays in row order, the folds of the days' arrays that include/trmc.h defines."""
+        ``"total"``; trmc_stream_summary_total, synchronous): a dict with ``"days"`` and, for the parts of the summary, their
+        totals under the parts' names (``stream_products.SUMMARY``; the steps int64, 1-based from the stream's first step) --
+        [nseg] arrays in row order, the folds of the days' arrays that include/trmc.h defines."""
         mask = getattr(self, "_stream_summary", 0)
-        n = self.nseg
-        out = {}
-        if mask & _lib.SUMMARY_PEAK:
-            out["peak_flow"], out["peak_step"] = np.empty(n, self.dtype), np.empty(n, np.int64)
-        if mask & _lib.SUMMARY_MEAN:
-            out["mean_flow"] = np.empty(n, self.dtype)
-        if mask & _lib.SUMMARY_PEAK_DEPTH:
-            out["peak_depth"], out["peak_depth_step"] = np.empty(n, self.dtype), np.empty(n, np.int64)
+        out = {p.name: np.empty(self.nseg, SP.dtype_of(p, self.dtype, total=True)) for p in SP.SUMMARY if mask & _lib.SUMMARY_NAMES[p.on]}
         days = C.c_int64(0)
-        _lib.check(_lib.lib().trmc_stream_summary_total(self._h, *(_lib.ptr(out.get(k)) for k in (
-            "peak_flow", "peak_step", "mean_flow", "peak_depth", "peak_depth_step")), C.byref(days)))
+        _lib.check(_lib.lib().trmc_stream_summary_total(self._h, *(_lib.ptr(out.get(p.name)) for p in SP.SUMMARY), C.byref(days)))
         out["days"] = int(days.value)
         return out
 

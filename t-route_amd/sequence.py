@@ -28,6 +28,7 @@ import time
 import numpy as np
 
 from . import _lib
+from . import stream_products as SP
 
 
 def pinned_like(array):
@@ -245,6 +246,168 @@ class DaySequence:
                 "days_routed": total, "last_plan": r._state_plans[0], "day_ms": day_ms}
 
 
+# ---- the parts of RouteStream.route: each keeps one thing from day to day ------------------------------------------------
+def days_spanned(lag, tpd):
+    """the days that a lag of ``lag`` tiles spans, at ``tpd`` tiles per day"""
+    return -(-lag // tpd)
+
+
+def ring_sizes(lmax_mine, lmax_all, tpd, want_fvd, low, slots_asked):
+    """(slots asked of ``stream_begin``, days ``behind`` its push at which a day is delivered, days the host's staging ``ring``
+    holds).  lmax_mine: the largest lag of this rank's rows, in tiles; lmax_all: of every rank's (None: one GPU).
+    slots -- a day's (q, v, d) block takes most of a day to cross PCIe (0.79 GB of a CONUS day with hourly output: 14.5 ms): it is
+    handed over a day later than the other products would be, so that the host never waits for a copy while the device runs out
+    of queued days, and the ring holds a slot more for it.  Several ranks hand a day over in the same iteration -- when the rank
+    whose rows run furthest behind (the trunk's owner) has it: a rank's ring must hold its days that long.
+    behind -- a day's products are waited for a day after they were queued (the host then never waits for launches it has just
+    queued: the device always holds a day of work); low (latency="low"): right after the day's own push, which is flushed.
+    ring -- a staging buffer is read by the copy that the day's push queues, and only the delivery of a day makes the host wait
+    for that copy: before day d is staged the days up to d - 1 - behind have been delivered, so their forcing has been read.  The
+    ring of a day's forcing and tables must therefore be behind + 1 days deep -- with three, a host that ran ahead of the device
+    (several ranks: the first delivery comes days after the first push) overwrote the forcing of a day not copied yet."""
+    slots, later = slots_asked, 1 if want_fvd else 0
+    if lmax_all is not None:
+        slots = max(slots, days_spanned(lmax_all, tpd) + 3 + later)
+    elif want_fvd:
+        slots = max(slots, 3 + days_spanned(lmax_mine + 1, tpd))
+    behind = 0 if low else days_spanned(lmax_mine if lmax_all is None else lmax_all, tpd) + 1 + later
+    return slots, behind, max(3, behind + 1)
+
+
+def _next_of(it, what, day):
+    try:
+        return next(it)
+    except StopIteration:
+        raise ValueError(f"{what} ended before the forcings (day {day})") from None
+
+
+class ProductRing:
+    """A stream's page-locked destinations: day d hands over into slot d % slots.  A slot holds one array per row of
+    ``stream_products.PRODUCTS`` that the stream carries (``has``: what the rows' ``on`` ask for), under the row's name --
+    nothing is allocated for a product the stream does not hand over."""
+
+    def __init__(self, slots, plan_dtype, dims, has):
+        carried = [p for p in SP.PRODUCTS if p.on is None or has.get(p.on)]
+        self._slots = [{p.name: _lib.result_empty(SP.shape_of(p, dims), SP.dtype_of(p, plan_dtype), always_pinned=True) for p in carried}
+                       for _ in range(slots)]
+        self._keywords = [SP.push_keywords(a) for a in self._slots]
+        self.parts = SP.SUMMARY[:len(self._keywords[0].get("summary", ()))]     # the parts a day's dict names (None: not asked for)
+
+    def arrays(self, day):
+        return self._slots[day % len(self._slots)]
+
+    def keywords(self, day):        # (the slot as ``RoutingPlan.stream_push`` takes it)
+        return self._keywords[day % len(self._slots)]
+
+
+class ForcingStage:
+    """Page-locked staging buffers for forcing that is not page-locked where it is: made when a day needs one, ``depth`` days deep."""
+
+    def __init__(self, depth, shape, dtype):
+        self.depth, self.shape, self.dtype, self._bufs = depth, shape, dtype, {}
+
+    def pinned(self, day, q):
+        if _lib.is_pinned(q) and q.dtype == self.dtype and q.flags.c_contiguous:
+            return q
+        if day % self.depth not in self._bufs:
+            self._bufs[day % self.depth] = _lib.result_empty(self.shape, self.dtype, always_pinned=True)
+        self._bufs[day % self.depth][...] = q
+        return self._bufs[day % self.depth]
+
+
+class GageCarry:
+    """The gages' last observations from day to day, as between two calls of the window path: the values as they are, the times
+    less the day's length.  ``nudging(day, usgs_values)``: the day's tables as ``stream_push(nudging=...)`` takes them, in
+    page-locked arrays of a ring ``depth`` days deep; ``lastobs(day)``: (lastobs_times, lastobs_values) as that day left them, once."""
+
+    def __init__(self, ngage, nsteps, dtype, routing_period, depth, lastobs=None, da_parameters=None):
+        from .routing.fast_reach import simple_da
+        self._resolve = simple_da.resolve_tables
+        dap = {"da_decay_coefficient": 120.0, "routing_period": None, **(da_parameters or {})}
+        self.nsteps, self.decay = nsteps, dap["da_decay_coefficient"]
+        self.period = routing_period if dap["routing_period"] is None else dap["routing_period"]
+        nan = np.full(ngage, np.nan, dtype=np.float32)
+        self.lv, self.lt = (nan, nan.copy()) if lastobs is None else (np.asarray(x, dtype=np.float32) for x in lastobs[:2])
+        if self.lv.shape != (ngage,) or self.lt.shape != (ngage,):
+            raise ValueError("lastobs must be (lastobs_values [ngage], time_since_lastobs [ngage])")
+        self.day_len = np.float32(nsteps * self.period)
+        self._tabs = [[_lib.result_empty(s, t, always_pinned=True) for s, t in (
+            ((ngage, nsteps), np.uint8), ((ngage, nsteps), dtype), ((ngage, nsteps), dtype), ((ngage,), dtype))] for _ in range(depth)]
+        self._left = {}
+
+    def nudging(self, day, usgs):
+        mode, a, w, lt_fin, lv_fin = self._resolve(self.nsteps, self.period, self.decay, usgs, self.lv, self.lt)
+        tabs = self._tabs[day % len(self._tabs)]
+        tabs[0][...], tabs[1][...], tabs[2][...] = mode, a, w
+        u = np.asarray(usgs, dtype=np.float32)
+        tabs[3][...] = u[:, 0] if (u.ndim == 2 and u.shape[1] > 0) else np.nan     # (mc_reach.pyx:404-411)
+        self._left[day] = (lt_fin, lv_fin)
+        self.lv, self.lt = lv_fin, (lt_fin - self.day_len).astype(np.float32)      # (the next day counts from its own start)
+        return tuple(tabs)
+
+    def lastobs(self, day):
+        return self._left.pop(day, (None, None))
+
+
+class ReservoirDaCarry:
+    """The host's copy of the state of every reservoir-DA table row, as the reference's loop hands it from run set to run set
+    (mc_reach.pyx:820-837).  ``rda``: the router's declaration (kind, table_row, usgs, usace, rfc[, ids]); ``tuples(state, tsidx)``
+    of the next day delivered: the three tuples that day left -- the device's values in a reservoir's rows, the others' times a day less."""
+
+    def __init__(self, rda, nsteps, period):
+        f32, i32 = (lambda a: np.array(a, dtype=np.float32)), (lambda a: np.array(a, dtype=np.int32))
+        self.kind, self.trow = np.asarray(rda[0]).tolist(), np.asarray(rda[1], dtype=np.int64).tolist()
+        n_of = [0 if t is None else len(t[0]) for t in rda[2:5]]
+        ids = rda[5] if len(rda) > 5 else [np.arange(n) for n in n_of]
+        self.hyb = [[i32(ids[k])] + ([f32(rda[2 + k][2])[:, j] for j in range(4)] if n_of[k] else [f32([])] * 4) for k in (0, 1)]
+        self.rfc = [i32(ids[2]), f32(rda[4][1]) if n_of[2] else f32([]), i32(rda[4][2])[:, 0] if n_of[2] else i32([])]
+        self.t_end = np.float32(np.float32(nsteps) * np.float32(period))
+
+    def tuples(self, state, tsidx):
+        hyb, rfc = self.hyb, self.rfc
+        for times in (hyb[0][1], hyb[0][4], hyb[1][1], hyb[1][4], rfc[1]):
+            times -= self.t_end
+        for i, (kd, tr) in enumerate(zip(self.kind, self.trow)):
+            if kd in (2, 3):
+                for j in range(4):
+                    hyb[kd - 2][1 + j][tr] = state[i, j]
+            elif kd in (4, 5):
+                rfc[1][tr], rfc[2][tr] = state[i, 0], tsidx[i]
+        return tuple(tuple(x.copy() for x in t) for t in (hyb[0], hyb[1], rfc))     # (the caller's own: the carry moves on)
+
+
+class CutExchange:
+    """The daily exchange of the cut-edge hydrographs between ranks: ``exchange(day)``, when every rank's cut rows are through
+    ``day`` -- gathered, all-gathered, into the trunk's boundary rows.  on_device: everything in HBM on the router's exchange
+    stream, double-buffered; otherwise through the host (any communicator with ``all_gather_rows_host``)."""
+
+    def __init__(self, router, plan, comm, on_device, nsteps):
+        self.r, self.P, self.comm, self.on_device, self.nsteps = router, plan, comm, on_device, nsteps
+        self.ncut = int(router.cut_rows.shape[0])
+        if on_device:
+            self.nbytes = max(router._max_cut, 1) * nsteps * np.dtype(plan.dtype).itemsize
+            self.send = [router._X.DeviceBuffer(router._dev, self.nbytes) for _ in range(2)]
+            self.recv = [router._X.DeviceBuffer(router._dev, router.world * self.nbytes) for _ in range(2)]
+
+    def exchange(self, day):
+        r, P = self.r, self.P
+        if self.ncut == 0 or day < 0:
+            return
+        if not self.on_device:
+            parts = self.comm.all_gather_rows_host(P.stream_gather_host(day, r._rsS_cut))
+            if r.plan1 is not None:
+                cut_q = np.zeros((self.ncut, self.nsteps), dtype=P.dtype)
+                for k, blk in enumerate(parts):
+                    cut_q[r.cut_owner == k] = blk
+                P.stream_boundary_host(day, cut_q[r.b_cut_index])
+            return
+        send, recv = self.send[day % 2], self.recv[day % 2]
+        P.stream_gather(day, r._rsS_cut, send.ptr, stream=r._sc)
+        self.comm.all_gather(send.ptr, recv.ptr, self.nbytes, r._sc)
+        if r.plan1 is not None:
+            P.stream_boundary(day, recv.ptr, self.nsteps, index_ptr=r._d_b_index.ptr, stream=r._sc)
+
+
 class RouteStream:
     """The product's run-set loop (the reference: ``for run in run_sets: nwm_route(...) -> compute_nhd_routing_v02(...); new_q0;
     assemble_forcings(next)``, nwm_routing/__main__.py:195-333) as an iterator over days::
@@ -261,18 +424,17 @@ class RouteStream:
     of its ``rows``), with ``output_stride=n`` also every n-th step of (q, v, d) of those rows.  The arrays belong to a ring:
     copy what is kept beyond the next few days.
 
-    ``summary=("peak", "mean")`` (or one of them): every tuple ends in a dict with ``"peak_flow"``, ``"peak_step"`` (int32, the
-    1-based step of the day at which the peak was first reached) and ``"mean_flow"`` -- [rows] ring arrays over this rank's
-    ``rows`` in the order of the final state, formed on the device from ALL nsteps flows of the day (include/trmc.h,
+    ``summary=("peak", "mean")`` (or one of them): every tuple ends in a dict with the day's peak flow, the 1-based step at which
+    it was first reached (int32) and the mean flow, under the names of ``stream_products.SUMMARY`` -- [rows] ring arrays over
+    this rank's ``rows`` in the order of the final state, formed on the device from ALL nsteps flows of the day (include/trmc.h,
     trmc_stream_set_summary; None for what was not asked).  A router with reservoirs or gages: its trailing dict gains these
-    keys.  ``"peak_depth"`` adds ``"peak_depth"`` and ``"peak_depth_step"`` (int32) to that dict: the highest depth of the day
-    -- the pool's water elevation at a reservoir row, (0, 1) at a rank's boundary copies, which nobody routes -- and the step
-    it was first reached at, carried by the tile kernels through every step (a router with ``reservoir_da``: NotImplementedError).
-    ``"total"`` (with at least one of the others) keeps the maximum and the mean of the whole forecast on the device:
-    ``rs.total`` holds ``RoutingPlan.stream_summary_total()`` -- ``"days"``, ``"peak_flow"``, ``"peak_step"`` (int64, 1-based from
-    the stream's first step), ``"mean_flow"``, ``"peak_depth"``, ``"peak_depth_step"`` over this rank's ``rows`` -- once
-    ``route()`` has yielded its last day; ``daily_summary=False`` then leaves the per-day dict out (the tuples of
-    ``summary=None``) and no per-day summary array crosses to the host.
+    keys.  ``"peak_depth"`` adds the table's two further parts: the highest depth of the day -- the pool's water elevation at a
+    reservoir row, (0, 1) at a rank's boundary copies, which nobody routes -- and the step it was first reached at, carried by
+    the tile kernels through every step (a router with ``reservoir_da``: NotImplementedError).  ``"total"`` (with at least one
+    of the others) keeps the maximum and the mean of the whole forecast on the device: ``rs.total`` holds
+    ``RoutingPlan.stream_summary_total()`` -- ``"days"`` and the same keys over this rank's ``rows``, the steps int64 and 1-based
+    from the stream's first step -- once ``route()`` has yielded its last day; ``daily_summary=False`` then leaves the per-day
+    dict out (the tuples of ``summary=None``) and no per-day summary array crosses to the host.
 
     Underneath is ONE stream of tile launches (include/trmc.h, trmc_stream_*): the tile index runs on over the days, every
     launch routes every row through the next K steps of its own place in the stream -- a row deep in the network works on an
@@ -358,7 +520,7 @@ class RouteStream:
             mine = int(lag0[r.my_cut_local].max()) if r.my_cut_local.size else 0
             pmax = int(comm.all_reduce_max_host(np.array([mine], dtype=np.float64))[0])
             tpd = self.nsteps // self._tile_steps(r.plan0)
-            dc = -(-(pmax + 1) // tpd)                      # days after which every rank's cut rows are through a day
+            dc = days_spanned(pmax + 1, tpd)                # days after which every rank's cut rows are through a day
             P = r.stream_plan((dc + 1) * tpd)               # ... and the tiles the trunk must run behind for that
             self._dc = dc
         self.plan = P
@@ -397,7 +559,7 @@ class RouteStream:
         P, multi = self.plan, self.world > 1
         lag, _, _ = P.lags()
         tpd = self.nsteps // self._tile_steps(P)
-        fill = -(-int(lag.max(initial=0)) // tpd) + 1 + (self._dc + 1 if multi else 0) + (1 if (self.output_stride or self.full_output) else 0)
+        fill = ring_sizes(int(lag.max(initial=0)), None, tpd, bool(self.output_stride or self.full_output), False, 0)[1] + (self._dc + 1 if multi else 0)
         if multi:
             fill = int(self.comm.all_reduce_max_host(np.array([fill], dtype=np.float64))[0])
         wu = max(int(warmup), fill)
@@ -458,255 +620,104 @@ class RouteStream:
         persistence_index, persistence_update_time) for usgs and usace, (ids, update_time, timeseries_idx) for rfc, the times
         counted from the next day's start -- which a caller writes back into its ``*_param_df`` as ``update_after_compute``
         does.  Rows of a table that no reservoir of the router uses pass through as the loop passes them."""
-        r, nsteps, qts = self.r, self.nsteps, self.qts
+        multi, low = self.world > 1, self.latency == "low"
+        if low and multi:
+            raise ValueError("latency='low' is a one-GPU option")
+        r, nsteps = self.r, self.nsteps
         P = self.plan if self.plan is not None else self._setup()
-        res, gages = getattr(r, "_reservoirs", None), getattr(r, "_gages", None)
-        extras = res is not None or gages is not None
-        nres = 0 if res is None else res[0].shape[0]
-        ngage = 0 if gages is None else gages.shape[0]
-        rda = getattr(r, "_reservoir_da", None)
+        res, gages, rda = (getattr(r, a, None) for a in ("_reservoirs", "_gages", "_reservoir_da"))
+        nres, ngage = 0 if res is None else res[0].shape[0], 0 if gages is None else gages.shape[0]
         if reservoir_da is not None and rda is None:
             raise ValueError("reservoir_da needs a router with data-assimilation reservoirs (ShardedRouter(..., stream=True, "
                              "reservoirs=..., reservoir_da=...))")
-        if rda is not None:
-            if reservoir_da is None:
-                raise ValueError("the router has data-assimilation reservoirs: route(..., reservoir_da=...) must yield every day's tables")
-            rda_it = iter(reservoir_da)
-            rda_kind, rda_trow = rda[0], np.asarray(rda[1], dtype=np.int64)
-            f32, i32 = (lambda a: np.array(a, dtype=np.float32)), (lambda a: np.array(a, dtype=np.int32))
-            n_of = [0 if t is None else len(t[0]) for t in rda[2:5]]
-            ids = rda[5] if len(rda) > 5 else [np.arange(n) for n in n_of]
-            # the state of every table row as the reference's loop hands it from run set to run set (mc_reach.pyx:820-837)
-            hyb = [[i32(ids[k])] + ([f32(rda[2 + k][2])[:, j] for j in range(4)] if n_of[k] else [f32([])] * 4) for k in (0, 1)]
-            rfc_state = [i32(ids[2]), f32(rda[4][1]) if n_of[2] else f32([]), i32(rda[4][2])[:, 0] if n_of[2] else i32([])]
-            rda_t_end = np.float32(np.float32(nsteps) * np.float32(res[2]))
-
-            def rda_tuples(state, tsidx):
-                for k in (0, 1):
-                    hyb[k][1], hyb[k][4] = hyb[k][1] - rda_t_end, hyb[k][4] - rda_t_end
-                    hyb[k][2], hyb[k][3] = hyb[k][2].copy(), hyb[k][3].copy()
-                rfc_state[1], rfc_state[2] = rfc_state[1] - rda_t_end, rfc_state[2].copy()
-                for i, (kd, tr) in enumerate(zip(rda_kind.tolist(), rda_trow.tolist())):
-                    if kd in (2, 3):
-                        for j in range(4):
-                            hyb[kd - 2][1 + j][tr] = state[i, j]
-                    elif kd in (4, 5):
-                        rfc_state[1][tr], rfc_state[2][tr] = state[i, 0], tsidx[i]
-                return tuple(hyb[0]), tuple(hyb[1]), tuple(rfc_state)
+        if rda is not None and reservoir_da is None:
+            raise ValueError("the router has data-assimilation reservoirs: route(..., reservoir_da=...) must yield every day's tables")
         if observations is not None and not ngage:
             raise ValueError("observations need a router with gages (ShardedRouter(..., stream=True, gages=rows))")
-        if ngage:
-            from .routing.fast_reach import simple_da as _da
-            if observations is None:
-                raise ValueError("the router has gages: route(..., observations=...) must yield every day's usgs_values")
-            obs_it = iter(observations)
-            dap = {"da_decay_coefficient": 120.0, "routing_period": None, **(da_parameters or {})}
-            if dap["routing_period"] is None:
-                dap["routing_period"] = float(r._mk["params"][0, _lib.PARAM_COLS.index("dt")])
-            nan = np.full(ngage, np.nan, dtype=np.float32)
-            lv, lt = (nan, nan.copy()) if lastobs is None else (np.asarray(lastobs[0], dtype=np.float32), np.asarray(lastobs[1], dtype=np.float32))
-            if lv.shape != (ngage,) or lt.shape != (ngage,):
-                raise ValueError("lastobs must be (lastobs_values [ngage], time_since_lastobs [ngage])")
-            day_len = np.float32(nsteps * dap["routing_period"])
-        world, multi = self.world, self.world > 1
-        rows = self.rows
-        local = multi or rows.shape[0] != r.nseg
-        it = iter(forcings)
-        try:
-            first = next(it)
-        except StopIteration:
-            return
-        nq = first.shape[1]
-        dtype = P.dtype
-        nrows = rows.shape[0]
-
-        def take(q):
-            return q[rows] if (local and not prepared) else q
-        # the state and the shape of the forcing
-        q0 = None if state0 is None else np.ascontiguousarray(state0[rows] if (local and state0.shape[0] == r.nseg) else state0, dtype=dtype)
-        P.upload_forcing(nsteps, np.ascontiguousarray(take(first), dtype=dtype), q0)
-        slots = self.slots
+        if ngage and observations is None:
+            raise ValueError("the router has gages: route(..., observations=...) must yield every day's usgs_values")
         want_fvd = bool(self.output_stride or self.full_output)
         lmax_mine = int(P.lags()[0].max(initial=0))
-        tpd0 = nsteps // self._tile_steps(P)
-        if want_fvd and not multi:
-            # a day's (q, v, d) block takes most of a day to cross PCIe (0.79 GB of a CONUS day with hourly output: 14.5 ms):
-            # it is handed over a day later than the other products would be, so that the host never waits for a copy while the
-            # device runs out of queued days -- and the ring holds a slot more for it
-            slots = max(slots, 3 + -(-(lmax_mine + 1) // tpd0))
-        if multi:
-            # every rank hands a day over in the same iteration -- when the rank whose rows run furthest behind (the trunk's owner)
-            # has it: a rank's ring must hold its days that long
-            lmax_all = int(self.comm.all_reduce_max_host(np.array([lmax_mine], dtype=np.float64))[0])
-            slots = max(slots, (-(-lmax_all // tpd0) if lmax_all else 0) + 3 + (1 if want_fvd else 0))
+        lmax_all = int(self.comm.all_reduce_max_host(np.array([lmax_mine], dtype=np.float64))[0]) if multi else None
+        slots, behind, depth = ring_sizes(lmax_mine, lmax_all, nsteps // self._tile_steps(P), want_fvd, low, self.slots)
+        rdac = ReservoirDaCarry(rda, nsteps, res[2]) if rda is not None else None
+        gage = GageCarry(ngage, nsteps, P.dtype, float(r._mk["params"][0, _lib.PARAM_COLS.index("dt")]), depth, lastobs,
+                         da_parameters) if ngage else None
+        it, obs_it, rda_it = (None if x is None else iter(x) for x in (forcings, observations, reservoir_da))
+        nxt = next(it, None)
+        if nxt is None:
+            return
+        rows, local = self.rows, multi or self.rows.shape[0] != r.nseg
+        pick = local and not prepared                       # (the forcings hold global rows: this rank's are picked out)
+        q0 = None if state0 is None else np.ascontiguousarray(state0[rows] if (local and state0.shape[0] == r.nseg) else state0, dtype=P.dtype)
+        P.upload_forcing(nsteps, np.ascontiguousarray(nxt[rows] if pick else nxt, dtype=P.dtype), q0)   # the state and the shape of the forcing
         if self.summary or getattr(P, "_stream_summary", 0):   # (the declaration outlives a stream: an earlier one's is withdrawn)
             P.stream_set_summary(self.summary)
-        P.stream_begin(nsteps, qts, slots=slots, full_output=self.full_output and not self.output_stride,
-                       output_stride=self.output_stride,
+        P.stream_begin(nsteps, self.qts, slots=slots, full_output=self.full_output and not self.output_stride, output_stride=self.output_stride,
                        **({} if rda is None else {"reservoir_da": True if self._rda_ncol is None else self._rda_ncol}))
         self.info = info = P.stream_info()
-        D, tpd, lmax = info["slots"], info["tiles_per_day"], info["lag_max"]
-        keep = nsteps // self.output_stride if self.output_stride else nsteps
-        nout = r._outS_global.shape[0]
-        daily = bool(self.summary) and self.daily_summary
-        want_peak, want_mean, want_pd = (daily and w in self.summary for w in ("peak", "mean", "peak_depth"))
-
-        def products():
-            """a day's page-locked destinations under the names ``RoutingPlan.stream_push`` takes them by: only what the stream
-            hands over is allocated (None: not asked for)"""
-            def new(on, shape, t=dtype):
-                return _lib.result_empty(shape, t, always_pinned=True) if on else None
-            rec = {"hyd": new(True, (max(nout, 1), nsteps)), "q0": new(True, (nrows, 3)), "fvd": new(want_fvd, (nrows, keep, 3))}
-            if extras:                              # (reservoirs and gages: the day's records)
-                rec.update(nudge=new(ngage, (ngage, nsteps)), reservoir_inflow=new(nres, (nres, nsteps)))
-            if rda is not None:
-                rec["reservoir_da_state"] = (new(True, (nres, 4), np.float32), new(True, (nres,), np.int32))
-            if daily:
-                rec["summary"] = (new(want_peak, (nrows,)), new(want_peak, (nrows,), np.int32), new(want_mean, (nrows,))) + (
-                    (new(True, (nrows,)), new(True, (nrows,), np.int32)) if want_pd else ())
-            return rec
-        prods = [products() for _ in range(D)]      # the ring of the days' products: day d hands over into prods[d % D]
-        stage = {}                                  # (page-locked staging buffers of the forcing: made when a day needs one, see `ring`)
-        tabs = {}                                   # (the day's nudging tables, page-locked: on the same ring as the forcing)
         self.total = None
-        lastobs_of = {}
-        # when a day's products are waited for: a day after they were queued (the host then never waits for launches it has
-        # just queued -- the device always holds a day of work); latency="low": right after the day's own push (flushed)
-        low = self.latency == "low"
-        behind = 0 if low else (-(-lmax // tpd) if lmax else 0) + 1 + (1 if want_fvd else 0)
-        if multi:
-            comm = self.comm
-            on_device = self.exchange == "device"
-            ncut = int(r.cut_rows.shape[0])
-            if on_device:
-                X, dev = r._X, r._dev
-                e = np.dtype(dtype).itemsize
-                mc = max(r._max_cut, 1)
-                send = [X.DeviceBuffer(dev, mc * nsteps * e) for _ in range(2)]
-                recv = [X.DeviceBuffer(dev, world * mc * nsteps * e) for _ in range(2)]
-                sc = r._sc
-            behind = (-(-lmax_all // tpd) if lmax_all else 0) + 1 + (1 if want_fvd else 0)   # (every rank hands a day over in the same iteration)
-            order = None
-        # A staging buffer is read by the copy that the day's push queues, and nothing makes the host wait for that copy but the
-        # delivery of a day: before day d is staged the days up to d - 1 - behind have been delivered, so their forcing (which
-        # their launches waited for) has been read.  The ring that the host writes the forcing and the tables of a day into
-        # must therefore be behind + 1 days deep -- with three, a host that ran ahead of the device (several ranks whose first
-        # exchange and first delivery come days after the first push) overwrote the forcing of a day that had not been copied yet.
-        ring = max(3, behind + 1)
-        self._out_rows = np.sort(r._outS_global) if not multi else None
-        sel_own = np.argsort(r._outS_global, kind="stable")
-
-        def exchange(day):
-            """the cut-edge hydrographs of `day` (through on every rank): gathered, all-gathered, into the trunk's boundary rows"""
-            if not multi or ncut == 0 or day < 0:
-                return
-            if not on_device:                           # through the host: any communicator with all_gather_rows_host
-                parts = comm.all_gather_rows_host(P.stream_gather_host(day, r._rsS_cut))
-                if r.plan1 is not None:
-                    cut_q = np.zeros((ncut, nsteps), dtype=dtype)
-                    for k, blk in enumerate(parts):
-                        cut_q[r.cut_owner == k] = blk
-                    P.stream_boundary_host(day, cut_q[r.b_cut_index])
-                return
-            k = day % 2
-            P.stream_gather(day, r._rsS_cut, send[k].ptr, stream=sc)
-            comm.all_gather(send[k].ptr, recv[k].ptr, mc * nsteps * e, sc)
-            if r.plan1 is not None:
-                P.stream_boundary(day, recv[k].ptr, nsteps, index_ptr=r._d_b_index.ptr, stream=sc)
-
-        def deliver(day):
-            nonlocal order
-            P.stream_wait(day)
-            rec = prods[day % D]
-            hyd = rec["hyd"][:nout]
-            if multi:
-                parts = comm.all_gather_rows_host(np.ascontiguousarray(hyd))
-                if order is None:
-                    rows_all = np.concatenate(comm.all_gather_rows_host(np.ascontiguousarray(r._outS_global.astype(np.int64)[:, None])))[:, 0]
-                    order = np.argsort(rows_all, kind="stable")
-                    self._out_rows = rows_all[order]
-                hyd = np.concatenate(parts, 0)[order] if (self.rank == 0 or self._hyd_everywhere) else None
-                fin = [rec["q0"]]
-                fvd = [rec["fvd"]] if want_fvd else None
-            else:
-                hyd = hyd[sel_own]
-                fin, fvd = rec["q0"], rec["fvd"]
-            item = (day, hyd, fin, fvd) if want_fvd else (day, hyd, fin)
-            if extras:
-                item += ({"reservoir_inflow": rec["reservoir_inflow"], "nudge": rec["nudge"], "lastobs": lastobs_of.pop(day, (None, None))},)
-                if rda is not None:                     # (days are delivered in order: the host's copy of the state moves on with them)
-                    item[-1]["reservoir_da"] = rda_tuples(*rec["reservoir_da_state"])
-            if daily:                                   # (three parts, five with "peak_depth")
-                sm = dict(zip(("peak_flow", "peak_step", "mean_flow", "peak_depth", "peak_depth_step"), rec["summary"]))
-                if extras:
-                    item[-1].update(sm)
-                else:
-                    item += (sm,)
-            return item
-
-        d, nxt, pending = 0, first, 0
-        delivered = 0
+        daily = bool(self.summary) and self.daily_summary
+        ring = ProductRing(info["slots"], P.dtype,
+                           {"rows": rows.shape[0], "nsteps": nsteps, "keep": nsteps // self.output_stride if self.output_stride else nsteps,
+                            "outlets": max(r._outS_global.shape[0], 1), "nres": nres, "ngage": ngage},
+                           {"fvd": want_fvd, "ngage": ngage, "nres": nres, "rda": rda is not None, **{w: daily for w in self.summary}})
+        stage = ForcingStage(depth, (rows.shape[0], nxt.shape[1]), P.dtype)
+        xch = CutExchange(r, P, self.comm, self.exchange == "device", nsteps) if multi else None
+        self._out_rows, self._order = (None, None) if multi else (np.sort(r._outS_global), np.argsort(r._outS_global, kind="stable"))
+        extras = res is not None or gages is not None
+        d = delivered = 0
         while nxt is not None:
-            q = take(nxt)
-            if not (_lib.is_pinned(q) and q.dtype == dtype and q.flags.c_contiguous):
-                buf = stage.get(d % ring)
-                if buf is None:
-                    buf = stage[d % ring] = _lib.result_empty((nrows, nq), dtype, always_pinned=True)
-                buf[...] = q
-                q = buf
-            nudging = None
-            if ngage:
-                try:
-                    usgs = next(obs_it)
-                except StopIteration:
-                    raise ValueError(f"observations ended before the forcings (day {d})") from None
-                mode, a, w, lt_fin, lv_fin = _da.resolve_tables(nsteps, dap["routing_period"], dap["da_decay_coefficient"], usgs, lv, lt)
-                nudging = tabs.get(d % ring)
-                if nudging is None:
-                    nudging = tabs[d % ring] = (_lib.result_empty((ngage, nsteps), np.uint8, always_pinned=True),
-                                                _lib.result_empty((ngage, nsteps), dtype, always_pinned=True),
-                                                _lib.result_empty((ngage, nsteps), dtype, always_pinned=True),
-                                                _lib.result_empty((ngage,), dtype, always_pinned=True))
-                nudging[0][...], nudging[1][...], nudging[2][...] = mode, a, w
-                u = np.asarray(usgs, dtype=np.float32)
-                nudging[3][...] = u[:, 0] if (u.ndim == 2 and u.shape[1] > 0) else np.nan     # (mc_reach.pyx:404-411)
-                lastobs_of[d] = (lt_fin, lv_fin)
-                lv, lt = lv_fin, (lt_fin - day_len).astype(np.float32)       # (the next day counts from its own start)
-            more = {"nudging": nudging} if extras else {}
-            if rda is not None:
-                try:
-                    more["reservoir_da"] = next(rda_it)
-                except StopIteration:
-                    raise ValueError(f"reservoir_da ended before the forcings (day {d})") from None
-            P.stream_push(q, rowset=r._rsS_out, **prods[d % D], **more)
+            more = {"nudging": gage.nudging(d, _next_of(obs_it, "observations", d)) if gage else None} if extras else {}
+            if rdac is not None:
+                more["reservoir_da"] = _next_of(rda_it, "reservoir_da", d)
+            P.stream_push(stage.pinned(d, nxt[rows] if pick else nxt), rowset=r._rsS_out, **ring.keywords(d), **more)
             if low:
-                if multi:
-                    raise ValueError("latency='low' is a one-GPU option")
                 P.stream_flush()
-            exchange(d - self._dc)
+            if xch is not None:
+                xch.exchange(d - self._dc)
             while delivered <= d - behind:
-                yield deliver(delivered)
+                yield self._deliver(delivered, ring, gage, rdac, extras)
                 delivered += 1
             d += 1
-            try:
-                nxt = next(it)
-            except StopIteration:
-                nxt = None
-        total = d
+            nxt = next(it, None)
         # the days still under way: no new day starts, the stream advances a day's launches at a time (the exchange of the last
         # days' cut-edge hydrographs between them), until every day has been queued to its end
-        if multi:
-            if low:
-                raise ValueError("latency='low' is a one-GPU option")
-            for k in range(self._dc):
-                P.stream_advance(tpd)
-                exchange(total + k - self._dc)
+        for k in range(self._dc):       # (0 on one GPU)
+            P.stream_advance(info["tiles_per_day"])
+            xch.exchange(d + k - self._dc)
         P.stream_flush()
         if "total" in self.summary:     # (every day has been handed over on the device: the totals of the whole stream)
             self.total = P.stream_summary_total()
-        while delivered < total:
-            yield deliver(delivered)
+        while delivered < d:
+            yield self._deliver(delivered, ring, gage, rdac, extras)
             delivered += 1
         self.last_info = P.stream_info()
         P.stream_end()
         self.info = None
+
+    def _deliver(self, day, ring, gage, rdac, extras):
+        """day's tuple, once its products are on the host (days are delivered in order: the carries move on with them)"""
+        self.plan.stream_wait(day)
+        a = ring.arrays(day)
+        hyd, fin, fvd = a["hyd"][:self.r._outS_global.shape[0]], a["q0"], a.get("fvd")
+        if self.world > 1:
+            parts = self.comm.all_gather_rows_host(np.ascontiguousarray(hyd))
+            if self._order is None:
+                own = np.ascontiguousarray(self.r._outS_global.astype(np.int64)[:, None])
+                rows_all = np.concatenate(self.comm.all_gather_rows_host(own))[:, 0]
+                self._order = np.argsort(rows_all, kind="stable")
+                self._out_rows = rows_all[self._order]
+            hyd = np.concatenate(parts, 0)[self._order] if (self.rank == 0 or self._hyd_everywhere) else None
+            fin, fvd = [fin], [fvd]
+        else:
+            hyd = hyd[self._order]
+        item = (day, hyd, fin, fvd) if "fvd" in a else (day, hyd, fin)
+        more = {p.name: a.get(p.name) for p in SP.RECORDS} if extras else {}    # (reservoirs and gages: the day's records)
+        if extras:
+            more["lastobs"] = gage.lastobs(day) if gage is not None else (None, None)
+            if rdac is not None:
+                more["reservoir_da"] = rdac.tuples(a["reservoir_da_state"], a["reservoir_da_tsidx"])
+        more.update((p.name, a.get(p.name)) for p in ring.parts)
+        return item + (more,) if (extras or ring.parts) else item
+

@@ -110,12 +110,39 @@ class OracleStreamPlan(OraclePlan):
         return {"slots": s["slots"], "tiles_per_day": s["tpd"], "lag_max": s["lmax"], "wide_levels": self._W, "cluster_levels": self._C,
                 "days_pushed": len(s["days"]), "days_complete": done, "launches": s["launches"]}
 
-    def stream_push(self, qlat, boundary_q_ptr=None, rowset=None, hyd=None, q0=None, fvd=None):
+    # the per-row summary of a day, its flow parts only: (peak_flow, peak_step, mean_flow) as include/trmc.h defines them
+    _summary = ()
+
+    def stream_set_summary(self, what):
+        self._summary = tuple(what or ())
+
+    def _summary_of(self, day):
+        q = self._s["days"][day]["fvd"][:, 1:, 0]
+        at = np.argmax(q, axis=1)                           # (the FIRST step that reaches the peak; the flows are finite)
+        return (q[np.arange(q.shape[0]), at], (at + 1).astype(np.int32),
+                np.cumsum(q, axis=1, dtype=np.float32)[:, -1] / np.float32(q.shape[1]))
+
+    def stream_summary_total(self):
+        n = self.stream_info()["days_complete"]
+        assert "total" in self._summary and n > 0, "RuntimeError: begun without 'total', or no day of the stream is complete"
+        self._compute_through(n - 1)
+        pk, st, mn = self._summary_of(0)
+        st = st.astype(np.int64)
+        for d in range(1, n):                               # (the folds of include/trmc.h, in day order)
+            p, t, m = self._summary_of(d)
+            st, pk, mn = np.where(p > pk, d * self._s["nsteps"] + t, st), np.where(p > pk, p, pk), mn + m
+        out = {"peak_flow": pk, "peak_step": st} if "peak" in self._summary else {}
+        if "mean" in self._summary:
+            out["mean_flow"] = mn / np.float32(n)
+        return {**out, "days": n}
+
+    def stream_push(self, qlat, boundary_q_ptr=None, rowset=None, hyd=None, q0=None, fvd=None, summary=None):
         s = self._s
+        assert summary is None or (len(summary) == 3 and self._summary), "a summary tuple in a stream without a summary"
         assert s["g"] <= len(s["days"]) * s["tpd"] - 1 or self.stream_info()["days_complete"] == len(s["days"]), "advanced, not flushed"
         assert fvd is None or s["stride"] or s["full"], "no (q, v, d) block in a stream begun without full_output / output_stride"
         s["days"].append({"qlat": np.array(qlat, np.float32), "bq": None, "rowset": rowset, "hyd": hyd, "q0": q0, "fvd": None,
-                          "fvd_out": fvd})
+                          "fvd_out": fvd, "summary": summary})
         s["g"] = len(s["days"]) * s["tpd"] - 1
         s["launches"] += s["tpd"]
         return len(s["days"]) - 1
@@ -183,6 +210,9 @@ class OracleStreamPlan(OraclePlan):
         if rec["fvd_out"] is not None:                      # every stride-th step (or every step) of every row's (q, v, d)
             n = s["stride"] or 1
             rec["fvd_out"][...] = rec["fvd"][:, 1:, :][:, n - 1::n, :]
+        for dst, part in zip(rec["summary"] or (), self._summary_of(day)):
+            if dst is not None:
+                dst[...] = part
 
     def stream_day_ms(self, day):
         return 0.0
