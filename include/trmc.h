@@ -673,6 +673,32 @@ int trmc_download_fvd_strided(trmc_plan *plan, int stride, void *fvd_out);
  * per-network loop :1399-1738): with the set = the table's rows grouped by tailwater, each of those is a slice of fvd_out and
  * the host never permutes the block. */
 int trmc_download_fvd_rowset(trmc_plan *plan, int stride, int32_t rowset, void *fvd_out);
+/*
+ * Per-row summary of the last WINDOW, reduced on the device from the same result trmc_download_fvd copies -- every step of it,
+ * whatever stride the caller takes the block itself at: a few bytes per row cross the host link instead of nsteps * 3 values.
+ *   peak_flow, peak_step                  the largest flow of the window and the 1-based step it was FIRST reached at
+ *   mean_flow                             the flows summed left to right in the plan's precision, divided by nsteps
+ *                                         (np.cumsum(q, dtype=T)[-1] / T(nsteps))
+ *   peak_depth, peak_depth_step           the same compare on the depths
+ *   peak_velocity, peak_velocity_step     ... and on the velocities
+ * A peak is `pk = x[1]; at = 1; for t = 2..nsteps: if (x[t] > pk) { pk = x[t]; at = t; }`: of equal values the first wins, a NaN
+ * never replaces a number.  The first five are what a stream of days leaves with TRMC_SUMMARY_PEAK | _MEAN | _PEAK_DEPTH, bit
+ * for bit.  Value destinations hold nrows elements of the plan's precision, step destinations nrows int32; any of them may be
+ * NULL (all NULL: TRMC_EINVAL), a step destination needs its value destination.  rowset: -1 = every row in row order, else a
+ * registered set (trmc_rowset_create): its rows, in its order.  Valid wherever trmc_download_fvd is -- after a window of either
+ * engine, either timestep mode, either precision and either arithmetic -- and TRMC_ESTATE before any window, while a window is
+ * open and while a stream of windows is in progress (a stream does not fill the plan's window result).  Synchronous: one kernel
+ * on the plan's stream behind the window, the columns into plan-owned scratch, then to the host.  nseg == 0: nothing is written.
+ *
+ * trmc_window_summary_tile: the kernel's tile for a precision (32 / 64) -- rows per block and steps per chunk of a row's record
+ * (csrc/k_window_summary.inc); the sizes at which its tests probe the tile's edges.  Host only.
+ * trmc_window_summary_kernel_ms: device time of the last trmc_window_summary's kernel on this plan, from events around it (the
+ * copies to the host not included); TRMC_ESTATE before the first.  Host only.
+ */
+int trmc_window_summary(trmc_plan *plan, int32_t rowset, void *peak_flow, int32_t *peak_step, void *mean_flow,
+                        void *peak_depth, int32_t *peak_depth_step, void *peak_velocity, int32_t *peak_velocity_step);
+int trmc_window_summary_tile(int precision, int32_t *rows, int32_t *steps);
+int trmc_window_summary_kernel_ms(const trmc_plan *plan, double *ms_out);
 /* on != 0: trmc_upload_forcing turns every NaN of qlat and q0 into 0 on the device, behind the copy.  The reference's reindexed
  * tables hold NaN on waterbody rows (compute.py:1466-1467), which the Muskingum-Cunge rows never read; the drop-in used to screen
  * the caller's frames for them on the host -- 20 ms of a CONUS call.  Default off: values go to the kernels as they are. */

@@ -423,6 +423,8 @@ void trmc_plan_destroy(trmc_plan *pl)
     if (pl->ev_fetch_ready) (void)hipEventDestroy(pl->ev_fetch_ready);
     if (pl->ev_fetch_done) (void)hipEventDestroy(pl->ev_fetch_done);
     if (pl->ev_gather) (void)hipEventDestroy(pl->ev_gather);
+    for (hipEvent_t e : pl->ev_wsum)
+        if (e) (void)hipEventDestroy(e);
     for (DevBuf *b : {&pl->lagk, &pl->cblk_ptr, &pl->params, &pl->up_ptr, &pl->up_idx, &pl->up2, &pl->level, &pl->row_of_pos, &pl->pos_of_row, &pl->it_prev, &pl->it_sum, &pl->lag, &pl->d_state, &pl->ticket, &pl->ticket_map, &pl->rank, &pl->dbg, &pl->prio, &pl->cuq_ptr, &pl->cuq_blk, &pl->cuq_head, &pl->cu_index, &pl->cuq_perm, &pl->d_gran, &pl->raw_of_pos, &pl->da_raw, &pl->gage_of_pos,
                       &pl->da_mode, &pl->da_a, &pl->da_w, &pl->da_nudge, &pl->res_of_pos, &pl->res_par, &pl->res_inflow, &pl->res_da,
                       &pl->in_qlat, &pl->in_q0, &pl->in_bfvd, &pl->qlat_tm, &pl->qlat_alt, &pl->tm, &pl->out, &pl->scratch, &pl->gathered, &pl->cls_last, &pl->hot_list, &pl->hot_cnt})
@@ -1418,6 +1420,86 @@ int trmc_download_fvd_rowset(trmc_plan *pl, int stride, int32_t rowset, void *fv
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(fvd_out, pl->gathered.p, bytes, hipMemcpyDeviceToHost, pl->stream));
     HIP_TRY(hipStreamSynchronize(pl->stream));
+    return 0;
+}
+
+int trmc_window_summary_tile(int precision, int32_t *rows, int32_t *steps)
+{
+    if (precision != 32 && precision != 64) return fail(TRMC_EINVAL, "precision must be 32 or 64");
+    if (rows) *rows = kWsumRows;
+    if (steps) *steps = precision == 32 ? kWsumSteps<float> : kWsumSteps<double>;
+    return 0;
+}
+
+int trmc_window_summary(trmc_plan *pl, int32_t rowset, void *peak_flow, int32_t *peak_step, void *mean_flow, void *peak_depth,
+                        int32_t *peak_depth_step, void *peak_velocity, int32_t *peak_velocity_step)
+{
+    if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
+    // `out` is assembled by windows only, and whole only once the window has ended: a stream of days leaves its own summaries
+    // (trmc_stream_set_summary) and, without full_output, assembles no result at all; trmc_stream_begin also forgets the last window
+    if (stream_active(pl))
+        return fail(TRMC_ESTATE, "a stream of windows is in progress: a window's summary is formed from the result the plan assembles for a "
+                                 "window, which a stream does not fill (trmc_stream_set_summary is the stream's own)");
+    if (pl->run.active)
+        return fail(TRMC_ESTATE, "a routing window is in progress: its result is not assembled before trmc_route_end");
+    if (pl->routed_nsteps < 0) return fail(TRMC_ESTATE, "nothing routed yet");
+    if (!peak_flow && !peak_step && !mean_flow && !peak_depth && !peak_depth_step && !peak_velocity && !peak_velocity_step)
+        return fail(TRMC_EINVAL, "every destination is NULL: nothing to summarise");
+    if ((peak_step && !peak_flow) || (peak_depth_step && !peak_depth) || (peak_velocity_step && !peak_velocity))
+        return fail(TRMC_EINVAL, "the step of a peak comes with the peak: its value destination is NULL");
+    if (rowset < -1 || rowset >= (int32_t)pl->rowsets.size()) return fail(TRMC_EINVAL, "unknown row set");
+    const int64_t nrows = rowset < 0 ? pl->nseg : pl->rowset_n[(size_t)rowset];
+    if (pl->nseg == 0 || nrows == 0) return 0;
+    const int32_t nsteps = pl->routed_nsteps;
+    if (nsteps < 1) return fail(TRMC_ESTATE, "the last window had no timesteps");
+    if (int rc = use_device(pl)) return rc;
+    // seven columns [nrows] in the plan's scratch block, each on a 256-byte boundary; then to the host
+    void *const host[7] = {peak_flow, peak_step, mean_flow, peak_depth, peak_depth_step, peak_velocity, peak_velocity_step};
+    const size_t width[7] = {pl->esz, 4, pl->esz, pl->esz, 4, pl->esz, 4};
+    size_t off[7], total = 0;
+    for (int k = 0; k < 7; ++k) {
+        off[k] = total;
+        if (host[k]) total += ((size_t)nrows * width[k] + 255) / 256 * 256;
+    }
+    if (int rc = pl->scratch.ensure(total)) return rc;
+    const int32_t *rp = rowset < 0 ? nullptr : (const int32_t *)pl->rowsets[(size_t)rowset].p;
+    for (hipEvent_t &e : pl->ev_wsum)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    pl->wsum_ms = -1.0;
+    HIP_TRY(hipEventRecord(pl->ev_wsum[0], pl->stream));
+    const int rc = by_precision(pl, [&](auto t) -> int {
+        using T = decltype(t);
+        char *const s = (char *)pl->scratch.p;
+        auto col = [&](int k) { return host[k] ? s + off[k] : nullptr; };
+        const WsumOut<T> o{(T *)col(0), (int32_t *)col(1), (T *)col(2), (T *)col(3), (int32_t *)col(4), (T *)col(5), (int32_t *)col(6)};
+        const dim3 grid((unsigned)((nrows + kWsumRows - 1) / kWsumRows)), block(kWsumRows);
+        // (16-byte loads where every row's record starts on a 16-byte boundary: k_window_summary's head)
+        if (nsteps % (16 / (int)sizeof(T)) == 0)
+            hipLaunchKernelGGL((k_window_summary<T, true>), grid, block, 0, pl->stream, (const T *)pl->out.p, rp, (const int32_t *)pl->row_of_pos.p,
+                               o, nrows, nsteps);
+        else
+            hipLaunchKernelGGL((k_window_summary<T, false>), grid, block, 0, pl->stream, (const T *)pl->out.p, rp, (const int32_t *)pl->row_of_pos.p,
+                               o, nrows, nsteps);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    });
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(pl->ev_wsum[1], pl->stream));
+    for (int k = 0; k < 7; ++k)
+        if (host[k])
+            HIP_TRY(hipMemcpyAsync(host[k], (char *)pl->scratch.p + off[k], (size_t)nrows * width[k], hipMemcpyDeviceToHost, pl->stream));
+    HIP_TRY(hipStreamSynchronize(pl->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, pl->ev_wsum[0], pl->ev_wsum[1]));
+    pl->wsum_ms = ms;
+    return 0;
+}
+
+int trmc_window_summary_kernel_ms(const trmc_plan *pl, double *ms_out)
+{
+    if (!pl || !ms_out) return fail(TRMC_EINVAL, "plan/ms_out is NULL");
+    if (pl->wsum_ms < 0) return fail(TRMC_ESTATE, "no window summary has been formed on this plan");
+    *ms_out = pl->wsum_ms;
     return 0;
 }
 

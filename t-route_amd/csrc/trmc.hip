@@ -74,6 +74,7 @@ namespace {
 #include "dev_math.inc"
 #include "kernels_levels.inc"
 #include "kernels_flow.inc"
+#include "k_window_summary.inc"
 // ---------------------------------------------------------------- plan
 struct DevBuf {
     void *p = nullptr;
@@ -255,6 +256,8 @@ struct trmc_plan {
     // (TRMC_SETUP_ASIDE) waits for before it lets a new window's tiles overwrite them
     hipEvent_t ev_gather = nullptr;
     bool gather_pending = false;
+    hipEvent_t ev_wsum[2] = {nullptr, nullptr}; // around the last trmc_window_summary's kernel (trmc_window_summary_kernel_ms)
+    double wsum_ms = -1.0;
     // trmc_plan_clone: a second set of WINDOW buffers on the static data (topology, parameters) of `parent`
     trmc_plan *parent = nullptr;
     int32_t clones = 0;                  // live clones of this plan

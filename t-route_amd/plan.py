@@ -653,6 +653,50 @@ class RoutingPlan:
             _lib.check(_lib.lib().trmc_download_fvd_strided(self._h, stride, _lib.ptr(out)))
         return out
 
+    # window_summary's parts -> the arrays each brings (value arrays in the plan's dtype, steps int32), in trmc_window_summary's order
+    WINDOW_SUMMARY_PARTS = {"peak": ("peak_flow", "peak_step"), "mean": ("mean_flow",), "peak_depth": ("peak_depth", "peak_depth_step"),
+                            "peak_velocity": ("peak_velocity", "peak_velocity_step")}
+
+    @staticmethod
+    def window_summary_tile(precision=32):
+        """(rows, steps) of the reduction kernel's tile for a precision (trmc_window_summary_tile)"""
+        rows, steps = C.c_int32(0), C.c_int32(0)
+        _lib.check(_lib.lib().trmc_window_summary_tile(int(precision), C.byref(rows), C.byref(steps)))
+        return rows.value, steps.value
+
+    def window_summary(self, parts=("peak", "mean", "peak_depth", "peak_velocity"), rowset=None):
+        """Per-row summary of the last window, reduced on the device over EVERY step of its result (trmc_window_summary): a dict
+        with ``peak_flow`` / ``peak_step`` ("peak"), ``mean_flow`` ("mean"), ``peak_depth`` / ``peak_depth_step`` ("peak_depth") and
+        ``peak_velocity`` / ``peak_velocity_step`` ("peak_velocity") -- the parts asked for only.  Values [rows] in the plan's
+        dtype, steps int32, 1-based, the first of equal peaks; the first five are a stream day's summary of the same names, bit
+        for bit.  rowset (``rowset(rows)``): the rows of that set, in its order."""
+        parts = (parts,) if isinstance(parts, str) else tuple(parts or ())
+        unknown = [p for p in parts if p not in self.WINDOW_SUMMARY_PARTS]
+        if unknown:
+            raise ValueError(f"unknown part(s) of a window summary {unknown}: one of {sorted(self.WINDOW_SUMMARY_PARTS)}")
+        if not parts:
+            raise ValueError("window_summary: no part asked for")
+        n = self.nseg if rowset is None else self._rowset_n[rowset]
+        order = ("peak_flow", "peak_step", "mean_flow", "peak_depth", "peak_depth_step", "peak_velocity", "peak_velocity_step")
+        asked = [name for part, names in self.WINDOW_SUMMARY_PARTS.items() if part in parts for name in names]
+        # ONE block for the arrays asked for (page-locked and pooled when it is large, like a downloaded result), each a view of it
+        dtype_of = lambda name: np.dtype(np.int32 if name.endswith("_step") else self.dtype)      # noqa: E731
+        pitch = {name: -(-n * dtype_of(name).itemsize // 256) * 256 for name in asked}
+        block = _lib.result_empty((sum(pitch.values()),), np.uint8)
+        out, at = dict.fromkeys(order), 0
+        for name in order:
+            if name in pitch:
+                out[name] = block[at:at + n * dtype_of(name).itemsize].view(dtype_of(name))
+                at += pitch[name]
+        _lib.check(_lib.lib().trmc_window_summary(self._h, -1 if rowset is None else int(rowset), *(_lib.ptr(out[k]) for k in order)))
+        return {k: out[k] for k in order if out[k] is not None}
+
+    def window_summary_kernel_ms(self):
+        """device time (ms) of the last ``window_summary``'s kernel, from events around it (trmc_window_summary_kernel_ms)"""
+        ms = C.c_double(0)
+        _lib.check(_lib.lib().trmc_window_summary_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def set_nan_is_zero(self, on=True):
         """uploads of forcing and state: NaN -> 0 on the device (trmc_plan_set_nan_is_zero)"""
         _lib.check(_lib.lib().trmc_plan_set_nan_is_zero(self._h, int(bool(on))))

@@ -178,6 +178,7 @@ def compute_nhd_routing_v02(
     precision=32,
     device=0,
     output_stride=None,
+    summary=None,
 ):
     """Route every independent network of the call for ``nts`` timesteps.
 
@@ -198,6 +199,11 @@ def compute_nhd_routing_v02(
     only -- the steps n, 2n, ..., which are the ones the reference's writers take when n = ``qts_subdivisions``
     (nwm_routing/output.py:209-216, :232-240) -- decimated on the device (``compute_network_structured``); with ``nts`` a
     multiple of n the last step is among them, so ``new_q0`` works on the result as it is.
+
+    ``summary`` (keyword-only; None = the reference's result): a tuple of parts ("peak", "mean", "peak_depth", "peak_velocity",
+    ``compute_network_structured``) -- every tailwater's tuple then has an eleventh member, the dict of per-row arrays (peak flow /
+    depth / velocity with the 1-based step of each, mean flow) over EVERY step of the window for the rows of its member [0], whatever
+    ``output_stride`` keeps of the block itself.
     """
     if parallel_compute_method not in _PARALLEL_METHODS and parallel_compute_method is not None:
         raise ValueError(f"unknown parallel_compute_method {parallel_compute_method!r}")
@@ -311,7 +317,7 @@ def compute_nhd_routing_v02(
         *res_da_args,
         e_i1, e_i1, e_f1, e_i1, e_f1, e_i1, e_i1, e_f2,
         upstream_results, assume_short_ts, return_courant, from_files=from_files, precision=precision, device=device,
-        output_stride=output_stride, result_order=net["order"] if grouped else None, nan_is_zero=True)
+        output_stride=output_stride, result_order=net["order"] if grouped else None, nan_is_zero=True, summary=summary)
     rids = r[0].astype("int64")                  # (the rows of upstream_results are masked out, mc_reach.pyx:451,:812)
     fvd, upstream = r[1], r[6]
     gage_ids, lastobs_times, lastobs_values = r[3]
@@ -337,8 +343,10 @@ def compute_nhd_routing_v02(
         bounds = np.searchsorted(owner[order], np.arange(len(tws) + 1))
     if grouped:                                  # (compute_network_structured has handed its rows back in that order)
         ids_o, fvd_o, up_o = rids.astype(np.intp), fvd, upstream
+        sum_o = r[-1] if summary is not None else None
     else:
         ids_o, fvd_o = rids[order].astype(np.intp), fvd[order]
+        sum_o = {k: v[order] for k, v in r[-1].items()} if summary is not None else None
         # (the upstream-inflow series are zero except on waterbody rows, mc_reach.pyx:487,:710: without waterbodies any order of
         # an all-zero block is the block itself -- 3.1 GB for a CONUS day that need not be permuted)
         up_o = upstream[order] if len(lake_segs) else upstream
@@ -360,7 +368,8 @@ def compute_nhd_routing_v02(
             gk = np.flatnonzero((gage_row >= 0) & (gage_owner == k))                          # this network's gages
             gt = (np.asarray(gage_ids)[gk], np.asarray(lastobs_times)[gk], np.asarray(lastobs_values)[gk])
         results.append((ids_o[lo:hi], fvd_o[lo:hi], 0, gt if ngage else no_gage, state_of(k, r[4], e5), state_of(k, r[5], e5),
-                        up_o[lo:hi], state_of(k, r[7], e3), nudge[gk] if ngage else no_nudge, e4))
+                        up_o[lo:hi], state_of(k, r[7], e3), nudge[gk] if ngage else no_nudge, e4)
+                       + (({name: v[lo:hi] for name, v in sum_o.items()},) if sum_o is not None else ()))
     return results, subnetwork_list
 
 

@@ -377,6 +377,7 @@ def compute_network_structured(
     output_stride=None,
     result_order=None,
     nan_is_zero=False,
+    summary=None,
 ):
     """Route one (sub)network for ``nsteps`` timesteps on the GPU.
 
@@ -396,8 +397,19 @@ def compute_network_structured(
     ``upstream_results`` rows only), ``nan_is_zero`` (True: NaN in ``qlat_values`` and
     ``initial_conditions`` -- the waterbody rows of the reference's reindexed tables,
     compute.py:1466-1467, which no Muskingum-Cunge row reads -- become 0 on the device
-    behind the upload instead of in a pass over the arrays on the host).
+    behind the upload instead of in a pass over the arrays on the host),
+    ``summary`` (None, or a tuple of parts of ``RoutingPlan.window_summary`` -- "peak",
+    "mean", "peak_depth", "peak_velocity": a dict of per-row arrays -- peak flow / depth /
+    velocity, the 1-based step of each, the mean flow -- reduced on the device over EVERY
+    step of the window is appended to the returned tuple, behind the stats dict when
+    ``return_stats`` is set; its rows are the rows of element [0], in that order; it
+    combines with ``output_stride``: the hourly block for the files, the peaks from all
+    steps).
     """
+    if summary is not None:
+        summary = (summary,) if isinstance(summary, str) else tuple(summary)
+        if not summary:
+            raise ValueError("summary: no part asked for (None switches it off)")
     stride = 1 if output_stride is None else int(output_stride)
     if stride < 1:
         raise ValueError("output_stride must be a positive number of timesteps")
@@ -619,6 +631,7 @@ def compute_network_structured(
                 hit = sets[okey] = (result_order, plan.rowset(result_order))
             oset = hit[1]
         fvd = plan.download_fvd(stride, rowset=oset)
+        window_summary = plan.window_summary(summary, rowset=oset) if summary is not None else None
         if nudging is not None:
             nudge[nudging[4], 1:] = plan.download_nudge()
         res_inflow = plan.download_reservoir_inflow() if res_rows else None
@@ -693,7 +706,11 @@ def compute_network_structured(
         ),
     )
     if return_stats:
-        return result + (stats,)
+        result = result + (stats,)
+    if window_summary is not None:
+        if not fill_index_mask.all():      # (rows spliced in from upstream_results are masked out of element [0]: here too)
+            window_summary = {k: v[fill_index_mask] for k, v in window_summary.items()}
+        result = result + (window_summary,)
     return result
 
 
