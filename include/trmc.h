@@ -699,6 +699,36 @@ int trmc_window_summary(trmc_plan *plan, int32_t rowset, void *peak_flow, int32_
                         void *peak_depth, int32_t *peak_depth_step, void *peak_velocity, int32_t *peak_velocity_step);
 int trmc_window_summary_tile(int precision, int32_t *rows, int32_t *steps);
 int trmc_window_summary_kernel_ms(const trmc_plan *plan, double *ms_out);
+/*
+ * Courant metrics of the last WINDOW: for every row and step the triple (cn, ck, X) -- Courant number ck * dt / dx, kinematic
+ * celerity and the Muskingum weighting factor the step ended on -- in the order of the reference's output_buf[3:6] and of its
+ * writers' columns (mc_reach.pyx:128-131, nwm_routing/output.py:262-272; compute_parameters.return_courant).  No routing kernel
+ * forms them: one pass (csrc/k_window_courant.inc) recomputes every row-step from what the plan still holds after the window --
+ * the assembled result, the initial state, the staged forcing, the upstream lists -- in the plan's own precision and arithmetic,
+ * so the triple is the one the step itself would have left (trmc_segments at the same inputs, bit for bit).  A gage's stored flow
+ * is the nudged one; the triple is that of the un-nudged step at those inputs.  Reservoir rows of every type and boundary rows
+ * route no Muskingum-Cunge step: (0, 0, 0).
+ *   trmc_window_courant          dst[rows][nsteps / stride][3] in the plan's precision; kept steps stride, 2 stride, ... as in
+ *                                trmc_download_fvd_rowset, and only those are computed.  rowset: -1 = every row in row order,
+ *                                else a registered set (trmc_rowset_create): its rows, in its order.
+ *   trmc_window_courant_summary  per row: the highest cn of the window, the 1-based step it was FIRST reached at (the rule of
+ *                                trmc_window_summary: pk = cn[1]; t = 2..: if (cn[t] > pk) -- the first of equal peaks wins, a NaN
+ *                                never replaces a number, a NaN at step 1 stays) and the number of steps with cn > limit (compared
+ *                                in the plan's precision; a NaN is not counted).  Nothing of size rows x nsteps is written.  Any
+ *                                destination may be NULL (all NULL: TRMC_EINVAL); peak_cn_step needs peak_cn.
+ * Refusals as trmc_window_summary's: TRMC_EINVAL for a NULL plan, an unknown row set, stride < 1; TRMC_ESTATE before any window,
+ * while a window is open, while a stream of windows is in progress, and after trmc_plan_chain_from has overwritten the state the
+ * last window began from; TRMC_EUNSUPPORTED for a plan with lagged rows (trmc_plan_set_lag).  Valid until the next upload or
+ * staging of a forcing.  Synchronous, on the plan's stream.
+ *   trmc_window_courant_tile       rows per block and steps per chunk of the kernel, for a precision (32 / 64).  Host only.
+ *   trmc_window_courant_kernel_ms  device time of the last of the two calls' kernel on this plan, from events around it (copies
+ *                                  to the host not included); TRMC_ESTATE before the first.  Host only.
+ */
+int trmc_window_courant(trmc_plan *plan, int32_t rowset, int stride, void *dst);
+int trmc_window_courant_summary(trmc_plan *plan, int32_t rowset, double limit, void *peak_cn, int32_t *peak_cn_step,
+                                int32_t *steps_over);
+int trmc_window_courant_tile(int precision, int32_t *rows, int32_t *steps);
+int trmc_window_courant_kernel_ms(const trmc_plan *plan, double *ms_out);
 /* on != 0: trmc_upload_forcing turns every NaN of qlat and q0 into 0 on the device, behind the copy.  The reference's reindexed
  * tables hold NaN on waterbody rows (compute.py:1466-1467), which the Muskingum-Cunge rows never read; the drop-in used to screen
  * the caller's frames for them on the host -- 20 ms of a CONUS call.  Default off: values go to the kernels as they are. */

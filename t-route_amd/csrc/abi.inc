@@ -425,6 +425,8 @@ void trmc_plan_destroy(trmc_plan *pl)
     if (pl->ev_gather) (void)hipEventDestroy(pl->ev_gather);
     for (hipEvent_t e : pl->ev_wsum)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : pl->ev_cour)
+        if (e) (void)hipEventDestroy(e);
     for (DevBuf *b : {&pl->lagk, &pl->cblk_ptr, &pl->params, &pl->up_ptr, &pl->up_idx, &pl->up2, &pl->level, &pl->row_of_pos, &pl->pos_of_row, &pl->it_prev, &pl->it_sum, &pl->lag, &pl->d_state, &pl->ticket, &pl->ticket_map, &pl->rank, &pl->dbg, &pl->prio, &pl->cuq_ptr, &pl->cuq_blk, &pl->cuq_head, &pl->cu_index, &pl->cuq_perm, &pl->d_gran, &pl->raw_of_pos, &pl->da_raw, &pl->gage_of_pos,
                       &pl->da_mode, &pl->da_a, &pl->da_w, &pl->da_nudge, &pl->res_of_pos, &pl->res_par, &pl->res_inflow, &pl->res_da,
                       &pl->in_qlat, &pl->in_q0, &pl->in_bfvd, &pl->qlat_tm, &pl->qlat_alt, &pl->tm, &pl->out, &pl->scratch, &pl->gathered, &pl->cls_last, &pl->hot_list, &pl->hot_cnt})
@@ -1503,6 +1505,125 @@ int trmc_window_summary_kernel_ms(const trmc_plan *pl, double *ms_out)
     return 0;
 }
 
+int trmc_window_courant_tile(int precision, int32_t *rows, int32_t *steps)
+{
+    if (precision != 32 && precision != 64) return fail(TRMC_EINVAL, "precision must be 32 or 64");
+    if (rows) *rows = kCourantRows;
+    if (steps) *steps = kCourantSteps;
+    return 0;
+}
+
+static int window_courant_check(trmc_plan *pl, int32_t rowset)
+{
+    if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
+    // the triples are recomputed from the result a window assembles and from its forcing and initial state (k_window_courant): a
+    // stream of days assembles no such result and recycles the buffers day by day
+    if (stream_active(pl))
+        return fail(TRMC_ESTATE, "a stream of windows is in progress: the Courant metrics are recomputed from the result the plan assembles "
+                                 "for a window, which a stream does not fill");
+    if (pl->run.active)
+        return fail(TRMC_ESTATE, "a routing window is in progress: its result is not assembled before trmc_route_end");
+    if (pl->routed_nsteps < 0) return fail(TRMC_ESTATE, "nothing routed yet");
+    if (pl->maxlag > 0)
+        return fail(TRMC_EUNSUPPORTED, "a plan with lagged rows (trmc_plan_set_lag) routes rows of other ranks' trunks at shifted steps: the "
+                                       "Courant metrics of such a window are not built");
+    if (pl->row0_replaced)
+        return fail(TRMC_ESTATE, "trmc_plan_chain_from has replaced the initial state of the plan's last window since it ended");
+    if (rowset < -1 || rowset >= (int32_t)pl->rowsets.size()) return fail(TRMC_EINVAL, "unknown row set");
+    return 0;
+}
+int trmc_window_courant(trmc_plan *pl, int32_t rowset, int stride, void *dst)
+{
+    if (int rc = window_courant_check(pl, rowset)) return rc;
+    if (stride < 1) return fail(TRMC_EINVAL, "stride must be >= 1");
+    const int64_t nrows = rowset < 0 ? pl->nseg : pl->rowset_n[(size_t)rowset];
+    const int32_t nkeep = pl->routed_nsteps / stride;
+    if (pl->nseg == 0 || nrows == 0 || nkeep == 0) return 0;
+    if (!dst) return fail(TRMC_EINVAL, "dst is NULL");
+    if (int rc = use_device(pl)) return rc;
+    const size_t bytes = (size_t)nrows * nkeep * 3 * pl->esz;
+    if (int rc = pl->gathered.ensure(bytes)) return rc; // (the plan's scratch block for gathers of its result)
+    pl->gathered_bytes = 0;
+    for (hipEvent_t &e : pl->ev_cour)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    pl->cour_ms = -1.0;
+    HIP_TRY(hipEventRecord(pl->ev_cour[0], pl->stream));
+    const int rc = by_precision(pl, [&](auto t) -> int {
+        using T = decltype(t);
+        CourantArgs<T> a;
+        window_courant_args<T>(pl, rowset, a);
+        a.stride = stride;
+        a.nkeep = nkeep;
+        a.dst = (T *)pl->gathered.p;
+        window_courant_launch<T, false>(pl, a);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    });
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(pl->ev_cour[1], pl->stream));
+    HIP_TRY(hipMemcpyAsync(dst, pl->gathered.p, bytes, hipMemcpyDeviceToHost, pl->stream));
+    HIP_TRY(hipStreamSynchronize(pl->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, pl->ev_cour[0], pl->ev_cour[1]));
+    pl->cour_ms = ms;
+    return 0;
+}
+
+int trmc_window_courant_summary(trmc_plan *pl, int32_t rowset, double limit, void *peak_cn, int32_t *peak_cn_step, int32_t *steps_over)
+{
+    if (int rc = window_courant_check(pl, rowset)) return rc;
+    if (!peak_cn && !peak_cn_step && !steps_over) return fail(TRMC_EINVAL, "every destination is NULL: nothing to summarise");
+    if (peak_cn_step && !peak_cn) return fail(TRMC_EINVAL, "the step of a peak comes with the peak: its value destination is NULL");
+    const int64_t nrows = rowset < 0 ? pl->nseg : pl->rowset_n[(size_t)rowset];
+    if (pl->nseg == 0 || nrows == 0) return 0;
+    if (pl->routed_nsteps < 1) return fail(TRMC_ESTATE, "the last window had no timesteps");
+    if (int rc = use_device(pl)) return rc;
+    // three columns [nrows] in the plan's scratch block, each on a 256-byte boundary; then to the host
+    void *const host[3] = {peak_cn, peak_cn_step, steps_over};
+    const size_t width[3] = {pl->esz, 4, 4};
+    size_t off[3], total = 0;
+    for (int k = 0; k < 3; ++k) {
+        off[k] = total;
+        if (host[k]) total += ((size_t)nrows * width[k] + 255) / 256 * 256;
+    }
+    if (int rc = pl->scratch.ensure(total)) return rc;
+    for (hipEvent_t &e : pl->ev_cour)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    pl->cour_ms = -1.0;
+    HIP_TRY(hipEventRecord(pl->ev_cour[0], pl->stream));
+    const int rc = by_precision(pl, [&](auto t) -> int {
+        using T = decltype(t);
+        char *const s = (char *)pl->scratch.p;
+        CourantArgs<T> a;
+        window_courant_args<T>(pl, rowset, a);
+        a.peak_cn = host[0] ? (T *)(s + off[0]) : nullptr;
+        a.peak_step = host[1] ? (int32_t *)(s + off[1]) : nullptr;
+        a.steps_over = host[2] ? (int32_t *)(s + off[2]) : nullptr;
+        a.limit = (T)limit;
+        window_courant_launch<T, true>(pl, a);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    });
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(pl->ev_cour[1], pl->stream));
+    for (int k = 0; k < 3; ++k)
+        if (host[k])
+            HIP_TRY(hipMemcpyAsync(host[k], (char *)pl->scratch.p + off[k], (size_t)nrows * width[k], hipMemcpyDeviceToHost, pl->stream));
+    HIP_TRY(hipStreamSynchronize(pl->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, pl->ev_cour[0], pl->ev_cour[1]));
+    pl->cour_ms = ms;
+    return 0;
+}
+
+int trmc_window_courant_kernel_ms(const trmc_plan *pl, double *ms_out)
+{
+    if (!pl || !ms_out) return fail(TRMC_EINVAL, "plan/ms_out is NULL");
+    if (pl->cour_ms < 0) return fail(TRMC_ESTATE, "no Courant metrics have been formed on this plan");
+    *ms_out = pl->cour_ms;
+    return 0;
+}
+
 int trmc_plan_set_nan_is_zero(trmc_plan *pl, int on)
 {
     if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
@@ -1852,6 +1973,7 @@ int trmc_plan_chain_from(trmc_plan *dst, trmc_plan *src)
         || dst->topo.row_of_pos != src->topo.row_of_pos)
         return fail(TRMC_EINVAL, "the two plans must hold the same network in the same order (same inputs, same cost hint)");
     if (int rc = use_device(dst)) return rc;
+    dst->row0_replaced = true; // (what trmc_window_courant reads as the last window's initial state; the next window clears it)
     return by_precision(dst, [&](auto t) { return chain_from_t<decltype(t)>(dst, src, dst->staged_nsteps); });
 }
 

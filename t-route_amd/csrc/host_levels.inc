@@ -385,6 +385,7 @@ template <class T> int route_begin_t(trmc_plan *pl, int nsteps, int qts, int sho
     }
     pl->chain_staged = false;
     pl->q0_staged = false; // (consumed: the next staging gathers this window's final state)
+    pl->row0_replaced = false;
     RouteRun &r = pl->run;
     r = RouteRun{};
     r.active = true;

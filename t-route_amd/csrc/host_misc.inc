@@ -226,3 +226,56 @@ int check_device(int device)
     return 0;
 }
 
+// trmc_window_courant / trmc_window_courant_summary (abi.inc): k_window_courant's arguments up to its destinations ...
+template <class T> int window_courant_args(trmc_plan *pl, int32_t rowset, CourantArgs<T> &a)
+{
+    a.par = (const T *)pl->params.p;
+    a.nseg_pad = pl->nseg_pad;
+    a.up_ptr = (const int32_t *)pl->up_ptr.p;
+    a.up_idx = (const int32_t *)pl->up_idx.p;
+    a.row_of_pos = (const int32_t *)pl->row_of_pos.p;
+    a.pos_of_row = (const int32_t *)pl->pos_of_row.p;
+    a.res_of_pos = pl->nres > 0 ? (const int32_t *)pl->res_of_pos.p : nullptr;
+    const bool raw = pl->ngage > 0 && pl->nraw > 0 && !pl->run.short_ts;
+    a.raw_of_pos = raw ? (const int32_t *)pl->raw_of_pos.p : nullptr;
+    a.da_raw = raw ? (const T *)pl->da_raw.p : nullptr;
+    a.qlat_tm = (const T *)pl->qlat_tm.p;
+    a.out = (const T *)pl->out.p;
+    if (pl->flow) { // the dataflow engine keeps no time row 0: the state the window began from is still the staged one
+        a.s0q = (const T *)pl->in_q0.p;
+        a.s0d = a.s0q + 2;
+        a.s0_stride = 3;
+        a.s0_by_row = 1;
+    } else {        // the level engine: time row 0 of the flow and depth planes, which no step of a window writes
+        a.s0q = (const T *)pl->tm.p;
+        a.s0d = a.s0q + 2 * (size_t)(pl->routed_nsteps + 1) * (size_t)pl->nseg_pad;
+        a.s0_stride = 1;
+        a.s0_by_row = 0;
+    }
+    a.rowset_pos = rowset < 0 ? nullptr : (const int32_t *)pl->rowsets[(size_t)rowset].p;
+    a.nrows = rowset < 0 ? pl->nseg : pl->rowset_n[(size_t)rowset];
+    a.nboundary = (int32_t)pl->topo.nboundary;
+    a.nsteps = pl->routed_nsteps;
+    a.qts = pl->run.qts;
+    a.short_ts = pl->run.short_ts;
+    a.stride = 1;
+    a.nkeep = pl->routed_nsteps;
+    a.sane = pl->params_sane ? 1 : 0;
+    a.dst = nullptr;
+    a.peak_cn = nullptr;
+    a.peak_step = a.steps_over = nullptr;
+    a.limit = T(0);
+    return 0;
+}
+// ... and its launch in the plan's arithmetic
+template <class T, bool SUMMARY> void window_courant_launch(trmc_plan *pl, const CourantArgs<T> &a)
+{
+    const dim3 grid((unsigned)((a.nrows + kCourantRows - 1) / kCourantRows)), block(kCourantRows * 64);
+    if constexpr (std::is_same<T, float>::value) {
+        if (pl->opt.tol) {
+            hipLaunchKernelGGL((k_window_courant<float, true, SUMMARY>), grid, block, 0, pl->stream, a);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_window_courant<T, false, SUMMARY>), grid, block, 0, pl->stream, a);
+}

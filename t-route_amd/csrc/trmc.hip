@@ -75,6 +75,7 @@ namespace {
 #include "kernels_levels.inc"
 #include "kernels_flow.inc"
 #include "k_window_summary.inc"
+#include "k_window_courant.inc"
 // ---------------------------------------------------------------- plan
 struct DevBuf {
     void *p = nullptr;
@@ -258,6 +259,9 @@ struct trmc_plan {
     bool gather_pending = false;
     hipEvent_t ev_wsum[2] = {nullptr, nullptr}; // around the last trmc_window_summary's kernel (trmc_window_summary_kernel_ms)
     double wsum_ms = -1.0;
+    hipEvent_t ev_cour[2] = {nullptr, nullptr}; // ... and around the last trmc_window_courant / _summary's (trmc_window_courant_kernel_ms)
+    double cour_ms = -1.0;
+    bool row0_replaced = false;          // trmc_plan_chain_from has overwritten time row 0 -- the last window's initial state -- since it ended
     // trmc_plan_clone: a second set of WINDOW buffers on the static data (topology, parameters) of `parent`
     trmc_plan *parent = nullptr;
     int32_t clones = 0;                  // live clones of this plan

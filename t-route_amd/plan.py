@@ -697,6 +697,44 @@ class RoutingPlan:
         _lib.check(_lib.lib().trmc_window_summary_kernel_ms(self._h, C.byref(ms)))
         return ms.value
 
+    @staticmethod
+    def window_courant_tile(precision=32):
+        """(rows, steps) of the Courant kernel's tile for a precision (trmc_window_courant_tile)"""
+        rows, steps = C.c_int32(0), C.c_int32(0)
+        _lib.check(_lib.lib().trmc_window_courant_tile(int(precision), C.byref(rows), C.byref(steps)))
+        return rows.value, steps.value
+
+    def window_courant(self, stride=1, rowset=None):
+        """Courant metrics of the last window [rows, nsteps // stride, 3] = (cn, ck, X) per kept step (the steps stride, 2 stride,
+        ... counted from 1, as ``download_fvd``), recomputed on the device from the window's result, state and forcing in the
+        plan's own arithmetic (trmc_window_courant).  Reservoir and boundary rows are zeros.  rowset (``rowset(rows)``): the rows
+        of that set, in its order."""
+        stride = int(stride)
+        if stride < 1:
+            raise ValueError("stride must be >= 1")
+        n = self.nseg if rowset is None else self._rowset_n[rowset]
+        out = _lib.result_empty((n, (self._nsteps or 0) // stride, 3), self.dtype)
+        # (an empty block is still asked for: the call's refusals -- nothing routed, a stream in progress -- hold for it too)
+        _lib.check(_lib.lib().trmc_window_courant(self._h, -1 if rowset is None else int(rowset), stride, _lib.ptr(out) if out.size else None))
+        return out
+
+    def window_courant_summary(self, limit=1.0, rowset=None):
+        """Per row of the last window: ``peak_cn`` (the highest Courant number, plan dtype), ``peak_cn_step`` (the 1-based step it
+        was first reached at, int32) and ``steps_over`` (steps with cn > limit, int32), reduced on the device over every step
+        (trmc_window_courant_summary).  Where cn > 1, dt is too long for that reach's dx."""
+        n = self.nseg if rowset is None else self._rowset_n[rowset]
+        out = {"peak_cn": _lib.result_empty((n,), self.dtype), "peak_cn_step": _lib.result_empty((n,), np.int32),
+               "steps_over": _lib.result_empty((n,), np.int32)}
+        _lib.check(_lib.lib().trmc_window_courant_summary(self._h, -1 if rowset is None else int(rowset), float(limit),
+                                                          *(_lib.ptr(v) for v in out.values())))
+        return out
+
+    def window_courant_kernel_ms(self):
+        """device time (ms) of the last ``window_courant`` / ``window_courant_summary``'s kernel (trmc_window_courant_kernel_ms)"""
+        ms = C.c_double(0)
+        _lib.check(_lib.lib().trmc_window_courant_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def set_nan_is_zero(self, on=True):
         """uploads of forcing and state: NaN -> 0 on the device (trmc_plan_set_nan_is_zero)"""
         _lib.check(_lib.lib().trmc_plan_set_nan_is_zero(self._h, int(bool(on))))

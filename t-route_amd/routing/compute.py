@@ -344,8 +344,10 @@ def compute_nhd_routing_v02(
     if grouped:                                  # (compute_network_structured has handed its rows back in that order)
         ids_o, fvd_o, up_o = rids.astype(np.intp), fvd, upstream
         sum_o = r[-1] if summary is not None else None
+        cou_o = r[2]
     else:
         ids_o, fvd_o = rids[order].astype(np.intp), fvd[order]
+        cou_o = r[2][order] if return_courant else 0
         sum_o = {k: v[order] for k, v in r[-1].items()} if summary is not None else None
         # (the upstream-inflow series are zero except on waterbody rows, mc_reach.pyx:487,:710: without waterbodies any order of
         # an all-zero block is the block itself -- 3.1 GB for a CONUS day that need not be permuted)
@@ -367,7 +369,7 @@ def compute_nhd_routing_v02(
         if ngage:
             gk = np.flatnonzero((gage_row >= 0) & (gage_owner == k))                          # this network's gages
             gt = (np.asarray(gage_ids)[gk], np.asarray(lastobs_times)[gk], np.asarray(lastobs_values)[gk])
-        results.append((ids_o[lo:hi], fvd_o[lo:hi], 0, gt if ngage else no_gage, state_of(k, r[4], e5), state_of(k, r[5], e5),
+        results.append((ids_o[lo:hi], fvd_o[lo:hi], cou_o[lo:hi] if return_courant else 0, gt if ngage else no_gage, state_of(k, r[4], e5), state_of(k, r[5], e5),
                         up_o[lo:hi], state_of(k, r[7], e3), nudge[gk] if ngage else no_nudge, e4)
                        + (({name: v[lo:hi] for name, v in sum_o.items()},) if sum_o is not None else ()))
     return results, subnetwork_list

@@ -404,7 +404,9 @@ def compute_network_structured(
     step of the window is appended to the returned tuple, behind the stats dict when
     ``return_stats`` is set; its rows are the rows of element [0], in that order; it
     combines with ``output_stride``: the hourly block for the files, the peaks from all
-    steps).
+    steps).  ``return_courant=True``: element [2] -- the literal 0 otherwise, as in the
+    reference's V02 loop -- is an array [rows, kept steps * 3] of (cn, ck, X) per step
+    (``RoutingPlan.window_courant``): the rows, the kept steps and the dtype of element [1].
     """
     if summary is not None:
         summary = (summary,) if isinstance(summary, str) else tuple(summary)
@@ -632,6 +634,9 @@ def compute_network_structured(
             oset = hit[1]
         fvd = plan.download_fvd(stride, rowset=oset)
         window_summary = plan.window_summary(summary, rowset=oset) if summary is not None else None
+        # (compute_parameters.return_courant: the reference's V02 loop takes the flag and returns the literal 0, mc_reach.pyx:737-740,
+        # :814; here the triples its kernel would have filled, :128-131, recomputed on the device from the window just routed)
+        courant = plan.window_courant(stride, rowset=oset) if return_courant else None
         if nudging is not None:
             nudge[nudging[4], 1:] = plan.download_nudge()
         res_inflow = plan.download_reservoir_inflow() if res_rows else None
@@ -642,6 +647,10 @@ def compute_network_structured(
     flowveldepth = fvd.reshape(nseg, (nsteps // stride) * 3).astype(out_dtype, copy=False)
     if not fill_index_mask.all():          # (no copy of the result when no off-network upstream rows were spliced in)
         flowveldepth = flowveldepth[fill_index_mask]
+    if courant is not None:                # (cn, ck, X) per kept step: the rows, steps and dtype of element [1]
+        courant = courant.reshape(nseg, (nsteps // stride) * 3).astype(out_dtype, copy=False)
+        if not fill_index_mask.all():
+            courant = courant[fill_index_mask]
     upstream = np.zeros((nseg, nsteps), dtype="float32")  # np.empty in the reference (:487), reservoir rows filled (:710)
     if res_rows:
         upstream[res_rows] = res_inflow
@@ -671,7 +680,7 @@ def compute_network_structured(
     result = (
         np.asarray(data_idx, dtype=np.intp)[fill_index_mask] if result_order is None else np.asarray(data_idx, dtype=np.intp)[result_order],
         flowveldepth,
-        0,
+        0 if courant is None else courant,
         (
             np.asarray([data_idx[p] for p in usgs_positions]),
             (lt_fin if gages_size else np.full(0, np.nan, dtype="float32")),
