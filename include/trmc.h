@@ -848,7 +848,8 @@ int trmc_plan_chain_from(trmc_plan *receiver, trmc_plan *source);
  * narrow levels finish.  The clone inherits the plan's options (trmc_plan_options) and the lag of its rows
  * (trmc_plan_set_lag: set it BEFORE cloning); reservoir / nudging tables, row sets and the cost collection are per clone
  * (set them on each).  Destroy order is free: the shared memory goes with the last user, the window buffers of a destroyed
- * original at once.
+ * original at once -- and with them everything else of it: a destroyed handle, of an original or of a clone, is simply
+ * invalid from then on, for trmc_plan_clone as for every other call (clone from a plan that is alive).
  */
 int trmc_plan_clone(trmc_plan *plan, trmc_plan **out);
 

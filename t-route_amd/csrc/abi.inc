@@ -1,6 +1,5 @@
 // abi.inc -- included by trmc.hip inside extern "C": the entry points of include/trmc.h (the stream of windows: stream.inc).
 
-static void stream_release(trmc_plan *pl); // (stream.inc)
 static bool stream_active(const trmc_plan *pl);
 
 const char *trmc_last_error(void) { return g_err.c_str(); }
@@ -178,6 +177,28 @@ int trmc_plan_create_ex(int64_t nseg, const int64_t *up_ptr, const int64_t *up_i
     return trmc_plan_create_opt(nseg, up_ptr, up_idx, params, boundary, cost_hint, precision, device, flags, nullptr, out);
 }
 
+// the streams and events every plan has from the start (the others are made where they are first needed)
+static int plan_streams(trmc_plan *pl)
+{
+    HIP_TRY(hipSetDevice(pl->device));
+    // step launches on a high-priority stream, the overlapped transpose on a low-priority one:
+    // the transpose should fill gaps, not displace the VALU-bound step kernel
+    int prio_lo = 0, prio_hi = 0;
+    HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+    if (int rc = pl->stream.ensure(hipStreamNonBlocking, prio_hi)) return rc;
+    if (int rc = pl->stream2.ensure(hipStreamNonBlocking, prio_lo)) return rc;
+    if (int rc = pl->ev_emit.ensure(false)) return rc;
+    if (pl->flow) {
+        if (int rc = pl->fstream.ensure(hipStreamNonBlocking, prio_hi)) return rc;
+        for (DevEvent &e : pl->ev_chunk)
+            if (int rc = e.ensure(false)) return rc;
+        if (int rc = pl->ev_ctl.ensure(false)) return rc;
+    }
+    for (DevEvent &e : pl->ev)
+        if (int rc = e.ensure(true)) return rc;
+    return 0;
+}
+
 int trmc_plan_create_opt(int64_t nseg, const int64_t *up_ptr, const int64_t *up_idx, const float *params,
                          const uint8_t *boundary, const uint8_t *cost_hint, int precision, int device, int flags,
                          const trmc_plan_options *options, trmc_plan **out)
@@ -204,6 +225,7 @@ int trmc_plan_create_opt(int64_t nseg, const int64_t *up_ptr, const int64_t *up_
 
     trmc_plan *pl = new (std::nothrow) trmc_plan();
     if (!pl) return fail(TRMC_ENOMEM, "out of host memory");
+    pl->sh = std::make_shared<PlanShared>();
     if (engine == TRMC_ENGINE_AUTO) {
         if (precision != 32)
             engine = TRMC_ENGINE_LEVELS;
@@ -280,7 +302,7 @@ int trmc_plan_create_opt(int64_t nseg, const int64_t *up_ptr, const int64_t *up_
     // the first tickets: topology.hpp, stem_min_rows)
     int32_t stem_min_rows = 0;
     if (pl->flow && (flags & TRMC_PLAN_FULL_TS)) stem_min_rows = o.stem_min_rows < 0 ? 0 : (o.stem_min_rows > 0 ? o.stem_min_rows : 1024);
-    const int trc = trmc::build_topology(nseg, up_ptr, up_idx, boundary, pl->topo, err, cost_hint, pl->flow ? kFlowBlock : 0, tiers,
+    const int trc = trmc::build_topology(nseg, up_ptr, up_idx, boundary, pl->sh->topo, err, cost_hint, pl->flow ? kFlowBlock : 0, tiers,
                                          (tiers && !pl->flow) ? kWideMaxLevels : 0, wide_min_rows, wide_max_levels, stem_min_rows,
                                          mid_min_rows, mid_max_levels, cluster_rows, pl->opt.cluster_late_lag, kCtileBlock);
     if (trc) {
@@ -294,7 +316,7 @@ int trmc_plan_create_opt(int64_t nseg, const int64_t *up_ptr, const int64_t *up_
     pl->nseg = nseg;
     pl->nseg_pad = (nseg + 63) / 64 * 64;
     if (pl->nseg_pad == 0) pl->nseg_pad = 64;
-    pl->nrouted = nseg - pl->topo.nboundary;
+    pl->nrouted = nseg - pl->sh->topo.nboundary;
     pl->dt_uniform = true;
     pl->dt = nseg ? params[TRMC_P_DT] : 0.0;
     for (int64_t r = 1; r < nseg; ++r)
@@ -307,36 +329,21 @@ int trmc_plan_create_opt(int64_t nseg, const int64_t *up_ptr, const int64_t *up_
         trmc_plan_destroy(pl);
         return rc;
     };
-    {
-        hipError_t e = hipSetDevice(device);
-        // step launches on a high-priority stream, the overlapped transpose on a low-priority one:
-        // the transpose should fill gaps, not displace the VALU-bound step kernel
-        int prio_lo = 0, prio_hi = 0;
-        if (e == hipSuccess) e = hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-        if (e == hipSuccess) e = hipStreamCreateWithPriority(&pl->stream, hipStreamNonBlocking, prio_hi);
-        if (e == hipSuccess) e = hipStreamCreateWithPriority(&pl->stream2, hipStreamNonBlocking, prio_lo);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&pl->ev_emit, hipEventDisableTiming);
-        if (e == hipSuccess && pl->flow) {
-            e = hipStreamCreateWithPriority(&pl->fstream, hipStreamNonBlocking, prio_hi);
-            for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&pl->ev_chunk[i], hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&pl->ev_ctl, hipEventDisableTiming);
-        }
-        for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreate(&pl->ev[i]);
-        if (e != hipSuccess) return bail(fail(TRMC_EHIP, std::string("stream/event setup: ") + hipGetErrorString(e)));
-    }
-    int rc = by_precision(pl, [&](auto t) { return upload_params<decltype(t)>(pl, params); });
+    int rc = plan_streams(pl);
+    if (rc) return bail(rc);
+    rc = by_precision(pl, [&](auto t) { return upload_params<decltype(t)>(pl, params); });
     if (rc) return bail(rc);
     std::vector<int32_t> level_plan((size_t)pl->nseg_pad, 0);
-    for (int64_t p = 0; p < nseg; ++p) level_plan[p] = pl->topo.level_of_row[pl->topo.row_of_pos[p]];
-    if ((rc = upload_i32(pl->level, level_plan, 1))) return bail(rc);
-    if (pl->topo.ncl > 0) {
-        std::vector<int32_t> lagk(pl->topo.lagk_of_pos);
+    for (int64_t p = 0; p < nseg; ++p) level_plan[p] = pl->sh->topo.level_of_row[pl->sh->topo.row_of_pos[p]];
+    if ((rc = upload_i32(pl->sh->level, level_plan, 1))) return bail(rc);
+    if (pl->sh->topo.ncl > 0) {
+        std::vector<int32_t> lagk(pl->sh->topo.lagk_of_pos);
         lagk.resize((size_t)pl->nseg_pad, 0);
-        if ((rc = upload_i32(pl->lagk, lagk, 1))) return bail(rc);
-        if ((rc = upload_i32(pl->cblk_ptr, pl->topo.cblk_ptr, 1))) return bail(rc);
+        if ((rc = upload_i32(pl->sh->lagk, lagk, 1))) return bail(rc);
+        if ((rc = upload_i32(pl->sh->cblk_ptr, pl->sh->topo.cblk_ptr, 1))) return bail(rc);
     }
-    if ((rc = upload_i32(pl->up_ptr, pl->topo.up_ptr, 1))) return bail(rc);
-    if ((rc = upload_i32(pl->up_idx, pl->topo.up_idx, 1))) return bail(rc);
+    if ((rc = upload_i32(pl->sh->up_ptr, pl->sh->topo.up_ptr, 1))) return bail(rc);
+    if ((rc = upload_i32(pl->sh->up_idx, pl->sh->topo.up_idx, 1))) return bail(rc);
     {
         if (nseg >= (int64_t)1 << 30) return bail(fail(TRMC_EINVAL, "more than 2**30 segments in one plan"));
         // (the step kernels address a column with a 32-bit BYTE offset: position * element size)
@@ -344,45 +351,45 @@ int trmc_plan_create_opt(int64_t nseg, const int64_t *up_ptr, const int64_t *up_
             return bail(fail(TRMC_EINVAL, "too many segments for one plan at this precision (column size reaches 4 GiB)"));
         std::vector<int32_t> up2((size_t)pl->nseg_pad * 2, -1);
         for (int64_t p = 0; p < nseg; ++p) {
-            const int32_t k0 = pl->topo.up_ptr[p], k1 = pl->topo.up_ptr[p + 1];
-            if (k1 - k0 >= 1) up2[2 * p] = pl->topo.up_idx[k0];
-            if (k1 - k0 >= 2) up2[2 * p + 1] = pl->topo.up_idx[k0 + 1] | (k1 - k0 > 2 ? 0x40000000 : 0);
+            const int32_t k0 = pl->sh->topo.up_ptr[p], k1 = pl->sh->topo.up_ptr[p + 1];
+            if (k1 - k0 >= 1) up2[2 * p] = pl->sh->topo.up_idx[k0];
+            if (k1 - k0 >= 2) up2[2 * p + 1] = pl->sh->topo.up_idx[k0 + 1] | (k1 - k0 > 2 ? 0x40000000 : 0);
         }
-        if ((rc = upload_i32(pl->up2, up2, 2))) return bail(rc);
+        if ((rc = upload_i32(pl->sh->up2, up2, 2))) return bail(rc);
     }
-    if (pl->flow && (rc = upload_i32(pl->rank, pl->topo.rank_of_pos, 1))) return bail(rc);
+    if (pl->flow && (rc = upload_i32(pl->sh->rank, pl->sh->topo.rank_of_pos, 1))) return bail(rc);
     if (pl->flow) {
-        if ((rc = pl->prio.ensure(pl->topo.prio_of_wave.size() + 1))) return bail(rc);
-        if (!pl->topo.prio_of_wave.empty()
-            && hipMemcpy(pl->prio.p, pl->topo.prio_of_wave.data(), pl->topo.prio_of_wave.size(), hipMemcpyHostToDevice) != hipSuccess)
+        if ((rc = pl->sh->prio.ensure(pl->sh->topo.prio_of_wave.size() + 1))) return bail(rc);
+        if (!pl->sh->topo.prio_of_wave.empty()
+            && hipMemcpy(pl->sh->prio.p, pl->sh->topo.prio_of_wave.data(), pl->sh->topo.prio_of_wave.size(), hipMemcpyHostToDevice) != hipSuccess)
             return bail(fail(TRMC_EHIP, "uploading the wavefront priorities failed"));
         if ((rc = flow_place_blocks(pl))) return bail(rc);
         // The stems' blocks take the first tickets and wait IN PLACE for their inflows: nothing deadlocks as long as the device
         // holds more workgroups of the kernel at once than there are such blocks -- the others then still find slots.  Asked
         // of the runtime for THIS device (occupancy x compute units; a smaller part, a masked one); a plan whose stems would
         // take more than half of the slots routes in the plain ticket order instead.
-        if (!pl->topo.early_blocks.empty()) {
+        if (!pl->sh->topo.early_blocks.empty()) {
             int per_cu = 0, ncu = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_mc_flow<false, false>, kFlowBlock, 0) != hipSuccess) per_cu = 0;
             (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, pl->device);
-            if ((int64_t)pl->topo.early_blocks.size() * 2 > (int64_t)per_cu * ncu) pl->topo.early_blocks.clear();
+            if ((int64_t)pl->sh->topo.early_blocks.size() * 2 > (int64_t)per_cu * ncu) pl->sh->topo.early_blocks.clear();
         }
-        if (!pl->topo.early_blocks.empty()) { // ticket -> block: the stems' blocks, then everybody else in order
-            const int32_t nb = pl->topo.nblocks;
+        if (!pl->sh->topo.early_blocks.empty()) { // ticket -> block: the stems' blocks, then everybody else in order
+            const int32_t nb = pl->sh->topo.nblocks;
             std::vector<int32_t> map;
             map.reserve((size_t)nb);
             std::vector<uint8_t> early((size_t)nb, 0);
-            for (const int32_t b : pl->topo.early_blocks) {
+            for (const int32_t b : pl->sh->topo.early_blocks) {
                 early[(size_t)b] = 1;
                 map.push_back(b);
             }
             for (int32_t b = 0; b < nb; ++b)
                 if (!early[(size_t)b]) map.push_back(b);
-            if ((rc = upload_i32(pl->ticket_map, map, 1))) return bail(rc);
+            if ((rc = upload_i32(pl->sh->ticket_map, map, 1))) return bail(rc);
         }
     }
-    if ((rc = upload_i32(pl->row_of_pos, pl->topo.row_of_pos, 1))) return bail(rc);
-    if ((rc = upload_i32(pl->pos_of_row, pl->topo.pos_of_row, 1))) return bail(rc);
+    if ((rc = upload_i32(pl->sh->row_of_pos, pl->sh->topo.row_of_pos, 1))) return bail(rc);
+    if ((rc = upload_i32(pl->sh->pos_of_row, pl->sh->topo.pos_of_row, 1))) return bail(rc);
     if ((rc = pl->it_prev.ensure((size_t)pl->nseg_pad))) return bail(rc);
     *out = pl;
     return 0;
@@ -391,71 +398,8 @@ int trmc_plan_create_opt(int64_t nseg, const int64_t *up_ptr, const int64_t *up_
 void trmc_plan_destroy(trmc_plan *pl)
 {
     if (!pl) return;
-    if (pl->clones > 0) {
-        // its clones still use its STATIC buffers (topology, parameter columns, placement tables, the lag table): those go with
-        // the last of them.  Everything else -- the window buffers, gigabytes of planes and results -- is freed now (hipFree
-        // waits for the device); the handle is dead for the caller from here on.
-        if (!pl->zombie) {
-            (void)hipSetDevice(pl->device);
-            for (DevBuf &b : pl->rowsets) b.release();
-            pl->rowsets.clear();
-            for (DevBuf *b : {&pl->dec, &pl->fetch_hyd, &pl->fetch_q0, &pl->fetch_fvd, &pl->it_prev, &pl->it_sum, &pl->d_state, &pl->ticket, &pl->dbg, &pl->cuq_head, &pl->d_gran,
-                              &pl->raw_of_pos, &pl->da_raw, &pl->gage_of_pos, &pl->da_mode, &pl->da_a, &pl->da_w, &pl->da_nudge, &pl->res_of_pos,
-                              &pl->res_par, &pl->res_inflow, &pl->res_da, &pl->in_qlat, &pl->in_q0, &pl->in_bfvd, &pl->qlat_tm, &pl->qlat_alt, &pl->tm, &pl->out, &pl->scratch,
-                              &pl->gathered, &pl->cls_last, &pl->hot_list, &pl->hot_cnt})
-                b->release();
-        }
-        pl->zombie = true;
-        return;
-    }
-    trmc_plan *const parent = pl->parent;
     (void)hipSetDevice(pl->device);
-    stream_release(pl);
-    if (pl->ev_forcing) (void)hipEventDestroy(pl->ev_forcing);
-    for (DevBuf &b : pl->rowsets) b.release();
-    pl->fetch_hyd.release();
-    pl->fetch_q0.release();
-    pl->fetch_fvd.release();
-    pl->dec.release();
-    if (pl->ev_dec) (void)hipEventDestroy(pl->ev_dec);
-    if (pl->cstream) (void)hipStreamDestroy(pl->cstream);
-    if (pl->hstream) (void)hipStreamDestroy(pl->hstream);
-    if (pl->ev_fetch_ready) (void)hipEventDestroy(pl->ev_fetch_ready);
-    if (pl->ev_fetch_done) (void)hipEventDestroy(pl->ev_fetch_done);
-    if (pl->ev_gather) (void)hipEventDestroy(pl->ev_gather);
-    for (hipEvent_t e : pl->ev_wsum)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : pl->ev_cour)
-        if (e) (void)hipEventDestroy(e);
-    for (DevBuf *b : {&pl->lagk, &pl->cblk_ptr, &pl->params, &pl->up_ptr, &pl->up_idx, &pl->up2, &pl->level, &pl->row_of_pos, &pl->pos_of_row, &pl->it_prev, &pl->it_sum, &pl->lag, &pl->d_state, &pl->ticket, &pl->ticket_map, &pl->rank, &pl->dbg, &pl->prio, &pl->cuq_ptr, &pl->cuq_blk, &pl->cuq_head, &pl->cu_index, &pl->cuq_perm, &pl->d_gran, &pl->raw_of_pos, &pl->da_raw, &pl->gage_of_pos,
-                      &pl->da_mode, &pl->da_a, &pl->da_w, &pl->da_nudge, &pl->res_of_pos, &pl->res_par, &pl->res_inflow, &pl->res_da,
-                      &pl->in_qlat, &pl->in_q0, &pl->in_bfvd, &pl->qlat_tm, &pl->qlat_alt, &pl->tm, &pl->out, &pl->scratch, &pl->gathered, &pl->cls_last, &pl->hot_list, &pl->hot_cnt})
-        b->release();
-    for (auto &e : pl->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &e : pl->tile_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (pl->ev_emit) (void)hipEventDestroy(pl->ev_emit);
-    if (pl->stream2) (void)hipStreamDestroy(pl->stream2);
-    for (hipEvent_t e : pl->ev_chain)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : pl->ev_released)
-        if (e) (void)hipEventDestroy(e);
-    if (pl->wstream) (void)hipStreamDestroy(pl->wstream);
-    for (auto *v : {&pl->wide_t0, &pl->wide_t1})
-        for (auto &e : *v)
-            if (e) (void)hipEventDestroy(e);
-    if (pl->ev_tail) (void)hipEventDestroy(pl->ev_tail);
-    if (pl->fstream) (void)hipStreamDestroy(pl->fstream);
-    for (auto &e : pl->ev_chunk)
-        if (e) (void)hipEventDestroy(e);
-    if (pl->ev_ctl) (void)hipEventDestroy(pl->ev_ctl);
-    if (pl->stream) (void)hipStreamDestroy(pl->stream);
-    delete pl;
-    if (parent && --parent->clones == 0 && parent->zombie) {
-        parent->zombie = false;
-        trmc_plan_destroy(parent);
-    }
+    delete pl; // (the members release themselves, in the order the head of trmc_plan describes)
 }
 
 static int final_state_into(trmc_plan *pl, void *dst, int32_t nsteps_of_window = -1);
@@ -466,15 +410,12 @@ int trmc_plan_clone(trmc_plan *src, trmc_plan **out)
     if (!out) return fail(TRMC_EINVAL, "out is NULL");
     *out = nullptr;
     if (!src) return fail(TRMC_EINVAL, "plan is NULL");
-    if (src->parent) src = src->parent; // (a clone of a clone shares the same original)
-    if (src->zombie) return fail(TRMC_ESTATE, "the plan has been destroyed");
     if (int rc = use_device(src)) return rc;
     trmc_plan *pl = new (std::nothrow) trmc_plan();
     if (!pl) return fail(TRMC_ENOMEM, "out of host memory");
     pl->device = src->device;
     pl->precision = src->precision;
     pl->esz = src->esz;
-    pl->topo = src->topo;
     pl->nseg = src->nseg;
     pl->nseg_pad = src->nseg_pad;
     pl->nrouted = src->nrouted;
@@ -486,48 +427,18 @@ int trmc_plan_clone(trmc_plan *src, trmc_plan **out)
     pl->watchdog_ticks = src->watchdog_ticks;
     pl->opt = src->opt;
     pl->ncuq = src->ncuq;
-    pl->parent = src;
-    ++src->clones;
+    // static data: the original's (plan order, parameters and constants, the dataflow engine's placement tables), shared with
+    // it and with every other clone of it -- a clone of a clone holds the same block
+    pl->sh = src->sh;
+    pl->is_clone = true;
     auto bail = [&](int rc) {
         trmc_plan_destroy(pl);
         return rc;
     };
-    {
-        hipError_t e = hipSuccess;
-        int prio_lo = 0, prio_hi = 0;
-        e = hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-        if (e == hipSuccess) e = hipStreamCreateWithPriority(&pl->stream, hipStreamNonBlocking, prio_hi);
-        if (e == hipSuccess) e = hipStreamCreateWithPriority(&pl->stream2, hipStreamNonBlocking, prio_lo);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&pl->ev_emit, hipEventDisableTiming);
-        if (e == hipSuccess && pl->flow) {
-            e = hipStreamCreateWithPriority(&pl->fstream, hipStreamNonBlocking, prio_hi);
-            for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&pl->ev_chunk[i], hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&pl->ev_ctl, hipEventDisableTiming);
-        }
-        for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreate(&pl->ev[i]);
-        if (e != hipSuccess) return bail(fail(TRMC_EHIP, std::string("stream/event setup: ") + hipGetErrorString(e)));
-    }
-    // static data: the original's buffers (plan order, parameters and constants, the dataflow engine's placement tables)
-    pl->params.borrow(src->params);
-    pl->up_ptr.borrow(src->up_ptr);
-    pl->up_idx.borrow(src->up_idx);
-    pl->up2.borrow(src->up2);
-    pl->level.borrow(src->level);
-    pl->lagk.borrow(src->lagk);
-    pl->cblk_ptr.borrow(src->cblk_ptr);
-    pl->row_of_pos.borrow(src->row_of_pos);
-    pl->pos_of_row.borrow(src->pos_of_row);
-    pl->rank.borrow(src->rank);
-    pl->prio.borrow(src->prio);
-    pl->ticket_map.borrow(src->ticket_map);
-    pl->cuq_ptr.borrow(src->cuq_ptr);
-    pl->cuq_blk.borrow(src->cuq_blk);
-    pl->cu_index.borrow(src->cu_index);
-    pl->cuq_perm.borrow(src->cuq_perm);
+    if (int rc = plan_streams(pl)) return bail(rc);
     // the lag of its rows (trmc_plan_set_lag: the trunk of a cut basin riding behind its owner's sub-basins) is part of how
     // the plan routes: the clone routes the same way (row sets and the cost collection are per plan and start empty)
     if (src->maxlag > 0) {
-        pl->lag.borrow(src->lag);
         pl->lag_of_row = src->lag_of_row;
         pl->maxlag = src->maxlag;
     }
@@ -588,10 +499,10 @@ int trmc_stage_forcing(trmc_plan *pl, int nsteps, const void *qlat, int64_t nq)
         const dim3 grid((n + 63) / 64, (unsigned)((nq + 31) / 32));
         if (pl->precision == 32)
             hipLaunchKernelGGL((k_prep_qlat<float>), grid, dim3(kBlock), 0, pl->hstream, (const float *)pl->in_qlat.p,
-                               (const int32_t *)pl->row_of_pos.p, (float *)pl->qlat_alt.p, n, pl->nseg_pad, (int32_t)nq);
+                               (const int32_t *)pl->sh->row_of_pos.p, (float *)pl->qlat_alt.p, n, pl->nseg_pad, (int32_t)nq);
         else
             hipLaunchKernelGGL((k_prep_qlat<double>), grid, dim3(kBlock), 0, pl->hstream, (const double *)pl->in_qlat.p,
-                               (const int32_t *)pl->row_of_pos.p, (double *)pl->qlat_alt.p, n, pl->nseg_pad, (int32_t)nq);
+                               (const int32_t *)pl->sh->row_of_pos.p, (double *)pl->qlat_alt.p, n, pl->nseg_pad, (int32_t)nq);
         HIP_TRY(hipGetLastError());
         pl->qlat_alt_ready = true;
     }
@@ -601,7 +512,7 @@ int trmc_stage_forcing(trmc_plan *pl, int nsteps, const void *qlat, int64_t nq)
     pl->nq = nq;
     // (a plan with boundary rows: their hydrographs of the staged window arrive in ranges while it runs --
     // trmc_set_boundary_flow_range, the multi-GPU hand-off -- or with trmc_set_boundary_flow_device before it begins)
-    pl->have_boundary = pl->topo.nboundary == 0;
+    pl->have_boundary = pl->sh->topo.nboundary == 0;
     pl->ngage = 0; // nudging tables belong to one window (the launches of a window in progress carry their own copy of the pointers)
     pl->nraw = 0;
     pl->staged_nsteps = nsteps;
@@ -615,7 +526,7 @@ int trmc_plan_info(const trmc_plan *pl, int64_t *nseg, int64_t *nseg_routed, int
     if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
     if (nseg) *nseg = pl->nseg;
     if (nseg_routed) *nseg_routed = pl->nrouted;
-    if (nlevels) *nlevels = pl->topo.nlevels;
+    if (nlevels) *nlevels = pl->sh->topo.nlevels;
     if (precision) *precision = pl->precision;
     if (device) *device = pl->device;
     return 0;
@@ -624,7 +535,7 @@ int trmc_plan_info(const trmc_plan *pl, int64_t *nseg, int64_t *nseg_routed, int
 int trmc_plan_lags(const trmc_plan *pl, int32_t *lag_of_row, int32_t *wide_levels, int32_t *cluster_levels)
 {
     if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
-    const trmc::Topology &t = pl->topo;
+    const trmc::Topology &t = pl->sh->topo;
     if (t.cl_rows <= 0) return fail(TRMC_EINVAL, "the plan is not in cluster order (trmc_plan_options.cluster_rows)");
     for (int64_t r = 0; lag_of_row && r < pl->nseg; ++r)
         lag_of_row[r] = t.level_of_row[r] < 0 ? -1 : t.lagk_of_pos[(size_t)t.pos_of_row[r]];
@@ -636,7 +547,7 @@ int trmc_plan_lags(const trmc_plan *pl, int32_t *lag_of_row, int32_t *wide_level
 int trmc_plan_cluster_blocks(const trmc_plan *pl, int32_t *block_of_row, int32_t *block_width, int32_t *cluster_blocks)
 {
     if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
-    const trmc::Topology &t = pl->topo;
+    const trmc::Topology &t = pl->sh->topo;
     if (t.cl_rows <= 0) return fail(TRMC_EINVAL, "the plan is not in cluster order (trmc_plan_options.cluster_rows)");
     const int32_t nb = t.ncl > 0 ? (int32_t)t.cblk_ptr.size() - 1 : 0;
     if (block_of_row) {
@@ -653,8 +564,8 @@ int trmc_plan_levels(const trmc_plan *pl, int32_t *level_of_row, int64_t *plan_p
 {
     if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
     for (int64_t r = 0; r < pl->nseg; ++r) {
-        if (level_of_row) level_of_row[r] = pl->topo.level_of_row[r];
-        if (plan_pos_of_row) plan_pos_of_row[r] = pl->topo.pos_of_row[r];
+        if (level_of_row) level_of_row[r] = pl->sh->topo.level_of_row[r];
+        if (plan_pos_of_row) plan_pos_of_row[r] = pl->sh->topo.pos_of_row[r];
     }
     return 0;
 }
@@ -664,7 +575,7 @@ static int final_state_into(trmc_plan *pl, void *dst, int32_t nsteps_of_window)
 {
     const int32_t n = (int32_t)pl->nseg, T_ = nsteps_of_window >= 0 ? nsteps_of_window : pl->routed_nsteps;
     const size_t plane = (size_t)(T_ + 1) * pl->nseg_pad;
-    const int32_t *rop = (const int32_t *)pl->row_of_pos.p;
+    const int32_t *rop = (const int32_t *)pl->sh->row_of_pos.p;
     if (pl->flow) {
         hipLaunchKernelGGL((k_final_state<float>), dim3(blocks_for(n)), dim3(kBlock), 0, pl->stream, (const float *)pl->tm.p,
                            (const float *)pl->d_state.p, rop, (float *)dst, n, pl->nseg_pad, T_, 2, 0);
@@ -699,14 +610,14 @@ static int stage_state(trmc_plan *pl, int nsteps, int64_t nq, const void *q0, co
             if (int rc = final_state_into(pl, pl->in_q0.p)) return rc;
         } // (else: q0_staged -- the state an earlier staging of this window put into in_q0 stands, upload_check)
     }
-    if (pl->topo.nboundary > 0 && boundary_fvd) {
-        const size_t b = (size_t)pl->topo.nboundary * nsteps * 3 * e;
+    if (pl->sh->topo.nboundary > 0 && boundary_fvd) {
+        const size_t b = (size_t)pl->sh->topo.nboundary * nsteps * 3 * e;
         if (int rc = pl->in_bfvd.ensure(b)) return rc;
         HIP_TRY(hipMemcpyAsync(pl->in_bfvd.p, boundary_fvd, b, hipMemcpyHostToDevice, pl->stream));
     }
     HIP_TRY(hipStreamSynchronize(pl->stream));
     pl->nq = nq;
-    pl->have_boundary = pl->topo.nboundary == 0 || boundary_fvd != nullptr;
+    pl->have_boundary = pl->sh->topo.nboundary == 0 || boundary_fvd != nullptr;
     pl->ngage = 0; // nudging tables belong to one window: trmc_set_nudging() after each upload
     pl->nraw = 0;
     pl->staged_nsteps = nsteps;
@@ -781,7 +692,7 @@ int trmc_upload_forcing_packed(trmc_plan *pl, int nsteps, int64_t nq, int64_t nf
     const int64_t n = pl->nseg;
     std::vector<int32_t> feat_of_pos((size_t)(n > 0 ? n : 1), -1);
     for (int64_t p = 0; p < n; ++p) {
-        const int64_t f = feat_of_row[pl->topo.row_of_pos[p]];
+        const int64_t f = feat_of_row[pl->sh->topo.row_of_pos[p]];
         if (f >= nfeat) return fail(TRMC_EINVAL, "feat_of_row entry outside the feature axis");
         feat_of_pos[(size_t)p] = f < 0 ? -1 : (int32_t)f;
     }
@@ -815,7 +726,7 @@ int trmc_set_boundary_flow_device(trmc_plan *pl, int nsteps, const void *q_dev)
     if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
     if (pl->staged_nsteps < 0) return fail(TRMC_ESTATE, "trmc_upload_forcing must precede trmc_set_boundary_flow_device");
     if (nsteps != pl->staged_nsteps) return fail(TRMC_EINVAL, "nsteps differs from the staged forcing");
-    const int64_t nb = pl->topo.nboundary;
+    const int64_t nb = pl->sh->topo.nboundary;
     if (nb == 0) return 0;
     if (!q_dev) return fail(TRMC_EINVAL, "q_dev is NULL");
     if (int rc = use_device(pl)) return rc;
@@ -844,9 +755,9 @@ int trmc_set_reservoirs(trmc_plan *pl, int64_t nres, const int64_t *res_rows, co
     for (int64_t i = 0; i < nres; ++i) {
         const int64_t r = res_rows[i];
         if (r < 0 || r >= pl->nseg) return fail(TRMC_EINVAL, "reservoir row out of range");
-        if (pl->topo.level_of_row[r] < 0) return fail(TRMC_EINVAL, "reservoir on a boundary row");
-        if (r_of_pos[pl->topo.pos_of_row[r]] >= 0) return fail(TRMC_EINVAL, "two reservoirs on one row");
-        r_of_pos[pl->topo.pos_of_row[r]] = (int32_t)i;
+        if (pl->sh->topo.level_of_row[r] < 0) return fail(TRMC_EINVAL, "reservoir on a boundary row");
+        if (r_of_pos[pl->sh->topo.pos_of_row[r]] >= 0) return fail(TRMC_EINVAL, "two reservoirs on one row");
+        r_of_pos[pl->sh->topo.pos_of_row[r]] = (int32_t)i;
     }
     if (int rc = upload_i32(pl->res_of_pos, r_of_pos, 1)) return rc;
     const size_t bytes = (size_t)nres * 9 * pl->esz;
@@ -1020,11 +931,11 @@ int trmc_set_nudging(trmc_plan *pl, int nsteps, int64_t ngage, const int64_t *ga
     for (int64_t g = 0; g < ngage; ++g) {
         const int64_t r = gage_rows[g];
         if (r < 0 || r >= pl->nseg) return fail(TRMC_EINVAL, "gage row out of range");
-        if (pl->topo.level_of_row[r] < 0) return fail(TRMC_EINVAL, "gage on a boundary row");
+        if (pl->sh->topo.level_of_row[r] < 0) return fail(TRMC_EINVAL, "gage on a boundary row");
         // (the reservoir branch of the kernels ends a row's step before the nudging hook)
-        if (!res_of_pos.empty() && res_of_pos[(size_t)pl->topo.pos_of_row[r]] >= 0)
+        if (!res_of_pos.empty() && res_of_pos[(size_t)pl->sh->topo.pos_of_row[r]] >= 0)
             return fail(TRMC_EINVAL, "a gage on a reservoir row is not supported (row " + std::to_string(r) + ")");
-        g_of_pos[pl->topo.pos_of_row[r]] = (int32_t)g; // one gage per segment: the last listed wins, as reach_has_gage does
+        g_of_pos[pl->sh->topo.pos_of_row[r]] = (int32_t)g; // one gage per segment: the last listed wins, as reach_has_gage does
     }
     const size_t n = (size_t)ngage * nsteps, e = pl->esz;
     if (int rc = upload_i32(pl->gage_of_pos, g_of_pos, 1)) return rc;
@@ -1062,10 +973,10 @@ int trmc_set_nudging_successors(trmc_plan *pl, int64_t ngage, const int64_t *suc
     for (int64_t g = 0; g < ngage; ++g) {
         const int64_t r = successor_rows[g];
         if (r < 0) continue;
-        if (r >= pl->nseg || pl->topo.level_of_row[r] < 0) return fail(TRMC_EINVAL, "successor row out of range or a boundary row");
-        const int32_t p = pl->topo.pos_of_row[r];
+        if (r >= pl->nseg || pl->sh->topo.level_of_row[r] < 0) return fail(TRMC_EINVAL, "successor row out of range or a boundary row");
+        const int32_t p = pl->sh->topo.pos_of_row[r];
         // the segment below a gage inside a reach has exactly one upstream row: that gage's segment
-        if (pl->topo.up_ptr[p + 1] - pl->topo.up_ptr[p] != 1 || g_of_pos[(size_t)pl->topo.up_idx[pl->topo.up_ptr[p]]] != (int32_t)g)
+        if (pl->sh->topo.up_ptr[p + 1] - pl->sh->topo.up_ptr[p] != 1 || g_of_pos[(size_t)pl->sh->topo.up_idx[pl->sh->topo.up_ptr[p]]] != (int32_t)g)
             return fail(TRMC_EINVAL, "successor row " + std::to_string(r) + " is not the segment directly below gage " + std::to_string(g));
         raw[(size_t)p] = (int32_t)g;
     }
@@ -1095,7 +1006,7 @@ static int route_check(trmc_plan *pl, int nsteps, int qts_subdivisions, bool bou
     if (stream_active(pl)) return fail(TRMC_ESTATE, "a stream of windows is in progress (trmc_stream_end it first)");
     if (nsteps < 1) return fail(TRMC_EINVAL, "nsteps must be >= 1");
     if (qts_subdivisions < 1) return fail(TRMC_EINVAL, "qts_subdivisions must be >= 1");
-    if (pl->topo.nboundary > 0 && nsteps != pl->staged_nsteps)
+    if (pl->sh->topo.nboundary > 0 && nsteps != pl->staged_nsteps)
         return fail(TRMC_EINVAL, "nsteps differs from the staged boundary hydrographs");
     if (!pl->have_boundary && !boundary_later)
         return fail(TRMC_ESTATE, "plan has boundary rows but no boundary hydrographs were supplied");
@@ -1112,7 +1023,7 @@ static int route_check(trmc_plan *pl, int nsteps, int qts_subdivisions, bool bou
 
 static int lag_check(trmc_plan *pl, int assume_short_ts)
 {
-    if ((pl->topo.tail_from_level > 0 || pl->topo.ncl > 0) && !assume_short_ts)
+    if ((pl->sh->topo.tail_from_level > 0 || pl->sh->topo.ncl > 0) && !assume_short_ts)
         return fail(TRMC_EINVAL, "this plan was created for assume_short_ts (TRMC_PLAN_SHORT_TS on the level engine: its deeper rows are "
                                  "ordered in clusters or by cost, not by level); create a plan for the general mode");
     if (pl->maxlag > 0 && !assume_short_ts)
@@ -1218,7 +1129,8 @@ int trmc_plan_set_lag(trmc_plan *pl, const int32_t *lag_of_row)
     if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
     if (pl->run.active) return fail(TRMC_ESTATE, "a routing window is in progress");
     if (!pl->rowsets.empty()) return fail(TRMC_ESTATE, "set the lag before registering row sets");
-    if (pl->clones > 0 || pl->parent) return fail(TRMC_ESTATE, "set the lag before cloning the plan (a clone shares the lag table)");
+    // (a clone for its whole life; an original while anybody else holds the shared block, that is while a clone of it lives)
+    if (pl->is_clone || pl->sh.use_count() > 1) return fail(TRMC_ESTATE, "set the lag before cloning the plan (a clone shares the lag table)");
     pl->maxlag = 0;
     pl->lag_of_row.clear();
     pl->wide_safe_pos = -1;
@@ -1233,19 +1145,19 @@ int trmc_plan_set_lag(trmc_plan *pl, const int32_t *lag_of_row)
     std::vector<int32_t> by_pos((size_t)pl->nseg_pad, 0);
     for (int64_t r = 0; r < pl->nseg; ++r) {
         if (lag_of_row[r] != 0 && lag_of_row[r] != mx) return fail(TRMC_EINVAL, "lag must be 0 or one common value");
-        by_pos[(size_t)pl->topo.pos_of_row[r]] = lag_of_row[r];
+        by_pos[(size_t)pl->sh->topo.pos_of_row[r]] = lag_of_row[r];
     }
-    for (int64_t p = pl->topo.nboundary; p < pl->nseg; ++p)
-        for (int32_t k = pl->topo.up_ptr[p]; k < pl->topo.up_ptr[p + 1]; ++k) {
-            const int32_t u = pl->topo.up_idx[k];
-            if (u >= pl->topo.nboundary && by_pos[(size_t)u] > by_pos[(size_t)p])
+    for (int64_t p = pl->sh->topo.nboundary; p < pl->nseg; ++p)
+        for (int32_t k = pl->sh->topo.up_ptr[p]; k < pl->sh->topo.up_ptr[p + 1]; ++k) {
+            const int32_t u = pl->sh->topo.up_idx[k];
+            if (u >= pl->sh->topo.nboundary && by_pos[(size_t)u] > by_pos[(size_t)p])
                 return fail(TRMC_EINVAL, "a lagged row feeds a row that is not lagged");
-            if (u < pl->topo.nboundary && by_pos[(size_t)p] != mx)
+            if (u < pl->sh->topo.nboundary && by_pos[(size_t)p] != mx)
                 return fail(TRMC_EINVAL, "with a lag, boundary rows may only feed lagged rows");
         }
     if (int rc = use_device(pl)) return rc;
-    if (int rc = pl->lag.ensure((size_t)pl->nseg_pad * sizeof(int32_t))) return rc;
-    HIP_TRY(hipMemcpy(pl->lag.p, by_pos.data(), (size_t)pl->nseg_pad * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (int rc = pl->sh->lag.ensure((size_t)pl->nseg_pad * sizeof(int32_t))) return rc;
+    HIP_TRY(hipMemcpy(pl->sh->lag.p, by_pos.data(), (size_t)pl->nseg_pad * sizeof(int32_t), hipMemcpyHostToDevice));
     pl->lag_of_row.assign(lag_of_row, lag_of_row + pl->nseg);
     pl->maxlag = mx;
     return 0;
@@ -1259,7 +1171,7 @@ int trmc_rowset_create(trmc_plan *pl, const int64_t *rows, int64_t nrows, int32_
     std::vector<int32_t> pos((size_t)nrows);
     for (int64_t i = 0; i < nrows; ++i) {
         if (rows[i] < 0 || rows[i] >= pl->nseg) return fail(TRMC_EINVAL, "row out of range");
-        pos[i] = pl->topo.pos_of_row[rows[i]];
+        pos[i] = pl->sh->topo.pos_of_row[rows[i]];
     }
     DevBuf b;
     if (int rc = b.ensure((size_t)(nrows > 0 ? nrows : 1) * sizeof(int32_t))) return rc;
@@ -1267,12 +1179,12 @@ int trmc_rowset_create(trmc_plan *pl, const int64_t *rows, int64_t nrows, int32_
     int32_t rs_lag = 0; // a set with lagged rows is complete `maxlag` launches later
     if (pl->maxlag > 0)
         for (int64_t i = 0; i < nrows; ++i) rs_lag = std::max(rs_lag, pl->lag_of_row[(size_t)rows[i]]);
-    pl->rowsets.push_back(b);
+    pl->rowsets.push_back(std::move(b));
     pl->rowset_n.push_back(nrows);
     pl->rowset_lag.push_back(rs_lag);
     int32_t lk = 0;
-    if (!pl->topo.lagk_of_pos.empty())
-        for (int64_t i = 0; i < nrows; ++i) lk = std::max(lk, pl->topo.lagk_of_pos[(size_t)pos[i]]);
+    if (!pl->sh->topo.lagk_of_pos.empty())
+        for (int64_t i = 0; i < nrows; ++i) lk = std::max(lk, pl->sh->topo.lagk_of_pos[(size_t)pos[i]]);
     pl->rowset_lagk.push_back(lk);
     *id_out = (int32_t)pl->rowsets.size() - 1;
     return 0;
@@ -1323,7 +1235,7 @@ int trmc_set_boundary_flow_range_indexed(trmc_plan *pl, int t_begin, int t_end, 
     if (t_begin != r.boundary_through || t_end < t_begin || t_end > r.nsteps)
         return fail(TRMC_EINVAL, "ranges must continue where the staged boundary hydrographs end (step "
                                      + std::to_string(r.boundary_through) + ")");
-    const int64_t nb = pl->topo.nboundary;
+    const int64_t nb = pl->sh->topo.nboundary;
     if (nb == 0 || t_end == t_begin) {
         r.boundary_through = t_end;
         return 0;
@@ -1344,7 +1256,7 @@ int trmc_set_boundary_flow_range_indexed(trmc_plan *pl, int t_begin, int t_end, 
     }
     if (pl->flow) {
         hipLaunchKernelGGL(k_flow_boundary, dim3(blocks_for(work)), dim3(kBlock), 0, st, (const float *)q_dev,
-                           (unsigned long long *)pl->tm.p, (float *)pl->out.p, (const int32_t *)pl->row_of_pos.p, (int32_t)nb,
+                           (unsigned long long *)pl->tm.p, (float *)pl->out.p, (const int32_t *)pl->sh->row_of_pos.p, (int32_t)nb,
                            r.nsteps, pl->nseg_pad, t_begin, t_end, src_stride, 1, 1, pl->tag_base, src_index_dev);
     } else if (pl->precision == 32) {
         float *q = (float *)pl->tm.p;
@@ -1412,7 +1324,7 @@ int trmc_download_fvd_rowset(trmc_plan *pl, int stride, int32_t rowset, void *fv
     if (int rc = pl->gathered.ensure(bytes)) return rc;
     pl->gathered_bytes = 0;
     const int64_t work = nrows * (int64_t)nkeep;
-    const int32_t *rp = (const int32_t *)pl->rowsets[(size_t)rowset].p, *rop = (const int32_t *)pl->row_of_pos.p;
+    const int32_t *rp = (const int32_t *)pl->rowsets[(size_t)rowset].p, *rop = (const int32_t *)pl->sh->row_of_pos.p;
     if (pl->precision == 32)
         hipLaunchKernelGGL((k_decimate_rows<float>), dim3(blocks_for(work)), dim3(kBlock), 0, pl->stream, (const float *)pl->out.p,
                            (float *)pl->gathered.p, rp, rop, nrows, pl->routed_nsteps, stride, nkeep);
@@ -1465,8 +1377,8 @@ int trmc_window_summary(trmc_plan *pl, int32_t rowset, void *peak_flow, int32_t 
     }
     if (int rc = pl->scratch.ensure(total)) return rc;
     const int32_t *rp = rowset < 0 ? nullptr : (const int32_t *)pl->rowsets[(size_t)rowset].p;
-    for (hipEvent_t &e : pl->ev_wsum)
-        if (!e) HIP_TRY(hipEventCreate(&e));
+    for (DevEvent &e : pl->ev_wsum)
+        if (int rc = e.ensure(true)) return rc;
     pl->wsum_ms = -1.0;
     HIP_TRY(hipEventRecord(pl->ev_wsum[0], pl->stream));
     const int rc = by_precision(pl, [&](auto t) -> int {
@@ -1477,10 +1389,10 @@ int trmc_window_summary(trmc_plan *pl, int32_t rowset, void *peak_flow, int32_t 
         const dim3 grid((unsigned)((nrows + kWsumRows - 1) / kWsumRows)), block(kWsumRows);
         // (16-byte loads where every row's record starts on a 16-byte boundary: k_window_summary's head)
         if (nsteps % (16 / (int)sizeof(T)) == 0)
-            hipLaunchKernelGGL((k_window_summary<T, true>), grid, block, 0, pl->stream, (const T *)pl->out.p, rp, (const int32_t *)pl->row_of_pos.p,
+            hipLaunchKernelGGL((k_window_summary<T, true>), grid, block, 0, pl->stream, (const T *)pl->out.p, rp, (const int32_t *)pl->sh->row_of_pos.p,
                                o, nrows, nsteps);
         else
-            hipLaunchKernelGGL((k_window_summary<T, false>), grid, block, 0, pl->stream, (const T *)pl->out.p, rp, (const int32_t *)pl->row_of_pos.p,
+            hipLaunchKernelGGL((k_window_summary<T, false>), grid, block, 0, pl->stream, (const T *)pl->out.p, rp, (const int32_t *)pl->sh->row_of_pos.p,
                                o, nrows, nsteps);
         HIP_TRY(hipGetLastError());
         return 0;
@@ -1544,8 +1456,8 @@ int trmc_window_courant(trmc_plan *pl, int32_t rowset, int stride, void *dst)
     const size_t bytes = (size_t)nrows * nkeep * 3 * pl->esz;
     if (int rc = pl->gathered.ensure(bytes)) return rc; // (the plan's scratch block for gathers of its result)
     pl->gathered_bytes = 0;
-    for (hipEvent_t &e : pl->ev_cour)
-        if (!e) HIP_TRY(hipEventCreate(&e));
+    for (DevEvent &e : pl->ev_cour)
+        if (int rc = e.ensure(true)) return rc;
     pl->cour_ms = -1.0;
     HIP_TRY(hipEventRecord(pl->ev_cour[0], pl->stream));
     const int rc = by_precision(pl, [&](auto t) -> int {
@@ -1587,8 +1499,8 @@ int trmc_window_courant_summary(trmc_plan *pl, int32_t rowset, double limit, voi
         if (host[k]) total += ((size_t)nrows * width[k] + 255) / 256 * 256;
     }
     if (int rc = pl->scratch.ensure(total)) return rc;
-    for (hipEvent_t &e : pl->ev_cour)
-        if (!e) HIP_TRY(hipEventCreate(&e));
+    for (DevEvent &e : pl->ev_cour)
+        if (int rc = e.ensure(true)) return rc;
     pl->cour_ms = -1.0;
     HIP_TRY(hipEventRecord(pl->ev_cour[0], pl->stream));
     const int rc = by_precision(pl, [&](auto t) -> int {
@@ -1670,7 +1582,7 @@ int trmc_download_cost(trmc_plan *pl, uint16_t *cost_out, int32_t *nsteps_out)
     if (int rc = use_device(pl)) return rc;
     std::vector<uint16_t> by_pos((size_t)pl->nseg_pad);
     HIP_TRY(hipMemcpy(by_pos.data(), pl->it_sum.p, (size_t)pl->nseg_pad * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    for (int64_t p = 0; p < pl->nseg; ++p) cost_out[pl->topo.row_of_pos[p]] = by_pos[(size_t)p];
+    for (int64_t p = 0; p < pl->nseg; ++p) cost_out[pl->sh->topo.row_of_pos[p]] = by_pos[(size_t)p];
     if (nsteps_out) *nsteps_out = pl->cost_nsteps;
     return 0;
 }
@@ -1682,7 +1594,7 @@ int trmc_download_iterations(trmc_plan *pl, uint8_t *iters_out)
     if (int rc = use_device(pl)) return rc;
     std::vector<uint8_t> by_pos((size_t)pl->nseg_pad);
     HIP_TRY(hipMemcpy(by_pos.data(), pl->it_prev.p, (size_t)pl->nseg_pad, hipMemcpyDeviceToHost));
-    for (int64_t p = 0; p < pl->nseg; ++p) iters_out[pl->topo.row_of_pos[p]] = by_pos[(size_t)p];
+    for (int64_t p = 0; p < pl->nseg; ++p) iters_out[pl->sh->topo.row_of_pos[p]] = by_pos[(size_t)p];
     return 0;
 }
 
@@ -1711,13 +1623,12 @@ static int ensure_copy_stream(trmc_plan *pl)
     // carries the result transposes.
     int prio_lo = 0, prio_hi = 0;
     HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-    HIP_TRY(hipStreamCreateWithPriority(&pl->cstream, hipStreamNonBlocking, prio_lo));
+    if (int rc = pl->cstream.ensure(hipStreamNonBlocking, prio_lo)) return rc;
     // (a stream per direction: a day's decimated result on its way out -- 0.8 GB for a CONUS day, most of a window -- does not
     // hold the next day's forcing back, which the plan's next set-up waits for)
-    HIP_TRY(hipStreamCreateWithPriority(&pl->hstream, hipStreamNonBlocking, prio_lo));
-    HIP_TRY(hipEventCreateWithFlags(&pl->ev_fetch_ready, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&pl->ev_fetch_done, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&pl->ev_forcing, hipEventDisableTiming));
+    if (int rc = pl->hstream.ensure(hipStreamNonBlocking, prio_lo)) return rc;
+    for (DevEvent *e : {&pl->ev_fetch_ready, &pl->ev_fetch_done, &pl->ev_forcing})
+        if (int rc = e->ensure(false)) return rc;
     return 0;
 }
 
@@ -1791,11 +1702,11 @@ int trmc_fetch_begin_fvd(trmc_plan *pl, int32_t rowset, void *hyd_host, void *q0
         if (pl->precision == 32) {
             const float *q = (const float *)pl->tm.p;
             hipLaunchKernelGGL((k_decimate_planes<float>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pl->stream, q, q + plane, q + 2 * plane,
-                               (const int32_t *)pl->row_of_pos.p, (float *)pl->dec.p, (int32_t)pl->nseg, pl->nseg_pad, stride, nkeep, lo, hi);
+                               (const int32_t *)pl->sh->row_of_pos.p, (float *)pl->dec.p, (int32_t)pl->nseg, pl->nseg_pad, stride, nkeep, lo, hi);
         } else {
             const double *q = (const double *)pl->tm.p;
             hipLaunchKernelGGL((k_decimate_planes<double>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pl->stream, q, q + plane, q + 2 * plane,
-                               (const int32_t *)pl->row_of_pos.p, (double *)pl->dec.p, (int32_t)pl->nseg, pl->nseg_pad, stride, nkeep, lo, hi);
+                               (const int32_t *)pl->sh->row_of_pos.p, (double *)pl->dec.p, (int32_t)pl->nseg, pl->nseg_pad, stride, nkeep, lo, hi);
         }
         HIP_TRY(hipGetLastError());
         if (int rc = note_gather(pl, in_window)) return rc;
@@ -1831,7 +1742,7 @@ int trmc_fetch_begin_fvd(trmc_plan *pl, int32_t rowset, void *hyd_host, void *q0
     if (fb) {
         if (int rc = to_host(fvd_host, fvd_src, fb)) return rc;
         if (stride == 1 || from_dec) { // (copied from `out` / `dec` themselves: the plan's next window, which writes them, starts behind the copy)
-            if (!pl->ev_dec) HIP_TRY(hipEventCreateWithFlags(&pl->ev_dec, hipEventDisableTiming));
+            if (int rc = pl->ev_dec.ensure(false)) return rc;
             HIP_TRY(hipEventRecord(pl->ev_dec, pl->cstream));
             pl->dec_pending = true;
         }
@@ -1861,7 +1772,7 @@ int trmc_gather_flow_rows(trmc_plan *pl, const int64_t *rows, int64_t nrows, voi
     std::vector<int32_t> pos((size_t)nrows);
     for (int64_t i = 0; i < nrows; ++i) {
         if (rows[i] < 0 || rows[i] >= pl->nseg) return fail(TRMC_EINVAL, "row out of range");
-        pos[i] = pl->topo.pos_of_row[rows[i]];
+        pos[i] = pl->sh->topo.pos_of_row[rows[i]];
     }
     const int32_t T_ = pl->routed_nsteps;
     const size_t obytes = (size_t)nrows * T_ * pl->esz;
@@ -1970,7 +1881,7 @@ int trmc_plan_chain_from(trmc_plan *dst, trmc_plan *src)
     if (src->run.active && src->run.t_done < src->run.nsteps + (src->run.short_ts ? src->maxlag : 0))
         return fail(TRMC_ESTATE, "the source plan's window has not been queued to its end (trmc_route_advance)");
     if (dst->nseg != src->nseg || dst->precision != src->precision || dst->device != src->device
-        || dst->topo.row_of_pos != src->topo.row_of_pos)
+        || dst->sh->topo.row_of_pos != src->sh->topo.row_of_pos)
         return fail(TRMC_EINVAL, "the two plans must hold the same network in the same order (same inputs, same cost hint)");
     if (int rc = use_device(dst)) return rc;
     dst->row0_replaced = true; // (what trmc_window_courant reads as the last window's initial state; the next window clears it)

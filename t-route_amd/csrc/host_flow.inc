@@ -9,7 +9,7 @@
 int flow_place_blocks(trmc_plan *pl)
 {
     pl->ncuq = 0;
-    const int32_t nb = pl->topo.nblocks;
+    const int32_t nb = pl->sh->topo.nblocks;
     if (nb <= 0) return 0;
     constexpr int kKeys = 4096;
     // which compute units are there?
@@ -29,7 +29,7 @@ int flow_place_blocks(trmc_plan *pl)
         if (hs[k]) cu_index[k] = Q++;
     if (Q < 2) return 0;
     // cost of every block
-    const std::vector<uint8_t> &wc = pl->topo.cost_of_wave;
+    const std::vector<uint8_t> &wc = pl->sh->topo.cost_of_wave;
     int hi = 0;
     for (const uint8_t c : wc) hi = std::max(hi, (int)c);
     const bool sixteenths = hi > 7;
@@ -82,11 +82,11 @@ int flow_place_blocks(trmc_plan *pl)
         for (const int32_t b : queue[(size_t)c]) blk.push_back(b);
         ptr[(size_t)c + 1] = (int32_t)blk.size();
     }
-    if (int rc = pl->cuq_perm.ensure(perm.size())) return rc;
-    HIP_TRY(hipMemcpy(pl->cuq_perm.p, perm.data(), perm.size(), hipMemcpyHostToDevice));
-    if (int rc = upload_i32(pl->cuq_ptr, ptr, 1)) return rc;
-    if (int rc = upload_i32(pl->cuq_blk, blk, 1)) return rc;
-    if (int rc = upload_i32(pl->cu_index, cu_index, 1)) return rc;
+    if (int rc = pl->sh->cuq_perm.ensure(perm.size())) return rc;
+    HIP_TRY(hipMemcpy(pl->sh->cuq_perm.p, perm.data(), perm.size(), hipMemcpyHostToDevice));
+    if (int rc = upload_i32(pl->sh->cuq_ptr, ptr, 1)) return rc;
+    if (int rc = upload_i32(pl->sh->cuq_blk, blk, 1)) return rc;
+    if (int rc = upload_i32(pl->sh->cu_index, cu_index, 1)) return rc;
     if (int rc = pl->cuq_head.ensure((size_t)Q * 2 * sizeof(int32_t))) return rc;
     pl->ncuq = Q;
     return 0;
@@ -110,19 +110,19 @@ FlowArgs flow_args(trmc_plan *pl, int nsteps, int qts, bool short_ts)
     a.s0_n = col<float>(pl, TRMC_NPARAM + 4);
     a.s0_ncc = col<float>(pl, TRMC_NPARAM + 5);
     a.inv_n = col<float>(pl, TRMC_NPARAM + 6);
-    a.up_ptr = (const int32_t *)pl->up_ptr.p;
-    a.up_idx = (const int32_t *)pl->up_idx.p;
-    a.up2 = (const int2 *)pl->up2.p;
+    a.up_ptr = (const int32_t *)pl->sh->up_ptr.p;
+    a.up_idx = (const int32_t *)pl->sh->up_idx.p;
+    a.up2 = (const int2 *)pl->sh->up2.p;
     // short-timestep mode: the skew of trmc_plan_set_lag; general mode: the level rank inside the block
-    a.lag = short_ts ? (pl->maxlag > 0 ? (const int32_t *)pl->lag.p : nullptr)
-                     : (pl->topo.maxrank > 0 ? (const int32_t *)pl->rank.p : nullptr);
-    a.ticket_map = short_ts ? nullptr : (const int32_t *)pl->ticket_map.p;
+    a.lag = short_ts ? (pl->maxlag > 0 ? (const int32_t *)pl->sh->lag.p : nullptr)
+                     : (pl->sh->topo.maxrank > 0 ? (const int32_t *)pl->sh->rank.p : nullptr);
+    a.ticket_map = short_ts ? nullptr : (const int32_t *)pl->sh->ticket_map.p;
     a.qlat_tm = (const float *)pl->qlat_tm.p;
     a.gran = (unsigned long long *)pl->tm.p;
     a.d_state = (float *)pl->d_state.p;
     a.d_gran = (unsigned long long *)pl->d_gran.p;
     a.out = (float *)pl->out.p;
-    a.row_of_pos = (const int32_t *)pl->row_of_pos.p;
+    a.row_of_pos = (const int32_t *)pl->sh->row_of_pos.p;
     a.it_prev = (uint8_t *)pl->it_prev.p;
     a.it_sum = pl->collect_cost ? (uint16_t *)pl->it_sum.p : nullptr;
     a.sane = pl->params_sane;
@@ -142,13 +142,13 @@ FlowArgs flow_args(trmc_plan *pl, int nsteps, int qts, bool short_ts)
     a.nsteps = nsteps;
     a.qts = qts;
     a.nseg = (int32_t)pl->nseg;
-    a.first = (int32_t)pl->topo.nboundary;
+    a.first = (int32_t)pl->sh->topo.nboundary;
     a.tag_base = pl->tag_base;
     a.ticket = (int32_t *)pl->ticket.p;
     a.watchdog_ticks = pl->watchdog_ticks;
     a.dbg = pl->opt.flow_debug ? (unsigned long long *)pl->dbg.p : nullptr; // (trmc_plan_options.flow_debug: when did every block run?)
-    a.nblocks_dbg = pl->topo.nblocks;
-    a.prio = (const uint8_t *)pl->prio.p;
+    a.nblocks_dbg = pl->sh->topo.nblocks;
+    a.prio = (const uint8_t *)pl->sh->prio.p;
     a.cuq_ptr = a.cuq_blk = a.cu_index = nullptr; // (flow_route_advance switches the queues on for lean launches)
     a.cuq_perm = nullptr;
     a.cuq_head = nullptr;
@@ -158,7 +158,7 @@ FlowArgs flow_args(trmc_plan *pl, int nsteps, int qts, bool short_ts)
 
 int flow_route_begin(trmc_plan *pl, int nsteps, int qts, int short_ts)
 {
-    const trmc::Topology &tp = pl->topo;
+    const trmc::Topology &tp = pl->sh->topo;
     const int32_t n = (int32_t)pl->nseg;
     const int64_t np = pl->nseg_pad;
     hipStream_t st = pl->stream;
@@ -187,7 +187,7 @@ int flow_route_begin(trmc_plan *pl, int nsteps, int qts, int short_ts)
     }
     pl->tag_base += (uint32_t)pl->tag_span;
     pl->tag_span = nsteps + 1;
-    const int32_t *row_of_pos = (const int32_t *)pl->row_of_pos.p;
+    const int32_t *row_of_pos = (const int32_t *)pl->sh->row_of_pos.p;
     HIP_TRY(hipEventRecord(pl->ev[0], st));
     pl->q0_staged = false; // (consumed by this window)
     if (pl->dec_pending) { // (trmc_fetch_begin_fvd: the copy stream reads `out`)
@@ -243,7 +243,7 @@ static bool flow_lean(const trmc_plan *pl, int nsteps)
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, pl->device);
     const int32_t force = pl->opt.flow_lean; // (trmc_plan_options.flow_lean: > 0 always, < 0 never -- A/B measurements)
     return (uint64_t)pl->nseg * (uint64_t)nsteps * 3ull < (1ull << 32)
-           && (force ? force > 0 : pl->topo.nblocks <= TRMC_LEAN_WAVES * (256 / kFlowBlock) * ncu);
+           && (force ? force > 0 : pl->sh->topo.nblocks <= TRMC_LEAN_WAVES * (256 / kFlowBlock) * ncu);
 }
 // Optional (trmc_plan_options.flow_overlap; off by default): consecutive launches of a short-timestep window on the lean kernel
 // alternate between two compute streams.  Rows hand their state from launch to launch through granules (flow plane,
@@ -270,15 +270,15 @@ int flow_route_advance(trmc_plan *pl, int t_end)
         a.ticket += 8 * which;                                       // every compute stream has its own block tickets
         HIP_TRY(hipMemsetAsync(a.ticket, 0, sizeof(int32_t), st));   // they restart; the abort flag stays
         if (lean && pl->ncuq > 0) { // blocks by compute unit (lean_pick_block)
-            a.cuq_ptr = (const int32_t *)pl->cuq_ptr.p;
-            a.cuq_blk = (const int32_t *)pl->cuq_blk.p;
-            a.cu_index = (const int32_t *)pl->cu_index.p;
-            a.cuq_perm = (const uint8_t *)pl->cuq_perm.p;
+            a.cuq_ptr = (const int32_t *)pl->sh->cuq_ptr.p;
+            a.cuq_blk = (const int32_t *)pl->sh->cuq_blk.p;
+            a.cu_index = (const int32_t *)pl->sh->cu_index.p;
+            a.cuq_perm = (const uint8_t *)pl->sh->cuq_perm.p;
             a.cuq_head = (int32_t *)pl->cuq_head.p + (size_t)pl->ncuq * which;
             a.ncuq = pl->ncuq;
             HIP_TRY(hipMemsetAsync(a.cuq_head, 0, (size_t)pl->ncuq * sizeof(int32_t), st));
         }
-        const dim3 grid((unsigned)pl->topo.nblocks), block(kFlowBlock);
+        const dim3 grid((unsigned)pl->sh->topo.nblocks), block(kFlowBlock);
         if (a.res_da) { // (exact arithmetic: trmc_set_reservoir_da)
             if (lean && a.lag) hipLaunchKernelGGL((k_mc_flow_lean_rda<true>), grid, block, 0, st, a, r.t_done, t_end);
             else if (lean) hipLaunchKernelGGL((k_mc_flow_lean_rda<false>), grid, block, 0, st, a, r.t_done, t_end);
@@ -332,12 +332,12 @@ int flow_route_end(trmc_plan *pl)
         const uint64_t np = (uint64_t)pl->nseg_pad;
         return fail(TRMC_EHIP, "dataflow engine: a row waited longer than the watchdog allows for an upstream flow "
                                "(boundary hydrographs missing for the steps routed, or an internal error); window abandoned"
-                               " [waited for position " + std::to_string(idx % np) + " (" + (idx % np < (uint64_t)pl->topo.nboundary ? "a boundary row" : "a routed row")
+                               " [waited for position " + std::to_string(idx % np) + " (" + (idx % np < (uint64_t)pl->sh->topo.nboundary ? "a boundary row" : "a routed row")
                                + ") at step " + std::to_string(idx / np) + ", tag " + std::to_string((uint32_t)flags[4]) + ", found tag "
                                + std::to_string((uint32_t)flags[5]) + ", window tag base " + std::to_string(pl->tag_base) + "]");
     }
-    if (pl->opt.flow_debug && pl->topo.nblocks > 0) { // developer aid: when did every block run?
-        const int32_t nb = pl->topo.nblocks;
+    if (pl->opt.flow_debug && pl->sh->topo.nblocks > 0) { // developer aid: when did every block run?
+        const int32_t nb = pl->sh->topo.nblocks;
         std::vector<unsigned long long> d((size_t)nb * 2);
         HIP_TRY(hipMemcpy(d.data(), pl->dbg.p, d.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         std::vector<uint32_t> cu_key(nb);
@@ -356,7 +356,7 @@ int flow_route_end(trmc_plan *pl)
                     std::fprintf(f, "%d %u %.5f %.5f", b, cu_key[b], d[2 * b] * 1e-5, d[2 * b + 1] * 1e-5);
                     for (int q = 0; q < kFlowBlock / 64; ++q) {
                         const size_t w = (size_t)b * (kFlowBlock / 64) + q;
-                        std::fprintf(f, " %d", w < pl->topo.cost_of_wave.size() ? (int)pl->topo.cost_of_wave[w] : -1);
+                        std::fprintf(f, " %d", w < pl->sh->topo.cost_of_wave.size() ? (int)pl->sh->topo.cost_of_wave[w] : -1);
                     }
                     for (int q = 0; q < kFlowBlock / 64; ++q) std::fprintf(f, " %llu", dx[(size_t)4 * b + q]);
                     std::fprintf(f, "\n");
@@ -393,7 +393,7 @@ int flow_route_end(trmc_plan *pl)
     trmc_stats &s = pl->stats;
     s.nseg = pl->nseg;
     s.nseg_routed = pl->nrouted;
-    s.nlevels = pl->topo.nlevels;
+    s.nlevels = pl->sh->topo.nlevels;
     s.nsteps = r.nsteps;
     s.assume_short_ts = r.short_ts;
     s.main_launches = r.launches;

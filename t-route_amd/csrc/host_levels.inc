@@ -1,6 +1,6 @@
 // host_levels.inc -- included by trmc.hip: a routing window on the level engine (route_begin_t / route_advance_t / route_end_t).
 
-template <class T> T *col(trmc_plan *pl, int c) { return (T *)pl->params.p + (size_t)c * pl->nseg_pad; }
+template <class T> T *col(trmc_plan *pl, int c) { return (T *)pl->sh->params.p + (size_t)c * pl->nseg_pad; }
 
 template <class T> int upload_params(trmc_plan *pl, const float *params)
 {
@@ -12,7 +12,7 @@ template <class T> int upload_params(trmc_plan *pl, const float *params)
     auto in_range = [](float v) { return v >= 0x1p-14f && v <= 0x1p17f; };
     auto within = [](float v, float lo, float hi) { return v >= lo && v <= hi; };
     for (int64_t p = 0; p < n; ++p) {
-        const float *src = params + (size_t)pl->topo.row_of_pos[p] * TRMC_NPARAM;
+        const float *src = params + (size_t)pl->sh->topo.row_of_pos[p] * TRMC_NPARAM;
         for (int c = 0; c < TRMC_NPARAM; ++c) host[(size_t)c * np + p] = (T)src[c];
         const float cs = src[TRMC_P_CS];
         // (the operands of those divisions are made of bw, the side slope, n, ncc, twcc and the depth only)
@@ -23,11 +23,11 @@ template <class T> int upload_params(trmc_plan *pl, const float *params)
                && within(src[TRMC_P_S0], 0x1p-30f, 0x1p10f);
     }
     pl->params_sane = sane && sizeof(T) == 4;
-    if (int rc = pl->params.ensure(all_cols * sizeof(T))) return rc;
-    HIP_TRY(hipMemcpy(pl->params.p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
+    if (int rc = pl->sh->params.ensure(all_cols * sizeof(T))) return rc;
+    HIP_TRY(hipMemcpy(pl->sh->params.p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
     if (n > 0) {
         hipLaunchKernelGGL((k_make_const<T>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, pl->stream,
-                           (T *)pl->params.p, (int32_t)n, np);
+                           (T *)pl->sh->params.p, (int32_t)n, np);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(pl->stream));
     }
@@ -52,22 +52,29 @@ int use_device(const trmc_plan *pl)
 template <class F> inline int by_precision(const trmc_plan *pl, F &&f) { return pl->precision == 32 ? f(float()) : f(double()); }
 
 // `v` grown to n events: ones that time (hipEventCreate) or ones that only order streams (hipEventDisableTiming)
-inline int ensure_events(std::vector<hipEvent_t> &v, size_t n, bool timing)
+inline int ensure_events(std::vector<DevEvent> &v, size_t n, bool timing)
 {
     while (v.size() < n) {
-        hipEvent_t e = nullptr;
-        if (timing) HIP_TRY(hipEventCreate(&e));
-        else HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        v.push_back(e);
+        DevEvent e;
+        if (int rc = e.ensure(timing)) return rc;
+        v.push_back(std::move(e));
     }
     return 0;
+}
+
+// the stream the tiles run on (k_mc_tile, k_mc_ctile) and its "every tile queued so far is complete", made on first use.
+// Ordinary priority: between the tail's step launches (high) and the result transpose (low); one hardware queue each
+inline int ensure_tile_stream(trmc_plan *pl)
+{
+    if (int rc = pl->wstream.ensure(hipStreamNonBlocking)) return rc;
+    return pl->ev_tail.ensure(false);
 }
 
 // a kernel that reads the result planes of the last window has just been queued on the plan's stream (outside a window)
 int note_gather(trmc_plan *pl, bool also_in_window = false)
 {
     if (pl->run.active && !also_in_window) return 0;
-    if (!pl->ev_gather) HIP_TRY(hipEventCreateWithFlags(&pl->ev_gather, hipEventDisableTiming));
+    if (int rc = pl->ev_gather.ensure(false)) return rc;
     HIP_TRY(hipEventRecord(pl->ev_gather, pl->stream));
     pl->gather_pending = true;
     return 0;
@@ -110,11 +117,11 @@ template <class T> StepArgs<T> step_args(trmc_plan *pl, int nsteps, int qts)
     a.res_da_carry = nullptr; // (a stream of days with reservoir data assimilation: stream_args)
     a.slot_rda = 0;
     a.res_t_end = 0.0f;
-    a.up_ptr = (const int32_t *)pl->up_ptr.p;
-    a.up_idx = (const int32_t *)pl->up_idx.p;
-    a.up2 = (const int2 *)pl->up2.p;
-    a.level = (const int32_t *)pl->level.p;
-    a.lag = pl->maxlag > 0 ? (const int32_t *)pl->lag.p : nullptr;
+    a.up_ptr = (const int32_t *)pl->sh->up_ptr.p;
+    a.up_idx = (const int32_t *)pl->sh->up_idx.p;
+    a.up2 = (const int2 *)pl->sh->up2.p;
+    a.level = (const int32_t *)pl->sh->level.p;
+    a.lag = pl->maxlag > 0 ? (const int32_t *)pl->sh->lag.p : nullptr;
     a.it_prev = (uint8_t *)pl->it_prev.p;
     a.it_sum = pl->collect_cost ? (uint16_t *)pl->it_sum.p : nullptr;
     a.sane = pl->params_sane;
@@ -140,7 +147,7 @@ template <class T> StepArgs<T> step_args(trmc_plan *pl, int nsteps, int qts)
     a.nsteps = nsteps;
     a.qts = qts;
     a.out = (T *)pl->out.p;
-    a.row_of_pos = (const int32_t *)pl->row_of_pos.p;
+    a.row_of_pos = (const int32_t *)pl->sh->row_of_pos.p;
     a.out_vec = sizeof(T) == 4 && nsteps % 4 == 0 && pl->run.wide_k % 4 == 0;
     a.cls_last = nullptr; // (tile_args switches the in-block partition on for the tiles of a window or a stream)
     return a;
@@ -175,7 +182,7 @@ inline int tile_setup(trmc_plan *pl, hipStream_t st, int32_t W)
     if (int rc = pl->cls_last.ensure(np)) return rc;
     if (fresh) HIP_TRY(hipMemsetAsync(pl->cls_last.p, 0, np, st));
     if (!tile_hot_rows_on(pl, W)) return 0;
-    const int32_t rows = pl->topo.lvl_ptr[W] - pl->topo.lvl_ptr[0];
+    const int32_t rows = pl->sh->topo.lvl_ptr[W] - pl->sh->topo.lvl_ptr[0];
     const int32_t cap = std::max<int32_t>(kTileBlock, (rows / 32 + kTileBlock - 1) / kTileBlock * kTileBlock);
     if (pl->hot_cap != cap || !pl->hot_list.p) {
         const size_t hl = ((size_t)3 * cap + 2 * np) * sizeof(int32_t); // (lists + the two mark columns, k_mc_tile)
@@ -297,15 +304,15 @@ template <class T> int emit_tiles_through(trmc_plan *pl, int32_t t_complete) // 
         HIP_TRY(hipStreamWaitEvent(pl->stream2, pl->tile_ev[r.tiles_done], 0));
         // (rows of the wide levels wrote their results themselves, k_mc_tile: their positions are left out)
         // (with cluster tiles every routed row has: only boundary rows are left to this pass)
-        const int32_t skip_lo = (r.wide > 0 || r.cl) ? pl->topo.lvl_ptr[0] : 0;
-        const int32_t skip_hi = r.cl ? pl->topo.lvl_ptr[pl->topo.nlevels] : (r.wide > 0 ? pl->topo.lvl_ptr[r.wide + r.mid] : 0);
+        const int32_t skip_lo = (r.wide > 0 || r.cl) ? pl->sh->topo.lvl_ptr[0] : 0;
+        const int32_t skip_hi = r.cl ? pl->sh->topo.lvl_ptr[pl->sh->topo.nlevels] : (r.wide > 0 ? pl->sh->topo.lvl_ptr[r.wide + r.mid] : 0);
         const int32_t shift_from = (skip_lo + 63) / 64 * 64, shift = std::max(0, (skip_hi - shift_from) / 64 * 64);
         const int32_t n_emit = n - shift;
         if (n_emit > 0) {
             const int32_t tb = r.tiles_done * kTile, te = min(nsteps, tb + kTile);
             hipLaunchKernelGGL((k_emit<T>), dim3((n_emit + 63) / 64, (unsigned)((te - tb + kEmitSteps - 1) / kEmitSteps)),
                                dim3(kBlock), 0, pl->stream2, q_tm, q_tm + plane, q_tm + 2 * plane,
-                               (const int32_t *)pl->row_of_pos.p, (T *)pl->out.p, n, pl->nseg_pad, nsteps, tb, te, shift_from, shift,
+                               (const int32_t *)pl->sh->row_of_pos.p, (T *)pl->out.p, n, pl->nseg_pad, nsteps, tb, te, shift_from, shift,
                                skip_lo, skip_hi);
         }
         ++r.tiles_done;
@@ -315,7 +322,7 @@ template <class T> int emit_tiles_through(trmc_plan *pl, int32_t t_complete) // 
 
 template <class T> int route_begin_t(trmc_plan *pl, int nsteps, int qts, int short_ts)
 {
-    const trmc::Topology &tp = pl->topo;
+    const trmc::Topology &tp = pl->sh->topo;
     const int32_t n = (int32_t)pl->nseg;
     const int64_t np = pl->nseg_pad;
     hipStream_t st = pl->stream;
@@ -333,7 +340,7 @@ template <class T> int route_begin_t(trmc_plan *pl, int nsteps, int qts, int sho
         pl->cost_nsteps = nsteps;
     }
     StepArgs<T> a = step_args<T>(pl, nsteps, qts);
-    const int32_t *row_of_pos = (const int32_t *)pl->row_of_pos.p;
+    const int32_t *row_of_pos = (const int32_t *)pl->sh->row_of_pos.p;
     constexpr int32_t kTile = TRMC_EMIT_TILE;
     const int32_t ntiles = (nsteps + kTile - 1) / kTile;
     if (int rc = ensure_events(pl->tile_ev, (size_t)std::max(0, ntiles), false)) return rc;
@@ -453,11 +460,7 @@ template <class T> int route_begin_t(trmc_plan *pl, int nsteps, int qts, int sho
             r.mid = M;
             r.mid_k = M > 0 ? std::max(1, std::min(r.wide_k, pl->opt.mid_k)) : 0;
             r.cl_next = W;
-            if (!pl->wstream) {
-                // ordinary priority: between the tail's step launches (high) and the result transpose (low); one hardware queue each
-                HIP_TRY(hipStreamCreateWithFlags(&pl->wstream, hipStreamNonBlocking));
-                HIP_TRY(hipEventCreateWithFlags(&pl->ev_tail, hipEventDisableTiming));
-            }
+            if (int rc = ensure_tile_stream(pl)) return rc;
             HIP_TRY(hipStreamWaitEvent(pl->wstream, pl->ev[1], 0)); // the tiles start behind the window's set-up
             const size_t ntile = (size_t)std::max(1, (nsteps + r.wide_k - 1) / r.wide_k + W - 1);
             if (int rc = ensure_events(pl->wide_t0, ntile, true)) return rc; // (only the first is used: a tile starts where the one before it ended)
@@ -488,7 +491,7 @@ template <class T> int route_end_queue(trmc_plan *pl)
 
 template <class T> int route_advance_t(trmc_plan *pl, int t_end)
 {
-    const trmc::Topology &tp = pl->topo;
+    const trmc::Topology &tp = pl->sh->topo;
     RouteRun &r = pl->run;
     constexpr int32_t kTile = TRMC_EMIT_TILE;
     const int32_t nsteps = r.nsteps, t0 = r.t_done;
@@ -523,7 +526,7 @@ template <class T> int route_advance_t(trmc_plan *pl, int t_end)
             // what the tiles of this window are launched with: the in-block partition and the hot rows (tile_setup: made and
             // cleared on the first call only), the decimated output
             StepArgs<T> at = a;
-            if (r.cl) at.level = (const int32_t *)pl->lagk.p; // (tiles every position runs behind: the level in the slices)
+            if (r.cl) at.level = (const int32_t *)pl->sh->lagk.p; // (tiles every position runs behind: the level in the slices)
             if (pl->out_stride > 0 && nsteps / pl->out_stride >= 1) {
                 r.dec_stride = pl->out_stride;
                 r.dec_keep = nsteps / pl->out_stride;
@@ -593,7 +596,7 @@ template <class T> int route_advance_t(trmc_plan *pl, int t_end)
                 const int32_t C = tp.ncl;
                 const int32_t te = std::min(t_end, nsteps);
                 const int32_t j_end = te <= 0 ? W - 1 : W + C - 1 + (te + K - 1) / K - 1;
-                const int32_t *cblk_ptr = (const int32_t *)pl->cblk_ptr.p;
+                const int32_t *cblk_ptr = (const int32_t *)pl->sh->cblk_ptr.p;
                 StepArgs<T> ac = at;
                 ac.hot_list = ac.hot_cnt = nullptr;
                 for (; r.cl_next <= j_end; ++r.cl_next) {
@@ -681,7 +684,7 @@ template <class T> int route_advance_t(trmc_plan *pl, int t_end)
 
 template <class T> int route_end_t(trmc_plan *pl)
 {
-    const trmc::Topology &tp = pl->topo;
+    const trmc::Topology &tp = pl->sh->topo;
     RouteRun &r = pl->run;
     const int32_t nsteps = r.nsteps;
     if (int rc = route_end_queue<T>(pl)) return rc;

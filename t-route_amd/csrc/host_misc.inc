@@ -26,9 +26,6 @@ template <class T> int segments_t(int64_t n, const void *in, void *out, bool tol
         if (e == hipSuccess && iters_out) e = hipMemcpy(iters_out, dit.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(TRMC_EHIP, std::string("trmc_segments: ") + hipGetErrorString(e));
     }
-    din.release();
-    dout.release();
-    dit.release();
     return rc;
 }
 
@@ -90,7 +87,6 @@ int reservoir_da_steps(bool hybrid, int64_t n, int32_t ncol, const float *obs, c
         if (e == hipSuccess && !hybrid) e = hipMemcpy(iout, diout.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(TRMC_EHIP, std::string("trmc_reservoir_da_steps: ") + hipGetErrorString(e));
     }
-    for (DevBuf *b : {&dobs, &dtime, &dfin, &diin, &dfout, &diout}) b->release();
     return rc;
 }
 
@@ -108,19 +104,16 @@ k_chain_state(const T *__restrict__ sq, const T *__restrict__ sv, const T *__res
 }
 template <class T> int chain_from_t(trmc_plan *dst, trmc_plan *src, int nsteps_dst)
 {
-    const trmc::Topology &tp = src->topo;
+    const trmc::Topology &tp = src->sh->topo;
     const int64_t np = src->nseg_pad;
     const int32_t ns = src->run.nsteps;
     const size_t plane_s = (size_t)(ns + 1) * np, plane_d = (size_t)(nsteps_dst + 1) * np;
     if (int rc = dst->tm.ensure(3 * plane_d * sizeof(T))) return rc;
     const T *sq = (const T *)src->tm.p + (size_t)ns * np, *sv = sq + plane_s, *sd = sv + plane_s;
     T *dq = (T *)dst->tm.p, *dv = dq + plane_d, *dd = dv + plane_d;
-    for (int i = 0; i < 4; ++i)
-        if (!dst->ev_chain[i]) HIP_TRY(hipEventCreateWithFlags(&dst->ev_chain[i], hipEventDisableTiming));
-    if (!dst->wstream) {
-        HIP_TRY(hipStreamCreateWithFlags(&dst->wstream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&dst->ev_tail, hipEventDisableTiming));
-    }
+    for (DevEvent &e : dst->ev_chain)
+        if (int rc = e.ensure(false)) return rc;
+    if (int rc = ensure_tile_stream(dst)) return rc;
     // the rows of the source's wide levels are final when its last tile is (they never wrote a velocity row: the velocity
     // of the initial state is not an input of the step); the other rows when its tail is
     const int32_t W = src->run.short_ts ? src->run.wide : 0, M = W > 0 ? src->run.mid : 0;
@@ -139,7 +132,7 @@ template <class T> int chain_from_t(trmc_plan *dst, trmc_plan *src, int nsteps_d
         // has ended, so the receiver's leading levels started after the source's whole window instead of behind its last
         // tile (the timeline of bench.py's sequence showed exactly that).  The source takes the events (its own objects)
         // and waits for them at its next trmc_route_begin -- a window later, when they have long fired.
-        if (!src->ev_released[0]) HIP_TRY(hipEventCreateWithFlags(&src->ev_released[0], hipEventDisableTiming));
+        if (int rc = src->ev_released[0].ensure(false)) return rc;
         HIP_TRY(hipEventRecord(src->ev_released[0], dst->wstream));
         src->released_pending[0] = true;
         // ... and the receiver's own stream does not read time row 0 of the wide rows before this copy has written it: its
@@ -153,7 +146,7 @@ template <class T> int chain_from_t(trmc_plan *dst, trmc_plan *src, int nsteps_d
     // (rows routed by cluster tiles wrote no velocity row either)
     if (s1 > m1) hipLaunchKernelGGL((k_chain_state<T>), dim3(blocks_for(s1 - m1)), dim3(kBlock), 0, dst->stream, sq, src->run.cl ? sq : sv, sd, dq, dv, dd, m1, s1);
     HIP_TRY(hipEventRecord(dst->ev_chain[3], dst->stream));
-    if (!src->ev_released[1]) HIP_TRY(hipEventCreateWithFlags(&src->ev_released[1], hipEventDisableTiming));
+    if (int rc = src->ev_released[1].ensure(false)) return rc;
     HIP_TRY(hipEventRecord(src->ev_released[1], dst->stream));
     src->released_pending[1] = true;
     HIP_TRY(hipGetLastError());
@@ -229,12 +222,12 @@ int check_device(int device)
 // trmc_window_courant / trmc_window_courant_summary (abi.inc): k_window_courant's arguments up to its destinations ...
 template <class T> int window_courant_args(trmc_plan *pl, int32_t rowset, CourantArgs<T> &a)
 {
-    a.par = (const T *)pl->params.p;
+    a.par = (const T *)pl->sh->params.p;
     a.nseg_pad = pl->nseg_pad;
-    a.up_ptr = (const int32_t *)pl->up_ptr.p;
-    a.up_idx = (const int32_t *)pl->up_idx.p;
-    a.row_of_pos = (const int32_t *)pl->row_of_pos.p;
-    a.pos_of_row = (const int32_t *)pl->pos_of_row.p;
+    a.up_ptr = (const int32_t *)pl->sh->up_ptr.p;
+    a.up_idx = (const int32_t *)pl->sh->up_idx.p;
+    a.row_of_pos = (const int32_t *)pl->sh->row_of_pos.p;
+    a.pos_of_row = (const int32_t *)pl->sh->pos_of_row.p;
     a.res_of_pos = pl->nres > 0 ? (const int32_t *)pl->res_of_pos.p : nullptr;
     const bool raw = pl->ngage > 0 && pl->nraw > 0 && !pl->run.short_ts;
     a.raw_of_pos = raw ? (const int32_t *)pl->raw_of_pos.p : nullptr;
@@ -254,7 +247,7 @@ template <class T> int window_courant_args(trmc_plan *pl, int32_t rowset, Couran
     }
     a.rowset_pos = rowset < 0 ? nullptr : (const int32_t *)pl->rowsets[(size_t)rowset].p;
     a.nrows = rowset < 0 ? pl->nseg : pl->rowset_n[(size_t)rowset];
-    a.nboundary = (int32_t)pl->topo.nboundary;
+    a.nboundary = (int32_t)pl->sh->topo.nboundary;
     a.nsteps = pl->routed_nsteps;
     a.qts = pl->run.qts;
     a.short_ts = pl->run.short_ts;

@@ -92,9 +92,21 @@ struct StreamProd {
     void *host[P_N] = {};         // the day's destinations (NULL: not asked for)
     int32_t rowset = -1;
     bool queued = false;          // the gathers and copies of this day are queued
-    hipEvent_t ev_done = nullptr; // ... and this fires when they are through
+    DevEvent ev_done;             // ... and this fires when they are through
 };
+// The order of the members is the order of teardown, reversed, as in trmc_plan: the forcing's stream and the events at the top go
+// last, behind the buffers (hipFree waits for the device).  The plan destroys this before anything of its own.
 struct StreamRun {
+    DevStream fst;                      // the forcing's own stream (H2D + its reordering; the products leave on the plan's copy stream)
+    DevEvent ev_begin, ev_bnd, ev_gat;
+    DevEvent ev_total;                  // (the totals over the days) the last fold queued is through
+    std::vector<DevEvent> ev_slab;      // ring: "slab launch g is complete" (the cluster launch g + 1 waits for it)
+    std::vector<DevEvent> ev_free;      // [slots] the day that used the slot has handed its products over
+    std::vector<DevEvent> ev_ready;     // [slots] the gathers of that day are through (copy stream waits)
+    std::vector<DevEvent> ev_forcing;   // [slots] the slot's forcing (and boundary rows) are in place
+    std::vector<DevEvent> ev_t0, ev_t1; // [slots] around the launches of the day's push on the stream that carries the slices (timing)
+    std::vector<StreamProd> prod;       // [slots]
+    HostBlock rda_stage;                // page-locked host image of every slot's reservoir-DA tables (the copy runs beside the launches)
     bool active = false;
     int32_t nsteps = 0, qts = 1, K = 0, tpd = 0, slots = 0, W = 0, C = 0, lmax = 0;
     int64_t nq = 0;
@@ -121,8 +133,6 @@ struct StreamRun {
     size_t slot_rda = 0;           // bytes of a slot's tables
     float t_end = 0.0f;            // float(nsteps) * float(routing period): what a day's end takes off the times
     DevBuf rda_tab, rda_carry;     // [slots][slot_rda]; ResDaState [nres]
-    void *rda_stage = nullptr;     // page-locked host image of every slot's tables (the copy runs beside the launches)
-    size_t rda_stage_bytes = 0;
     // the per-row summary of a day (see the head of this file).  sum_want: trmc_stream_set_summary, it outlives a stream as the gage
     // rows do; sum: the mask of the stream in progress
     int32_t sum_want = 0, sum = 0;
@@ -134,41 +144,12 @@ struct StreamRun {
     // the steps are int64 here); tot_days days are folded in (queued)
     DevBuf tot[P_N - P_PEAK];
     int64_t tot_days = 0;
-    hipEvent_t ev_total = nullptr; // the last fold queued is through
-    std::vector<hipEvent_t> ev_slab;    // ring: "slab launch g is complete" (the cluster launch g + 1 waits for it)
-    std::vector<hipEvent_t> ev_free;    // [slots] the day that used the slot has handed its products over
-    std::vector<hipEvent_t> ev_ready;   // [slots] the gathers of that day are through (copy stream waits)
-    std::vector<hipEvent_t> ev_forcing; // [slots] the slot's forcing (and boundary rows) are in place
-    std::vector<hipEvent_t> ev_t0, ev_t1; // [slots] around the launches of the day's push on the stream that carries the slices (timing)
-    std::vector<StreamProd> prod;       // [slots]
-    hipEvent_t ev_begin = nullptr, ev_bnd = nullptr, ev_gat = nullptr;
     bool bnd_pending = false;
-    hipStream_t fst = nullptr;          // the forcing's own stream (H2D + its reordering; the products leave on the plan's copy stream)
 };
 
 } // extern "C++"
-
-static void stream_release(trmc_plan *pl)
-{
-    StreamRun *S = pl->seq;
-    if (!S) return;
-    for (DevBuf *b : {&S->tm, &S->qlat, &S->out, &S->dec, &S->da_mode, &S->da_a, &S->da_w, &S->da_q0, &S->gage_of_pos, &S->gage_pos_dev, &S->rda_tab,
-                       &S->rda_carry, &S->pkd_d, &S->pkd_at})
-        b->release();
-    for (StreamProdRow &t : S->tab) t.buf.release();
-    for (DevBuf &b : S->tot) b.release();
-    if (S->rda_stage) (void)hipHostFree(S->rda_stage);
-    for (auto *v : {&S->ev_slab, &S->ev_free, &S->ev_ready, &S->ev_forcing, &S->ev_t0, &S->ev_t1})
-        for (hipEvent_t e : *v)
-            if (e) (void)hipEventDestroy(e);
-    for (StreamProd &p : S->prod)
-        if (p.ev_done) (void)hipEventDestroy(p.ev_done);
-    for (hipEvent_t e : {S->ev_begin, S->ev_bnd, S->ev_gat, S->ev_total})
-        if (e) (void)hipEventDestroy(e);
-    if (S->fst) (void)hipStreamDestroy(S->fst);
-    delete S;
-    pl->seq = nullptr;
-}
+trmc_plan::trmc_plan() = default;
+trmc_plan::~trmc_plan() = default;
 
 extern "C++" {
 namespace {
@@ -289,7 +270,7 @@ template <class T> StepArgs<T> stream_args(trmc_plan *pl, const StreamRun &S, in
     a.qlat_tm = (const T *)S.qlat.p;
     a.out = S.want_out ? (T *)S.out.p : nullptr;
     a.out_vec = sizeof(T) == 4 && S.nsteps % 4 == 0 && S.K % 4 == 0;
-    a.level = pl->topo.ncl > 0 ? (const int32_t *)pl->lagk.p : (const int32_t *)pl->level.p;
+    a.level = pl->sh->topo.ncl > 0 ? (const int32_t *)pl->sh->lagk.p : (const int32_t *)pl->sh->level.p;
     a.seq_slots = S.slots;
     a.seq_tpd = S.tpd;
     a.seq_days = (int32_t)days;
@@ -361,17 +342,17 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
                            (const int32_t *)pl->rowsets[(size_t)p.rowset].p, (T *)at(P_HYD), nrows, pl->nseg_pad, S.nsteps, 1);
     }
     if (bytes[P_Q0])
-        hipLaunchKernelGGL((k_final_state<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, q, d, (const int32_t *)pl->row_of_pos.p,
+        hipLaunchKernelGGL((k_final_state<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, q, d, (const int32_t *)pl->sh->row_of_pos.p,
                            (T *)at(P_Q0), (int32_t)pl->nseg, pl->nseg_pad, S.nsteps, 1, S.nsteps);
     T *const sum_peak = (T *)at(P_PEAK, want_peak), *const sum_mean = (T *)at(P_MEAN, want_mean), *const sum_pd = (T *)at(P_PD, want_pd);
     int32_t *const sum_step = (int32_t *)at(P_STEP, want_peak), *const sum_pds = (int32_t *)at(P_PDS, want_pd);
     if (want_peak || want_mean)
-        hipLaunchKernelGGL((k_stream_summary<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, q, (const int32_t *)pl->row_of_pos.p, sum_peak,
+        hipLaunchKernelGGL((k_stream_summary<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, q, (const int32_t *)pl->sh->row_of_pos.p, sum_peak,
                            sum_step, sum_mean, (int32_t)pl->nseg, pl->nseg_pad, S.nsteps);
     if (want_pd && S.carry)
         hipLaunchKernelGGL((k_stream_peak_depth<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, (const T *)S.pkd_d.p + (size_t)slot * (size_t)pl->nseg_pad,
-                           (const int32_t *)S.pkd_at.p + (size_t)slot * (size_t)pl->nseg_pad, (const int32_t *)pl->row_of_pos.p, sum_pd, sum_pds,
-                           (int32_t)pl->nseg, (int32_t)pl->topo.nboundary);
+                           (const int32_t *)S.pkd_at.p + (size_t)slot * (size_t)pl->nseg_pad, (const int32_t *)pl->sh->row_of_pos.p, sum_pd, sum_pds,
+                           (int32_t)pl->nseg, (int32_t)pl->sh->topo.nboundary);
     else if (want_pd)
         hipLaunchKernelGGL((k_stream_peak_depth_out<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, (const T *)S.out.p + (size_t)slot * S.slot_out,
                            sum_pd, sum_pds, (int32_t)pl->nseg, S.nsteps);
@@ -403,7 +384,7 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
 // plan's own (cluster launch g waits for slab launch g - 1: k_mc_ctile); days that reach their end are handed over
 template <class T> int stream_launch(trmc_plan *pl, StreamRun &S, int64_t g_from, int64_t g_to, int64_t days)
 {
-    const trmc::Topology &tp = pl->topo;
+    const trmc::Topology &tp = pl->sh->topo;
     const bool tol = pl->opt.tol;
     // (trmc_plan_options.stream_split = s > 0: the slices from level s on are a launch of their own on the clusters' stream, in front of
     // the cluster blocks -- two chains of launches whose ends do not coincide, each filling the device while the other drains)
@@ -446,7 +427,7 @@ template <class T> int stream_launch(trmc_plan *pl, StreamRun &S, int64_t g_from
                 ++S.launches;
             }
             if (ncblk > 0) {
-                launch_ctile<T>(cst, a, (const int32_t *)pl->cblk_ptr.p, 0, ncblk, tile, S.K, tol, pk_d, pk_at);
+                launch_ctile<T>(cst, a, (const int32_t *)pl->sh->cblk_ptr.p, 0, ncblk, tile, S.K, tol, pk_d, pk_at);
                 ++S.launches;
             }
         }
@@ -465,8 +446,8 @@ template <class T> int stream_launch(trmc_plan *pl, StreamRun &S, int64_t g_from
 
 template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int slots, int full_output, int output_stride)
 {
-    const trmc::Topology &tp = pl->topo;
-    if (!pl->seq) pl->seq = new StreamRun();
+    const trmc::Topology &tp = pl->sh->topo;
+    if (!pl->seq) pl->seq = std::make_unique<StreamRun>();
     StreamRun &S = *pl->seq;
     const int32_t K = pl->opt.wide_k > 0 ? pl->opt.wide_k : 16;
     if (nsteps % K != 0) return fail(TRMC_EINVAL, "a stream of windows needs nsteps to be a multiple of the plan's wide_k (" + std::to_string(K) + ")");
@@ -565,7 +546,8 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
     }
     S.tab[P_FVD].base = (char *)(S.dec_stride > 0 ? S.dec.p : S.out.p);
     if (S.rda) S.tab[P_RDA_IDX].base = S.tab[P_RDA].base + rda4;
-    if (tot && !S.ev_total) HIP_TRY(hipEventCreateWithFlags(&S.ev_total, hipEventDisableTiming));
+    if (tot)
+        if (int rc = S.ev_total.ensure(false)) return rc;
     // reservoir data assimilation: the slots' tables at their capacity, the carry with the state trmc_set_reservoir_da supplied
     // (or the plan's last window left in those tables); the days' state records are products (P_RDA)
     S.slot_rda = 0;
@@ -583,13 +565,7 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
         S.t_end = (float)nsteps * (float)pl->res_dt;
         if (int rc = S.rda_tab.ensure((size_t)S.slots * S.slot_rda)) return rc;
         if (int rc = S.rda_carry.ensure((size_t)pl->nres * sizeof(trmc::ResDaState))) return rc;
-        if (S.rda_stage_bytes < (size_t)S.slots * S.slot_rda) {
-            if (S.rda_stage) (void)hipHostFree(S.rda_stage);
-            S.rda_stage = nullptr;
-            S.rda_stage_bytes = 0;
-            HIP_TRY(hipHostMalloc(&S.rda_stage, (size_t)S.slots * S.slot_rda, hipHostMallocDefault));
-            S.rda_stage_bytes = (size_t)S.slots * S.slot_rda;
-        }
+        if (int rc = S.rda_stage.ensure((size_t)S.slots * S.slot_rda)) return rc;
         HIP_TRY(hipStreamSynchronize(pl->stream)); // (a window routed with these tables has left its state in them)
         std::vector<trmc::ResDaRec> rec((size_t)pl->nres);
         HIP_TRY(hipMemcpy(rec.data(), pl->res_da.p, rec.size() * sizeof(trmc::ResDaRec), hipMemcpyDeviceToHost));
@@ -598,10 +574,7 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
         HIP_TRY(hipMemcpy(S.rda_carry.p, carry.data(), carry.size() * sizeof(trmc::ResDaState), hipMemcpyHostToDevice));
     }
     if (int rc = ensure_copy_stream(pl)) return rc;
-    if (!pl->wstream) {
-        HIP_TRY(hipStreamCreateWithFlags(&pl->wstream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&pl->ev_tail, hipEventDisableTiming));
-    }
+    if (int rc = ensure_tile_stream(pl)) return rc;
     if (int rc = ensure_events(S.ev_slab, kSlabEvents, false)) return rc;
     for (auto *v : {&S.ev_free, &S.ev_ready, &S.ev_forcing})
         if (int rc = ensure_events(*v, (size_t)S.slots, false)) return rc;
@@ -609,13 +582,12 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
         if (int rc = ensure_events(*v, (size_t)S.slots, true)) return rc;
     S.prod.resize((size_t)S.slots);
     for (StreamProd &p : S.prod) {
-        if (!p.ev_done) HIP_TRY(hipEventCreateWithFlags(&p.ev_done, hipEventDisableTiming));
+        if (int rc = p.ev_done.ensure(false)) return rc;
         p.day = -1;
         p.queued = false;
     }
-    if (!S.ev_begin) HIP_TRY(hipEventCreateWithFlags(&S.ev_begin, hipEventDisableTiming));
-    if (!S.ev_bnd) HIP_TRY(hipEventCreateWithFlags(&S.ev_bnd, hipEventDisableTiming));
-    if (!S.ev_gat) HIP_TRY(hipEventCreateWithFlags(&S.ev_gat, hipEventDisableTiming));
+    for (DevEvent *e : {&S.ev_begin, &S.ev_bnd, &S.ev_gat})
+        if (int rc = e->ensure(false)) return rc;
     S.bnd_pending = false;
     S.days_pushed = S.day_min = S.days_complete = 0;
     S.g_done = -1;
@@ -635,7 +607,7 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
     if (pl->nseg > 0) {
         T *q = (T *)S.tm.p;
         hipLaunchKernelGGL((k_init_state<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, st, (const T *)pl->in_q0.p,
-                           (const int32_t *)pl->row_of_pos.p, q, q + S.plane /* (the velocity of the state is not an input) */,
+                           (const int32_t *)pl->sh->row_of_pos.p, q, q + S.plane /* (the velocity of the state is not an input) */,
                            q + S.plane, (int32_t)pl->nseg);
     }
     // the in-block partition and the hot rows of the slices: made and cleared here, in front of ev_begin (the launches' arguments:
@@ -644,7 +616,7 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
     if (!tile_partition_on(pl)) pl->cls_last.release();
     HIP_TRY(hipEventRecord(S.ev_begin, st));
     HIP_TRY(hipStreamWaitEvent(pl->wstream, S.ev_begin, 0));
-    if (!S.fst) HIP_TRY(hipStreamCreateWithFlags(&S.fst, hipStreamNonBlocking));
+    if (int rc = S.fst.ensure(hipStreamNonBlocking)) return rc;
     HIP_TRY(hipStreamWaitEvent(S.fst, S.ev_begin, 0));
     HIP_TRY(hipStreamWaitEvent(pl->hstream, S.ev_begin, 0));
     HIP_TRY(hipGetLastError());
@@ -659,7 +631,7 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
     StreamRun &S = *pl->seq;
     const void *const qlat = day.qlat, *const boundary_q_dev = day.boundary_q_dev;
     const int32_t rowset = day.rowset;
-    const trmc::Topology &tp = pl->topo;
+    const trmc::Topology &tp = pl->sh->topo;
     const int64_t d = S.days_pushed;
     const int32_t slot = (int32_t)(d % S.slots);
     const size_t np = (size_t)pl->nseg_pad;
@@ -699,7 +671,7 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
         HIP_TRY(hipMemcpyAsync(pl->in_qlat.p, qlat, bytes, hipMemcpyHostToDevice, hst));
         const int32_t n = (int32_t)pl->nseg;
         hipLaunchKernelGGL((k_prep_qlat<T>), dim3((n + 63) / 64, (unsigned)((S.nq + 31) / 32)), dim3(kBlock), 0, hst, (const T *)pl->in_qlat.p,
-                           (const int32_t *)pl->row_of_pos.p, (T *)S.qlat.p + (size_t)slot * S.slot_qlat, n, pl->nseg_pad, (int32_t)S.nq);
+                           (const int32_t *)pl->sh->row_of_pos.p, (T *)S.qlat.p + (size_t)slot * S.slot_qlat, n, pl->nseg_pad, (int32_t)S.nq);
     }
     if (S.slot_da > 0) {
         // the day's nudging tables [ngage][nsteps] into the slot, beside its forcing: behind ev_free (the slot's last day has been
@@ -717,7 +689,7 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
     }
     if (S.rda) {
         // the day's reservoir tables into the slot, as the nudging tables: behind ev_free, in front of ev_forcing
-        float *const img = (float *)((char *)S.rda_stage + (size_t)slot * S.slot_rda);
+        float *const img = (float *)((char *)S.rda_stage.p + (size_t)slot * S.slot_rda);
         stream_rda_image(pl, S, *day.reservoir_da, img);
         HIP_TRY(hipMemcpyAsync((char *)S.rda_tab.p + (size_t)slot * S.slot_rda, img, S.slot_rda, hipMemcpyHostToDevice, hst));
     }
@@ -761,7 +733,7 @@ static int stream_gages_check(trmc_plan *pl, const std::vector<int32_t> &gage_po
     HIP_TRY(hipMemcpy(res_of_pos.data(), pl->res_of_pos.p, res_of_pos.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (const int32_t p : gage_pos)
         if (res_of_pos[(size_t)p] >= 0)
-            return fail(TRMC_EINVAL, "a gage on a reservoir row is not supported (row " + std::to_string(pl->topo.row_of_pos[(size_t)p]) + ")");
+            return fail(TRMC_EINVAL, "a gage on a reservoir row is not supported (row " + std::to_string(pl->sh->topo.row_of_pos[(size_t)p]) + ")");
     return 0;
 }
 
@@ -779,7 +751,7 @@ int trmc_stream_begin(trmc_plan *pl, int nsteps, int qts_subdivisions, int slots
     if (int rc = stream_check(pl, false)) return rc;
     if (pl->flow) return fail(TRMC_EINVAL, "a stream of windows runs on the level engine");
     if (pl->run.active) return fail(TRMC_ESTATE, "a routing window is in progress");
-    const trmc::Topology &tp = pl->topo;
+    const trmc::Topology &tp = pl->sh->topo;
     if (!(tp.ncl > 0 || (tp.cl_rows > 0 && tp.cl_from_level == tp.nlevels)))
         return fail(TRMC_EINVAL, "a stream of windows needs a plan in cluster order (TRMC_PLAN_SHORT_TS on the level engine, "
                                  "trmc_plan_options.cluster_rows >= 0): every row is then routed in tiles");
@@ -813,7 +785,7 @@ int trmc_stream_set_gages(trmc_plan *pl, int64_t ngage, const int64_t *gage_rows
     if (pl->flow) return fail(TRMC_EINVAL, "a stream of windows runs on the level engine");
     if (ngage < 0) return fail(TRMC_EINVAL, "ngage < 0");
     if (ngage > 0 && !gage_rows) return fail(TRMC_EINVAL, "gage_rows is NULL");
-    if (!pl->seq) pl->seq = new StreamRun();
+    if (!pl->seq) pl->seq = std::make_unique<StreamRun>();
     StreamRun &S = *pl->seq;
     S.ngage = 0;
     S.gage_pos.clear();
@@ -822,8 +794,8 @@ int trmc_stream_set_gages(trmc_plan *pl, int64_t ngage, const int64_t *gage_rows
     for (int64_t g = 0; g < ngage; ++g) {
         const int64_t r = gage_rows[g];
         if (r < 0 || r >= pl->nseg) return fail(TRMC_EINVAL, "gage row out of range");
-        if (pl->topo.level_of_row[r] < 0) return fail(TRMC_EINVAL, "gage on a boundary row");
-        pos[(size_t)g] = pl->topo.pos_of_row[r];
+        if (pl->sh->topo.level_of_row[r] < 0) return fail(TRMC_EINVAL, "gage on a boundary row");
+        pos[(size_t)g] = pl->sh->topo.pos_of_row[r];
         g_of_pos[(size_t)pos[(size_t)g]] = (int32_t)g; // one gage per segment: the last listed wins (trmc_set_nudging)
     }
     if (int rc = stream_gages_check(pl, pos)) return rc;
@@ -842,7 +814,7 @@ int trmc_stream_set_reservoir_da(trmc_plan *pl, int on, int64_t usgs_ncol, int64
         return fail(TRMC_EINVAL, "a table's column capacity must be >= 0 (0: as many as the declared table has)");
     if (on)
         if (int rc = reservoir_da_plan_check(pl)) return rc;
-    if (!pl->seq) pl->seq = new StreamRun();
+    if (!pl->seq) pl->seq = std::make_unique<StreamRun>();
     StreamRun &S = *pl->seq;
     S.rda_want = on != 0;
     S.rda_cap_want[0] = usgs_ncol;
@@ -860,7 +832,7 @@ int trmc_stream_set_summary(trmc_plan *pl, int what)
         return fail(TRMC_EINVAL, "what: a mask of TRMC_SUMMARY_PEAK, TRMC_SUMMARY_MEAN, TRMC_SUMMARY_PEAK_DEPTH and TRMC_SUMMARY_TOTAL (0: no summary)");
     if ((what & TRMC_SUMMARY_TOTAL) && !(what & parts))
         return fail(TRMC_EINVAL, "TRMC_SUMMARY_TOTAL needs at least one of the parts it totals (TRMC_SUMMARY_PEAK, TRMC_SUMMARY_MEAN, TRMC_SUMMARY_PEAK_DEPTH)");
-    if (!pl->seq) pl->seq = new StreamRun();
+    if (!pl->seq) pl->seq = std::make_unique<StreamRun>();
     pl->seq->sum_want = what;
     return 0;
 }
@@ -1012,7 +984,7 @@ int trmc_stream_boundary(trmc_plan *pl, int64_t day, const void *q_dev, int64_t 
 {
     if (int rc = stream_check(pl, true)) return rc;
     StreamRun &S = *pl->seq;
-    const trmc::Topology &tp = pl->topo;
+    const trmc::Topology &tp = pl->sh->topo;
     if (tp.nboundary == 0) return 0;
     if (!q_dev) return fail(TRMC_EINVAL, "q_dev is NULL");
     if (day < 0 || day >= S.days_pushed) return fail(TRMC_EINVAL, "the day has not been pushed");
@@ -1154,7 +1126,7 @@ int trmc_stream_end(trmc_plan *pl)
         const int rc = by_precision(pl, [&](auto t) -> int {
             using T = decltype(t);
             const T *q = (const T *)S.tm.p + (size_t)slot * S.slot_tm;
-            hipLaunchKernelGGL((k_final_state<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, q, q + S.plane, (const int32_t *)pl->row_of_pos.p,
+            hipLaunchKernelGGL((k_final_state<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, q, q + S.plane, (const int32_t *)pl->sh->row_of_pos.p,
                                (T *)pl->in_q0.p, (int32_t)pl->nseg, pl->nseg_pad, S.nsteps, 1, S.nsteps);
             HIP_TRY(hipGetLastError());
             return 0;

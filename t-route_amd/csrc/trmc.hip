@@ -33,9 +33,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <memory>
 #include <new>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/trmc.h"
@@ -77,45 +79,7 @@ namespace {
 #include "k_window_summary.inc"
 #include "k_window_courant.inc"
 // ---------------------------------------------------------------- plan
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    bool borrowed = false; // the memory belongs to another plan (trmc_plan_clone): never freed, never regrown here
-    void borrow(const DevBuf &o)
-    {
-        release();
-        p = o.p;
-        bytes = o.bytes;
-        borrowed = true;
-    }
-    int ensure(size_t need, bool zero_new = false)
-    {
-        if (need <= bytes) return 0;
-        if (borrowed) return fail(TRMC_ESTATE, "a buffer shared with the plan this one was cloned from would have to grow");
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-        hipError_t e = hipMalloc(&p, need ? need : 1);
-        if (e != hipSuccess) return fail(TRMC_ENOMEM, std::string("hipMalloc(") + std::to_string(need) + "): " + hipGetErrorString(e));
-        bytes = need;
-        if (zero_new && need) { // (granule planes: recycled memory must not hold a tag that could pass for a live one)
-            // (hipMemset of device memory may return before it has run, on the null stream -- which the plans'
-            // non-blocking streams do not wait for: without the synchronisation the fill can land AFTER the first
-            // kernels of a window have written into the buffer; seen with two processes sharing one GPU)
-            e = hipMemset(p, 0, need);
-            if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-            if (e != hipSuccess) return fail(TRMC_EHIP, std::string("hipMemset: ") + hipGetErrorString(e));
-        }
-        return 0;
-    }
-    void release()
-    {
-        if (p && !borrowed) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-        borrowed = false;
-    }
-};
+#include "dev_owner.hpp"
 
 } // namespace
 
@@ -141,29 +105,65 @@ struct RouteRun { // the routing window in progress (route_begin_t .. route_end_
     int32_t dec_lo = 0, dec_hi = 0;       // ... the plan positions [dec_lo, dec_hi) that do
 };
 
+// What a plan and its clones (trmc_plan_clone) share: the static data on the device and its host image.  Nothing writes it once
+// trmc_plan_create_opt has returned -- but trmc_plan_set_lag, which is refused on a clone and on a plan that has live clones.
+// It goes with the last plan that holds it.
+struct PlanShared {
+    trmc::Topology topo;
+    DevBuf params; // 9 columns x nseg_pad
+    DevBuf up_ptr, up_idx, up2, level, row_of_pos, pos_of_row, lag; // plan order
+    DevBuf lagk, cblk_ptr;               // cluster order (topology.hpp): tiles every position runs behind level 0; the cluster blocks
+    DevBuf prio;                         // (dataflow engine) issue priority per wavefront
+    DevBuf ticket_map;                   // [nblocks] ticket -> block of a general-mode plan with long main stems (topo.early_blocks)
+    DevBuf rank;                         // level rank of a position inside its block
+    DevBuf cuq_ptr, cuq_blk, cu_index, cuq_perm; // blocks dealt to compute units by cost (flow_place_blocks)
+};
+
 struct StreamRun;
+// THE DECLARATION ORDER IS THE ORDER OF TEARDOWN, reversed (members are destroyed last to first): the stream of windows goes
+// first (`seq`, the last member), then the plan's own device buffers -- hipFree waits for the device, so whatever was queued has
+// run by then -- then its hold on the shared block, and the events and streams at the very end.  So: streams and events stay at
+// the top, a new buffer goes below `sh`, and `seq` stays last.  trmc_plan_destroy is `delete`; nothing else releases anything.
 struct trmc_plan {
+    trmc_plan();  // (both defaulted in stream.inc, where StreamRun is complete)
+    ~trmc_plan();
+    DevStream stream;
+    DevEvent ev[4];
+    DevStream stream2;                   // result transpose, overlapped with the step launches
+    DevStream wstream;                   // the wide tiles (k_mc_tile), ordinary priority: the narrow tail of the level order runs one
+                                         // step per launch on the plan's own high-priority stream BESIDE them -- the tail's 288
+                                         // dependent launches are the latency-critical part, the tiles fill whatever they leave
+    DevEvent ev_tail;                    // "every tile queued so far is complete" (tile stream -> plan stream)
+    std::vector<DevEvent> wide_t0, wide_t1; // timing events around the wide launches of the window (trmc_stats.ms_wide)
+    std::vector<DevEvent> tile_ev;       // "time tile b is complete" (main stream -> stream2)
+    DevEvent ev_emit;                    // "all tiles emitted" (stream2 -> main stream)
+    DevEvent ev_chain[4];                // trmc_plan_chain_from: source's tiles / tail done; this plan's two copies done
+    // as the SOURCE of a hand-over: "the receiver has read my planes" (its two copies), waited for at my next trmc_route_begin
+    DevEvent ev_released[2];
+    DevStream fstream;                   // dataflow engine, second compute stream: consecutive time chunks of a resident window overlap
+    DevEvent ev_chunk[2];                // the last launch queued on {stream, fstream}
+    DevEvent ev_ctl;                     // ordering of the two compute streams against each other
+    DevEvent ev_dec;                     // "the copy stream has read `out`" (a fetch of the decimated result): the next window's
+                                         // set-up goes behind it (dec_pending)
+    DevStream cstream;                   // copy stream: D2H of window k runs beside the kernels of window k + 1
+    DevStream hstream;                   // ... and the one of the other direction: a staged forcing on its way to the device
+    DevEvent ev_fetch_ready, ev_fetch_done;
+    // "the last gather queued on the plan's stream after a window has read the planes" -- what a set-up queued on ANOTHER stream
+    // (TRMC_SETUP_ASIDE) waits for before it lets a new window's tiles overwrite them
+    DevEvent ev_gather;
+    DevEvent ev_wsum[2];                 // around the last trmc_window_summary's kernel (trmc_window_summary_kernel_ms)
+    DevEvent ev_cour[2];                 // ... and around the last trmc_window_courant / _summary's (trmc_window_courant_kernel_ms)
+    DevEvent ev_forcing;                 // trmc_stage_forcing: the next window's forcing is on its way to in_qlat on the copy stream
+    // trmc_plan_clone: a second set of WINDOW buffers on the static data of the plan it was made from
+    std::shared_ptr<PlanShared> sh;
+    bool is_clone = false;               // for its whole life, whoever else still holds `sh` (trmc_plan_set_lag)
     int device = 0;
     int precision = 32;
     size_t esz = 4;
-    trmc::Topology topo;
     int64_t nseg = 0, nseg_pad = 0, nrouted = 0;
     bool dt_uniform = true;
     double dt = 0.0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipStream_t stream2 = nullptr;       // result transpose, overlapped with the step launches
-    hipStream_t wstream = nullptr;       // the wide tiles (k_mc_tile), ordinary priority: the narrow tail of the level order runs one
-                                         // step per launch on the plan's own high-priority stream BESIDE them -- the tail's 288
-                                         // dependent launches are the latency-critical part, the tiles fill whatever they leave
-    hipEvent_t ev_tail = nullptr;        // "every tile queued so far is complete" (tile stream -> plan stream)
-    std::vector<hipEvent_t> wide_t0, wide_t1; // timing events around the wide launches of the window (trmc_stats.ms_wide)
-    std::vector<hipEvent_t> tile_ev;     // "time tile b is complete" (main stream -> stream2)
-    hipEvent_t ev_emit = nullptr;        // "all tiles emitted" (stream2 -> main stream)
-    // static, plan order
-    DevBuf params; // 9 columns x nseg_pad
-    DevBuf up_ptr, up_idx, up2, level, row_of_pos, pos_of_row, it_prev, lag;
-    DevBuf lagk, cblk_ptr;               // cluster order (topology.hpp): tiles every position runs behind level 0; the cluster blocks
+    DevBuf it_prev;
     DevBuf it_sum;                       // per-position cost of the window (trmc_plan_collect_cost)
     bool collect_cost = false;
     bool hinted = false;                 // created with a cost hint: rows of a level are grouped by cost
@@ -173,10 +173,7 @@ struct trmc_plan {
     int64_t wide_safe_pos = -1;          // first plan position that is lagged or fed by a boundary row (-1: not looked for yet)
     // trmc_plan_chain_from: the next window's initial state has been set on the device from another plan's window
     bool chain_staged = false;
-    hipEvent_t ev_chain[4] = {nullptr, nullptr, nullptr, nullptr}; // source's tiles / tail done; this plan's two copies done
-    // as the SOURCE of a hand-over: "the receiver has read my planes" (its two copies), waited for at my next trmc_route_begin
-    hipEvent_t ev_released[2] = {nullptr, nullptr};
-    bool released_pending[2] = {false, false};
+    bool released_pending[2] = {false, false}; // (ev_released)
     std::vector<int32_t> lag_of_row;
     DevBuf gage_of_pos, da_mode, da_a, da_w, da_nudge; // nudging tables of the staged window
     DevBuf res_of_pos, res_par, res_inflow;             // level-pool reservoirs of the plan
@@ -204,16 +201,11 @@ struct trmc_plan {
     bool flow = false;
     uint32_t tag_base = 1;               // tag of step 0 of the current window (0 is never a live tag)
     int32_t tag_span = 0;                // tags the current window may use (nsteps + 1)
-    DevBuf prio;                         // issue priority per wavefront
     DevBuf d_gran;                       // depth hand-over granules (k_mc_flow_lean)
-    hipStream_t fstream = nullptr;       // second compute stream: consecutive time chunks of a resident window overlap
-    hipEvent_t ev_chunk[2] = {nullptr, nullptr}; // the last launch queued on {stream, fstream}
-    hipEvent_t ev_ctl = nullptr;         // ordering of the two compute streams against each other
-    int flow_next = 0;                   // which of the two the next trmc_route_advance uses (only toggles in overlap mode)
+    int flow_next = 0;                   // which of the two compute streams the next trmc_route_advance uses (only toggles in overlap mode)
     int flow_last = 0;                   // ... and which one the last launch went to
-    DevBuf ticket_map;                   // [nblocks] ticket -> block of a general-mode plan with long main stems (topo.early_blocks)
-    DevBuf d_state, ticket, rank, dbg;   // depth column; {block ticket, abort flag}; level rank of a position inside its block
-    DevBuf cuq_ptr, cuq_blk, cuq_head, cu_index, cuq_perm; // blocks dealt to compute units by cost (flow_place_blocks); heads: one set per compute stream
+    DevBuf d_state, ticket, dbg;         // depth column; {block ticket, abort flag}
+    DevBuf cuq_head;                     // heads of the shared block's compute-unit queues: one set per compute stream
     int32_t ncuq = 0;                    // number of queues (= compute units found), 0 = block tickets
     uint64_t watchdog_ticks = 3000000000ull; // 30 s of wall_clock64 (100 MHz): long enough for a device that is shared or profiled (TRMC_FLOW_WATCHDOG_MS)
     // trmc_plan_options, resolved at creation (a clone copies them)
@@ -247,33 +239,17 @@ struct trmc_plan {
     int32_t nstamp_windows = 0;
     int64_t stamp_seq = -1;               // windows begun since the ring was set, minus one
     DevBuf fetch_hyd, fetch_q0, fetch_fvd;
-    hipEvent_t ev_dec = nullptr;         // "the copy stream has read `out`" (a fetch of the decimated result): the next window's
-    bool dec_pending = false;            // set-up goes behind it
-    hipStream_t cstream = nullptr;       // copy stream: D2H of window k runs beside the kernels of window k + 1
-    hipStream_t hstream = nullptr;       // ... and the one of the other direction: a staged forcing on its way to the device
-    hipEvent_t ev_fetch_ready = nullptr, ev_fetch_done = nullptr;
+    bool dec_pending = false;            // (ev_dec)
     bool fetch_pending = false;
-    // "the last gather queued on the plan's stream after a window has read the planes" -- what a set-up queued on ANOTHER stream
-    // (TRMC_SETUP_ASIDE) waits for before it lets a new window's tiles overwrite them
-    hipEvent_t ev_gather = nullptr;
-    bool gather_pending = false;
-    hipEvent_t ev_wsum[2] = {nullptr, nullptr}; // around the last trmc_window_summary's kernel (trmc_window_summary_kernel_ms)
+    bool gather_pending = false;         // (ev_gather)
     double wsum_ms = -1.0;
-    hipEvent_t ev_cour[2] = {nullptr, nullptr}; // ... and around the last trmc_window_courant / _summary's (trmc_window_courant_kernel_ms)
     double cour_ms = -1.0;
     bool row0_replaced = false;          // trmc_plan_chain_from has overwritten time row 0 -- the last window's initial state -- since it ended
-    // trmc_plan_clone: a second set of WINDOW buffers on the static data (topology, parameters) of `parent`
-    trmc_plan *parent = nullptr;
-    int32_t clones = 0;                  // live clones of this plan
-    bool zombie = false;                 // destroyed while clones were alive: freed with the last of them
-    // trmc_stage_forcing: the next window's forcing is on its way to in_qlat on the copy stream
-    hipEvent_t ev_forcing = nullptr;
-    bool forcing_pending = false;
+    bool forcing_pending = false;        // (ev_forcing)
     bool state_missing = false;          // ... and there is no initial state yet: trmc_plan_chain_from must supply it
     bool q0_staged = false;              // in_q0 holds the initial state of the window that is staged (an upload's q0, or the last
                                          // window's final state gathered by an upload with q0 = NULL / trmc_stage_forcing): valid
                                          // until a window consumes it, whatever routed_nsteps says in the meantime
-    struct StreamRun *seq = nullptr;     // trmc_stream_*: a stream of windows on a ring of day slots (stream.inc)
     DevBuf hot_list, hot_cnt;            // k_mc_tile's hot rows (StepArgs::hot_list): [3][hot_cap] positions, [3] lengths
     int32_t hot_cap = 0;
     bool nan_is_zero = false;            // uploads of forcing and state: NaN -> 0 on the device (trmc_plan_set_nan_is_zero)
@@ -283,6 +259,7 @@ struct trmc_plan {
     std::vector<int64_t> rowset_n;
     std::vector<int32_t> rowset_lag;
     std::vector<int32_t> rowset_lagk;   // cluster order: the largest tile lag among the set's rows (trmc_stream_gather)
+    std::unique_ptr<StreamRun> seq;     // trmc_stream_*: a stream of windows on a ring of day slots (stream.inc).  LAST: it goes first
 };
 
 namespace {
