@@ -729,6 +729,46 @@ int trmc_window_courant_summary(trmc_plan *plan, int32_t rowset, double limit, v
                                 int32_t *steps_over);
 int trmc_window_courant_tile(int precision, int32_t *rows, int32_t *steps);
 int trmc_window_courant_kernel_ms(const trmc_plan *plan, double *ms_out);
+/*
+ * Threshold exceedance of the last WINDOW: did a row go over its threshold -- bankfull, an action / flood stage, a recurrence
+ * flow --, when first, until when and for how long.  For an output row i, a quantity x (flow, velocity or depth: the columns 0,
+ * 1, 2 of the window's result out[row][t][c]) and a level k < K (1 <= K <= 4), with x[t], t = 1..nsteps, and the row's threshold
+ * th[row][k] in the plan's precision:  over(t) := x[t] > th, compared in the plan's precision -- false if either side is a NaN,
+ * and equality is not over.
+ *   steps_over[i][k]   number of t with over(t)
+ *   first_step[i][k]   the smallest such t, 1-based; 0 if none
+ *   last_step[i][k]    the largest such t; 0 if none
+ *   longest_run[i][k]  length of the longest run of consecutive t with over(t); 0 if none
+ * All four int32 [nrows][K], row-major.  The levels need not be ascending.  -inf is always over: (nsteps, 1, nsteps, nsteps);
+ * +inf and a NaN never are.  EVERY step of the window is seen, whatever trmc_plan_set_output_stride keeps of the block.
+ *   trmc_plan_set_thresholds   th: host array [nseg][nlevels], row order, the plan's precision; copied to a device table the plan
+ *                              handle owns, so thresholds -- static per network -- cross PCIe once, not once per window, and stay
+ *                              across windows until replaced.  nlevels == 0 or th == NULL clears the table; nlevels outside 0..4
+ *                              is TRMC_EINVAL; TRMC_ESTATE while a window is open or a stream of windows is in progress.  Per
+ *                              handle: a clone (trmc_plan_clone) has none until they are set on it, as with reservoir and
+ *                              nudging tables and row sets.
+ *   trmc_window_exceedance     quantity: TRMC_X_*.  rowset as in trmc_window_summary (-1: every row in row order); a set's row i
+ *                              is compared with the thresholds of the row it names.  Any destination may be NULL (all NULL:
+ *                              TRMC_EINVAL); only those asked for are formed.  Valid and refused as trmc_window_summary, plus
+ *                              TRMC_ESTATE with no thresholds set and TRMC_EINVAL for an unknown quantity or row set.
+ *                              Synchronous: one kernel (csrc/k_window_exceed.inc) on the plan's stream behind the window, then
+ *                              the columns to the host.  nseg == 0 writes nothing.  Independent of trmc_window_summary and
+ *                              trmc_window_courant*: the three may follow one window in any order.
+ *   trmc_window_exceedance_tile, trmc_window_exceedance_kernel_ms   as trmc_window_summary_tile / _kernel_ms.  Host only.
+ *   trmc_plan_bankfull_depth   dst[nseg], row order, the plan's precision: the bankfull depth the step kernels use (the plan's own
+ *                              column; MUSKINGCUNGE f90:55-61:  bw > tw: bw / 0.00001;  bw == tw: bw / (2 z);  else (tw - bw) /
+ *                              (2 z), with z = 1 / cs, 1 where cs == 0).  Rows that route no Muskingum-Cunge step at the time of
+ *                              the call -- boundary rows, rows declared by trmc_set_reservoirs: a pool's elevation has no
+ *                              bankfull -- get +inf.  "Out of bank" is then quantity = TRMC_X_DEPTH against this array.
+ * A stream of windows (trmc_stream_*) has no exceedance product.
+ */
+enum { TRMC_X_FLOW = 0, TRMC_X_VELOCITY = 1, TRMC_X_DEPTH = 2 };
+int trmc_plan_set_thresholds(trmc_plan *plan, int32_t nlevels, const void *th);
+int trmc_window_exceedance(trmc_plan *plan, int32_t rowset, int quantity, int32_t *steps_over, int32_t *first_step,
+                           int32_t *last_step, int32_t *longest_run);
+int trmc_window_exceedance_tile(int precision, int32_t *rows, int32_t *steps);
+int trmc_window_exceedance_kernel_ms(const trmc_plan *plan, double *ms_out);
+int trmc_plan_bankfull_depth(trmc_plan *plan, void *dst);
 /* on != 0: trmc_upload_forcing turns every NaN of qlat and q0 into 0 on the device, behind the copy.  The reference's reindexed
  * tables hold NaN on waterbody rows (compute.py:1466-1467), which the Muskingum-Cunge rows never read; the drop-in used to screen
  * the caller's frames for them on the host -- 20 ms of a CONUS call.  Default off: values go to the kernels as they are. */

@@ -108,6 +108,8 @@ RESERVOIR_DA_HYBRID, RESERVOIR_DA_RFC = 2, 4
 SUMMARY_PEAK, SUMMARY_MEAN = 1, 2   # trmc_stream_set_summary's mask (include/trmc.h)
 SUMMARY_PEAK_DEPTH, SUMMARY_TOTAL = 4, 8
 SUMMARY_NAMES = {"peak": SUMMARY_PEAK, "mean": SUMMARY_MEAN, "peak_depth": SUMMARY_PEAK_DEPTH, "total": SUMMARY_TOTAL}
+TRMC_X_FLOW, TRMC_X_VELOCITY, TRMC_X_DEPTH = 0, 1, 2   # trmc_window_exceedance's quantity (include/trmc.h)
+X_NAMES = {"flow": TRMC_X_FLOW, "velocity": TRMC_X_VELOCITY, "depth": TRMC_X_DEPTH}
 _P = C.POINTER
 # name -> (restype, argtypes); must list every symbol include/trmc.h declares
 SIGNATURES = {
@@ -179,6 +181,11 @@ SIGNATURES = {
     "trmc_window_courant_summary": (_int, [_vp, _i32, C.c_double, _vp, _vp, _vp]),
     "trmc_window_courant_tile": (_int, [_int, _P(_i32), _P(_i32)]),
     "trmc_window_courant_kernel_ms": (_int, [_vp, _P(C.c_double)]),
+    "trmc_plan_set_thresholds": (_int, [_vp, _i32, _vp]),
+    "trmc_window_exceedance": (_int, [_vp, _i32, _int, _vp, _vp, _vp, _vp]),
+    "trmc_window_exceedance_tile": (_int, [_int, _P(_i32), _P(_i32)]),
+    "trmc_window_exceedance_kernel_ms": (_int, [_vp, _P(C.c_double)]),
+    "trmc_plan_bankfull_depth": (_int, [_vp, _vp]),
     "trmc_plan_set_nan_is_zero": (_int, [_vp, _int]),
     "trmc_host_alloc": (_int, [C.c_size_t, C.POINTER(C.c_void_p)]),
     "trmc_host_free": (_int, [_vp]),
@@ -253,7 +260,7 @@ _LIB = None
 # entry points that never touch the HIP runtime (everything else may initialise it: single_hw_queue_per_priority must know)
 _HOST_ONLY = {"trmc_last_error", "trmc_abi_version", "trmc_topology_levels", "trmc_topology_levels_hinted", "trmc_topology_blocks", "trmc_topology_clusters",
               "trmc_topology_blocks_general", "trmc_get_stats", "trmc_plan_info", "trmc_plan_levels", "trmc_plan_lags", "trmc_plan_cluster_blocks", "trmc_plan_engine",
-              "trmc_plan_arithmetic", "trmc_stream_info", "trmc_window_summary_tile", "trmc_window_summary_kernel_ms", "trmc_window_courant_tile", "trmc_window_courant_kernel_ms", "trdw_last_error", "trdw_last_timing", "trdw_configure", "trmc_comm_info"}
+              "trmc_plan_arithmetic", "trmc_stream_info", "trmc_window_summary_tile", "trmc_window_summary_kernel_ms", "trmc_window_courant_tile", "trmc_window_courant_kernel_ms", "trmc_window_exceedance_tile", "trmc_window_exceedance_kernel_ms", "trdw_last_error", "trdw_last_timing", "trdw_configure", "trmc_comm_info"}
 
 
 class _Marking:

@@ -765,6 +765,7 @@ int trmc_set_reservoirs(trmc_plan *pl, int64_t nres, const int64_t *res_rows, co
     HIP_TRY(hipMemcpy(pl->res_par.p, par, bytes, hipMemcpyHostToDevice));
     pl->nres = nres;
     pl->res_dt = routing_period;
+    pl->res_rows.assign(res_rows, res_rows + nres);
     pl->routed_nsteps = -1;
     return 0;
 }
@@ -1534,6 +1535,128 @@ int trmc_window_courant_kernel_ms(const trmc_plan *pl, double *ms_out)
     if (pl->cour_ms < 0) return fail(TRMC_ESTATE, "no Courant metrics have been formed on this plan");
     *ms_out = pl->cour_ms;
     return 0;
+}
+
+int trmc_plan_set_thresholds(trmc_plan *pl, int32_t nlevels, const void *th)
+{
+    if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
+    if (nlevels < 0 || nlevels > 4) return fail(TRMC_EINVAL, "nlevels must be 0..4");
+    if (stream_active(pl)) return fail(TRMC_ESTATE, "a stream of windows is in progress (trmc_stream_end it first)");
+    if (pl->run.active) return fail(TRMC_ESTATE, "a routing window is in progress");
+    if (nlevels == 0 || !th) {
+        if (pl->thresholds.p) {
+            if (int rc = use_device(pl)) return rc;
+            pl->thresholds.release();
+        }
+        pl->th_levels = pl->th_pad = 0;
+        return 0;
+    }
+    // the device table's rows are 1, 2 or 4 wide (k_window_exceed's KP), +inf -- never over -- behind the caller's levels
+    const int32_t pad = nlevels == 3 ? 4 : nlevels;
+    pl->th_levels = pl->th_pad = 0; // (nothing half-set if the copy fails)
+    if (pl->nseg > 0) {
+        if (int rc = use_device(pl)) return rc;
+        const int rc = by_precision(pl, [&](auto t) -> int {
+            using T = decltype(t);
+            const T *const src = (const T *)th;
+            std::vector<T> host((size_t)pl->nseg * pad, std::numeric_limits<T>::infinity());
+            for (int64_t r = 0; r < pl->nseg; ++r)
+                for (int32_t k = 0; k < nlevels; ++k) host[(size_t)r * pad + k] = src[(size_t)r * nlevels + k];
+            if (int rc = pl->thresholds.ensure(host.size() * sizeof(T))) return rc;
+            // (synchronous: the table is whole before the call returns, whichever stream reads it)
+            HIP_TRY(hipMemcpy(pl->thresholds.p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
+            return 0;
+        });
+        if (rc) return rc;
+    }
+    pl->th_levels = nlevels;
+    pl->th_pad = pad;
+    return 0;
+}
+
+int trmc_window_exceedance_tile(int precision, int32_t *rows, int32_t *steps)
+{
+    if (precision != 32 && precision != 64) return fail(TRMC_EINVAL, "precision must be 32 or 64");
+    if (rows) *rows = kWexcRows;
+    if (steps) *steps = precision == 32 ? kWexcSteps<float> : kWexcSteps<double>;
+    return 0;
+}
+
+int trmc_window_exceedance(trmc_plan *pl, int32_t rowset, int quantity, int32_t *steps_over, int32_t *first_step, int32_t *last_step,
+                           int32_t *longest_run)
+{
+    if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
+    // (the refusals of trmc_window_summary, for its reasons: `out` is a finished window's or nothing)
+    if (stream_active(pl))
+        return fail(TRMC_ESTATE, "a stream of windows is in progress: a window's exceedance is formed from the result the plan assembles for "
+                                 "a window, which a stream does not fill");
+    if (pl->run.active)
+        return fail(TRMC_ESTATE, "a routing window is in progress: its result is not assembled before trmc_route_end");
+    if (pl->routed_nsteps < 0) return fail(TRMC_ESTATE, "nothing routed yet");
+    if (pl->th_levels < 1) return fail(TRMC_ESTATE, "no thresholds set on this plan (trmc_plan_set_thresholds)");
+    if (!steps_over && !first_step && !last_step && !longest_run) return fail(TRMC_EINVAL, "every destination is NULL: nothing to form");
+    if (quantity != TRMC_X_FLOW && quantity != TRMC_X_VELOCITY && quantity != TRMC_X_DEPTH)
+        return fail(TRMC_EINVAL, "quantity must be TRMC_X_FLOW, TRMC_X_VELOCITY or TRMC_X_DEPTH");
+    if (rowset < -1 || rowset >= (int32_t)pl->rowsets.size()) return fail(TRMC_EINVAL, "unknown row set");
+    const int64_t nrows = rowset < 0 ? pl->nseg : pl->rowset_n[(size_t)rowset];
+    if (pl->nseg == 0 || nrows == 0) return 0;
+    const int32_t nsteps = pl->routed_nsteps;
+    if (nsteps < 1) return fail(TRMC_ESTATE, "the last window had no timesteps");
+    if (int rc = use_device(pl)) return rc;
+    // the columns asked for, [nrows][K] int32 each, in the plan's scratch block on 256-byte boundaries; then to the host
+    int32_t *const host[4] = {steps_over, first_step, last_step, longest_run};
+    const size_t col_bytes = (size_t)nrows * pl->th_levels * sizeof(int32_t);
+    size_t off[4], total = 0;
+    for (int k = 0; k < 4; ++k) {
+        off[k] = total;
+        if (host[k]) total += (col_bytes + 255) / 256 * 256;
+    }
+    if (int rc = pl->scratch.ensure(total)) return rc;
+    for (DevEvent &e : pl->ev_wexc)
+        if (int rc = e.ensure(true)) return rc;
+    pl->wexc_ms = -1.0;
+    HIP_TRY(hipEventRecord(pl->ev_wexc[0], pl->stream));
+    char *const s = (char *)pl->scratch.p;
+    auto col = [&](int k) { return host[k] ? (int32_t *)(s + off[k]) : nullptr; };
+    if (int rc = window_exceed_launch(pl, rowset, quantity, WexcOut{col(0), col(1), col(2), col(3)}, nrows, nsteps)) return rc;
+    HIP_TRY(hipEventRecord(pl->ev_wexc[1], pl->stream));
+    for (int k = 0; k < 4; ++k)
+        if (host[k]) HIP_TRY(hipMemcpyAsync(host[k], s + off[k], col_bytes, hipMemcpyDeviceToHost, pl->stream));
+    HIP_TRY(hipStreamSynchronize(pl->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, pl->ev_wexc[0], pl->ev_wexc[1]));
+    pl->wexc_ms = ms;
+    return 0;
+}
+
+int trmc_window_exceedance_kernel_ms(const trmc_plan *pl, double *ms_out)
+{
+    if (!pl || !ms_out) return fail(TRMC_EINVAL, "plan/ms_out is NULL");
+    if (pl->wexc_ms < 0) return fail(TRMC_ESTATE, "no window exceedance has been formed on this plan");
+    *ms_out = pl->wexc_ms;
+    return 0;
+}
+
+int trmc_plan_bankfull_depth(trmc_plan *pl, void *dst)
+{
+    if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
+    if (pl->nseg == 0) return 0;
+    if (!dst) return fail(TRMC_EINVAL, "dst is NULL");
+    if (int rc = use_device(pl)) return rc;
+    return by_precision(pl, [&](auto t) -> int {
+        using T = decltype(t);
+        // the plan's own column (k_make_const: make_const's bfd), plan order -> row order
+        std::vector<T> by_pos((size_t)pl->nseg);
+        HIP_TRY(hipMemcpy(by_pos.data(), col<T>(pl, TRMC_NPARAM + 1), by_pos.size() * sizeof(T), hipMemcpyDeviceToHost));
+        T *const out = (T *)dst;
+        const trmc::Topology &topo = pl->sh->topo;
+        // rows that route no Muskingum-Cunge step have no bankfull: boundary rows, and a pool's elevation is not a channel's depth
+        for (int64_t r = 0; r < pl->nseg; ++r)
+            out[r] = topo.level_of_row[r] < 0 ? std::numeric_limits<T>::infinity() : by_pos[(size_t)topo.pos_of_row[r]];
+        if (pl->nres > 0)
+            for (int64_t r : pl->res_rows) out[r] = std::numeric_limits<T>::infinity();
+        return 0;
+    });
 }
 
 int trmc_plan_set_nan_is_zero(trmc_plan *pl, int on)

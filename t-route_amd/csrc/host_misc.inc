@@ -272,3 +272,39 @@ template <class T, bool SUMMARY> void window_courant_launch(trmc_plan *pl, const
     }
     hipLaunchKernelGGL((k_window_courant<T, false, SUMMARY>), grid, block, 0, pl->stream, a);
 }
+
+// trmc_window_exceedance (abi.inc): k_window_exceed's instance for the plan's precision, the alignment of the rows' records, the
+// column of (q, v, d) and the width of the threshold table's rows, on the plan's stream
+template <class T, bool VEC, int COL> int window_exceed_launch_kp(trmc_plan *pl, const int32_t *rp, const WexcOut &o, int64_t nrows, int32_t nsteps)
+{
+    const dim3 grid((unsigned)((nrows + kWexcRows - 1) / kWexcRows)), block(kWexcRows);
+    const T *const out = (const T *)pl->out.p, *const th = (const T *)pl->thresholds.p;
+    const int32_t *const row_of_pos = (const int32_t *)pl->sh->row_of_pos.p;
+    switch (pl->th_pad) {
+    case 1: hipLaunchKernelGGL((k_window_exceed<T, VEC, COL, 1>), grid, block, 0, pl->stream, out, rp, row_of_pos, th, o, nrows, nsteps, pl->th_levels); break;
+    case 2: hipLaunchKernelGGL((k_window_exceed<T, VEC, COL, 2>), grid, block, 0, pl->stream, out, rp, row_of_pos, th, o, nrows, nsteps, pl->th_levels); break;
+    case 4: hipLaunchKernelGGL((k_window_exceed<T, VEC, COL, 4>), grid, block, 0, pl->stream, out, rp, row_of_pos, th, o, nrows, nsteps, pl->th_levels); break;
+    default: return fail(TRMC_ESTATE, "no thresholds set on this plan (trmc_plan_set_thresholds)");
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+template <class T, bool VEC> int window_exceed_launch_col(trmc_plan *pl, const int32_t *rp, int column, const WexcOut &o, int64_t nrows, int32_t nsteps)
+{
+    switch (column) {
+    case 0: return window_exceed_launch_kp<T, VEC, 0>(pl, rp, o, nrows, nsteps);
+    case 1: return window_exceed_launch_kp<T, VEC, 1>(pl, rp, o, nrows, nsteps);
+    case 2: return window_exceed_launch_kp<T, VEC, 2>(pl, rp, o, nrows, nsteps);
+    }
+    return fail(TRMC_EINVAL, "unknown quantity");
+}
+int window_exceed_launch(trmc_plan *pl, int32_t rowset, int column, const WexcOut &o, int64_t nrows, int32_t nsteps)
+{
+    const int32_t *const rp = rowset < 0 ? nullptr : (const int32_t *)pl->rowsets[(size_t)rowset].p;
+    return by_precision(pl, [&](auto t) -> int {
+        using T = decltype(t);
+        // (16-byte loads where every row's record starts on a 16-byte boundary: k_window_exceed's head)
+        if (nsteps % (16 / (int)sizeof(T)) == 0) return window_exceed_launch_col<T, true>(pl, rp, column, o, nrows, nsteps);
+        return window_exceed_launch_col<T, false>(pl, rp, column, o, nrows, nsteps);
+    });
+}

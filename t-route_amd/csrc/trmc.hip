@@ -33,6 +33,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <limits>
 #include <memory>
 #include <new>
 #include <string>
@@ -78,6 +79,7 @@ namespace {
 #include "kernels_flow.inc"
 #include "k_window_summary.inc"
 #include "k_window_courant.inc"
+#include "k_window_exceed.inc"
 // ---------------------------------------------------------------- plan
 #include "dev_owner.hpp"
 
@@ -153,6 +155,7 @@ struct trmc_plan {
     DevEvent ev_gather;
     DevEvent ev_wsum[2];                 // around the last trmc_window_summary's kernel (trmc_window_summary_kernel_ms)
     DevEvent ev_cour[2];                 // ... and around the last trmc_window_courant / _summary's (trmc_window_courant_kernel_ms)
+    DevEvent ev_wexc[2];                 // ... and around the last trmc_window_exceedance's (trmc_window_exceedance_kernel_ms)
     DevEvent ev_forcing;                 // trmc_stage_forcing: the next window's forcing is on its way to in_qlat on the copy stream
     // trmc_plan_clone: a second set of WINDOW buffers on the static data of the plan it was made from
     std::shared_ptr<PlanShared> sh;
@@ -179,6 +182,9 @@ struct trmc_plan {
     DevBuf res_of_pos, res_par, res_inflow;             // level-pool reservoirs of the plan
     int64_t nres = 0;
     double res_dt = 0.0;
+    std::vector<int64_t> res_rows;       // the rows trmc_set_reservoirs declared (trmc_plan_bankfull_depth)
+    DevBuf thresholds;                   // trmc_plan_set_thresholds: [nseg][th_pad] in the plan's precision, row order, +inf behind
+    int32_t th_levels = 0, th_pad = 0;   // the th_levels levels of a row (th_pad = 1, 2 or 4: k_window_exceed's KP); 0 levels: none set
     DevBuf res_da;                       // data-assimilation tables of those reservoirs for the staged window (reservoir_da.hpp)
     bool res_da_on = false;
     std::vector<int32_t> res_da_kind, res_da_trow; // what trmc_set_reservoir_da declared, and its tables' shapes {usgs, usace, rfc}:
@@ -244,6 +250,7 @@ struct trmc_plan {
     bool gather_pending = false;         // (ev_gather)
     double wsum_ms = -1.0;
     double cour_ms = -1.0;
+    double wexc_ms = -1.0;
     bool row0_replaced = false;          // trmc_plan_chain_from has overwritten time row 0 -- the last window's initial state -- since it ended
     bool forcing_pending = false;        // (ev_forcing)
     bool state_missing = false;          // ... and there is no initial state yet: trmc_plan_chain_from must supply it

@@ -143,6 +143,7 @@ class RoutingPlan:
         self.engine = "flow" if f.value else "levels"
         self._nsteps = None
         self._stream_keep = {}
+        self._th_levels = 0                                                 # levels of set_thresholds (0: none set)
         self.maxlag = 0
 
     # -- lifetime ---------------------------------------------------------------------
@@ -359,6 +360,7 @@ class RoutingPlan:
         other._h = h
         other._nsteps = None
         other._stream_keep = {}
+        other._th_levels = 0
         return other
 
     def set_sequence_mode(self, on=True):
@@ -734,6 +736,79 @@ class RoutingPlan:
         ms = C.c_double(0)
         _lib.check(_lib.lib().trmc_window_courant_kernel_ms(self._h, C.byref(ms)))
         return ms.value
+
+    # window_exceedance's parts, in trmc_window_exceedance's order
+    WINDOW_EXCEEDANCE_PARTS = ("steps_over", "first_step", "last_step", "longest_run")
+
+    @staticmethod
+    def window_exceedance_tile(precision=32):
+        """(rows, steps) of the exceedance kernel's tile for a precision (trmc_window_exceedance_tile)"""
+        rows, steps = C.c_int32(0), C.c_int32(0)
+        _lib.check(_lib.lib().trmc_window_exceedance_tile(int(precision), C.byref(rows), C.byref(steps)))
+        return rows.value, steps.value
+
+    def set_thresholds(self, th):
+        """Thresholds of every row, [nseg] (one level) or [nseg, K] with K <= 4, cast to the plan's dtype and kept on the device
+        until replaced (trmc_plan_set_thresholds); ``None`` clears them.  Per plan object: a ``clone`` has none until set."""
+        if th is None:
+            _lib.check(_lib.lib().trmc_plan_set_thresholds(self._h, 0, None))
+            self._th_levels = 0
+            return
+        th = np.asarray(th)
+        if th.ndim == 1:
+            th = th[:, None]
+        if th.ndim != 2 or th.shape[0] != self.nseg:
+            raise ValueError(f"thresholds must be [nseg] or [nseg, K] with nseg = {self.nseg}: got {th.shape}")
+        if not 1 <= th.shape[1] <= 4:
+            raise ValueError(f"thresholds: 1 to 4 levels a row, got {th.shape[1]}")
+        th = np.ascontiguousarray(th, dtype=self.dtype)
+        _lib.check(_lib.lib().trmc_plan_set_thresholds(self._h, th.shape[1], _lib.ptr(th)))
+        self._th_levels = th.shape[1]
+
+    def window_exceedance(self, quantity="flow", parts=WINDOW_EXCEEDANCE_PARTS, rowset=None):
+        """Per row of the last window and per level of ``set_thresholds``: ``steps_over`` (steps t with x[t] > threshold, compared
+        in the plan's dtype; a NaN on either side is not over, nor is equality), ``first_step`` and ``last_step`` (the first and the
+        last such t, 1-based, 0 if none) and ``longest_run`` (the longest run of consecutive such steps) of ``quantity`` ("flow",
+        "velocity" or "depth"), reduced on the device over EVERY step of the result (trmc_window_exceedance): a dict of int32
+        [rows, K] arrays, the parts asked for only.  rowset (``rowset(rows)``): the rows of that set, in its order, each against
+        the thresholds of the row it names."""
+        if quantity not in _lib.X_NAMES:
+            raise ValueError(f"unknown quantity {quantity!r}: one of {sorted(_lib.X_NAMES)}")
+        parts = (parts,) if isinstance(parts, str) else tuple(parts or ())
+        unknown = [p for p in parts if p not in self.WINDOW_EXCEEDANCE_PARTS]
+        if unknown:
+            raise ValueError(f"unknown part(s) of a window exceedance {unknown}: one of {list(self.WINDOW_EXCEEDANCE_PARTS)}")
+        if not parts:
+            raise ValueError("window_exceedance: no part asked for")
+        n = self.nseg if rowset is None else self._rowset_n[rowset]
+        k = getattr(self, "_th_levels", 0)
+        # ONE block for the arrays asked for (page-locked and pooled when it is large), each a view of it -- as window_summary's
+        pitch = -(-n * k * 4 // 256) * 256
+        order = self.WINDOW_EXCEEDANCE_PARTS
+        block = _lib.result_empty((pitch * sum(name in parts for name in order),), np.uint8)
+        out, at = dict.fromkeys(order), 0
+        for name in order:
+            if name in parts:
+                out[name] = block[at:at + n * k * 4].view(np.int32).reshape(n, k)
+                at += pitch
+        # (without thresholds the arrays are empty and the library refuses the call)
+        _lib.check(_lib.lib().trmc_window_exceedance(self._h, -1 if rowset is None else int(rowset), _lib.X_NAMES[quantity],
+                                                     *(_lib.ptr(out[name]) for name in order)))
+        return {name: out[name] for name in order if out[name] is not None}
+
+    def window_exceedance_kernel_ms(self):
+        """device time (ms) of the last ``window_exceedance``'s kernel, from events around it (trmc_window_exceedance_kernel_ms)"""
+        ms = C.c_double(0)
+        _lib.check(_lib.lib().trmc_window_exceedance_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def bankfull_depth(self):
+        """[nseg] in the plan's dtype: the bankfull depth the step kernels use, +inf on rows that route no Muskingum-Cunge step
+        (boundary rows, reservoirs) -- trmc_plan_bankfull_depth.  ``set_thresholds(plan.bankfull_depth())`` and
+        ``window_exceedance("depth")``: the steps a row was out of bank."""
+        out = np.empty((self.nseg,), self.dtype)
+        _lib.check(_lib.lib().trmc_plan_bankfull_depth(self._h, _lib.ptr(out) if out.size else None))
+        return out
 
     def set_nan_is_zero(self, on=True):
         """uploads of forcing and state: NaN -> 0 on the device (trmc_plan_set_nan_is_zero)"""

@@ -178,6 +178,7 @@ def compute_nhd_routing_v02(
     precision=32,
     device=0,
     output_stride=None,
+    exceedance=None,
     summary=None,
 ):
     """Route every independent network of the call for ``nts`` timesteps.
@@ -204,6 +205,12 @@ def compute_nhd_routing_v02(
     ``compute_network_structured``) -- every tailwater's tuple then has an eleventh member, the dict of per-row arrays (peak flow /
     depth / velocity with the 1-based step of each, mean flow) over EVERY step of the window for the rows of its member [0], whatever
     ``output_stride`` keeps of the block itself.
+
+    ``exceedance`` (keyword-only; None = the reference's result): ``(quantity, thresholds)`` with quantity "flow", "velocity" or
+    "depth" and thresholds a DataFrame indexed by segment id with one column per level (at most four; segments it does not hold
+    get +inf: never over), or ``(quantity, "bankfull")`` -- the depth against the channel's own bankfull depth.  Every tailwater's
+    dict (the eleventh member, shared with ``summary``) gains ``steps_over``, ``first_step``, ``last_step`` and ``longest_run``,
+    int32 [rows, levels], over EVERY step of the window (``compute_network_structured``, ``RoutingPlan.window_exceedance``).
     """
     if parallel_compute_method not in _PARALLEL_METHODS and parallel_compute_method is not None:
         raise ValueError(f"unknown parallel_compute_method {parallel_compute_method!r}")
@@ -254,6 +261,10 @@ def compute_nhd_routing_v02(
             return v
         return df.reindex(table_index).fillna(0.0).values.astype("float32")
     q0_v, qlat_v = rows_of(q0), rows_of(qlats)
+
+    exceedance_arg = exceedance
+    if exceedance is not None and not isinstance(exceedance[1], str):      # the frame in the table's row order, +inf where it has no row
+        exceedance_arg = (exceedance[0], exceedance[1].reindex(table_index, fill_value=np.inf).values)
 
     upstream_results = {}
     for u in offnetwork_upstreams:                                       # compute.py:1649-1655
@@ -317,7 +328,8 @@ def compute_nhd_routing_v02(
         *res_da_args,
         e_i1, e_i1, e_f1, e_i1, e_f1, e_i1, e_i1, e_f2,
         upstream_results, assume_short_ts, return_courant, from_files=from_files, precision=precision, device=device,
-        output_stride=output_stride, result_order=net["order"] if grouped else None, nan_is_zero=True, summary=summary)
+        output_stride=output_stride, result_order=net["order"] if grouped else None, nan_is_zero=True, summary=summary,
+        exceedance=exceedance_arg)
     rids = r[0].astype("int64")                  # (the rows of upstream_results are masked out, mc_reach.pyx:451,:812)
     fvd, upstream = r[1], r[6]
     gage_ids, lastobs_times, lastobs_values = r[3]
@@ -341,14 +353,15 @@ def compute_nhd_routing_v02(
         owner = owner[keep]
         order = np.argsort(owner, kind="stable")
         bounds = np.searchsorted(owner[order], np.arange(len(tws) + 1))
+    with_dict = summary is not None or exceedance is not None     # (one dict of per-row arrays behind the ten members)
     if grouped:                                  # (compute_network_structured has handed its rows back in that order)
         ids_o, fvd_o, up_o = rids.astype(np.intp), fvd, upstream
-        sum_o = r[-1] if summary is not None else None
+        sum_o = r[-1] if with_dict else None
         cou_o = r[2]
     else:
         ids_o, fvd_o = rids[order].astype(np.intp), fvd[order]
         cou_o = r[2][order] if return_courant else 0
-        sum_o = {k: v[order] for k, v in r[-1].items()} if summary is not None else None
+        sum_o = {k: v[order] for k, v in r[-1].items()} if with_dict else None
         # (the upstream-inflow series are zero except on waterbody rows, mc_reach.pyx:487,:710: without waterbodies any order of
         # an all-zero block is the block itself -- 3.1 GB for a CONUS day that need not be permuted)
         up_o = upstream[order] if len(lake_segs) else upstream

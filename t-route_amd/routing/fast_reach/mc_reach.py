@@ -377,6 +377,7 @@ def compute_network_structured(
     output_stride=None,
     result_order=None,
     nan_is_zero=False,
+    exceedance=None,
     summary=None,
 ):
     """Route one (sub)network for ``nsteps`` timesteps on the GPU.
@@ -407,7 +408,31 @@ def compute_network_structured(
     steps).  ``return_courant=True``: element [2] -- the literal 0 otherwise, as in the
     reference's V02 loop -- is an array [rows, kept steps * 3] of (cn, ck, X) per step
     (``RoutingPlan.window_courant``): the rows, the kept steps and the dtype of element [1].
+    ``exceedance`` (None, or ``(quantity, thresholds)`` with quantity "flow", "velocity" or
+    "depth" and thresholds [len(data_idx)] or [len(data_idx), K], K <= 4, in ``data_idx``
+    order -- or the string "bankfull": the depth against ``RoutingPlan.bankfull_depth()``):
+    the int32 [rows, K] arrays ``steps_over``, ``first_step``, ``last_step`` and
+    ``longest_run`` of ``RoutingPlan.window_exceedance``, from EVERY step of the window
+    whatever ``output_stride`` keeps, join the dict that ``summary`` appends -- the dict
+    with these four keys alone when ``summary`` is None; rows as for ``summary``).
     """
+    exc_quantity = exc_th = None
+    if exceedance is not None:
+        try:
+            exc_quantity, exc_th = exceedance
+        except (TypeError, ValueError):
+            raise ValueError('exceedance: (quantity, thresholds) or (quantity, "bankfull")') from None
+        if exc_quantity not in _lib.X_NAMES:
+            raise ValueError(f"exceedance: unknown quantity {exc_quantity!r}: one of {sorted(_lib.X_NAMES)}")
+        if isinstance(exc_th, str):
+            if exc_th != "bankfull" or exc_quantity != "depth":
+                raise ValueError('exceedance: the only named thresholds are ("depth", "bankfull")')
+        else:
+            exc_th = np.asarray(exc_th)
+            if exc_th.ndim == 1:
+                exc_th = exc_th[:, None]
+            if exc_th.ndim != 2 or exc_th.shape[0] != len(data_idx) or not 1 <= exc_th.shape[1] <= 4:
+                raise ValueError(f"exceedance: thresholds must be [{len(data_idx)}] or [{len(data_idx)}, K] with K <= 4, got {exc_th.shape}")
     if summary is not None:
         summary = (summary,) if isinstance(summary, str) else tuple(summary)
         if not summary:
@@ -637,6 +662,21 @@ def compute_network_structured(
         # (compute_parameters.return_courant: the reference's V02 loop takes the flag and returns the literal 0, mc_reach.pyx:737-740,
         # :814; here the triples its kernel would have filled, :128-131, recomputed on the device from the window just routed)
         courant = plan.window_courant(stride, rowset=oset) if return_courant else None
+        window_exceedance = None
+        if exceedance is not None:
+            # (thresholds are static per network and the callable keeps its plans: they cross PCIe when they differ from what
+            # the plan holds -- the bankfull column belongs to the plan's parameters and reservoirs, which are its cache key)
+            held = plan.__dict__.get("_exceedance_held")
+            if isinstance(exc_th, str):
+                if not isinstance(held, str):
+                    plan.set_thresholds(plan.bankfull_depth())
+                    plan._exceedance_held = "bankfull"
+            else:
+                th = np.ascontiguousarray(exc_th, dtype=plan.dtype)
+                if isinstance(held, str) or held is None or held.shape != th.shape or held.tobytes() != th.tobytes():
+                    plan.set_thresholds(th)
+                    plan._exceedance_held = th.copy()
+            window_exceedance = plan.window_exceedance(exc_quantity, rowset=oset)
         if nudging is not None:
             nudge[nudging[4], 1:] = plan.download_nudge()
         res_inflow = plan.download_reservoir_inflow() if res_rows else None
@@ -716,7 +756,8 @@ def compute_network_structured(
     )
     if return_stats:
         result = result + (stats,)
-    if window_summary is not None:
+    if window_summary is not None or window_exceedance is not None:
+        window_summary = {**(window_summary or {}), **(window_exceedance or {})}
         if not fill_index_mask.all():      # (rows spliced in from upstream_results are masked out of element [0]: here too)
             window_summary = {k: v[fill_index_mask] for k, v in window_summary.items()}
         result = result + (window_summary,)
