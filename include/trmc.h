@@ -918,10 +918,27 @@ int trmc_stage_forcing(trmc_plan *plan, int nsteps, const void *qlat, int64_t nq
  *              over all 2**23, exponents uniform over the ranges, both ends included; one triple in eight has a divisor
  *              whose significand is all ones, all ones but the last bit, zero or one (the hard cases of division by a
  *              refined reciprocal)
- * checked_out receives the number of values / triples compared, mismatches_out how many results differ in any bit
- * (0 is the claim).  No routing state is touched.
+ *   what = 2   the refined reciprocal (v_rcp_f32 and one Newton step) against the correctly rounded reciprocal for ALL
+ *              2**23 significands of the binade 2**n, n in [-126, 126] (seed is ignored): the hypothesis under which
+ *              DevMathF::quot forms a correctly rounded quotient in three operations.  The library's compiled-in set of
+ *              excepted significands is EMPTY, so any mismatch is one outside it; a plan created on a device that has one
+ *              takes the plain divisions (checked once per device where its first plan is created).
+ *   what = 3   DevMathF::quot(a, b, refined reciprocal of b) against a / b: 65 666 divisors (2**16 significands at a stride
+ *              of 128 and every one within 64 of 0 and of 2**23 - 1, exponents drawn from [-14, 35]), each with n
+ *              numerators drawn from `seed` -- random significands at every exponent distance in [-40, 50], and
+ *              a = b*q moved by -1, 0, +1 units in the last place for q next to the boundary between two floats (bits going
+ *              on ...0111... or ...1000...) -- and with the numerator +0, whose quotient must be +0
+ * checked_out receives the number of values / triples / pairs compared, mismatches_out how many results differ in any
+ * bit (0 is the claim).  No routing state is touched.
  */
 int trmc_selfcheck_fast_arith(int device, int what, int64_t n, uint64_t seed, int64_t *checked_out, int64_t *mismatches_out);
+
+/*
+ * The values behind what = 2 above, for a caller that forms the correctly rounded reciprocals itself: out[s], s in
+ * [0, 2**23), receives the device's refined reciprocal of the float with significand s in the binade 2**exponent
+ * (exponent in [-126, 126]; `out` holds 2**23 floats of host memory).  No routing state is touched.
+ */
+int trmc_selfcheck_rcp_values(int device, int exponent, float *out);
 
 /*
  * ---- communicator: the ranks of a multi-GPU job on one node (one process, or thread, per rank) ------------------

@@ -210,6 +210,7 @@ SIGNATURES = {
     "trmc_plan_clone": (_int, [_vp, _P(_vp)]),
     "trmc_stage_forcing": (_int, [_vp, _int, _vp, _i64]),
     "trmc_selfcheck_fast_arith": (_int, [_int, _int, _i64, C.c_uint64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "trmc_selfcheck_rcp_values": (_int, [_int, _int, _vp]),
     # communicator + device plumbing of the multi-GPU path (csrc/comm.hip)
     "trmc_comm_unique_id": (_int, [_vp]),
     "trmc_comm_init": (_int, [_int, _int, _vp, _int, _P(_vp)]),

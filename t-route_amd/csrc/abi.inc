@@ -2014,8 +2014,10 @@ int trmc_plan_chain_from(trmc_plan *dst, trmc_plan *src)
 int trmc_selfcheck_fast_arith(int device, int what, int64_t n, uint64_t seed, int64_t *checked_out, int64_t *mismatches_out)
 {
     if (!checked_out || !mismatches_out) return fail(TRMC_EINVAL, "checked_out/mismatches_out is NULL");
-    if (what != 0 && what != 1) return fail(TRMC_EINVAL, "what must be 0 (square root) or 1 (division, maximum)");
-    if (what == 1 && n < 0) return fail(TRMC_EINVAL, "n < 0");
+    if (what < 0 || what > 3)
+        return fail(TRMC_EINVAL, "what must be 0 (square root), 1 (division, maximum), 2 (refined reciprocal) or 3 (three-operation quotient)");
+    if ((what == 1 || what == 3) && n < 0) return fail(TRMC_EINVAL, "n < 0");
+    if (what == 2 && (n < -126 || n > 126)) return fail(TRMC_EINVAL, "n (the binade's exponent) outside [-126, 126]");
     if (int rc = check_device(device)) return rc;
     HIP_TRY(hipSetDevice(device));
     DevBuf cnt;
@@ -2027,9 +2029,15 @@ int trmc_selfcheck_fast_arith(int device, int what, int64_t n, uint64_t seed, in
             const uint32_t lo = (uint32_t)(127 - 60) << 23, hi = (uint32_t)(127 + 63) << 23; // 2**-60 .. 2**63 inclusive
             checked = (int64_t)hi - (int64_t)lo + 1;
             hipLaunchKernelGGL(k_selfcheck_sqrt, dim3(8192), dim3(kBlock), 0, 0, lo, hi, (unsigned long long *)cnt.p);
-        } else {
+        } else if (what == 1) {
             checked = n;
             if (n > 0) hipLaunchKernelGGL(k_selfcheck_div, dim3(8192), dim3(kBlock), 0, 0, n, seed, (unsigned long long *)cnt.p);
+        } else if (what == 2) {
+            checked = (int64_t)1 << 23;
+            hipLaunchKernelGGL(k_selfcheck_rcp, dim3((1u << 23) / kBlock), dim3(kBlock), 0, 0, (uint32_t)(n + 127), (unsigned long long *)cnt.p);
+        } else {
+            checked = kQuotDivisors * (n + 1); // (+1: the numerator +0 of every divisor)
+            hipLaunchKernelGGL(k_selfcheck_quot, dim3(8192), dim3(kBlock), 0, 0, n, seed, (unsigned long long *)cnt.p);
         }
         e = hipGetLastError();
     }
@@ -2043,3 +2051,17 @@ int trmc_selfcheck_fast_arith(int device, int what, int64_t n, uint64_t seed, in
     return 0;
 }
 
+int trmc_selfcheck_rcp_values(int device, int exponent, float *out)
+{
+    if (!out) return fail(TRMC_EINVAL, "out is NULL");
+    if (exponent < -126 || exponent > 126) return fail(TRMC_EINVAL, "exponent outside [-126, 126]");
+    if (int rc = check_device(device)) return rc;
+    HIP_TRY(hipSetDevice(device));
+    const size_t n = (size_t)1 << 23;
+    DevBuf y;
+    if (int rc = y.ensure(n * sizeof(float))) return rc;
+    hipLaunchKernelGGL(k_rcp_values, dim3((unsigned)(n / kBlock)), dim3(kBlock), 0, 0, (uint32_t)(exponent + 127), (float *)y.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, y.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}

@@ -38,7 +38,8 @@ struct DevMathF {
     // n2, n3 are differences of two such floats, hence +0 or of magnitude >= 2**-45; so no scaling,
     // no fix-up, every quotient normal or +0 (for which the refinement returns +0 as IEEE does).  Then
     // the same instructions are issued, minus the three helpers, and y1 once instead of four times:
-    // bit-identical by construction.  Anything else takes the plain divisions.
+    // bit-identical by construction -- and of those, the second correction of each quotient is not
+    // issued either (see quot).  Anything else takes the plain divisions.
     // The divisions of the hydraulic point (hydraulics_at: radius and composite n by the wetted perimeter, the top-width
     // term of the celerity, the reciprocal of the composite n) under the same argument.  `sane` is established once per
     // plan on the host (params_sane: bw, n, cs, twcc, ncc in [2**-14, 2**17], cs, twcc and ncc possibly 0; dt, dx, s0 as at k_of); with the in-bank and
@@ -112,29 +113,50 @@ struct DevMathF {
     {
         return a / b;
     }
+    // a / b in THREE operations, y1 = refined_rcp(b).  The compiler's expansion (above) corrects q0 = a*y1 twice; the second
+    // correction never changes a bit, so it is not issued.  Why:
+    //   Markstein's theorem (P. Markstein, "Computation of elementary functions on the IBM RISC System/6000 processor", IBM
+    //   J. Res. Dev. 34, 1990; Muller et al., Handbook of Floating-Point Arithmetic, section 4.7): in radix 2, if y = RN(1/b)
+    //   and q0 is within one unit in the last place of a/b, then r = fma(-b, q0, a) is exact and fma(r, y, q0) = RN(a/b),
+    //   provided nothing overflows, underflows or is subnormal on the way.
+    //   (1) y1 = RN(1/b).  v_rcp_f32 is within one unit in the last place and one Newton step follows; whether that lands on
+    //       the correctly rounded reciprocal is a property of the hardware's table (the classical failure is a significand
+    //       of all ones).  Both operations commute with scaling by a power of two for a normal b with a normal reciprocal, so
+    //       the 2**23 significands of one binade decide it: on gfx950 (MI355X) ALL of them give RN(1/b), against
+    //       (float)(1.0 / (double)b), exact because fp64 carries more than 2*24 + 2 bits -- the compiled-in set of
+    //       exceptions is EMPTY (profiles/r21_quotient_exhaustive.txt; tests/test_gpu_quotient.py at 2**-14, 2**0, 2**35).
+    //       A device is not taken on trust: the first plan created on it runs k_selfcheck_rcp over the 2**23 significands
+    //       (quot_selfcheck, host_misc.inc), and ONE mismatch clears `sane` for every plan there and c_quot_ok for
+    //       coef_guard, i.e. selects the plain divisions everywhere: slower, never other bits.
+    //   (2) q0 = a*y1 against a/b: |y1 - 1/b| <= ulp(1/b)/2 and one rounding.  With a, b scaled into [1, 2) that is
+    //       |q0 - a/b| <= a 2**-25 + ulp(q0)/2: below one unit in the last place when a >= b (quotient in [1, 2)), and below
+    //       (a + 1)/2 < 3/2 units when a < b (quotient in (1/2, 1)).  So the hypothesis holds in the looser sense only -- a
+    //       host count finds q0 more than one unit of the quotient's binade away for about one pair in a hundred when a is
+    //       close below b, and r then needs 25 bits now and then -- and the theorem alone does not close the case a < b.
+    //       What closes it is exhaustion: for normal operands and results quot(a, b, y1) commutes with scaling a and b by
+    //       powers of two, so the 2**23 x 2**23 pairs of significands decide every pair, and tools/quotient_probe.hip
+    //       compares quot(a, b, refined_rcp(b)) with a / b for ALL 2**46 of them on the device: no mismatch (20 s of one
+    //       MI355X; same file).  Given (1), every operation involved is an IEEE one, so the result holds for any device
+    //       that passes the self-check.
+    //   (3) no overflow, underflow or subnormal: the ranges proved at div4, fast_ok and k_of (every divisor, numerator and
+    //       quotient normal, numerators at least 2**-64, so r -- a multiple of 2**-47 a -- is normal or zero).  A numerator
+    //       +0 (div4's n4) gives q0 = +0, r = fma(-b, +0, +0) = +0 and fma(+0, y1, +0) = +0, as IEEE does.
+    //   IEEE division has one correctly rounded result, so these are the bits of the five operations, two fewer issued.
     __device__ __forceinline__ static float quot(float a, float b, float y1)
     {
         const float q0 = a * y1;
-        const float q1 = __builtin_fmaf(__builtin_fmaf(-b, q0, a), y1, q0);
-        return __builtin_fmaf(__builtin_fmaf(-b, q1, a), y1, q1);
+        return __builtin_fmaf(__builtin_fmaf(-b, q0, a), y1, q0);
     }
     bool coef_ok;
-    __device__ __forceinline__ static float refined_quot(float a, float b, float y1)
-    {
-        const float q0 = a * y1;
-        const float q1 = __builtin_fmaf(__builtin_fmaf(-b, q0, a), y1, q0);
-        return __builtin_fmaf(__builtin_fmaf(-b, q1, a), y1, q1);
-    }
     __device__ __forceinline__ void div4(float n1, float n2, float n3, float n4, float d, float &q1, float &q2,
                                          float &q3, float &q4) const
     {
         if (coef_ok && d <= 0x1p52f) {
-            const float y0 = __builtin_amdgcn_rcpf(d);
-            const float y1 = __builtin_fmaf(__builtin_fmaf(-d, y0, 1.0f), y0, y0);
-            q1 = refined_quot(n1, d, y1);
-            q2 = refined_quot(n2, d, y1);
-            q3 = refined_quot(n3, d, y1);
-            q4 = refined_quot(n4, d, y1);
+            const float y1 = refined_rcp(d);
+            q1 = quot(n1, d, y1);
+            q2 = quot(n2, d, y1);
+            q3 = quot(n3, d, y1);
+            q4 = quot(n4, d, y1);
         } else {
             q1 = n1 / d;
             q2 = n2 / d;
@@ -247,11 +269,14 @@ __device__ __forceinline__ const uint64_t *stage_pow_tables(uint64_t *s_tab)
     __syncthreads();
     return s_tab;
 }
+// 1 unless this device's refined reciprocal failed the self-check (quot_selfcheck, host_misc.inc; see DevMathF::quot)
+__constant__ int32_t c_quot_ok = 1;
 // the once-per-segment-step part of DevMathF::div4's proof obligation (see there)
 __device__ __forceinline__ bool coef_guard(float dt, float ql)
 {
     const float n4 = ql * dt, an4 = __builtin_fabsf(n4);
-    return (dt >= 0x1p-20f) && (dt <= 0x1p40f) && ((__float_as_uint(n4) == 0u) || (an4 >= 0x1p-60f && an4 <= 0x1p60f));
+    return (c_quot_ok != 0) && (dt >= 0x1p-20f) && (dt <= 0x1p40f)
+           && ((__float_as_uint(n4) == 0u) || (an4 >= 0x1p-60f && an4 <= 0x1p60f));
 }
 __device__ __forceinline__ bool coef_guard(double, double) { return false; }
 // TOL: the plan's arithmetic is TRMC_ARITH_TOLERANCE (fp32 plans only)

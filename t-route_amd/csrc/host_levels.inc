@@ -1,5 +1,7 @@
 // host_levels.inc -- included by trmc.hip: a routing window on the level engine (route_begin_t / route_advance_t / route_end_t).
 
+int quot_selfcheck(int device, bool *ok); // host_misc.inc
+
 template <class T> T *col(trmc_plan *pl, int c) { return (T *)pl->sh->params.p + (size_t)c * pl->nseg_pad; }
 
 template <class T> int upload_params(trmc_plan *pl, const float *params)
@@ -22,7 +24,10 @@ template <class T> int upload_params(trmc_plan *pl, const float *params)
                && within(src[TRMC_P_DT], 0x1p-20f, 0x1p40f) && within(src[TRMC_P_DX], 0x1p-10f, 0x1p19f)
                && within(src[TRMC_P_S0], 0x1p-30f, 0x1p10f);
     }
-    pl->params_sane = sane && sizeof(T) == 4;
+    // (... and all of them stand on this device's refined reciprocal being the correctly rounded one: DevMathF::quot)
+    bool quot_ok = false;
+    if (int rc = quot_selfcheck(pl->device, &quot_ok)) return rc;
+    pl->params_sane = sane && quot_ok && sizeof(T) == 4;
     if (int rc = pl->sh->params.ensure(all_cols * sizeof(T))) return rc;
     HIP_TRY(hipMemcpy(pl->sh->params.p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
     if (n > 0) {

@@ -206,6 +206,96 @@ k_selfcheck_div(int64_t n, uint64_t seed, unsigned long long *mismatches)
     }
     if (bad) atomicAdd(mismatches, bad);
 }
+// refined_rcp(b) against the correctly rounded reciprocal for all 2**23 significands of the binade 2**(ebits - 127): hypothesis
+// (1) of DevMathF::quot.  (float)(1.0 / (double)b) is exact: fp64 carries more than 2*24 + 2 bits.  Grid: 2**23 / kBlock blocks.
+__global__ void __launch_bounds__(kBlock)
+k_selfcheck_rcp(uint32_t ebits, unsigned long long *mismatches)
+{
+    const float b = __uint_as_float((ebits << 23) | (blockIdx.x * (uint32_t)kBlock + threadIdx.x));
+    if (__float_as_uint(DevMathF::refined_rcp(b)) != __float_as_uint((float)(1.0 / (double)b))) atomicAdd(mismatches, 1ull);
+}
+// ... and the values themselves, for a host that forms the correctly rounded reciprocals itself (trmc_selfcheck_rcp_values):
+// y[s] = refined_rcp of significand s in the binade 2**(ebits - 127); y holds 2**23 floats, the grid is 2**23 / kBlock blocks
+__global__ void __launch_bounds__(kBlock)
+k_rcp_values(uint32_t ebits, float *__restrict__ y)
+{
+    const uint32_t s = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
+    y[s] = DevMathF::refined_rcp(__uint_as_float((ebits << 23) | s));
+}
+// the divisors of k_selfcheck_quot: 2**16 significands at a stride of 128, then those within 64 of 0 and of 2**23 - 1 (the
+// compiled-in set of reciprocal exceptions is empty, or their neighbourhoods would follow here)
+constexpr int64_t kQuotDivisors = 65536 + 65 + 65;
+__device__ __forceinline__ uint32_t selfcheck_divisor_sig(int64_t i)
+{
+    return i < 65536 ? (uint32_t)i * 128u : i < 65536 + 65 ? (uint32_t)(i - 65536) : 0x7fffffu - (uint32_t)(i - 65536 - 65);
+}
+// DevMathF::quot(a, b, refined_rcp(b)) against a / b, bit for bit: per divisor (exponent drawn from [-14, 35]) `per` numerators --
+//   even j   a random significand at the exponent of b plus -40 + (j/2) % 91: every exponent distance in [-40, 50]
+//   odd j    a = RN(b * q) moved by -1, 0 or +1 units in its last place, q = (m + t) 2**(e - 23) for a random 24-bit m and
+//            t = 1/2 - 2**-k (a quotient whose bits go on ...0111...) or t = 1/2 + 2**-k, k in [2, 24], or t = 1/2 (...1000...):
+//            quotients next to the boundary between two floats, the hard cases of a rounded division
+// and the numerator +0, whose quotient must be +0.  One thread per (divisor, 64 numerators).
+__global__ void __launch_bounds__(kBlock)
+k_selfcheck_quot(int64_t per, uint64_t seed, unsigned long long *mismatches)
+{
+    const int64_t chunks = (per + 63) / 64, total = kQuotDivisors * chunks;
+    unsigned long long bad = 0;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t w = (int64_t)blockIdx.x * kBlock + threadIdx.x; w < total; w += stride) {
+        const int64_t ib = w / chunks, c = w - ib * chunks;
+        const uint64_t rb = selfcheck_mix(seed ^ (0x5851f42d4c957f2dull * (uint64_t)(ib + 1)));
+        const int eb = -14 + (int)((rb >> 32) % 50u);
+        const float b = __uint_as_float(((uint32_t)(eb + 127) << 23) | selfcheck_divisor_sig(ib));
+        const float y1 = DevMathF::refined_rcp(b);
+        if (c == 0) bad += __float_as_uint(DevMathF::quot(0.0f, b, y1)) != 0u || __float_as_uint(0.0f / b) != 0u;
+        const int64_t j1 = (c + 1) * 64 < per ? (c + 1) * 64 : per;
+        for (int64_t j = c * 64; j < j1; ++j) {
+            const uint64_t r = selfcheck_mix(rb + (uint64_t)j);
+            const int rel = -40 + (int)((j >> 1) % 91);
+            float a;
+            if ((j & 1) == 0) {
+                a = __uint_as_float(((uint32_t)(eb + rel + 127) << 23) | ((uint32_t)r & 0x7fffffu));
+            } else {
+                const uint32_t k = 2u + (uint32_t)((r >> 24) % 23u), pick = (uint32_t)(r >> 32) % 3u;
+                const double eps = __longlong_as_double((long long)(1023u - k) << 52); // 2**-k
+                const double t = pick == 0 ? 0.5 - eps : pick == 1 ? 0.5 + eps : 0.5;
+                const double q = ((double)(0x800000u | ((uint32_t)r & 0x7fffffu)) + t) * 0x1p-23; // in [1, 2)
+                const double scale = __longlong_as_double((long long)(1023 + rel) << 52);         // 2**rel
+                const float a0 = (float)((double)b * q * scale); // normal: exponent within [-55, 87]
+                a = __uint_as_float(__float_as_uint(a0) + (uint32_t)(r >> 40) % 3u - 1u);
+            }
+            bad += __float_as_uint(DevMathF::quot(a, b, y1)) != __float_as_uint(a / b);
+        }
+    }
+    if (bad) atomicAdd(mismatches, bad);
+}
+
+// Hypothesis (1) of DevMathF::quot on the device a plan is about to use, once per device and process: all 2**23 significands.
+// A device that fails it gets c_quot_ok = 0 (coef_guard) and `ok` = false (the plan's `sane`): plain divisions everywhere.
+int quot_selfcheck(int device, bool *ok)
+{
+    static std::mutex mu;
+    static std::vector<int8_t> known; // per device ordinal: 0 not checked yet, 1 passed, -1 failed
+    std::lock_guard<std::mutex> lock(mu);
+    if ((size_t)device >= known.size()) known.resize((size_t)device + 1, 0);
+    if (known[(size_t)device] == 0) {
+        HIP_TRY(hipSetDevice(device));
+        DevBuf cnt;
+        if (int rc = cnt.ensure(sizeof(unsigned long long))) return rc;
+        HIP_TRY(hipMemset(cnt.p, 0, sizeof(unsigned long long)));
+        hipLaunchKernelGGL(k_selfcheck_rcp, dim3((1u << 23) / kBlock), dim3(kBlock), 0, 0, 127u, (unsigned long long *)cnt.p);
+        HIP_TRY(hipGetLastError());
+        unsigned long long bad = 0;
+        HIP_TRY(hipMemcpy(&bad, cnt.p, sizeof bad, hipMemcpyDeviceToHost));
+        if (bad) {
+            const int32_t zero = 0;
+            HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(c_quot_ok), &zero, sizeof zero));
+        }
+        known[(size_t)device] = bad ? -1 : 1;
+    }
+    *ok = known[(size_t)device] > 0;
+    return 0;
+}
 
 int check_device(int device)
 {
