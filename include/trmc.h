@@ -928,6 +928,15 @@ int trmc_stage_forcing(trmc_plan *plan, int nsteps, const void *qlat, int64_t nq
  *              numerators drawn from `seed` -- random significands at every exponent distance in [-40, 50], and
  *              a = b*q moved by -1, 0, +1 units in the last place for q next to the boundary between two floats (bits going
  *              on ...0111... or ...1000...) -- and with the numerator +0, whose quotient must be +0
+ *   what = 4   the same quotient over the operands of the four Muskingum coefficients (DevMathF::div4), which what = 3 does
+ *              not reach: the same 65 666 significands as divisors with exponents drawn from [-21, 52] (2**52 itself as the
+ *              top value), each with n numerators drawn from `seed` at ABSOLUTE magnitudes and of both signs -- in turn
+ *              2**-60 <= |a| <= 2**60 (ql*dt), 2**-45 <= |a| <= 2**52 twice (the two differences) and 2**-21 <= a <= 2**52
+ *              (the positive sum): exponent distances from -112 to +81 -- half of them random significands at exponents
+ *              uniform over the range, both ends included, half a = d*q moved by -1, 0, +1 units in the last place for q of
+ *              either sign next to the boundary between two floats; and with the numerators +0 and -0 through div4 under
+ *              coef_guard's verdict, which must give the +0 and the -0 of the IEEE division (-0, what a negative ql*dt that
+ *              underflows is, has to fail the guard).  n + 2 pairs per divisor.
  * checked_out receives the number of values / triples / pairs compared, mismatches_out how many results differ in any
  * bit (0 is the claim).  No routing state is touched.
  */

@@ -2014,9 +2014,10 @@ int trmc_plan_chain_from(trmc_plan *dst, trmc_plan *src)
 int trmc_selfcheck_fast_arith(int device, int what, int64_t n, uint64_t seed, int64_t *checked_out, int64_t *mismatches_out)
 {
     if (!checked_out || !mismatches_out) return fail(TRMC_EINVAL, "checked_out/mismatches_out is NULL");
-    if (what < 0 || what > 3)
-        return fail(TRMC_EINVAL, "what must be 0 (square root), 1 (division, maximum), 2 (refined reciprocal) or 3 (three-operation quotient)");
-    if ((what == 1 || what == 3) && n < 0) return fail(TRMC_EINVAL, "n < 0");
+    if (what < 0 || what > 4)
+        return fail(TRMC_EINVAL, "what must be 0 (square root), 1 (division, maximum), 2 (refined reciprocal), 3 (three-operation quotient) "
+                                 "or 4 (that quotient over the operands of the Muskingum coefficients)");
+    if ((what == 1 || what == 3 || what == 4) && n < 0) return fail(TRMC_EINVAL, "n < 0");
     if (what == 2 && (n < -126 || n > 126)) return fail(TRMC_EINVAL, "n (the binade's exponent) outside [-126, 126]");
     if (int rc = check_device(device)) return rc;
     HIP_TRY(hipSetDevice(device));
@@ -2035,9 +2036,12 @@ int trmc_selfcheck_fast_arith(int device, int what, int64_t n, uint64_t seed, in
         } else if (what == 2) {
             checked = (int64_t)1 << 23;
             hipLaunchKernelGGL(k_selfcheck_rcp, dim3((1u << 23) / kBlock), dim3(kBlock), 0, 0, (uint32_t)(n + 127), (unsigned long long *)cnt.p);
-        } else {
+        } else if (what == 3) {
             checked = kQuotDivisors * (n + 1); // (+1: the numerator +0 of every divisor)
             hipLaunchKernelGGL(k_selfcheck_quot, dim3(8192), dim3(kBlock), 0, 0, n, seed, (unsigned long long *)cnt.p);
+        } else {
+            checked = kQuotDivisors * (n + 2); // (+2: the numerators +0 and -0 of every divisor, through coef_guard and div4)
+            hipLaunchKernelGGL(k_selfcheck_quot_box, dim3(8192), dim3(kBlock), 0, 0, n, seed, (unsigned long long *)cnt.p);
         }
         e = hipGetLastError();
     }

@@ -35,11 +35,18 @@ struct DevMathF {
     // refinement above.  The kernel proves once per segment-step (`coef_ok`: dt in [2**-20, 2**40] and
     // n4 = ql*dt either +0 or 2**-60 <= |n4| <= 2**60) and once per coefficient set (D <= 2**52) that
     // all four divisions are of that kind: D >= dt/2 >= 2**-21; n1 = Km*X + dt/2 in [2**-21, 2**52];
-    // n2, n3 are differences of two such floats, hence +0 or of magnitude >= 2**-45; so no scaling,
-    // no fix-up, every quotient normal or +0 (for which the refinement returns +0 as IEEE does).  Then
+    // n2, n3 are differences of two such floats, hence +0 or of magnitude >= 2**-45; so for n1, n2, n3 no
+    // scaling, no fix-up, every quotient normal or +0 (for which the refinement returns +0 as IEEE does).  Then
     // the same instructions are issued, minus the three helpers, and y1 once instead of four times:
     // bit-identical by construction -- and of those, the second correction of each quotient is not
-    // issued either (see quot).  Anything else takes the plain divisions.
+    // issued either (see quot).  n4 is the exception to "by construction": |n4| down to 2**-60 over D up to 2**52 is
+    // 2**112 apart, more than the 2**96 inside which v_div_scale is the identity, so there the compiler's division DOES
+    // scale.  The bits agree all the same, because both sides are the correctly rounded quotient: the division by IEEE,
+    // quot by Markstein's theorem, whose side condition holds over the whole box -- q0 = n4*y1 >= 2**-113 and the quotient
+    // <= 2**82 are normal, the residual is 0 or a multiple of 2**-47 |n4| >= 2**-107, normal too (checked over that box on
+    // the device: trmc_selfcheck_fast_arith, what = 4).  A NEGATIVE zero n4 (ql = -0, or a negative product that underflows)
+    // is NOT admitted: quot(-0, D, y1) is +0 where IEEE gives -0, which is why coef_guard tests the bits of n4 for +0.
+    // Anything else takes the plain divisions.
     // The divisions of the hydraulic point (hydraulics_at: radius and composite n by the wetted perimeter, the top-width
     // term of the celerity, the reciprocal of the composite n) under the same argument.  `sane` is established once per
     // plan on the host (params_sane: bw, n, cs, twcc, ncc in [2**-14, 2**17], cs, twcc and ncc possibly 0; dt, dx, s0 as at k_of); with the in-bank and

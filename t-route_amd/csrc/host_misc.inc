@@ -269,6 +269,72 @@ k_selfcheck_quot(int64_t per, uint64_t seed, unsigned long long *mismatches)
     }
     if (bad) atomicAdd(mismatches, bad);
 }
+// The same over DevMathF::div4's OWN operand box (what = 4): the divisor's exponent drawn from [-21, 52], the numerators
+// SIGNED and at absolute magnitudes, by j % 4 the class of
+//   n4 = ql*dt   2**-60 <= |a| <= 2**60      n2, n3   2**-45 <= |a| <= 2**52      n1   2**-21 <= a <= 2**52 (positive)
+// -- exponent distances from -112 to +81, beyond the 2**96 within which the compiler's own division needs no scaling:
+//   j % 8 < 4    a random significand at an exponent uniform over the class's range, 2**hi itself as the top value
+//   else         a = RN(d * q) moved by -1, 0, +1 units in its last place for q next to a rounding boundary (as at what = 3),
+//                of either sign, at an exponent that keeps a two binades inside the class's range
+// and, through div4 itself under the verdict of coef_guard (dt = 1, ql = the numerator, so n4 = ql*dt is the numerator), the
+// numerators +0 and -0: +0 passes the guard and takes the three operations, -0 -- what a negative n4 that underflows is --
+// must fail it and get the -0 of the IEEE division.  One thread per (divisor, 64 numerators).
+struct QuotBox {
+    int lo, hi;
+    bool is_signed;
+};
+__device__ __forceinline__ QuotBox selfcheck_box(int64_t j)
+{
+    const int cls = (int)(j & 3);
+    return cls == 0 ? QuotBox{-60, 60, true} : cls == 3 ? QuotBox{-21, 52, false} : QuotBox{-45, 52, true};
+}
+__global__ void __launch_bounds__(kBlock)
+k_selfcheck_quot_box(int64_t per, uint64_t seed, unsigned long long *mismatches)
+{
+    const int64_t nchunk = per > 0 ? (per + 63) / 64 : 1, total = kQuotDivisors * nchunk; // (per = 0: the zeros alone)
+    unsigned long long bad = 0;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t w = (int64_t)blockIdx.x * kBlock + threadIdx.x; w < total; w += stride) {
+        const int64_t ib = w / nchunk, c = w - ib * nchunk;
+        const uint64_t rb = selfcheck_mix(seed ^ (0x5851f42d4c957f2dull * (uint64_t)(ib + 1)));
+        const int eb = -21 + (int)((rb >> 32) % 74u);                                         // [-21, 52]
+        const uint32_t sig = eb == 52 ? 0u : selfcheck_divisor_sig(ib);                      // (d <= 2**52: the top value itself)
+        const float b = __uint_as_float(((uint32_t)(eb + 127) << 23) | sig);
+        const float y1 = DevMathF::refined_rcp(b);
+        if (c == 0) {
+            for (int neg = 0; neg < 2; ++neg) {
+                const uint32_t sign = neg ? 0x80000000u : 0u;
+                const float z = __uint_as_float(sign);
+                DevMathF m{nullptr, false};
+                m.coef_ok = coef_guard(1.0f, z);
+                float q1, q2, q3, q4;
+                m.div4(b, z, z, z, b, q1, q2, q3, q4);
+                bad += __float_as_uint(q4) != __float_as_uint(z / b) || __float_as_uint(q4) != sign;
+            }
+        }
+        const int64_t j1 = (c + 1) * 64 < per ? (c + 1) * 64 : per;
+        for (int64_t j = c * 64; j < j1; ++j) {
+            const uint64_t r = selfcheck_mix(rb + (uint64_t)j);
+            const QuotBox box = selfcheck_box(j);
+            const uint32_t sign = (box.is_signed && ((r >> 63) & 1u)) ? 0x80000000u : 0u;
+            float a;
+            if ((j & 4) == 0) {
+                a = __uint_as_float(__float_as_uint(selfcheck_draw(r >> 1, box.lo, box.hi)) | sign);
+            } else {
+                const uint32_t k = 2u + (uint32_t)((r >> 24) % 23u), pick = (uint32_t)(r >> 32) % 3u;
+                const double eps = __longlong_as_double((long long)(1023u - k) << 52); // 2**-k
+                const double t = pick == 0 ? 0.5 - eps : pick == 1 ? 0.5 + eps : 0.5;
+                const double q = ((double)(0x800000u | ((uint32_t)r & 0x7fffffu)) + t) * 0x1p-23; // in [1, 2)
+                const int ea = box.lo + 1 + (int)((r >> 44) % (uint32_t)(box.hi - box.lo - 3));   // [lo + 1, hi - 3]
+                const double scale = __longlong_as_double((long long)(1023 + ea - eb) << 52);     // |ea - eb| <= 112
+                const float a0 = (float)((double)b * q * scale);                                  // in [2**ea, 2**(ea + 2))
+                a = __uint_as_float((__float_as_uint(a0) + (uint32_t)(r >> 40) % 3u - 1u) | sign);
+            }
+            bad += __float_as_uint(DevMathF::quot(a, b, y1)) != __float_as_uint(a / b);
+        }
+    }
+    if (bad) atomicAdd(mismatches, bad);
+}
 
 // Hypothesis (1) of DevMathF::quot on the device a plan is about to use, once per device and process: all 2**23 significands.
 // A device that fails it gets c_quot_ok = 0 (coef_guard) and `ok` = false (the plan's `sane`): plain divisions everywhere.

@@ -47,3 +47,17 @@ def test_quotient_has_the_bits_of_the_division():
     _lib.check(lib.trmc_selfcheck_fast_arith(0, 3, 4096, 1, C.byref(checked), C.byref(bad)))
     print(f"{checked.value} pairs, {bad.value} mismatches")
     assert checked.value == 65666 * 4097 and bad.value == 0, (checked.value, bad.value)
+
+
+def test_quotient_has_the_bits_of_the_division_over_the_operands_of_the_coefficients():
+    """The same over DevMathF::div4's own operand box (what = 4), which the test above does not reach: the 65 666 divisors at
+    exponents in [-21, 52], each with 4 096 numerators of both signs at absolute magnitudes -- 2**-60 .. 2**60 (ql*dt), 2**-45 ..
+    2**52 (the two differences), 2**-21 .. 2**52 (the sum): exponent distances from -112 to +81, past the 2**96 inside which the
+    compiler's division needs no scaling -- half of them a = d*q +- 1 ulp for q of either sign next to a rounding boundary; and
+    the numerators +0 and -0 through div4 under coef_guard's verdict, which must give the zeros of the IEEE division (-0 is what
+    a negative ql*dt that underflows becomes: it has to fail the guard).  No mismatch is allowed."""
+    lib = _lib.lib()
+    checked, bad = C.c_int64(0), C.c_int64(-1)
+    _lib.check(lib.trmc_selfcheck_fast_arith(0, 4, 4096, 1, C.byref(checked), C.byref(bad)))
+    print(f"{checked.value} pairs, {bad.value} mismatches")
+    assert checked.value == 65666 * 4098 and bad.value == 0, (checked.value, bad.value)
