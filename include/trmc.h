@@ -760,7 +760,7 @@ int trmc_window_courant_kernel_ms(const trmc_plan *plan, double *ms_out);
  *                              (2 z), with z = 1 / cs, 1 where cs == 0).  Rows that route no Muskingum-Cunge step at the time of
  *                              the call -- boundary rows, rows declared by trmc_set_reservoirs: a pool's elevation has no
  *                              bankfull -- get +inf.  "Out of bank" is then quantity = TRMC_X_DEPTH against this array.
- * A stream of windows (trmc_stream_*) has no exceedance product.
+ * A stream of windows (trmc_stream_*) has no exceedance PRODUCT of the day; it has the exceedance over all its days: below.
  */
 enum { TRMC_X_FLOW = 0, TRMC_X_VELOCITY = 1, TRMC_X_DEPTH = 2 };
 int trmc_plan_set_thresholds(trmc_plan *plan, int32_t nlevels, const void *th);
@@ -769,6 +769,34 @@ int trmc_window_exceedance(trmc_plan *plan, int32_t rowset, int quantity, int32_
 int trmc_window_exceedance_tile(int precision, int32_t *rows, int32_t *steps);
 int trmc_window_exceedance_kernel_ms(const trmc_plan *plan, double *ms_out);
 int trmc_plan_bankfull_depth(trmc_plan *plan, void *dst);
+/*
+ * Threshold exceedance OVER A WHOLE STREAM OF DAYS (trmc_stream_*): the four figures above for the flow of every row against the
+ * plan's thresholds, over every step of every day handed over since trmc_stream_begin -- t runs on over the days, 1-based from the
+ * stream's first step, and a run that is open at a day's last step goes on at the next day's first: a flood from day 3 to day 6
+ * is one run, which is why this is not a product of the day.  The state (per row and level: count, first, last, longest and
+ * current run) lives on the device outside the ring, as the totals of TRMC_SUMMARY_TOTAL do; where a day is handed over one pass
+ * over the day's flow plane (csrc/k_stream_exceed.inc, beside the summary's) folds it in, in day order.  Nothing of it is a member
+ * of trmc_stream_day or crosses to the host per day.  Off (the default): no buffer, no launch.
+ *   trmc_stream_set_exceedance  quantity: TRMC_X_FLOW, or -1 for none.  Before trmc_stream_begin; it stays until the next call, as
+ *                              trmc_stream_set_summary's mask does; TRMC_ESTATE while a stream is in progress, and without
+ *                              thresholds on this plan handle (trmc_plan_set_thresholds: the levels and values a stream uses are
+ *                              those set when it begins; trmc_stream_begin is TRMC_ESTATE if they were cleared meanwhile).
+ *                              TRMC_EUNSUPPORTED for TRMC_X_VELOCITY and TRMC_X_DEPTH: the ring's planes hold every step's flow
+ *                              but only a tile's last depth, and a stream without full_output forms no velocity -- route the
+ *                              day in question as a window (trmc_window_exceedance).  TRMC_EINVAL for any other value and on
+ *                              the dataflow engine, which runs no stream.  Works with full_output, output_stride or neither,
+ *                              with reservoirs (the pool's outflow), gages (the nudged flow) and reservoir data assimilation, in
+ *                              both arithmetics and precisions.  The steps are counted in 32 bits on the device:
+ *                              trmc_stream_push_day is TRMC_EUNSUPPORTED for the day that would take the stream past 2^31 - 1.
+ *   trmc_stream_exceedance     HOST arrays int64 [nseg][K], row order, exactly the K columns of trmc_plan_set_thresholds (any may
+ *                              be NULL); synchronous on the copy stream behind the last fold queued: returns when the figures
+ *                              over all days handed over so far are on the host and writes that number of days to days_out.
+ *                              TRMC_ESTATE when no stream is in progress, when it was begun without an exceedance or when no
+ *                              day is complete yet.
+ */
+int trmc_stream_set_exceedance(trmc_plan *plan, int quantity);
+int trmc_stream_exceedance(trmc_plan *plan, int64_t *steps_over, int64_t *first_step, int64_t *last_step, int64_t *longest_run,
+                           int64_t *days_out);
 /* on != 0: trmc_upload_forcing turns every NaN of qlat and q0 into 0 on the device, behind the copy.  The reference's reindexed
  * tables hold NaN on waterbody rows (compute.py:1466-1467), which the Muskingum-Cunge rows never read; the drop-in used to screen
  * the caller's frames for them on the host -- 20 ms of a CONUS call.  Default off: values go to the kernels as they are. */

@@ -186,6 +186,8 @@ SIGNATURES = {
     "trmc_window_exceedance_tile": (_int, [_int, _P(_i32), _P(_i32)]),
     "trmc_window_exceedance_kernel_ms": (_int, [_vp, _P(C.c_double)]),
     "trmc_plan_bankfull_depth": (_int, [_vp, _vp]),
+    "trmc_stream_set_exceedance": (_int, [_vp, _int]),
+    "trmc_stream_exceedance": (_int, [_vp, _vp, _vp, _vp, _vp, _P(_i64)]),
     "trmc_plan_set_nan_is_zero": (_int, [_vp, _int]),
     "trmc_host_alloc": (_int, [C.c_size_t, C.POINTER(C.c_void_p)]),
     "trmc_host_free": (_int, [_vp]),

@@ -58,6 +58,13 @@
 // THE TOTALS over the days of the stream (TRMC_SUMMARY_TOTAL) live outside the ring: [nseg] arrays in row order into which
 // k_stream_total folds every day's summary, in day order, right behind the kernels that formed it; trmc_stream_summary_total
 // fetches them.
+// THRESHOLD EXCEEDANCE OVER THE WHOLE STREAM (trmc_stream_set_exceedance) has that shape too, and for a stronger reason: a flood that
+// begins on day 3 and ends on day 6 is ONE run, which no product of a day can hold.  The state -- per row and level the count, the
+// first and the last step, the longest and the current run -- is an accumulator outside the ring; k_stream_exceed
+// (k_stream_exceed.inc) folds every day's flow plane into it where the day is handed over, in day order, against the plan's
+// threshold table, and trmc_stream_exceedance fetches it.  No row of the product table, no member of trmc_stream_day, nothing per
+// day on the copy stream.  Flows only: the planes hold a tile's last depth and a products-only stream forms no velocity.  Off (the
+// default): no buffer, no launch.
 extern "C++" {
 // THE PRODUCTS A DAY CAN HAND TO THE HOST, one row of StreamRun::tab each.  trmc_stream_begin fills the row (stream_begin_t: whether
 // the stream carries the product, a slot's bytes, where a slot's bytes begin on the device), a push names the day's destinations
@@ -100,6 +107,7 @@ struct StreamRun {
     DevStream fst;                      // the forcing's own stream (H2D + its reordering; the products leave on the plan's copy stream)
     DevEvent ev_begin, ev_bnd, ev_gat;
     DevEvent ev_total;                  // (the totals over the days) the last fold queued is through
+    DevEvent ev_exc;                    // (the exceedance over the days) likewise
     std::vector<DevEvent> ev_slab;      // ring: "slab launch g is complete" (the cluster launch g + 1 waits for it)
     std::vector<DevEvent> ev_free;      // [slots] the day that used the slot has handed its products over
     std::vector<DevEvent> ev_ready;     // [slots] the gathers of that day are through (copy stream waits)
@@ -144,6 +152,13 @@ struct StreamRun {
     // the steps are int64 here); tot_days days are folded in (queued)
     DevBuf tot[P_N - P_PEAK];
     int64_t tot_days = 0;
+    // the exceedance over the days (the head of this file).  exc_want: trmc_stream_set_exceedance's quantity (-1: none), it outlives
+    // a stream as sum_want does; exc, exc_K, exc_KP: of the stream in progress (the plan's levels and its table's row width, which
+    // cannot change while a stream runs); exc_acc: int32 [5][exc_KP][nseg_pad] in plan order; exc_rows: int64 [4][nseg][exc_K] in row
+    // order, what a fetch gathers for the host; exc_days days are folded in (queued)
+    int32_t exc_want = -1, exc = -1, exc_K = 0, exc_KP = 0;
+    DevBuf exc_acc, exc_rows;
+    int64_t exc_days = 0;
     bool bnd_pending = false;
 };
 
@@ -363,6 +378,22 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
         HIP_TRY(hipEventRecord(S.ev_total, pst));
         S.tot_days = e + 1;
     }
+    if (S.exc >= 0 && pl->nseg > 0) { // (the day's flow plane folded into the exceedance over the days: in day order, before the slot is freed)
+        const int32_t t0 = (int32_t)(e * S.nsteps);   // (stream_push_t keeps the stream's steps within int32)
+        auto fold = [&](auto kp) {
+            hipLaunchKernelGGL((k_stream_exceed<T, decltype(kp)::value>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, q,
+                               (const int32_t *)pl->sh->row_of_pos.p, (const T *)pl->thresholds.p, (int32_t *)S.exc_acc.p, (int32_t)pl->nseg,
+                               pl->nseg_pad, S.nsteps, t0);
+        };
+        switch (S.exc_KP) {
+        case 1: fold(std::integral_constant<int, 1>{}); break;
+        case 2: fold(std::integral_constant<int, 2>{}); break;
+        case 4: fold(std::integral_constant<int, 4>{}); break;
+        default: return fail(TRMC_ESTATE, "internal: the stream's exceedance has no threshold table");
+        }
+        HIP_TRY(hipEventRecord(S.ev_exc, pst));
+        S.exc_days = e + 1;
+    }
     HIP_TRY(hipGetLastError());
     if (!any) {
         HIP_TRY(hipEventRecord(S.ev_free[(size_t)slot], pst));
@@ -548,6 +579,23 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
     if (S.rda) S.tab[P_RDA_IDX].base = S.tab[P_RDA].base + rda4;
     if (tot)
         if (int rc = S.ev_total.ensure(false)) return rc;
+    // the exceedance over the days: the accumulator (zeroed below, in front of ev_begin) and what a fetch gathers into
+    S.exc = S.exc_want;
+    S.exc_days = 0;
+    if (S.exc >= 0 && pl->th_levels < 1)
+        return fail(TRMC_ESTATE, "the streams of this plan were told to form an exceedance (trmc_stream_set_exceedance), but its thresholds have been "
+                                 "cleared since (trmc_plan_set_thresholds)");
+    S.exc_K = S.exc >= 0 ? pl->th_levels : 0;
+    S.exc_KP = S.exc >= 0 ? pl->th_pad : 0;
+    const size_t exc_bytes = (size_t)kStreamExceedFields * (size_t)S.exc_KP * np * sizeof(int32_t);
+    if (S.exc < 0) {
+        S.exc_acc.release();
+        S.exc_rows.release();
+    } else {
+        if (int rc = S.exc_acc.ensure(exc_bytes)) return rc;
+        if (int rc = S.exc_rows.ensure(4 * (size_t)pl->nseg * (size_t)S.exc_K * sizeof(int64_t))) return rc;
+        if (int rc = S.ev_exc.ensure(false)) return rc;
+    }
     // reservoir data assimilation: the slots' tables at their capacity, the carry with the state trmc_set_reservoir_da supplied
     // (or the plan's last window left in those tables); the days' state records are products (P_RDA)
     S.slot_rda = 0;
@@ -599,6 +647,7 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
         pl->forcing_pending = false;
     }
     HIP_TRY(hipMemsetAsync(pl->it_prev.p, 0, (size_t)np, st));
+    if (S.exc >= 0 && exc_bytes > 0) HIP_TRY(hipMemsetAsync(S.exc_acc.p, 0, exc_bytes, st));
     if (pl->collect_cost) {
         if (int rc = pl->it_sum.ensure(np * sizeof(uint16_t))) return rc;
         HIP_TRY(hipMemsetAsync(pl->it_sum.p, 0, np * sizeof(uint16_t), st));
@@ -638,6 +687,9 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
     hipStream_t hst = S.fst; // (the forcing's own stream: the products of earlier days leave on the plan's copy stream meanwhile)
     if (d >= S.slots && S.days_complete <= d - S.slots)
         return fail(TRMC_ESTATE, "internal: the slot of the new day still belongs to a day that has not been queued to its end");
+    if (S.exc >= 0 && (d + 1) * (int64_t)S.nsteps > (int64_t)INT32_MAX)
+        return fail(TRMC_EUNSUPPORTED, "the exceedance over the days of a stream counts its steps in 32 bits on the device: this day would take the "
+                                       "stream past 2^31 - 1 steps -- begin a new stream");
     StreamProd &p = S.prod[(size_t)slot];
     // (the host image of the slot's reservoir tables is written below: the copy of the slot's last day must have read it)
     if (S.rda && p.day >= 0) HIP_TRY(hipEventSynchronize(S.ev_forcing[(size_t)slot]));
@@ -894,6 +946,51 @@ int trmc_stream_summary_total(trmc_plan *pl, void *peak_flow, int64_t *peak_step
             for (size_t i = 0; i < n; ++i) m[i] = m[i] / (double)days;
         }
     }
+    if (days_out) *days_out = days;
+    return 0;
+}
+
+int trmc_stream_set_exceedance(trmc_plan *pl, int quantity)
+{
+    if (int rc = stream_check(pl, false)) return rc;
+    if (quantity == -1) { // (withdrawn: the next stream holds no accumulator and queues no fold)
+        if (pl->seq) pl->seq->exc_want = -1;
+        return 0;
+    }
+    if (quantity == TRMC_X_VELOCITY || quantity == TRMC_X_DEPTH)
+        return fail(TRMC_EUNSUPPORTED, "the exceedance of a stream of windows is formed from the flow planes of its ring, which hold every step's flow "
+                                       "of every row: they hold the depth of a tile's last step only, and a stream without full_output forms no "
+                                       "velocity -- for depth, velocity or out of bank route the day in question as a window "
+                                       "(trmc_window_exceedance)");
+    if (quantity != TRMC_X_FLOW) return fail(TRMC_EINVAL, "quantity must be TRMC_X_FLOW (or -1: no exceedance)");
+    if (pl->flow) return fail(TRMC_EINVAL, "a stream of windows runs on the level engine");
+    if (pl->th_levels < 1) return fail(TRMC_ESTATE, "no thresholds set on this plan (trmc_plan_set_thresholds)");
+    if (!pl->seq) pl->seq = std::make_unique<StreamRun>();
+    pl->seq->exc_want = quantity;
+    return 0;
+}
+
+int trmc_stream_exceedance(trmc_plan *pl, int64_t *steps_over, int64_t *first_step, int64_t *last_step, int64_t *longest_run, int64_t *days_out)
+{
+    if (int rc = stream_check(pl, true)) return rc;
+    StreamRun &S = *pl->seq;
+    if (S.exc < 0) return fail(TRMC_ESTATE, "the stream was begun without an exceedance (trmc_stream_set_exceedance precedes trmc_stream_begin)");
+    if (S.exc_days < 1)
+        return fail(TRMC_ESTATE, "no day of the stream is complete yet: its last rows run " + std::to_string(S.lmax)
+                                     + " tiles behind its first -- push further days or trmc_stream_flush");
+    const int64_t days = S.exc_days;
+    const size_t n = (size_t)pl->nseg * (size_t)S.exc_K;
+    int64_t *const dst[4] = {steps_over, first_step, last_step, longest_run};
+    // behind the last fold queued (nothing is queued meanwhile: the calls of a plan come from one thread)
+    HIP_TRY(hipStreamWaitEvent(pl->cstream, S.ev_exc, 0));
+    if (n && (steps_over || first_step || last_step || longest_run)) {
+        hipLaunchKernelGGL(k_stream_exceed_rows, dim3(blocks_for((int64_t)n)), dim3(kBlock), 0, pl->cstream, (const int32_t *)S.exc_acc.p,
+                           (const int32_t *)pl->sh->pos_of_row.p, (int64_t *)S.exc_rows.p, (int32_t)pl->nseg, pl->nseg_pad, S.exc_K, S.exc_KP);
+        HIP_TRY(hipGetLastError());
+        for (int f = 0; f < 4; ++f)
+            if (dst[f]) HIP_TRY(hipMemcpyAsync(dst[f], (const int64_t *)S.exc_rows.p + (size_t)f * n, n * sizeof(int64_t), hipMemcpyDeviceToHost, pl->cstream));
+    }
+    HIP_TRY(hipStreamSynchronize(pl->cstream));
     if (days_out) *days_out = days;
     return 0;
 }

@@ -81,6 +81,7 @@ namespace {
 #include "k_window_summary.inc"
 #include "k_window_courant.inc"
 #include "k_window_exceed.inc"
+#include "k_stream_exceed.inc"
 // ---------------------------------------------------------------- plan
 #include "dev_owner.hpp"
 

@@ -541,6 +541,53 @@ class RoutingPlan:
         out["days"] = int(days.value)
         return out
 
+    # what a stream cannot form an exceedance of, and why (include/trmc.h trmc_stream_set_exceedance says the same)
+    STREAM_EXCEEDANCE_FLOW_ONLY = ("the exceedance of a stream of days is formed from the flow planes of its ring, which hold every step's flow of "
+                                   "every row: they hold the depth of a tile's last step only and a stream without full_output forms no velocity, "
+                                   "so {what!r} is not available -- route the day in question as a window (RoutingPlan.window_exceedance, "
+                                   "the drop-in's exceedance=)")
+
+    @classmethod
+    def stream_exceedance_quantity(cls, quantity):
+        """``quantity`` of a stream's exceedance, checked: "flow" (returned as trmc's number) or None; NotImplementedError for
+        "depth", "velocity" and "bankfull", ValueError for anything else."""
+        if quantity is None:
+            return -1
+        if quantity in ("depth", "velocity", "bankfull"):
+            raise NotImplementedError(cls.STREAM_EXCEEDANCE_FLOW_ONLY.format(what=quantity))
+        if quantity != "flow":
+            raise ValueError(f"exceedance of a stream: quantity 'flow' or None, got {quantity!r}")
+        return _lib.TRMC_X_FLOW
+
+    def stream_set_exceedance(self, quantity="flow"):
+        """The streams on this plan keep, on the device and over ALL their days, the threshold exceedance of every row's flow
+        against ``set_thresholds`` (which must precede this call): steps over, first and last step, longest run, the steps counted
+        on over the days and a run carried over a day's end (trmc_stream_set_exceedance; ``stream_exceedance`` fetches).  Declared
+        before ``stream_begin``; it stays until the next call; ``None`` withdraws it.  Flow only: "depth", "velocity" and
+        "bankfull" raise NotImplementedError -- route the day in question as a window."""
+        q = self.stream_exceedance_quantity(quantity)
+        _lib.check(_lib.lib().trmc_stream_set_exceedance(self._h, q))
+        self._stream_exceedance = q
+
+    def stream_exceedance(self, parts=("steps_over", "first_step", "last_step", "longest_run")):
+        """The exceedance over all days of the stream in progress that have been handed over so far (trmc_stream_exceedance,
+        synchronous): a dict with ``"days"`` and, of ``steps_over``, ``first_step``, ``last_step`` and ``longest_run``, the parts
+        asked for -- int64 [nseg, K] arrays in row order, the steps 1-based from the stream's first step, as ``window_exceedance``
+        defines them over the days' flows one after the other."""
+        parts = (parts,) if isinstance(parts, str) else tuple(parts or ())
+        unknown = [p for p in parts if p not in self.WINDOW_EXCEEDANCE_PARTS]
+        if unknown:
+            raise ValueError(f"unknown part(s) of a stream's exceedance {unknown}: one of {list(self.WINDOW_EXCEEDANCE_PARTS)}")
+        if not parts:
+            raise ValueError("stream_exceedance: no part asked for")
+        k = getattr(self, "_th_levels", 0)
+        out = {name: (np.empty((self.nseg, k), np.int64) if name in parts else None) for name in self.WINDOW_EXCEEDANCE_PARTS}
+        days = C.c_int64(0)
+        _lib.check(_lib.lib().trmc_stream_exceedance(self._h, *(_lib.ptr(out[name]) for name in self.WINDOW_EXCEEDANCE_PARTS), C.byref(days)))
+        res = {"days": int(days.value)}
+        res.update((name, a) for name, a in out.items() if a is not None)
+        return res
+
     def stream_gather(self, day, rowset, device_ptr, stream=0):
         """Flows of a row set over `day` [rows, nsteps] into device memory (trmc_stream_gather)."""
         _lib.check(_lib.lib().trmc_stream_gather(self._h, int(day), int(rowset), C.c_void_p(device_ptr), C.c_void_p(stream or 0)))

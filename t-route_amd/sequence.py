@@ -436,6 +436,14 @@ class RouteStream:
     from the stream's first step -- once ``route()`` has yielded its last day; ``daily_summary=False`` then leaves the per-day
     dict out (the tuples of ``summary=None``) and no per-day summary array crosses to the host.
 
+    ``exceedance=("flow", thresholds)``: the device also keeps, over ALL days of the stream, every row's threshold exceedance --
+    ``thresholds`` [rows] or [rows, K] (K <= 4) in the router's row order, a rank of a multi-rank job taking its own ``rows`` of
+    them as it does of ``state0``; they are set on the plan that streams (``RoutingPlan.set_thresholds``).  ``rs.exceedance`` holds
+    ``RoutingPlan.stream_exceedance()`` -- ``"days"`` and int64 [rows, K] ``steps_over``, ``first_step``, ``last_step``,
+    ``longest_run`` over this rank's ``rows``, the steps 1-based from the stream's first step and a run carried over a day's end
+    -- once ``route()`` has yielded its last day, next to ``rs.total``.  It is not a product of the day: the tuples do not change.
+    Flow only ("depth", "velocity", "bankfull": NotImplementedError -- route the day in question as a window).
+
     Underneath is ONE stream of tile launches (include/trmc.h, trmc_stream_*): the tile index runs on over the days, every
     launch routes every row through the next K steps of its own place in the stream -- a row deep in the network works on an
     earlier tile than the headwaters, possibly of an earlier day -- so a day costs nsteps / K launches and nothing else, and a
@@ -450,7 +458,7 @@ class RouteStream:
 
     def __init__(self, router, nsteps, qts_subdivisions, output_stride=None, full_output=False, slots=0, latency="throughput",
                  hydrographs_on_every_rank=False, comm=None, exchange=None, reservoir_da_ncol=None, summary=None,
-                 daily_summary=True):
+                 daily_summary=True, exceedance=None):
         """comm / exchange (several ranks): the communicator -- default: the one given to ``router.enable_device_exchange`` -- and
         how the daily cut-edge hydrographs travel: "device" (gather kernel -> all-gather on the exchange stream -> boundary rows,
         everything in HBM: RCCL over xGMI) or "host" (through ``comm.all_gather_rows_host``: any communicator with that method,
@@ -469,6 +477,22 @@ class RouteStream:
         self.summary = summary
         self.daily_summary = bool(daily_summary)
         self.total = None
+        self.exceedance = None
+        self._exc_th = None
+        if exceedance is not None:
+            try:
+                quantity, th = exceedance
+            except (TypeError, ValueError):
+                raise ValueError("exceedance: (\"flow\", thresholds)") from None
+            if isinstance(th, str):     # (the drop-in's ("depth", "bankfull"): a depth)
+                quantity = th if quantity in _lib.X_NAMES else quantity
+            from .plan import RoutingPlan
+            RoutingPlan.stream_exceedance_quantity(quantity)
+            th = np.asarray(th)
+            th = th[:, None] if th.ndim == 1 else th
+            if th.ndim != 2 or th.shape[0] != router.nseg or not 1 <= th.shape[1] <= 4:
+                raise ValueError(f"exceedance: thresholds must be [rows] or [rows, K] with rows = {router.nseg} and K <= 4: got {th.shape}")
+            self._exc_th = th
         if latency not in ("throughput", "low"):
             raise ValueError("latency must be 'throughput' or 'low'")
         self.r = router
@@ -653,6 +677,12 @@ class RouteStream:
         P.upload_forcing(nsteps, np.ascontiguousarray(nxt[rows] if pick else nxt, dtype=P.dtype), q0)   # the state and the shape of the forcing
         if self.summary or getattr(P, "_stream_summary", 0):   # (the declaration outlives a stream: an earlier one's is withdrawn)
             P.stream_set_summary(self.summary)
+        if self._exc_th is not None:                           # (on the plan that streams: this rank's rows of them)
+            P.set_thresholds(self._exc_th[rows])
+            P.stream_set_exceedance("flow")
+        elif getattr(P, "_stream_exceedance", -1) >= 0:        # (an earlier stream's declaration is withdrawn, as its summary is)
+            P.stream_set_exceedance(None)
+        self.exceedance = None
         P.stream_begin(nsteps, self.qts, slots=slots, full_output=self.full_output and not self.output_stride, output_stride=self.output_stride,
                        **({} if rda is None else {"reservoir_da": True if self._rda_ncol is None else self._rda_ncol}))
         self.info = info = P.stream_info()
@@ -689,6 +719,8 @@ class RouteStream:
         P.stream_flush()
         if "total" in self.summary:     # (every day has been handed over on the device: the totals of the whole stream)
             self.total = P.stream_summary_total()
+        if self._exc_th is not None:    # (... and the exceedance over all of its steps)
+            self.exceedance = P.stream_exceedance()
         while delivered < d:
             yield self._deliver(delivered, ring, gage, rdac, extras)
             delivered += 1

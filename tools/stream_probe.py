@@ -9,7 +9,10 @@ row and the hydrographs of sampled rows bit for bit, and what a day costs either
                                                             of the one-by-one day's full result where that fits (nseg * 288 <= 2^26)
                                [--summary-depth]            ... and the peak depth with its step (carried by the tile kernels)
                                [--summary-total]            the totals over the days on the device, fetched once at the end; the
-                                                            days' own summary arrays then stay on the device"""
+                                                            days' own summary arrays then stay on the device
+                               [--exceedance K]             the threshold exceedance of every row's flow over ALL days of the stream at
+                                                            K levels (trmc_stream_set_exceedance), fetched once at the end; checked
+                                                            against the numpy loop over the one-by-one days' flows where that fits"""
 import argparse
 import os
 import sys
@@ -41,12 +44,15 @@ ap.add_argument("--reservoir-da", type=int, default=0, help="so many of the --re
 ap.add_argument("--summary", action="store_true", help="per-row peak flow, step of the peak and mean flow of every day as stream products")
 ap.add_argument("--summary-depth", action="store_true", help="the day's peak depth and its step as well (with or without --summary)")
 ap.add_argument("--summary-total", action="store_true", help="the totals over the days of the stream; no per-day summary array crosses to the host")
+ap.add_argument("--exceedance", type=int, default=0, metavar="K", help="exceedance of K (1..4) flow thresholds a row over the whole stream, kept on the device")
 ap.add_argument("--gages", type=int, default=0, help="nudged gages scattered over the network (observations: 70 %% valid, lognormal)")
 a = ap.parse_args()
 if a.reservoir_da > a.reservoirs:
     ap.error("--reservoir-da counts among the --reservoirs")
 if a.summary_total and not (a.summary or a.summary_depth):
     ap.error("--summary-total totals --summary and / or --summary-depth")
+if not 0 <= a.exceedance <= 4:
+    ap.error("--exceedance: 1 to 4 levels (0: none)")
 _lib.single_hw_queue_per_priority("stream_probe")
 nnet = S.CONUS_NNET if a.nseg == S.CONUS_NSEG else max(1, a.nseg // 185)
 net = S.generate(a.nseg, nnet, cache_dir=os.environ.get("TRMC_SYNTH_CACHE", "/tmp"))
@@ -139,7 +145,23 @@ def peak_of(q):
     return peak, step
 
 
+def exceedance_of(x, th):
+    """steps over, first step, last step, longest run [rows, K] (int64) of x [rows, steps] against th [rows, K]: include/trmc.h"""
+    count, first, last, longest, run = (np.zeros(th.shape, np.int64) for _ in range(5))
+    with np.errstate(invalid="ignore"):
+        for t in range(1, x.shape[1] + 1):
+            over = x[:, t - 1][:, None] > th
+            count = count + over
+            first = np.where(over & (first == 0), t, first)
+            last = np.where(over, t, last)
+            run = np.where(over, run + 1, 0)
+            longest = np.maximum(longest, run)
+    return {"steps_over": count, "first_step": first, "last_step": last, "longest_run": longest}
+
+
 any_summary = a.summary or a.summary_depth
+check_exc = a.exceedance and not a.no_check and n * nsteps * a.days <= 1 << 26
+ref_q = []
 daily = any_summary and not a.summary_total
 check_summary = any_summary and not a.no_check and n * nsteps <= 1 << 26
 ref_sum = []
@@ -179,6 +201,8 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
             if check_summary:
                 full = fvd if (a.full and not a.stride) else p.download_fvd()
                 ref_sum.append(summary_of(np.ascontiguousarray(full[:, :, 0])) + peak_of(np.ascontiguousarray(full[:, :, 2])))
+            if check_exc:
+                ref_q.append(np.ascontiguousarray((full if check_summary else p.download_fvd())[:, :, 0]))
             if a.reservoir_da:
                 da_state, da_tsidx = p.download_reservoir_da()
                 da_state[da_kind != 0, 0] -= da_t_end
@@ -192,6 +216,15 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
     p.upload_forcing(nsteps, days[0], q0)
     p.stream_set_summary((("peak", "mean") if a.summary else ()) + (("peak_depth",) if a.summary_depth else ())
                          + (("total",) if a.summary_total else ()) or None)
+    if a.exceedance:
+        # a row's levels: quantiles of its own flows over the stream where they are known (the check), else multiples of its forcing
+        if check_exc:
+            exc_x = np.concatenate(ref_q, axis=1)
+            exc_th = np.quantile(exc_x.astype(np.float64), (0.5, 0.25, 0.9, 0.75)[:a.exceedance], axis=1).T.astype(np.float32)
+        else:
+            exc_th = days[0].mean(axis=1, dtype=np.float32)[:, None] * np.array([1, 10, 100, 1000], np.float32)[None, :a.exceedance]
+        p.set_thresholds(exc_th)
+        p.stream_set_exceedance("flow")
     p.stream_begin(nsteps, qts, reservoir_da=bool(a.reservoir_da) or None, slots=a.slots + a.later if a.slots else (a.later and 2 + -(-(int(p.lags()[0].max(initial=0)) + 1) // (nsteps // p.tile_steps)) + a.later), full_output=a.full and not a.stride, output_stride=a.stride)
     info = p.stream_info()
     print("stream:", info, flush=True)
@@ -269,6 +302,17 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
                 if not np.array_equal((m / np.float32(a.days)).view(np.uint32), tot["mean_flow"].view(np.uint32)):
                     ok = False
                     print("   totals: mean_flow differs", flush=True)
+    if a.exceedance:
+        t1 = time.perf_counter()
+        exc = p.stream_exceedance()
+        print(f"   exceedance at {a.exceedance} level(s) over {exc['days']} days fetched in {(time.perf_counter() - t1) * 1e3:.2f} ms: "
+              f"{int(np.count_nonzero(exc['steps_over']))} of {exc['steps_over'].size} (row, level) pairs went over, longest run {int(exc['longest_run'].max())} steps;",
+              "not checked (no check asked for, or too large for a host loop)" if not check_exc else "", flush=True)
+        if check_exc:
+            want = exceedance_of(exc_x, exc_th)
+            same = exc["days"] == a.days and all(np.array_equal(exc[k], want[k]) for k in want)
+            ok = ok and same
+            print("   exceedance equals the numpy loop over the one-by-one days' flows:", same, flush=True)
     dev_ms = [p.stream_day_ms(e) for e in range(max(behind + 1, a.days - D + 1), a.days)]    # (days pushed into a full stream, still in the ring)
     p.stream_end()
     if dev_ms:
