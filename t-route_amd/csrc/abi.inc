@@ -1338,26 +1338,52 @@ int trmc_download_fvd_rowset(trmc_plan *pl, int stride, int32_t rowset, void *fv
     return 0;
 }
 
-int trmc_window_summary_tile(int precision, int32_t *rows, int32_t *steps)
+// ---- the per-row products of a FINISHED window: trmc_window_summary, _courant, _courant_summary, _exceedance
+
+// (rows, steps) of a product kernel's tile
+static int window_tile(int precision, int32_t *rows, int32_t *steps, int32_t tile_rows, int32_t steps32, int32_t steps64)
 {
     if (precision != 32 && precision != 64) return fail(TRMC_EINVAL, "precision must be 32 or 64");
-    if (rows) *rows = kWsumRows;
-    if (steps) *steps = precision == 32 ? kWsumSteps<float> : kWsumSteps<double>;
+    if (rows) *rows = tile_rows;
+    if (steps) *steps = precision == 32 ? steps32 : steps64;
     return 0;
+}
+
+// device time of a product's last kernel (`none`: the refusal while none has been timed)
+static int window_kernel_ms(const trmc_plan *pl, KernelTimer trmc_plan::*timer, double *ms_out, const char *none)
+{
+    if (!pl || !ms_out) return fail(TRMC_EINVAL, "plan/ms_out is NULL");
+    if ((pl->*timer).ms < 0) return fail(TRMC_ESTATE, none);
+    *ms_out = (pl->*timer).ms;
+    return 0;
+}
+
+// "The last finished window's result is there."  The products read `out` (the Courant metrics its forcing and initial state too),
+// which windows alone assemble and which is whole only once the window has ended: a stream of days leaves its own products and,
+// without full_output, assembles no result at all; it recycles the buffers day by day, and trmc_stream_begin forgets the last
+// window.  `formed`: the product, as the stream's refusal names it; `stream_own`: what a stream has in its place, if anything.
+// The row set is checked by the caller, BEHIND the product's own refusals: the order a caller sees them in is part of the ABI.
+static int window_result_check(const trmc_plan *pl, const char *formed, const char *stream_own = "")
+{
+    if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
+    if (stream_active(pl))
+        return fail(TRMC_ESTATE, std::string("a stream of windows is in progress: ") + formed
+                                     + " from the result the plan assembles for a window, which a stream does not fill" + stream_own);
+    if (pl->run.active)
+        return fail(TRMC_ESTATE, "a routing window is in progress: its result is not assembled before trmc_route_end");
+    if (pl->routed_nsteps < 0) return fail(TRMC_ESTATE, "nothing routed yet");
+    return 0;
+}
+
+int trmc_window_summary_tile(int precision, int32_t *rows, int32_t *steps)
+{
+    return window_tile(precision, rows, steps, kRecRows, kRecSteps<float>, kRecSteps<double>);
 }
 
 int trmc_window_summary(trmc_plan *pl, int32_t rowset, void *peak_flow, int32_t *peak_step, void *mean_flow, void *peak_depth,
                         int32_t *peak_depth_step, void *peak_velocity, int32_t *peak_velocity_step)
 {
-    if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
-    // `out` is assembled by windows only, and whole only once the window has ended: a stream of days leaves its own summaries
-    // (trmc_stream_set_summary) and, without full_output, assembles no result at all; trmc_stream_begin also forgets the last window
-    if (stream_active(pl))
-        return fail(TRMC_ESTATE, "a stream of windows is in progress: a window's summary is formed from the result the plan assembles for a "
-                                 "window, which a stream does not fill (trmc_stream_set_summary is the stream's own)");
-    if (pl->run.active)
-        return fail(TRMC_ESTATE, "a routing window is in progress: its result is not assembled before trmc_route_end");
-    if (pl->routed_nsteps < 0) return fail(TRMC_ESTATE, "nothing routed yet");
+    if (int rc = window_result_check(pl, "a window's summary is formed", " (trmc_stream_set_summary is the stream's own)")) return rc;
     if (!peak_flow && !peak_step && !mean_flow && !peak_depth && !peak_depth_step && !peak_velocity && !peak_velocity_step)
         return fail(TRMC_EINVAL, "every destination is NULL: nothing to summarise");
     if ((peak_step && !peak_flow) || (peak_depth_step && !peak_depth) || (peak_velocity_step && !peak_velocity))
@@ -1368,26 +1394,17 @@ int trmc_window_summary(trmc_plan *pl, int32_t rowset, void *peak_flow, int32_t 
     const int32_t nsteps = pl->routed_nsteps;
     if (nsteps < 1) return fail(TRMC_ESTATE, "the last window had no timesteps");
     if (int rc = use_device(pl)) return rc;
-    // seven columns [nrows] in the plan's scratch block, each on a 256-byte boundary; then to the host
-    void *const host[7] = {peak_flow, peak_step, mean_flow, peak_depth, peak_depth_step, peak_velocity, peak_velocity_step};
-    const size_t width[7] = {pl->esz, 4, pl->esz, pl->esz, 4, pl->esz, 4};
-    size_t off[7], total = 0;
-    for (int k = 0; k < 7; ++k) {
-        off[k] = total;
-        if (host[k]) total += ((size_t)nrows * width[k] + 255) / 256 * 256;
-    }
-    if (int rc = pl->scratch.ensure(total)) return rc;
+    WindowColumns cols; // seven, [nrows] each
+    if (int rc = cols.lay(pl, nrows, {{peak_flow, pl->esz}, {peak_step, 4}, {mean_flow, pl->esz}, {peak_depth, pl->esz}, {peak_depth_step, 4},
+                                      {peak_velocity, pl->esz}, {peak_velocity_step, 4}}))
+        return rc;
     const int32_t *rp = rowset < 0 ? nullptr : (const int32_t *)pl->rowsets[(size_t)rowset].p;
-    for (DevEvent &e : pl->ev_wsum)
-        if (int rc = e.ensure(true)) return rc;
-    pl->wsum_ms = -1.0;
-    HIP_TRY(hipEventRecord(pl->ev_wsum[0], pl->stream));
+    if (int rc = pl->t_wsum.begin(pl->stream)) return rc;
     const int rc = by_precision(pl, [&](auto t) -> int {
         using T = decltype(t);
-        char *const s = (char *)pl->scratch.p;
-        auto col = [&](int k) { return host[k] ? s + off[k] : nullptr; };
-        const WsumOut<T> o{(T *)col(0), (int32_t *)col(1), (T *)col(2), (T *)col(3), (int32_t *)col(4), (T *)col(5), (int32_t *)col(6)};
-        const dim3 grid((unsigned)((nrows + kWsumRows - 1) / kWsumRows)), block(kWsumRows);
+        const WsumOut<T> o{cols.dev<T>(0), cols.dev<int32_t>(1), cols.dev<T>(2), cols.dev<T>(3), cols.dev<int32_t>(4), cols.dev<T>(5),
+                           cols.dev<int32_t>(6)};
+        const dim3 grid((unsigned)((nrows + kRecRows - 1) / kRecRows)), block(kRecRows);
         // (16-byte loads where every row's record starts on a 16-byte boundary: k_window_summary's head)
         if (nsteps % (16 / (int)sizeof(T)) == 0)
             hipLaunchKernelGGL((k_window_summary<T, true>), grid, block, 0, pl->stream, (const T *)pl->out.p, rp, (const int32_t *)pl->sh->row_of_pos.p,
@@ -1399,44 +1416,23 @@ int trmc_window_summary(trmc_plan *pl, int32_t rowset, void *peak_flow, int32_t 
         return 0;
     });
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(pl->ev_wsum[1], pl->stream));
-    for (int k = 0; k < 7; ++k)
-        if (host[k])
-            HIP_TRY(hipMemcpyAsync(host[k], (char *)pl->scratch.p + off[k], (size_t)nrows * width[k], hipMemcpyDeviceToHost, pl->stream));
-    HIP_TRY(hipStreamSynchronize(pl->stream));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, pl->ev_wsum[0], pl->ev_wsum[1]));
-    pl->wsum_ms = ms;
-    return 0;
+    return window_product_finish(pl, pl->t_wsum, cols);
 }
 
 int trmc_window_summary_kernel_ms(const trmc_plan *pl, double *ms_out)
 {
-    if (!pl || !ms_out) return fail(TRMC_EINVAL, "plan/ms_out is NULL");
-    if (pl->wsum_ms < 0) return fail(TRMC_ESTATE, "no window summary has been formed on this plan");
-    *ms_out = pl->wsum_ms;
-    return 0;
+    return window_kernel_ms(pl, &trmc_plan::t_wsum, ms_out, "no window summary has been formed on this plan");
 }
 
 int trmc_window_courant_tile(int precision, int32_t *rows, int32_t *steps)
 {
-    if (precision != 32 && precision != 64) return fail(TRMC_EINVAL, "precision must be 32 or 64");
-    if (rows) *rows = kCourantRows;
-    if (steps) *steps = kCourantSteps;
-    return 0;
+    return window_tile(precision, rows, steps, kCourantRows, kCourantSteps, kCourantSteps);
 }
 
 static int window_courant_check(trmc_plan *pl, int32_t rowset)
 {
-    if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
-    // the triples are recomputed from the result a window assembles and from its forcing and initial state (k_window_courant): a
-    // stream of days assembles no such result and recycles the buffers day by day
-    if (stream_active(pl))
-        return fail(TRMC_ESTATE, "a stream of windows is in progress: the Courant metrics are recomputed from the result the plan assembles "
-                                 "for a window, which a stream does not fill");
-    if (pl->run.active)
-        return fail(TRMC_ESTATE, "a routing window is in progress: its result is not assembled before trmc_route_end");
-    if (pl->routed_nsteps < 0) return fail(TRMC_ESTATE, "nothing routed yet");
+    // (the triples are recomputed from the result AND from the window's forcing and initial state: k_window_courant)
+    if (int rc = window_result_check(pl, "the Courant metrics are recomputed")) return rc;
     if (pl->maxlag > 0)
         return fail(TRMC_EUNSUPPORTED, "a plan with lagged rows (trmc_plan_set_lag) routes rows of other ranks' trunks at shifted steps: the "
                                        "Courant metrics of such a window are not built");
@@ -1457,10 +1453,7 @@ int trmc_window_courant(trmc_plan *pl, int32_t rowset, int stride, void *dst)
     const size_t bytes = (size_t)nrows * nkeep * 3 * pl->esz;
     if (int rc = pl->gathered.ensure(bytes)) return rc; // (the plan's scratch block for gathers of its result)
     pl->gathered_bytes = 0;
-    for (DevEvent &e : pl->ev_cour)
-        if (int rc = e.ensure(true)) return rc;
-    pl->cour_ms = -1.0;
-    HIP_TRY(hipEventRecord(pl->ev_cour[0], pl->stream));
+    if (int rc = pl->t_cour.begin(pl->stream)) return rc;
     const int rc = by_precision(pl, [&](auto t) -> int {
         using T = decltype(t);
         CourantArgs<T> a;
@@ -1473,13 +1466,10 @@ int trmc_window_courant(trmc_plan *pl, int32_t rowset, int stride, void *dst)
         return 0;
     });
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(pl->ev_cour[1], pl->stream));
+    if (int rc = pl->t_cour.end(pl->stream)) return rc;
     HIP_TRY(hipMemcpyAsync(dst, pl->gathered.p, bytes, hipMemcpyDeviceToHost, pl->stream));
     HIP_TRY(hipStreamSynchronize(pl->stream));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, pl->ev_cour[0], pl->ev_cour[1]));
-    pl->cour_ms = ms;
-    return 0;
+    return pl->t_cour.read();
 }
 
 int trmc_window_courant_summary(trmc_plan *pl, int32_t rowset, double limit, void *peak_cn, int32_t *peak_cn_step, int32_t *steps_over)
@@ -1491,50 +1481,28 @@ int trmc_window_courant_summary(trmc_plan *pl, int32_t rowset, double limit, voi
     if (pl->nseg == 0 || nrows == 0) return 0;
     if (pl->routed_nsteps < 1) return fail(TRMC_ESTATE, "the last window had no timesteps");
     if (int rc = use_device(pl)) return rc;
-    // three columns [nrows] in the plan's scratch block, each on a 256-byte boundary; then to the host
-    void *const host[3] = {peak_cn, peak_cn_step, steps_over};
-    const size_t width[3] = {pl->esz, 4, 4};
-    size_t off[3], total = 0;
-    for (int k = 0; k < 3; ++k) {
-        off[k] = total;
-        if (host[k]) total += ((size_t)nrows * width[k] + 255) / 256 * 256;
-    }
-    if (int rc = pl->scratch.ensure(total)) return rc;
-    for (DevEvent &e : pl->ev_cour)
-        if (int rc = e.ensure(true)) return rc;
-    pl->cour_ms = -1.0;
-    HIP_TRY(hipEventRecord(pl->ev_cour[0], pl->stream));
+    WindowColumns cols; // three, [nrows] each
+    if (int rc = cols.lay(pl, nrows, {{peak_cn, pl->esz}, {peak_cn_step, 4}, {steps_over, 4}})) return rc;
+    if (int rc = pl->t_cour.begin(pl->stream)) return rc;
     const int rc = by_precision(pl, [&](auto t) -> int {
         using T = decltype(t);
-        char *const s = (char *)pl->scratch.p;
         CourantArgs<T> a;
         window_courant_args<T>(pl, rowset, a);
-        a.peak_cn = host[0] ? (T *)(s + off[0]) : nullptr;
-        a.peak_step = host[1] ? (int32_t *)(s + off[1]) : nullptr;
-        a.steps_over = host[2] ? (int32_t *)(s + off[2]) : nullptr;
+        a.peak_cn = cols.dev<T>(0);
+        a.peak_step = cols.dev<int32_t>(1);
+        a.steps_over = cols.dev<int32_t>(2);
         a.limit = (T)limit;
         window_courant_launch<T, true>(pl, a);
         HIP_TRY(hipGetLastError());
         return 0;
     });
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(pl->ev_cour[1], pl->stream));
-    for (int k = 0; k < 3; ++k)
-        if (host[k])
-            HIP_TRY(hipMemcpyAsync(host[k], (char *)pl->scratch.p + off[k], (size_t)nrows * width[k], hipMemcpyDeviceToHost, pl->stream));
-    HIP_TRY(hipStreamSynchronize(pl->stream));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, pl->ev_cour[0], pl->ev_cour[1]));
-    pl->cour_ms = ms;
-    return 0;
+    return window_product_finish(pl, pl->t_cour, cols);
 }
 
 int trmc_window_courant_kernel_ms(const trmc_plan *pl, double *ms_out)
 {
-    if (!pl || !ms_out) return fail(TRMC_EINVAL, "plan/ms_out is NULL");
-    if (pl->cour_ms < 0) return fail(TRMC_ESTATE, "no Courant metrics have been formed on this plan");
-    *ms_out = pl->cour_ms;
-    return 0;
+    return window_kernel_ms(pl, &trmc_plan::t_cour, ms_out, "no Courant metrics have been formed on this plan");
 }
 
 int trmc_plan_set_thresholds(trmc_plan *pl, int32_t nlevels, const void *th)
@@ -1576,23 +1544,13 @@ int trmc_plan_set_thresholds(trmc_plan *pl, int32_t nlevels, const void *th)
 
 int trmc_window_exceedance_tile(int precision, int32_t *rows, int32_t *steps)
 {
-    if (precision != 32 && precision != 64) return fail(TRMC_EINVAL, "precision must be 32 or 64");
-    if (rows) *rows = kWexcRows;
-    if (steps) *steps = precision == 32 ? kWexcSteps<float> : kWexcSteps<double>;
-    return 0;
+    return window_tile(precision, rows, steps, kRecRows, kRecSteps<float>, kRecSteps<double>);
 }
 
 int trmc_window_exceedance(trmc_plan *pl, int32_t rowset, int quantity, int32_t *steps_over, int32_t *first_step, int32_t *last_step,
                            int32_t *longest_run)
 {
-    if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
-    // (the refusals of trmc_window_summary, for its reasons: `out` is a finished window's or nothing)
-    if (stream_active(pl))
-        return fail(TRMC_ESTATE, "a stream of windows is in progress: a window's exceedance is formed from the result the plan assembles for "
-                                 "a window, which a stream does not fill");
-    if (pl->run.active)
-        return fail(TRMC_ESTATE, "a routing window is in progress: its result is not assembled before trmc_route_end");
-    if (pl->routed_nsteps < 0) return fail(TRMC_ESTATE, "nothing routed yet");
+    if (int rc = window_result_check(pl, "a window's exceedance is formed")) return rc;
     if (pl->th_levels < 1) return fail(TRMC_ESTATE, "no thresholds set on this plan (trmc_plan_set_thresholds)");
     if (!steps_over && !first_step && !last_step && !longest_run) return fail(TRMC_EINVAL, "every destination is NULL: nothing to form");
     if (quantity != TRMC_X_FLOW && quantity != TRMC_X_VELOCITY && quantity != TRMC_X_DEPTH)
@@ -1603,38 +1561,19 @@ int trmc_window_exceedance(trmc_plan *pl, int32_t rowset, int quantity, int32_t 
     const int32_t nsteps = pl->routed_nsteps;
     if (nsteps < 1) return fail(TRMC_ESTATE, "the last window had no timesteps");
     if (int rc = use_device(pl)) return rc;
-    // the columns asked for, [nrows][K] int32 each, in the plan's scratch block on 256-byte boundaries; then to the host
-    int32_t *const host[4] = {steps_over, first_step, last_step, longest_run};
-    const size_t col_bytes = (size_t)nrows * pl->th_levels * sizeof(int32_t);
-    size_t off[4], total = 0;
-    for (int k = 0; k < 4; ++k) {
-        off[k] = total;
-        if (host[k]) total += (col_bytes + 255) / 256 * 256;
-    }
-    if (int rc = pl->scratch.ensure(total)) return rc;
-    for (DevEvent &e : pl->ev_wexc)
-        if (int rc = e.ensure(true)) return rc;
-    pl->wexc_ms = -1.0;
-    HIP_TRY(hipEventRecord(pl->ev_wexc[0], pl->stream));
-    char *const s = (char *)pl->scratch.p;
-    auto col = [&](int k) { return host[k] ? (int32_t *)(s + off[k]) : nullptr; };
-    if (int rc = window_exceed_launch(pl, rowset, quantity, WexcOut{col(0), col(1), col(2), col(3)}, nrows, nsteps)) return rc;
-    HIP_TRY(hipEventRecord(pl->ev_wexc[1], pl->stream));
-    for (int k = 0; k < 4; ++k)
-        if (host[k]) HIP_TRY(hipMemcpyAsync(host[k], s + off[k], col_bytes, hipMemcpyDeviceToHost, pl->stream));
-    HIP_TRY(hipStreamSynchronize(pl->stream));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, pl->ev_wexc[0], pl->ev_wexc[1]));
-    pl->wexc_ms = ms;
-    return 0;
+    WindowColumns cols; // the four asked for, [nrows][K] int32 each
+    const size_t row_bytes = (size_t)pl->th_levels * sizeof(int32_t);
+    if (int rc = cols.lay(pl, nrows, {{steps_over, row_bytes}, {first_step, row_bytes}, {last_step, row_bytes}, {longest_run, row_bytes}}))
+        return rc;
+    if (int rc = pl->t_wexc.begin(pl->stream)) return rc;
+    const WexcOut o{cols.dev<int32_t>(0), cols.dev<int32_t>(1), cols.dev<int32_t>(2), cols.dev<int32_t>(3)};
+    if (int rc = window_exceed_launch(pl, rowset, quantity, o, nrows, nsteps)) return rc;
+    return window_product_finish(pl, pl->t_wexc, cols);
 }
 
 int trmc_window_exceedance_kernel_ms(const trmc_plan *pl, double *ms_out)
 {
-    if (!pl || !ms_out) return fail(TRMC_EINVAL, "plan/ms_out is NULL");
-    if (pl->wexc_ms < 0) return fail(TRMC_ESTATE, "no window exceedance has been formed on this plan");
-    *ms_out = pl->wexc_ms;
-    return 0;
+    return window_kernel_ms(pl, &trmc_plan::t_wexc, ms_out, "no window exceedance has been formed on this plan");
 }
 
 int trmc_plan_bankfull_depth(trmc_plan *pl, void *dst)

@@ -375,6 +375,49 @@ int check_device(int device)
     return 0;
 }
 
+// trmc_window_summary / _courant_summary / _exceedance (abi.inc): the optional per-row columns of a window's product.  lay() puts
+// those with a host destination into the plan's scratch block, each on a 256-byte boundary; dev<U>(k) is column k's place on the
+// device (NULL for one not asked for); fetch() queues their copies to the host behind whatever wrote them.
+struct WindowColumns {
+    struct Col {
+        void *host;
+        size_t row_bytes;
+    };
+    Col col[7];
+    size_t off[7];
+    int n = 0;
+    int64_t nrows = 0;
+    char *base = nullptr;
+    int lay(trmc_plan *pl, int64_t rows, std::initializer_list<Col> cols)
+    {
+        nrows = rows;
+        size_t total = 0;
+        for (const Col &c : cols) {
+            col[n] = c;
+            off[n++] = total;
+            if (c.host) total += ((size_t)nrows * c.row_bytes + 255) / 256 * 256;
+        }
+        if (int rc = pl->scratch.ensure(total)) return rc;
+        base = (char *)pl->scratch.p;
+        return 0;
+    }
+    template <class U> U *dev(int k) const { return col[k].host ? (U *)(base + off[k]) : nullptr; }
+    int fetch(hipStream_t st) const
+    {
+        for (int k = 0; k < n; ++k)
+            if (col[k].host) HIP_TRY(hipMemcpyAsync(col[k].host, base + off[k], (size_t)nrows * col[k].row_bytes, hipMemcpyDeviceToHost, st));
+        return 0;
+    }
+};
+// ... and the end of such a call, behind its launch: the timer's second event, the columns' way to the host, the wait for both
+int window_product_finish(trmc_plan *pl, KernelTimer &timer, const WindowColumns &cols)
+{
+    if (int rc = timer.end(pl->stream)) return rc;
+    if (int rc = cols.fetch(pl->stream)) return rc;
+    HIP_TRY(hipStreamSynchronize(pl->stream));
+    return timer.read();
+}
+
 // trmc_window_courant / trmc_window_courant_summary (abi.inc): k_window_courant's arguments up to its destinations ...
 template <class T> int window_courant_args(trmc_plan *pl, int32_t rowset, CourantArgs<T> &a)
 {
@@ -433,7 +476,7 @@ template <class T, bool SUMMARY> void window_courant_launch(trmc_plan *pl, const
 // column of (q, v, d) and the width of the threshold table's rows, on the plan's stream
 template <class T, bool VEC, int COL> int window_exceed_launch_kp(trmc_plan *pl, const int32_t *rp, const WexcOut &o, int64_t nrows, int32_t nsteps)
 {
-    const dim3 grid((unsigned)((nrows + kWexcRows - 1) / kWexcRows)), block(kWexcRows);
+    const dim3 grid((unsigned)((nrows + kRecRows - 1) / kRecRows)), block(kRecRows);
     const T *const out = (const T *)pl->out.p, *const th = (const T *)pl->thresholds.p;
     const int32_t *const row_of_pos = (const int32_t *)pl->sh->row_of_pos.p;
     switch (pl->th_pad) {

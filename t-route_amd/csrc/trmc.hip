@@ -78,12 +78,40 @@ namespace {
 #include "dev_math.inc"
 #include "kernels_levels.inc"
 #include "kernels_flow.inc"
+#include "k_record_tile.inc"
 #include "k_window_summary.inc"
 #include "k_window_courant.inc"
 #include "k_window_exceed.inc"
 #include "k_stream_exceed.inc"
 // ---------------------------------------------------------------- plan
 #include "dev_owner.hpp"
+
+// Device time of the last kernel of ONE kind of call on a plan, from a pair of events around it: begin(), the launch, end() on the
+// kernel's stream and, once that stream has been synchronised, read().  ms < 0: none timed yet, or the last call failed on its way.
+struct KernelTimer {
+    DevEvent ev[2];
+    double ms = -1.0;
+    int begin(hipStream_t st)
+    {
+        for (DevEvent &e : ev)
+            if (int rc = e.ensure(true)) return rc;
+        ms = -1.0;
+        HIP_TRY(hipEventRecord(ev[0], st));
+        return 0;
+    }
+    int end(hipStream_t st)
+    {
+        HIP_TRY(hipEventRecord(ev[1], st));
+        return 0;
+    }
+    int read()
+    {
+        float elapsed = 0;
+        HIP_TRY(hipEventElapsedTime(&elapsed, ev[0], ev[1]));
+        ms = elapsed;
+        return 0;
+    }
+};
 
 } // namespace
 
@@ -155,9 +183,9 @@ struct trmc_plan {
     // "the last gather queued on the plan's stream after a window has read the planes" -- what a set-up queued on ANOTHER stream
     // (TRMC_SETUP_ASIDE) waits for before it lets a new window's tiles overwrite them
     DevEvent ev_gather;
-    DevEvent ev_wsum[2];                 // around the last trmc_window_summary's kernel (trmc_window_summary_kernel_ms)
-    DevEvent ev_cour[2];                 // ... and around the last trmc_window_courant / _summary's (trmc_window_courant_kernel_ms)
-    DevEvent ev_wexc[2];                 // ... and around the last trmc_window_exceedance's (trmc_window_exceedance_kernel_ms)
+    KernelTimer t_wsum;                  // the last trmc_window_summary's kernel (trmc_window_summary_kernel_ms)
+    KernelTimer t_cour;                  // ... the last trmc_window_courant / _summary's (trmc_window_courant_kernel_ms)
+    KernelTimer t_wexc;                  // ... and the last trmc_window_exceedance's (trmc_window_exceedance_kernel_ms): each reports alone
     DevEvent ev_forcing;                 // trmc_stage_forcing: the next window's forcing is on its way to in_qlat on the copy stream
     // trmc_plan_clone: a second set of WINDOW buffers on the static data of the plan it was made from
     std::shared_ptr<PlanShared> sh;
@@ -250,9 +278,6 @@ struct trmc_plan {
     bool dec_pending = false;            // (ev_dec)
     bool fetch_pending = false;
     bool gather_pending = false;         // (ev_gather)
-    double wsum_ms = -1.0;
-    double cour_ms = -1.0;
-    double wexc_ms = -1.0;
     bool row0_replaced = false;          // trmc_plan_chain_from has overwritten time row 0 -- the last window's initial state -- since it ended
     bool forcing_pending = false;        // (ev_forcing)
     bool state_missing = false;          // ... and there is no initial state yet: trmc_plan_chain_from must supply it

@@ -707,11 +707,34 @@ class RoutingPlan:
                             "peak_velocity": ("peak_velocity", "peak_velocity_step")}
 
     @staticmethod
+    def _tile(fn, precision):
+        """(rows, steps) from one of the library's trmc_window_*_tile"""
+        rows, steps = C.c_int32(0), C.c_int32(0)
+        _lib.check(fn(int(precision), C.byref(rows), C.byref(steps)))
+        return rows.value, steps.value
+
+    def _kernel_ms(self, fn):
+        """milliseconds from one of the library's trmc_window_*_kernel_ms"""
+        ms = C.c_double(0)
+        _lib.check(fn(self._h, C.byref(ms)))
+        return ms.value
+
+    @staticmethod
+    def _column_block(columns):
+        """ONE block for the arrays of a window's product (page-locked and pooled when it is large, like a downloaded result), each
+        a view of it on a 256-byte boundary: {name: array} from (name, dtype, shape) triples."""
+        columns = [(name, np.dtype(dtype), shape, int(np.prod(shape)) * np.dtype(dtype).itemsize) for name, dtype, shape in columns]
+        block = _lib.result_empty((sum(-(-nbytes // 256) * 256 for *_, nbytes in columns),), np.uint8)
+        out, at = {}, 0
+        for name, dtype, shape, nbytes in columns:
+            out[name] = block[at:at + nbytes].view(dtype).reshape(shape)
+            at += -(-nbytes // 256) * 256
+        return out
+
+    @staticmethod
     def window_summary_tile(precision=32):
         """(rows, steps) of the reduction kernel's tile for a precision (trmc_window_summary_tile)"""
-        rows, steps = C.c_int32(0), C.c_int32(0)
-        _lib.check(_lib.lib().trmc_window_summary_tile(int(precision), C.byref(rows), C.byref(steps)))
-        return rows.value, steps.value
+        return RoutingPlan._tile(_lib.lib().trmc_window_summary_tile, precision)
 
     def window_summary(self, parts=("peak", "mean", "peak_depth", "peak_velocity"), rowset=None):
         """Per-row summary of the last window, reduced on the device over EVERY step of its result (trmc_window_summary): a dict
@@ -728,30 +751,18 @@ class RoutingPlan:
         n = self.nseg if rowset is None else self._rowset_n[rowset]
         order = ("peak_flow", "peak_step", "mean_flow", "peak_depth", "peak_depth_step", "peak_velocity", "peak_velocity_step")
         asked = [name for part, names in self.WINDOW_SUMMARY_PARTS.items() if part in parts for name in names]
-        # ONE block for the arrays asked for (page-locked and pooled when it is large, like a downloaded result), each a view of it
-        dtype_of = lambda name: np.dtype(np.int32 if name.endswith("_step") else self.dtype)      # noqa: E731
-        pitch = {name: -(-n * dtype_of(name).itemsize // 256) * 256 for name in asked}
-        block = _lib.result_empty((sum(pitch.values()),), np.uint8)
-        out, at = dict.fromkeys(order), 0
-        for name in order:
-            if name in pitch:
-                out[name] = block[at:at + n * dtype_of(name).itemsize].view(dtype_of(name))
-                at += pitch[name]
-        _lib.check(_lib.lib().trmc_window_summary(self._h, -1 if rowset is None else int(rowset), *(_lib.ptr(out[k]) for k in order)))
-        return {k: out[k] for k in order if out[k] is not None}
+        out = self._column_block((name, np.int32 if name.endswith("_step") else self.dtype, (n,)) for name in order if name in asked)
+        _lib.check(_lib.lib().trmc_window_summary(self._h, -1 if rowset is None else int(rowset), *(_lib.ptr(out.get(k)) for k in order)))
+        return out
 
     def window_summary_kernel_ms(self):
         """device time (ms) of the last ``window_summary``'s kernel, from events around it (trmc_window_summary_kernel_ms)"""
-        ms = C.c_double(0)
-        _lib.check(_lib.lib().trmc_window_summary_kernel_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._kernel_ms(_lib.lib().trmc_window_summary_kernel_ms)
 
     @staticmethod
     def window_courant_tile(precision=32):
         """(rows, steps) of the Courant kernel's tile for a precision (trmc_window_courant_tile)"""
-        rows, steps = C.c_int32(0), C.c_int32(0)
-        _lib.check(_lib.lib().trmc_window_courant_tile(int(precision), C.byref(rows), C.byref(steps)))
-        return rows.value, steps.value
+        return RoutingPlan._tile(_lib.lib().trmc_window_courant_tile, precision)
 
     def window_courant(self, stride=1, rowset=None):
         """Courant metrics of the last window [rows, nsteps // stride, 3] = (cn, ck, X) per kept step (the steps stride, 2 stride,
@@ -780,9 +791,7 @@ class RoutingPlan:
 
     def window_courant_kernel_ms(self):
         """device time (ms) of the last ``window_courant`` / ``window_courant_summary``'s kernel (trmc_window_courant_kernel_ms)"""
-        ms = C.c_double(0)
-        _lib.check(_lib.lib().trmc_window_courant_kernel_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._kernel_ms(_lib.lib().trmc_window_courant_kernel_ms)
 
     # window_exceedance's parts, in trmc_window_exceedance's order
     WINDOW_EXCEEDANCE_PARTS = ("steps_over", "first_step", "last_step", "longest_run")
@@ -790,9 +799,7 @@ class RoutingPlan:
     @staticmethod
     def window_exceedance_tile(precision=32):
         """(rows, steps) of the exceedance kernel's tile for a precision (trmc_window_exceedance_tile)"""
-        rows, steps = C.c_int32(0), C.c_int32(0)
-        _lib.check(_lib.lib().trmc_window_exceedance_tile(int(precision), C.byref(rows), C.byref(steps)))
-        return rows.value, steps.value
+        return RoutingPlan._tile(_lib.lib().trmc_window_exceedance_tile, precision)
 
     def set_thresholds(self, th):
         """Thresholds of every row, [nseg] (one level) or [nseg, K] with K <= 4, cast to the plan's dtype and kept on the device
@@ -829,25 +836,16 @@ class RoutingPlan:
             raise ValueError("window_exceedance: no part asked for")
         n = self.nseg if rowset is None else self._rowset_n[rowset]
         k = getattr(self, "_th_levels", 0)
-        # ONE block for the arrays asked for (page-locked and pooled when it is large), each a view of it -- as window_summary's
-        pitch = -(-n * k * 4 // 256) * 256
         order = self.WINDOW_EXCEEDANCE_PARTS
-        block = _lib.result_empty((pitch * sum(name in parts for name in order),), np.uint8)
-        out, at = dict.fromkeys(order), 0
-        for name in order:
-            if name in parts:
-                out[name] = block[at:at + n * k * 4].view(np.int32).reshape(n, k)
-                at += pitch
+        out = self._column_block((name, np.int32, (n, k)) for name in order if name in parts)
         # (without thresholds the arrays are empty and the library refuses the call)
         _lib.check(_lib.lib().trmc_window_exceedance(self._h, -1 if rowset is None else int(rowset), _lib.X_NAMES[quantity],
-                                                     *(_lib.ptr(out[name]) for name in order)))
-        return {name: out[name] for name in order if out[name] is not None}
+                                                     *(_lib.ptr(out.get(name)) for name in order)))
+        return out
 
     def window_exceedance_kernel_ms(self):
         """device time (ms) of the last ``window_exceedance``'s kernel, from events around it (trmc_window_exceedance_kernel_ms)"""
-        ms = C.c_double(0)
-        _lib.check(_lib.lib().trmc_window_exceedance_kernel_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._kernel_ms(_lib.lib().trmc_window_exceedance_kernel_ms)
 
     def bankfull_depth(self):
         """[nseg] in the plan's dtype: the bankfull depth the step kernels use, +inf on rows that route no Muskingum-Cunge step

@@ -141,7 +141,8 @@ def test_every_output_equals_numpy_on_the_full_block(path):
 @pytest.mark.parametrize("rows", ["1", "R-1", "R", "R+1"])
 def test_shapes_on_the_edges_of_the_tile(rows, precision):
     """nseg in {1, R - 1, R, R + 1} x nsteps in {1, C - 1, C, C + 1} x K in {1, 2, 3}, every row and a row set that is a permuted
-    subset, all four parts and subsets of them (NULL destinations)"""
+    subset, all four parts and subsets of them (NULL destinations); at R + 1 rows also nsteps in {VE, C + VE}: the wide loads
+    (every row's record 16-byte aligned) with a first chunk shorter than C, and with a short last chunk behind a whole one"""
     R, C, VE = tile(precision)
     nseg = {"1": 1, "R-1": R - 1, "R": R, "R+1": R + 1}[rows]
     nq = 3
@@ -154,7 +155,7 @@ def test_shapes_on_the_edges_of_the_tile(rows, precision):
     turn = 0
     with RoutingPlan(up_ptr, up_idx, params, precision=precision) as p:
         rs = p.rowset(subset)
-        for nsteps in (1, C - 1, C, C + 1):
+        for nsteps in (1, C - 1, C, C + 1) + ((VE, C + VE) if rows == "R+1" else ()):
             p.route(nsteps, qts_for(nsteps, nq), False, flashy(qlat).astype(p.dtype), q0.astype(p.dtype))
             fvd = p.download_fvd()
             assert fvd.shape == (nseg, nsteps, 3) and fvd[:, :, 0].max() > 0
