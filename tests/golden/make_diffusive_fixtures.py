@@ -16,8 +16,19 @@ and tests/golden/diffusive_small.npz (hand-made small mainstems, same call).
 (``usgs_df`` as nwm_route passes it on, nwm_routing/__main__.py:1292-1311 -> compute.py:1798-1803 -> fp_da_map :512-574):
 the table, the three DA arguments the reference made of it, and the reference Fortran's outputs WITH those arguments,
 which the script asserts are the bits of its outputs WITHOUT them (diffusive.f90:1282-1303: the branch is commented out).
+
+--sweep: only tests/golden/diffusive_sweep.npz -- out_q / out_elv / out_depth of the reference Fortran and a SHA-256 of the
+inputs for every named case of tests/diffusive_cases.py::SWEEP (boundary option 1 on hand-made domains, chains either side
+of every LDS limit and far beyond, junctions of two mainstem reaches, dry to far-over-bank regimes, 36-step windows); the
+inputs are not stored, the recipe regenerates them.  The same switch re-runs EVERY older diffusive golden (small, crosswalk,
+LowerColorado whole and at the windows the tests cut, natural + coastal, gage table) and asserts the committed outputs are
+those bits.
+
+c_diffnw carries state from call to call (911 fuzz domains called in one process: 158 spurious differences, the
+reference disagreeing with its own first answer; none from fresh processes), so every reference call of this script runs
+in a child process of its own (diffusive_ref_child.py), and --sweep makes every case in TWO children that must agree in
+every bit before anything is recorded.  Last run: 24 sweep cases and 13 older goldens, all reproduced twice.
 """
-import ctypes as C
 import importlib.util
 import os
 import sys
@@ -38,37 +49,67 @@ import helpers as H  # noqa: E402
 from make_fixtures import h5var, import_ref_nhd_network  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 
-ARG_ORDER = ["timestep_ar_g", "nts_ql_g", "nts_ub_g", "nts_db_g", "ntss_ev_g", "nts_qtrib_g", "nts_da_g", "mxncomp_g",
-             "nrch_g", "z_ar_g", "bo_ar_g", "traps_ar_g", "tw_ar_g", "twcc_ar_g", "mann_ar_g", "manncc_ar_g", "so_ar_g",
-             "dx_ar_g", "iniq", "frnw_col", "frnw_g", "qlat_g", "ubcd_g", "dbcd_g", "qtrib_g", "paradim", "para_ar_g",
-             "mxnbathy_g", "x_bathy_g", "z_bathy_g", "mann_bathy_g", "size_bathy_g", "usgs_da_g", "usgs_da_reach_g",
-             "rdx_ar_g", "cwnrow_g", "cwncol_g", "crosswalk_g", "z_thalweg_g"]
-INT_SCALARS = {"nts_ql_g", "nts_ub_g", "nts_db_g", "ntss_ev_g", "nts_qtrib_g", "nts_da_g", "mxncomp_g", "nrch_g", "frnw_col",
-               "paradim", "mxnbathy_g", "cwnrow_g", "cwncol_g"}
-INT_ARRAYS = {"frnw_g", "size_bathy_g", "usgs_da_reach_g"}
+import diffusive_cases as DC  # noqa: E402
+
+ARG_ORDER, INT_SCALARS, INT_ARRAYS = DC.ARG_ORDER, DC.INT_SCALARS, DC.INT_ARRAYS
 
 
 def call_reference(d):
-    """c_diffnw of the reference build on a diff_inputs dict (pydiffusive.f90:8-55); Fortran-ordered arrays."""
-    lib = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libdiff_ref.so"))
-    keep, args = [], []
-    for k in ARG_ORDER:
-        v = d[k]
-        if k in INT_SCALARS:
-            c = C.c_int(int(v))
-            keep.append(c)
-            args.append(C.byref(c))
-        else:
-            a = np.asfortranarray(v, dtype=np.int32 if k in INT_ARRAYS else np.float64)
-            if a.size == 0:
-                a = np.zeros(1, dtype=a.dtype)
-            keep.append(a)
-            args.append(a.ctypes.data_as(C.c_void_p))
-    shape = (int(d["ntss_ev_g"]), int(d["mxncomp_g"]), int(d["nrch_g"]))
-    outs = [np.zeros(shape, dtype=np.float64, order="F") for _ in range(3)]
-    args += [o.ctypes.data_as(C.c_void_p) for o in outs]
-    lib.c_diffnw(*args)
-    return outs
+    """c_diffnw of the reference build on a diff_inputs dict (pydiffusive.f90:8-55), in a child process that makes this
+    one call: the Fortran carries state from call to call, so no process calls it twice."""
+    return list(DC.reference_in_child(d))
+
+
+def reference_twice(jobs, workers=8):
+    """{label: outputs} for jobs {label: inputs}: every case through TWO fresh children, which must agree in every bit."""
+    from concurrent.futures import ThreadPoolExecutor
+    keys = [(label, rep) for label in jobs for rep in (0, 1)]
+    with ThreadPoolExecutor(workers) as pool:
+        res = dict(zip(keys, pool.map(lambda k: DC.reference_in_child(jobs[k[0]]), keys)))
+    for label in jobs:
+        assert all(DC.same_bits(x, y) for x, y in zip(res[label, 0], res[label, 1])), \
+            f"{label}: two fresh reference processes disagree -- choose another seed"
+    return {label: res[label, 0] for label in jobs}
+
+
+def sweep():
+    """tests/golden/diffusive_sweep.npz, and the confirmation of every older diffusive golden from fresh processes."""
+    import test_diffusive as TD
+    jobs = {("sweep", n): DC.sweep_case(n) for n in DC.SWEEP}
+    old = {}                                            # label -> (inputs, committed outputs, bitwise up to record)
+    for n in TD.SMALL:
+        old["small", n] = TD.load_small(n) + (None,)
+    for n in ("y3_cw", "y3_nat_cw"):
+        old["crosswalk", n] = TD.load_crosswalk(n) + (None,)
+    for nsteps in (None, 24, 6):                       # the whole run, and the windows the tests cut from it
+        old["lowercolorado", nsteps] = TD.load_lowercolorado(nsteps) + (nsteps,)
+    for nsteps in (None, 12):
+        old["lowercolorado_nat", nsteps] = TD.load_lowercolorado(nsteps, "diffusive_lowercolorado_nat.npz") + (nsteps,)
+    ins, g, _ = TD.gage_table_case()
+    old["da", None] = (ins, tuple(g[o] for o in DC.OUT_NAMES), None)
+    jobs.update({k: v[0] for k, v in old.items()})
+    got = reference_twice(jobs)
+    bad = []
+    for k, (_, want, window) in old.items():
+        if window is None:
+            ok = all(DC.same_bits(a, b) for a, b in zip(got[k], want))
+        else:       # a window's last record is reached by a truncated sub-step (TD.load_lowercolorado): 1e-13 there
+            ok = all(DC.same_bits(a[:-1], b[:-1]) and np.allclose(a[-1], b[-1], rtol=1e-13, atol=1e-13)
+                     for a, b in zip(got[k], want))
+        print("committed golden", k, "reproduced by two fresh reference processes" if ok else "DIFFERS")
+        bad += [] if ok else [k]
+    assert not bad, bad
+    z = {}
+    for n in DC.SWEEP:
+        outs = got["sweep", n]
+        assert all(np.isfinite(o).all() for o in outs), n
+        for o, a in zip(DC.OUT_NAMES, outs):
+            z[f"{n}__{o}"] = a
+        z[f"{n}__sha256"] = np.array(DC.input_hash(jobs["sweep", n]))
+        print(f"{n:18s} nodes {DC.mainstem_nodes(jobs['sweep', n]):5d} depth max {outs[2].max():8.3f} q max {outs[0].max():9.3f}")
+    path = os.path.join(HERE, "diffusive_sweep.npz")
+    np.savez_compressed(path, **z)
+    print(len(DC.SWEEP), "cases,", os.path.getsize(path), "bytes")
 
 
 def import_ref_diffusive_utils(nn):
@@ -308,6 +349,9 @@ def crosswalk_cases():
 
 if __name__ == "__main__":
     O.build()
+    if "--sweep" in sys.argv:
+        sweep()
+        sys.exit(0)
     if "--crosswalk" in sys.argv:       # only the crosswalk fixture (the others are unchanged)
         cwz = {}
         for name, d in crosswalk_cases():

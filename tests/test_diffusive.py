@@ -4,31 +4,35 @@ Parity chain:  reference Fortran diffnw built from its own sources (oracle/_ref/
 tests/golden/diffusive_*.npz, inputs marshalled by the reference's own diffusive_input_data_v02)
   == host instantiation of t-route_amd/csrc/diffusive_core.hpp (oracle/libdw_oracle.so), BITWISE
   == GPU (trdw_diffnw through troute_amd.routing.fast_reach.diffusive.compute_diffusive), BITWISE,
-the last link resting on det_pow64.h == libm pow (checked here on random arguments)."""
+the last link resting on det_pow64.h == libm pow (checked here on random arguments).
+
+What is pinned to the Fortran: five hand-made mainstems, two crosswalk cases, the LowerColorado coastal subset (synthetic
+and natural sections, both boundaries, with a gage table) -- and, in tests/golden/diffusive_sweep.npz, the 24 named cases of
+tests/diffusive_cases.py::SWEEP: boundary option 1 on hand-made domains, chains of 415 / 484 / 485 / 1 556 nodes (the last
+6-row and 5-row lengths in LDS, the first in global memory, far beyond), a junction of two mainstem reaches in every one
+of them, and flow regimes from 1 cm of water to 20 m over bank on flattened and steepened slopes.  The host restatement
+and the device are each held to those recordings bit for bit; nothing here compares the header only with itself.
+
+The reference's c_diffnw carries state from call to call: 911 widened fuzz domains called in ONE process gave 158
+differences from the host (depths of 14 832 m, one of 9e140), every one on the reference's side -- asked again it differed
+from its own first answer, the host never did, and the same domains in fresh processes showed no differing bit.  It is
+therefore only ever called once per process: recordings come from tests/golden/diffusive_ref_child.py, each case from two
+children that must agree, and the live comparison below starts one child per case.  From fresh processes every older
+diffusive golden was reproduced twice, and tools/fuzz_diffusive.py --reference found no difference (figures in
+tools/README.md)."""
 import ctypes as C
+import functools
 import os
 
 import numpy as np
 import pytest
 
+import diffusive_cases as DC
 import helpers as H
+from diffusive_cases import ARG_ORDER, INT_SCALARS, call_c, load_small, long_mainstem, same_bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARG_ORDER = ["timestep_ar_g", "nts_ql_g", "nts_ub_g", "nts_db_g", "ntss_ev_g", "nts_qtrib_g", "nts_da_g", "mxncomp_g",
-             "nrch_g", "z_ar_g", "bo_ar_g", "traps_ar_g", "tw_ar_g", "twcc_ar_g", "mann_ar_g", "manncc_ar_g", "so_ar_g",
-             "dx_ar_g", "iniq", "frnw_col", "frnw_g", "qlat_g", "ubcd_g", "dbcd_g", "qtrib_g", "paradim", "para_ar_g",
-             "mxnbathy_g", "x_bathy_g", "z_bathy_g", "mann_bathy_g", "size_bathy_g", "usgs_da_g", "usgs_da_reach_g",
-             "rdx_ar_g", "cwnrow_g", "cwncol_g", "crosswalk_g", "z_thalweg_g"]
-INT_SCALARS = {"nts_ql_g", "nts_ub_g", "nts_db_g", "ntss_ev_g", "nts_qtrib_g", "nts_da_g", "mxncomp_g", "nrch_g", "frnw_col",
-               "paradim", "mxnbathy_g", "cwnrow_g", "cwncol_g"}
-INT_ARRAYS = {"frnw_g", "size_bathy_g", "usgs_da_reach_g"}
 SMALL = ("chain1", "y3", "comb", "y3_nat", "comb_nat")       # *_nat: natural (bathymetry) cross sections
-
-
-def load_small(name):
-    z = np.load(os.path.join(H.GOLDEN, "diffusive_small.npz"))
-    d = {k.split("__", 1)[1]: z[k] for k in z.files if k.startswith(name + "__")}
-    return {k[3:]: v for k, v in d.items() if k.startswith("in_")}, (d["out_q"], d["out_elv"], d["out_depth"])
 
 
 def load_crosswalk(name):
@@ -61,35 +65,10 @@ def check_window(got, want):
         assert np.allclose(g[-1], w[-1], rtol=1e-13, atol=1e-13)
 
 
-def call_c(lib, sym, ins):
-    keep, args = [], []
-    for k in ARG_ORDER:
-        v = ins[k]
-        if k in INT_SCALARS:
-            c = C.c_int(int(v))
-            keep.append(c)
-            args.append(C.byref(c))
-        else:
-            a = np.asfortranarray(v, dtype=np.int32 if k in INT_ARRAYS else np.float64)
-            if a.size == 0:
-                a = np.zeros(1, dtype=a.dtype)
-            keep.append(a)
-            args.append(a.ctypes.data_as(C.c_void_p))
-    shape = (int(ins["ntss_ev_g"]), int(ins["mxncomp_g"]), int(ins["nrch_g"]))
-    outs = [np.zeros(shape, dtype=np.float64, order="F") for _ in range(3)]
-    args += [o.ctypes.data_as(C.c_void_p) for o in outs]
-    rc = getattr(lib, sym)(*args)
-    return rc, outs
-
-
 def host_oracle():
     from oracle import oracle as O
     O.build()
     return C.CDLL(os.path.join(ROOT, "oracle", "libdw_oracle.so"))
-
-
-def same_bits(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64))
 
 
 @pytest.mark.parametrize("name", SMALL)
@@ -404,7 +383,8 @@ def test_gpu_equals_reference_fortran_bitwise_lowercolorado():
 def test_gpu_solver_variants_give_the_same_bits(env, monkeypatch):
     """The parallel time loop's other forms -- the serial kernel it replaced, the chain state in global memory (domains
     too long for LDS), narrow windows (look-ups that leave the window take the full-column search) -- on the
-    LowerColorado golden and a small natural-section case: bit for bit the reference Fortran."""
+    LowerColorado golden, a small natural-section case, the 1 556-node chain, a nearly dry domain and one far over bank:
+    bit for bit the reference Fortran."""
     from troute_amd.routing.fast_reach import diffusive as D
     for k, v in env.items():
         monkeypatch.setenv(k, v)
@@ -413,6 +393,9 @@ def test_gpu_solver_variants_give_the_same_bits(env, monkeypatch):
     ins, want = load_small("comb_nat")
     for g, w in zip(D.compute_diffusive(ins), want):
         assert same_bits(g, w)
+    for name in ("long220", DC.DRY_CASE, DC.FLOOD_CASE):
+        for g, w, o in zip(D.compute_diffusive(DC.sweep_case(name)), sweep_recordings()[name][0], DC.OUT_NAMES):
+            assert same_bits(g, w), (name, o)
 
 
 @pytest.mark.gpu
@@ -502,10 +485,117 @@ def test_gpu_batch_of_domains_in_one_launch():
         D.compute_diffusive_batch([cases[0][0], bad])
 
 
+# ---- the sweep of tests/diffusive_cases.py against its recording of the reference Fortran (tests/golden/diffusive_sweep.npz)
+@functools.lru_cache(maxsize=None)
+def sweep_recordings():
+    return DC.load_sweep()
+
+
+def assert_equals_recording(name, got):
+    for g, w, o in zip(got, sweep_recordings()[name][0], DC.OUT_NAMES):
+        assert same_bits(g, w), (name, o)
+
+
+@pytest.mark.parametrize("name", DC.SWEEP)
+def test_host_restatement_equals_reference_fortran_bitwise_sweep(name):
+    """Every named case: the inputs are the ones the recording was made from (their hash), and the host instantiation of
+    diffusive_core.hpp gives the reference Fortran's flows, elevations and depths to the last bit."""
+    ins = DC.sweep_case(name)
+    assert DC.input_hash(ins) == sweep_recordings()[name][1], "the generator drifted: inputs are not those of the recording"
+    rc, got = call_c(host_oracle(), "dw_oracle_diffnw", ins)
+    assert rc == 0
+    assert_equals_recording(name, got)
+
+
+def test_live_reference_fortran_equals_its_recording_sweep():
+    """Where oracle/_ref is present: the reference Fortran run now, ONE fresh child process per case (c_diffnw carries
+    state from call to call), against the recording."""
+    from oracle import oracle as O
+    if not O.have_ref("libdiff_ref.so"):
+        pytest.skip("oracle/_ref/libdiff_ref.so is built from the reference tree only where that is present")
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(8) as pool:
+        live = list(pool.map(lambda n: DC.reference_in_child(DC.sweep_case(n)), DC.SWEEP))
+    for name, got in zip(DC.SWEEP, live):
+        assert_equals_recording(name, got)
+
+
+def test_sweep_census():
+    """The cases sit where they were meant to (figures in the docstring of tests/diffusive_cases.py), from the recorded
+    outputs and the regenerated inputs."""
+    rec = sweep_recordings()
+    dry, over, opt1, opt1_off_dt, so_dn, so_up, junction_lds, junction_global, records = [], [], [], [], [], [], [], [], 0
+    for name in DC.SWEEP:
+        ins, (q, elv, depth) = DC.sweep_case(name), rec[name][0]
+        fr = np.asarray(ins["frnw_g"])
+        nup = fr[:, 2]
+        main = fr[np.arange(fr.shape[0]), 3 + nup] == 555
+        node = np.zeros(depth.shape[1:], bool)
+        for j in np.flatnonzero(main):
+            node[:fr[j, 0], j] = True
+        assert all(np.isfinite(a).all() for a in (q, elv, depth)), name
+        records += int(node.sum()) * depth.shape[0]
+        if depth[:, node].max() < 0.15:
+            dry.append(name)
+        if int(ins["mxnbathy_g"]) == 0:      # bankfull depth of the synthetic section: hbf of make_section()
+            hbf = (ins["tw_ar_g"][node] - ins["bo_ar_g"][node]) / (2.0 * ins["traps_ar_g"][node])
+            if (depth[:, node] > hbf).any():
+                over.append(name)
+        if ins["para_ar_g"][10] == 1.0:
+            assert int(ins["nts_db_g"]) >= 2
+            opt1.append(name)
+            if ins["timestep_ar_g"][6] % ins["timestep_ar_g"][0] != 0.0:
+                opt1_off_dt.append(name)
+        slope = DC.RECIPES[name].get("slope", 1.0)
+        so_dn += [name] if slope < 1.0 else []
+        so_up += [name] if slope > 1.0 else []
+        # a mainstem reach fed by two mainstem reaches
+        two_main = any(sum(bool(main[u - 1]) for u in fr[j, 3:3 + nup[j]]) >= 2 for j in np.flatnonzero(main))
+        if two_main:
+            (junction_lds if DC.mainstem_nodes(ins) <= DC.LDS_NODES else junction_global).append(name)
+    assert len(DC.SWEEP) == 24 and records == 29_804
+    assert len(dry) >= 3 and len(over) >= 3 and len(opt1) >= 4 and len(opt1_off_dt) >= 1
+    assert len(so_dn) >= 2 and len(so_up) >= 2 and len(junction_lds) >= 1 and len(junction_global) >= 1
+    assert (len(dry), len(over), len(opt1), len(opt1_off_dt), len(so_dn), len(so_up)) == (4, 9, 7, 5, 3, 3)
+    assert (len(junction_lds), len(junction_global)) == (20, 2) and set(junction_global) == {"global_485", "long220"}
+    nodes = {n: DC.mainstem_nodes(DC.sweep_case(n)) for n in ("rows6_415", "lds_484", "global_485", "long220")}
+    assert nodes == {"rows6_415": 415, "lds_484": DC.LDS_NODES, "global_485": DC.LDS_NODES + 1, "long220": 1556}
+
+
 @pytest.mark.gpu
-def test_gpu_given_depth_boundary_equals_host_restatement():
-    """Downstream boundary option 1 (a prescribed depth series, the coastal coupling) has no reference golden here:
-    the GPU is held to the host instantiation, which is itself pinned to the reference on option 2."""
+@pytest.mark.parametrize("name", DC.SWEEP)
+def test_gpu_equals_reference_fortran_bitwise_sweep(name):
+    from troute_amd.routing.fast_reach import diffusive as D
+    assert_equals_recording(name, D.compute_diffusive(DC.sweep_case(name)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ("lds_484", "global_485"))
+def test_gpu_chain_state_in_global_memory_at_the_lds_limit(name, monkeypatch):
+    """The last length whose chain state fits LDS and the first that does not, both forced into global memory
+    (test_gpu_equals_reference_fortran_bitwise_sweep runs them where the host layer puts them)."""
+    from troute_amd.routing.fast_reach import diffusive as D
+    monkeypatch.setenv("TRDW_CHAIN_GLOBAL", "1")
+    assert_equals_recording(name, D.compute_diffusive(DC.sweep_case(name)))
+
+
+@pytest.mark.gpu
+def test_gpu_batch_of_sweep_cases_in_one_launch():
+    """One launch over chains that fit LDS and chains that do not (so the whole batch takes the global-memory kernel),
+    prescribed-depth and normal-depth boundaries, dry and over bank; and one over LDS chains only, which takes the
+    narrowest window of the batch: each result is its own recording."""
+    from troute_amd.routing.fast_reach import diffusive as D
+    for names in (["bc3_450", "global_485", DC.FLOOD_CASE, "depth_bc", "lds_484", DC.DRY_CASE, "mid8_36", "bc3_450"],
+                  ["rows6_415", "flood8_bc3600", "depth_bc_nat", "mid13_so_up", "dry5"]):
+        outs = D.compute_diffusive_batch([DC.sweep_case(n) for n in names])
+        for name, got in zip(names, outs):
+            assert_equals_recording(name, got)
+
+
+@pytest.mark.gpu
+def test_gpu_given_depth_boundary_equals_reference_fortran_bitwise():
+    """Downstream boundary option 1 (a prescribed depth series, the coastal coupling) on a hand-made domain: the device
+    against the host instantiation and against the reference Fortran's recording (`depth_bc` of the sweep)."""
     from troute_amd.routing.fast_reach import diffusive as D
     ins, _ = load_small("comb")
     ins = dict(ins)
@@ -516,111 +606,33 @@ def test_gpu_given_depth_boundary_equals_host_restatement():
     ins["dbcd_g"] = 0.6 + 0.3 * np.sin(np.arange(nts_db) / 2.0)
     ins["timestep_ar_g"] = ins["timestep_ar_g"].copy()
     ins["timestep_ar_g"][6] = 1350.0
+    assert DC.input_hash(ins) == DC.input_hash(DC.sweep_case("depth_bc")) == sweep_recordings()["depth_bc"][1]
     rc, want = call_c(host_oracle(), "dw_oracle_diffnw", ins)
     assert rc == 0
     got = D.compute_diffusive(ins)
     for g, w in zip(got, want):
         assert same_bits(g, w)
+    assert_equals_recording("depth_bc", got)
     assert np.isfinite(got[2]).all() and got[2].max() > 0.3
 
 
-def long_mainstem(nmain=220, seed=4):
-    """A synthetic domain much longer than anything that fits a compute unit's LDS: `nmain` mainstem reaches in series
-    (6-8 nodes each, about 1 500 nodes) with a tributary hydrograph at every fifth junction and a mainstem side branch of
-    three reaches joining half-way down -- the layout fp_network_map produces (reaches upstream first)."""
-    rng = np.random.default_rng(seed)
-    layout = []                      # dicts n, up (1-based reach ids), ds, main
-    # side branch (mainstem): reaches 1..3
-    for k in range(3):
-        layout.append(dict(n=int(rng.integers(4, 7)), up=[k] if k else [], ds=None, main=True))
-    join = nmain // 2
-    first_main = len(layout) + 1
-    trib_of = {}
-    for k in range(nmain):
-        up = [len(layout)] if k else []
-        if k == join:
-            up = up + [3]
-        if k and k % 5 == 0:
-            trib_of[k] = None
-        layout.append(dict(n=int(rng.integers(6, 9)), up=up, ds=None, main=True))
-    # tributaries (two nodes), appended where the reference lists them: anywhere before their junction is fine for frnw
-    for k in sorted(trib_of):
-        layout.insert(0, dict(n=2, up=[], ds=None, main=False))
-        for r in layout[1:]:
-            r["up"] = [u + 1 for u in r["up"]]
-        first_main += 1
-    ntrib = len(trib_of)
-    for idx, k in enumerate(sorted(trib_of)):
-        layout[first_main - 1 + k]["up"].append(ntrib - idx)
-    nrch = len(layout)
-    for j, r in enumerate(layout):
-        for u in r["up"]:
-            layout[u - 1]["ds"] = j + 1
-    layout[-1]["ds"] = -99
-    mx = max(r["n"] for r in layout)
-    nsteps, dt = 4, 300.0
-    tfin = dt * nsteps / 3600.0
-    ts = np.zeros(10)
-    ts[[0, 1, 2, 3, 4, 5, 7, 8, 9]] = [dt, 0.0, tfin, dt, 3600.0, dt, dt, dt, 10.0]
-    para = np.array([0.95, 0.5, 10.0, 10000.0, -15.0, -10.0, 1.0, 0.02831, 0.0001, 1.0, 2.0])
-    frnw = np.zeros((nrch, 20), np.int32)
-    geo = {k: np.zeros((mx, nrch)) for k in ("z", "bo", "traps", "tw", "twcc", "mann", "manncc", "so", "dx")}
-    iniq = np.zeros((mx, nrch))
-    zbot = {}
-    for j in reversed(range(nrch)):
-        r = layout[j]
-        n = r["n"]
-        frnw[j, 0], frnw[j, 1], frnw[j, 2] = n, r["ds"], len(r["up"])
-        frnw[j, 3:3 + len(r["up"])] = r["up"]
-        frnw[j, 3 + len(r["up"])] = 555 if r["main"] else -555
-        dx = rng.uniform(300.0, 1200.0, n)
-        so = rng.uniform(2e-4, 1.5e-3, n)
-        z = np.zeros(n)
-        z[n - 1] = 2.0 if r["ds"] < 0 else zbot[r["ds"] - 1]
-        for i in range(n - 2, -1, -1):
-            z[i] = z[i + 1] + so[i] * dx[i]
-        zbot[j] = z[0]
-        bw = rng.uniform(10.0, 40.0)
-        geo["z"][:n, j], geo["dx"][:n, j], geo["so"][:n, j] = z, dx, so
-        geo["bo"][:n, j] = bw
-        geo["traps"][:n, j] = rng.uniform(1.0, 3.0)
-        geo["tw"][:n, j] = bw * 2.0
-        geo["twcc"][:n, j] = bw * 6.0
-        geo["mann"][:n, j] = 0.035
-        geo["manncc"][:n, j] = 0.07
-        iniq[:n, j] = rng.uniform(2.0, 6.0)
-    nts_ql = max(1, int(np.ceil(tfin)))
-    qlat = rng.uniform(0.0, 2e-4, (nts_ql, mx, nrch))
-    nts_qtrib = nsteps + 1
-    qtrib = np.zeros((nts_qtrib, nrch))
-    for j, r in enumerate(layout):
-        if not r["main"]:
-            qtrib[:, j] = 2.0 + np.sin(np.arange(nts_qtrib) / 3.0 + j) ** 2
-    return {"timestep_ar_g": ts, "nts_ql_g": nts_ql, "nts_ub_g": nsteps, "nts_db_g": 1, "ntss_ev_g": nsteps + 1,
-            "nts_qtrib_g": nts_qtrib, "nts_da_g": 1, "mxncomp_g": mx, "nrch_g": nrch,
-            "z_ar_g": geo["z"], "bo_ar_g": geo["bo"], "traps_ar_g": geo["traps"], "tw_ar_g": geo["tw"],
-            "twcc_ar_g": geo["twcc"], "mann_ar_g": geo["mann"], "manncc_ar_g": geo["manncc"], "so_ar_g": geo["so"],
-            "dx_ar_g": geo["dx"], "iniq": iniq, "frnw_col": 20, "frnw_g": frnw, "qlat_g": qlat,
-            "ubcd_g": np.zeros((nsteps, nrch)), "dbcd_g": np.zeros(1), "qtrib_g": qtrib, "paradim": 11, "para_ar_g": para,
-            "mxnbathy_g": 0, "x_bathy_g": np.zeros((0, mx, nrch)), "z_bathy_g": np.zeros((0, mx, nrch)),
-            "mann_bathy_g": np.zeros((0, mx, nrch)), "size_bathy_g": np.zeros((mx, nrch), np.int32),
-            "usgs_da_g": np.full((1, nrch), -4444.0), "usgs_da_reach_g": np.zeros(nrch, np.int32),
-            "rdx_ar_g": np.zeros((0, 0)), "cwnrow_g": 0, "cwncol_g": 0, "crosswalk_g": np.zeros((0, 0)),
-            "z_thalweg_g": np.zeros((0, 0))}
-
-
 @pytest.mark.gpu
-def test_gpu_long_mainstem_with_a_side_branch_equals_host_restatement():
+def test_gpu_long_mainstem_with_a_side_branch_equals_reference_fortran_bitwise():
     """~1 500 mainstem nodes in 223 reaches (the chain state does not fit LDS: records and windows in global memory, the
     per-node phases in three passes of the 512 threads), a mainstem junction of two mainstem reaches, tributaries at 43
-    junctions: the parallel time loop against the host instantiation (itself pinned to the reference Fortran on the
-    goldens), bit for bit; the one-wavefront kernel gives the same."""
+    junctions: the parallel time loop against the host instantiation and against the reference Fortran's recording
+    (`long220` of the sweep), bit for bit; the one-wavefront kernel gives the same
+    (test_gpu_solver_variants_give_the_same_bits)."""
     from troute_amd.routing.fast_reach import diffusive as D
     ins = long_mainstem()
     nodes = int(ins["frnw_g"][ins["frnw_g"][np.arange(ins["nrch_g"]), 3 + ins["frnw_g"][:, 2]] == 555, 0].sum())
     assert nodes > 1400
+    assert DC.input_hash(ins) == sweep_recordings()["long220"][1]
     rc, want = call_c(host_oracle(), "dw_oracle_diffnw", ins)
     assert rc == 0 and np.isfinite(want[0]).all() and np.abs(want[0]).max() > 1.0
     got = D.compute_diffusive(ins)
     for g, w in zip(got, want):
         assert same_bits(g, w)
+    assert_equals_recording("long220", got)
+
+
