@@ -797,6 +797,31 @@ int trmc_plan_bankfull_depth(trmc_plan *plan, void *dst);
 int trmc_stream_set_exceedance(trmc_plan *plan, int quantity);
 int trmc_stream_exceedance(trmc_plan *plan, int64_t *steps_over, int64_t *first_step, int64_t *last_step, int64_t *longest_run,
                            int64_t *days_out);
+/*
+ * STAGE HYDROGRAPHS of a stream day: the depth of EVERY step at the rows of the day's row set (trmc_stream_day::rowset, the rows of
+ * its hydrographs), [rows of the set][nsteps] in the plan's precision -- column 2 of the same day routed as a window with the full
+ * result, at those rows, bit for bit.  A reservoir row (trmc_set_reservoirs) gives its pool's water elevation; nudging changes a
+ * gage row's flow only, its stage is the step's own depth; a boundary row has none: 0.  The ring's depth planes have room for every
+ * step; a stream told to carry stage launches the tile-kernel instances that write them all (one more coalesced store per row and
+ * step) and gathers the set's rows where the day is handed over; the array leaves on the copy stream with the day's other products.
+ * A stream with full_output gathers the day's full result instead.  Off (the default): no buffer, no launch, the kernels of a
+ * stream without it.
+ *   trmc_stream_set_stage   on != 0: the streams begun on this plan from now on carry stage; 0: they do not.  Before
+ *                           trmc_stream_begin; it stays until the next call, as trmc_stream_set_summary's mask does.  TRMC_ESTATE
+ *                           while a stream is in progress, TRMC_EINVAL on the dataflow engine, which runs no stream.
+ *                           trmc_stream_begin is then TRMC_EUNSUPPORTED on a plan whose stream carries reservoir data assimilation
+ *                           (trmc_stream_set_reservoir_da: the _rda tile instances do not write the depth plane), and, without
+ *                           full_output, with trmc_plan_options.velocity_on_demand < 0 -- as for TRMC_SUMMARY_PEAK_DEPTH.  Works
+ *                           with output_stride, full_output or neither, together with every summary part, in both precisions and
+ *                           arithmetics.
+ *   trmc_stream_stage_dest  where the stage of the NEXT day pushed goes: a page-locked HOST array [rows of that day's set][nsteps]
+ *                           (NULL: that day hands none over); the push consumes it, trmc_stream_wait covers it.  TRMC_ESTATE when
+ *                           no stream is in progress or it was begun without stage.  The push is TRMC_EINVAL if the day names no
+ *                           row set -- the array is then dropped, it does not wait for another day --, and TRMC_ESTATE for a larger
+ *                           set than the first one that asked for stage (as for hydrographs).
+ */
+int trmc_stream_set_stage(trmc_plan *plan, int on);
+int trmc_stream_stage_dest(trmc_plan *plan, void *stage_host);
 /* on != 0: trmc_upload_forcing turns every NaN of qlat and q0 into 0 on the device, behind the copy.  The reference's reindexed
  * tables hold NaN on waterbody rows (compute.py:1466-1467), which the Muskingum-Cunge rows never read; the drop-in used to screen
  * the caller's frames for them on the host -- 20 ms of a CONUS call.  Default off: values go to the kernels as they are. */

@@ -188,6 +188,8 @@ SIGNATURES = {
     "trmc_plan_bankfull_depth": (_int, [_vp, _vp]),
     "trmc_stream_set_exceedance": (_int, [_vp, _int]),
     "trmc_stream_exceedance": (_int, [_vp, _vp, _vp, _vp, _vp, _P(_i64)]),
+    "trmc_stream_set_stage": (_int, [_vp, _int]),
+    "trmc_stream_stage_dest": (_int, [_vp, _vp]),
     "trmc_plan_set_nan_is_zero": (_int, [_vp, _int]),
     "trmc_host_alloc": (_int, [C.c_size_t, C.POINTER(C.c_void_p)]),
     "trmc_host_free": (_int, [_vp]),

@@ -259,29 +259,37 @@ inline void launch_step(hipStream_t st, const StepArgs<T> &a, int32_t s0, int32_
 // The rows' peak depth of the day (TRMC_SUMMARY_PEAK_DEPTH) rides in instances of its own, k_mc_tile_pkd / k_mc_ctile_pkd: a launch
 // carries it when it is given the two columns (pk_d, pk_at: stream_launch) -- and only a launch of a LAZYV form is (tile_carries:
 // trmc_stream_begin refuses or reduces the full result wherever that does not hold).  Without the columns: the instances above.
+// The depth of every step into the slot's depth plane (trmc_stream_set_stage) rides in k_mc_tile_dpl / k_mc_ctile_dpl, by the same
+// rule: a launch told so (dpl: stream_launch) and of a LAZYV form; the peak depth's columns go along where the stream has both.
 template <class T> inline bool tile_carries(const StepArgs<T> &a) { return a.v_every != 0 && !a.out && !a.res_da; }
 template <class T>
 inline void launch_tile(hipStream_t st, const StepArgs<T> &a, int32_t p0, int32_t p1, int32_t tile, int32_t K, bool tol, T *pk_d = nullptr,
-                        int32_t *pk_at = nullptr)
+                        int32_t *pk_at = nullptr, bool dpl = false)
 {
     // (with hot rows: the first a.hot_home blocks take the list, the blocks behind them positions)
     const unsigned home = (unsigned)((p1 - p0 + kTileBlock - 1) / kTileBlock);
     const dim3 grid(home + (a.hot_list ? (unsigned)a.hot_home : 0u)), block(kTileBlock);
     with_tile_instance(a, tol, [&](auto rda, auto tl, auto dec, auto lazy) {
         if constexpr (rda()) hipLaunchKernelGGL((k_mc_tile_rda<dec()>), grid, block, 0, st, a, p0, p1, tile, K);
-        else if (pk_d && tile_carries(a)) hipLaunchKernelGGL((k_mc_tile_pkd<T, tl(), dec()>), grid, block, 0, st, a, p0, p1, tile, K, pk_d, pk_at);
+        else if (dpl && tile_carries(a)) {
+            if (pk_d) hipLaunchKernelGGL((k_mc_tile_dpl<T, tl(), dec(), true>), grid, block, 0, st, a, p0, p1, tile, K, pk_d, pk_at);
+            else hipLaunchKernelGGL((k_mc_tile_dpl<T, tl(), dec(), false>), grid, block, 0, st, a, p0, p1, tile, K, pk_d, pk_at);
+        } else if (pk_d && tile_carries(a)) hipLaunchKernelGGL((k_mc_tile_pkd<T, tl(), dec()>), grid, block, 0, st, a, p0, p1, tile, K, pk_d, pk_at);
         else hipLaunchKernelGGL((k_mc_tile<T, tl(), dec(), lazy()>), grid, block, 0, st, a, p0, p1, tile, K);
     });
 }
 // one launch of k_mc_ctile: the cluster blocks [b0, b1) of the plan at tile index `tile`
 template <class T>
 inline void launch_ctile(hipStream_t st, const StepArgs<T> &a, const int32_t *cblk_ptr, int32_t b0, int32_t b1, int32_t tile, int32_t K,
-                         bool tol, T *pk_d = nullptr, int32_t *pk_at = nullptr)
+                         bool tol, T *pk_d = nullptr, int32_t *pk_at = nullptr, bool dpl = false)
 {
     const dim3 grid((unsigned)(b1 - b0)), block(kCtileBlock);
     with_tile_instance(a, tol, [&](auto rda, auto tl, auto dec, auto lazy) {
         if constexpr (rda()) hipLaunchKernelGGL((k_mc_ctile_rda<dec()>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);
-        else if (pk_d && tile_carries(a)) hipLaunchKernelGGL((k_mc_ctile_pkd<T, tl(), dec()>), grid, block, 0, st, a, cblk_ptr, b0, tile, K, pk_d, pk_at);
+        else if (dpl && tile_carries(a)) {
+            if (pk_d) hipLaunchKernelGGL((k_mc_ctile_dpl<T, tl(), dec(), true>), grid, block, 0, st, a, cblk_ptr, b0, tile, K, pk_d, pk_at);
+            else hipLaunchKernelGGL((k_mc_ctile_dpl<T, tl(), dec(), false>), grid, block, 0, st, a, cblk_ptr, b0, tile, K, pk_d, pk_at);
+        } else if (pk_d && tile_carries(a)) hipLaunchKernelGGL((k_mc_ctile_pkd<T, tl(), dec()>), grid, block, 0, st, a, cblk_ptr, b0, tile, K, pk_d, pk_at);
         else hipLaunchKernelGGL((k_mc_ctile<T, tl(), dec(), lazy()>), grid, block, 0, st, a, cblk_ptr, b0, tile, K);
     });
 }

@@ -37,7 +37,7 @@ constexpr int kClusterRowsMax = 128; // the most rows of a cluster (trmc_plan_op
 static_assert(kCtileBlock % 64 == 0 && kCtileBlock >= kClusterRowsMax && kCtileBlock <= 1024,
               "TRMC_CTILE_BLOCK: whole wavefronts, at least one cluster, at most one workgroup");
 constexpr int kCtileStage = kCtileBlock > 512 ? kTileStage / 2 : kTileStage; // (steps staged per run: fp64 rows of 1024 threads within a CU's LDS)
-template <class T, bool TOL, bool DEC, bool LAZYV, bool RDA, bool PKD = false> // (see mc_step_rows; PKD: see k_mc_tile_pkd)
+template <class T, bool TOL, bool DEC, bool LAZYV, bool RDA, bool PKD = false, bool DPL = false> // (see mc_step_rows; PKD: see k_mc_tile_pkd; DPL: k_mc_tile_dpl)
 __device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_t *__restrict__ cblk_ptr, int32_t cb0, int32_t tile, int32_t K,
                                               T *pk_d = nullptr, int32_t *pk_at = nullptr);
 template <class T, bool TOL = false, bool DEC = false, bool LAZYV = false>
@@ -60,7 +60,15 @@ k_mc_ctile_pkd(const StepArgs<T> a, const int32_t *__restrict__ cblk_ptr, const 
 {
     mc_ctile_rows<T, TOL, DEC, true, false, true>(a, cblk_ptr, cb0, tile, K, pk_d, pk_at);
 }
-template <class T, bool TOL, bool DEC, bool LAZYV, bool RDA, bool PKD>
+// (the cluster rows' depth of every step into the slot's depth plane: k_mc_tile_dpl)
+template <class T, bool TOL = false, bool DEC = false, bool PKD = false>
+__global__ void __launch_bounds__(kCtileBlock, sizeof(T) == 4 ? TRMC_TILE_WAVES_LAZY : 1)
+k_mc_ctile_dpl(const StepArgs<T> a, const int32_t *__restrict__ cblk_ptr, const int32_t cb0, const int32_t tile, const int32_t K,
+               T *const pk_d, int32_t *const pk_at)
+{
+    mc_ctile_rows<T, TOL, DEC, true, false, PKD, true>(a, cblk_ptr, cb0, tile, K, pk_d, pk_at);
+}
+template <class T, bool TOL, bool DEC, bool LAZYV, bool RDA, bool PKD, bool DPL>
 __device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_t *__restrict__ cblk_ptr, const int32_t cb0,
                                               const int32_t tile, const int32_t K, T *const pk_d, int32_t *const pk_at)
 {
@@ -128,6 +136,7 @@ __device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_
     if (active) s_x[(size_t)((t_lo - 1) & 1) * kCtileBlock + sl] = q_prev;
     __syncthreads();
     T *q_up = q_tm + (size_t)(t_lo - 1) * np;
+    const ptrdiff_t d_of_q = DPL ? a.d_tm - a.q_tm : 0; // (as k_mc_tile)
     const int32_t v_every = (LAZYV && DEC) ? cold->v_every : 0; // (see StepArgs and k_mc_tile)
     int32_t v_left = v_every > 0 ? (v_every - 1) - ((t_lo - 1) % v_every) : 0;
     T dmax = T(0);
@@ -189,6 +198,9 @@ __device__ __forceinline__ void mc_ctile_rows(const StepArgs<T> &a, const int32_
             }
             asm volatile("" : "+v"(ob));
             at(q_up + np, ob) = q_new;
+            if constexpr (DPL) {
+                if (t != t_hi) at(q_up + np + d_of_q, ob) = d_new; // (the tile's last step: hand_on_row)
+            }
             s_x[(size_t)(t & 1) * kCtileBlock + sl] = q_new;
             hand_on_row<T>(cold, slot, slot_next, ob, np, t, t_hi, q_new, d_new);
             q_prev = q_new;

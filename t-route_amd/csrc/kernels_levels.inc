@@ -332,7 +332,7 @@ constexpr int64_t kMidDefaultRowsPerCu = 0; // default threshold of the second t
 // sequence, ms per day on the cost-ordered / the unordered plan: 6: 16.06 / 17.55, 16: 16.07 / 17.33, 40: 16.06 / 17.36
 #define TRMC_HOT_WAVE_MAX 16
 #endif
-template <class T, bool TOL, bool DEC, bool LAZYV, bool RDA, bool PKD = false> // (see mc_step_rows; PKD: see k_mc_tile_pkd)
+template <class T, bool TOL, bool DEC, bool LAZYV, bool RDA, bool PKD = false, bool DPL = false> // (see mc_step_rows; PKD: see k_mc_tile_pkd; DPL: k_mc_tile_dpl)
 __device__ __forceinline__ void mc_tile_rows(const StepArgs<T> &a, int32_t s_begin, int32_t s_end, int32_t tile, int32_t K,
                                              T *pk_d = nullptr, int32_t *pk_at = nullptr);
 template <class T, bool TOL = false, bool DEC = false, bool LAZYV = false> // (LAZYV: StepArgs::v_every != 0)
@@ -361,7 +361,22 @@ k_mc_tile_pkd(const StepArgs<T> a, const int32_t s_begin, const int32_t s_end, c
 {
     mc_tile_rows<T, TOL, DEC, true, false, true>(a, s_begin, s_end, tile, K, pk_d, pk_at);
 }
-template <class T, bool TOL, bool DEC, bool LAZYV, bool RDA, bool PKD>
+// DPL: THE DEPTH PLANE (trmc_stream_set_stage).  A stream's slot has a time-major depth plane with room for every step beside its
+// flow plane, and the instances above write the row of a tile's last step only (hand_on_row).  With DPL a row stores its depth of
+// EVERY step there, next to the step's flow store and through the same address -- the flow row's element moved by the distance
+// between the two planes, a launch constant -- so a wavefront writes 64 consecutive depths per step as it writes 64 consecutive
+// flows.  The tile's last step is still hand_on_row's: no row stores it twice.  A reservoir row's depth is its pool's elevation.
+// stream_complete_day gathers a row set's stage from the plane as it gathers its hydrographs from the flow plane.  Instances of
+// their own, as PKD has (the LAZYV forms; PKD rides along where the stream asks for the peak depth too), so that every other
+// instance compiles as it did.
+template <class T, bool TOL = false, bool DEC = false, bool PKD = false>
+__global__ void __launch_bounds__(kTileBlock, sizeof(T) == 4 ? TRMC_TILE_WAVES_LAZY : 1)
+k_mc_tile_dpl(const StepArgs<T> a, const int32_t s_begin, const int32_t s_end, const int32_t tile, const int32_t K, T *const pk_d,
+              int32_t *const pk_at)
+{
+    mc_tile_rows<T, TOL, DEC, true, false, PKD, true>(a, s_begin, s_end, tile, K, pk_d, pk_at);
+}
+template <class T, bool TOL, bool DEC, bool LAZYV, bool RDA, bool PKD, bool DPL>
 __device__ __forceinline__ void mc_tile_rows(const StepArgs<T> &a, const int32_t s_begin, const int32_t s_end, const int32_t tile,
                                              const int32_t K, T *const pk_d, int32_t *const pk_at)
 {
@@ -465,6 +480,7 @@ __device__ __forceinline__ void mc_tile_rows(const StepArgs<T> &a, const int32_t
     // flows of the step before (complete: earlier launches); advanced a row per step -- t differs from lane to lane (the
     // level skew), and (size_t)t * np in vector registers is a 64-bit multiplication per step
     T *q_up = q_tm + (size_t)(t_lo - 1) * np;
+    const ptrdiff_t d_of_q = DPL ? a.d_tm - a.q_tm : 0; // (DPL: from a slot's flow plane to its depth plane, in elements)
     // (asking for the upstream flows of step t + 1 while step t is computed -- they were all written by earlier launches -- was built
     // and measured in round 6: the CONUS stream 14.3 ms per day against 13.9, the ranks of an 8-way partition 2.76 against 2.70: two
     // more live registers in a kernel that already spills four cost more than the L2 trip they take off the chain)
@@ -526,6 +542,9 @@ __device__ __forceinline__ void mc_tile_rows(const StepArgs<T> &a, const int32_t
         }
         asm volatile("" : "+v"(ob));
         at(q_up + np, ob) = q_new;
+        if constexpr (DPL) {
+            if (t != t_hi) at(q_up + np + d_of_q, ob) = d_new; // (the tile's last step: hand_on_row)
+        }
         hand_on_row<T>(cold, slot, slot_next, ob, np, t, t_hi, q_new, d_new);
         q_prev = q_new;
         d_prev = d_new;
@@ -929,6 +948,20 @@ k_gather_rows(const T *__restrict__ q_tm, const int32_t *__restrict__ pos, T *__
     const int64_t r = i / nsteps;
     const int32_t t = (int32_t)(i % nsteps) + 1;
     out[i] = q_tm[((size_t)t * nseg_pad + pos[r]) * qs];
+}
+
+// the depths of selected positions from a full result out[row][step][q, v, d]: out_rows[r][t - 1] (a stream day's stage where the
+// stream assembles the full result: the same depths the depth plane of a stream without it holds)
+template <class T>
+__global__ void __launch_bounds__(kBlock)
+k_gather_rows_depth_out(const T *__restrict__ out, const int32_t *__restrict__ pos, const int32_t *__restrict__ row_of_pos,
+                        T *__restrict__ out_rows, int64_t nrows, int32_t nsteps)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nrows * nsteps) return;
+    const int64_t r = i / nsteps;
+    const int32_t t = (int32_t)(i % nsteps);
+    out_rows[i] = out[((size_t)row_of_pos[pos[r]] * (size_t)nsteps + (size_t)t) * 3 + 2];
 }
 
 // flows of selected positions over the steps (t_begin, t_end]: out[r * stride + (t - 1 - t_begin)]

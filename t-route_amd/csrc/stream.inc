@@ -65,6 +65,15 @@
 // threshold table, and trmc_stream_exceedance fetches it.  No row of the product table, no member of trmc_stream_day, nothing per
 // day on the copy stream.  Flows only: the planes hold a tile's last depth and a products-only stream forms no velocity.  Off (the
 // default): no buffer, no launch.
+// STAGE HYDROGRAPHS (trmc_stream_set_stage): the depth of EVERY step at the rows of the day's row set -- the hydrographs' rows --
+// for the caller who compares stage at forecast points and gages, and pool elevation at reservoirs, with action and flood stages.
+// A slot's depth plane has room for every step, but the tile kernels write the row of a tile's last step only; the stream that was
+// told to carry stage launches the instances that write them all (k_mc_tile_dpl, k_mc_ctile_dpl: one more coalesced store per
+// step), and where the day is handed over the hydrographs' gather kernel, pointed at the depth plane, forms the product
+// [rows of the set][nsteps] (P_STAGE), which leaves on the copy stream with the day's other products.  A reservoir row gives its
+// pool's elevation; nudging changes a gage row's flow only.  A stream with full_output runs the instances it always ran and
+// gathers the day's out[row][step][2] instead: the same bits.  Off (the default): no buffer, no launch, the instances of a stream
+// without it.
 extern "C++" {
 // THE PRODUCTS A DAY CAN HAND TO THE HOST, one row of StreamRun::tab each.  trmc_stream_begin fills the row (stream_begin_t: whether
 // the stream carries the product, a slot's bytes, where a slot's bytes begin on the device), a push names the day's destinations
@@ -86,17 +95,23 @@ enum : int {
     P_PDS,      // its step
     P_N
 };
+// ... and, behind the rows that the host's table (stream_products.PRODUCTS) mirrors one for one, the products whose destination a
+// call of its own names (StreamProdRow::next, as the summary parts'): rows of the same table, P_ALL in all
+enum : int {
+    P_STAGE = P_N, // stage hydrographs [rows of the day's set][nsteps]: sized and slotted as P_HYD is (trmc_stream_stage_dest)
+    P_ALL
+};
 struct StreamProdRow {
     bool on = false;      // the stream in progress carries the product
-    size_t bytes = 0;     // what a day's copy takes (P_HYD: of the day's row set, stream_prod_bytes)
+    size_t bytes = 0;     // what a day's copy takes (P_HYD, P_STAGE: of the day's row set, stream_prod_bytes)
     size_t stride = 0;    // a slot's bytes on the device: slot s begins at base + s * stride
     char *base = nullptr;
     DevBuf buf;           // [slots][stride], where the product has a buffer of its own
-    void *next = nullptr; // (summary parts) where the part of the NEXT day pushed goes: trmc_stream_summary_dest, _depth_dest
+    void *next = nullptr; // (summary parts, stage) where the part of the NEXT day pushed goes: trmc_stream_summary_dest, _depth_dest
 };
 struct StreamProd {
     int64_t day = -1;
-    void *host[P_N] = {};         // the day's destinations (NULL: not asked for)
+    void *host[P_ALL] = {};         // the day's destinations (NULL: not asked for)
     int32_t rowset = -1;
     bool queued = false;          // the gathers and copies of this day are queued
     DevEvent ev_done;             // ... and this fires when they are through
@@ -124,7 +139,7 @@ struct StreamRun {
     int32_t dec_stride = 0, dec_keep = 0;
     int32_t rowset = -1;
     DevBuf tm, qlat, out, dec;
-    StreamProdRow tab[P_N];        // the day's products (above)
+    StreamProdRow tab[P_ALL];        // the day's products (above)
     // reservoirs and gages (see the head of this file): per-slot element counts, the per-slot tables, and the gage rows of the
     // streams on this plan (trmc_stream_set_gages: they outlive a stream, unlike the window's tables of trmc_set_nudging)
     size_t slot_res = 0, slot_da = 0;
@@ -148,6 +163,9 @@ struct StreamRun {
     // is reduced)
     bool carry = false;
     DevBuf pkd_d, pkd_at;
+    // stage hydrographs (the head of this file).  stage_want: trmc_stream_set_stage, it outlives a stream as sum_want does; stage: of
+    // the stream in progress; dpl: its tile launches write the depth plane at every step (otherwise the full result is gathered)
+    bool stage_want = false, stage = false, dpl = false;
     // the totals over the days (TRMC_SUMMARY_TOTAL): [nseg] in row order, outside the ring, one per summary part (tot[k - P_PEAK]:
     // the steps are int64 here); tot_days days are folded in (queued)
     DevBuf tot[P_N - P_PEAK];
@@ -326,7 +344,7 @@ inline size_t stream_prod_bytes(const trmc_plan *pl, const StreamRun &S, const S
 {
     const StreamProdRow &t = S.tab[k];
     if (!t.on || !p.host[k]) return 0;
-    if (k == P_HYD) return p.rowset >= 0 ? (size_t)pl->rowset_n[(size_t)p.rowset] * (size_t)S.nsteps * (size_t)pl->esz : 0;
+    if (k == P_HYD || k == P_STAGE) return p.rowset >= 0 ? (size_t)pl->rowset_n[(size_t)p.rowset] * (size_t)S.nsteps * (size_t)pl->esz : 0;
     return t.bytes;
 }
 
@@ -338,9 +356,9 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
     S.days_complete = e + 1;
     if (p.day != e) return fail(TRMC_ESTATE, "internal: the slot of a completed day holds another day");
     const T *q = (const T *)S.tm.p + (size_t)slot * S.slot_tm, *d = q + S.plane;
-    size_t bytes[P_N]; // what the copy stream has to carry of every product
+    size_t bytes[P_ALL]; // what the copy stream has to carry of every product
     bool any = false;
-    for (int k = 0; k < P_N; ++k) any |= (bytes[k] = stream_prod_bytes(pl, S, p, k)) > 0;
+    for (int k = 0; k < P_ALL; ++k) any |= (bytes[k] = stream_prod_bytes(pl, S, p, k)) > 0;
     auto at = [&](int k, bool want = true) { return want ? S.tab[k].base + (size_t)slot * S.tab[k].stride : nullptr; }; // (the product's slot)
     // (the totals fold every day's summary: with them a part is formed whether or not the day's own arrays go to the host)
     const bool total = (S.sum & TRMC_SUMMARY_TOTAL) && pl->nseg > 0;
@@ -355,6 +373,16 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
         const int64_t nrows = pl->rowset_n[(size_t)p.rowset];
         hipLaunchKernelGGL((k_gather_rows<T>), dim3(blocks_for(nrows * S.nsteps)), dim3(kBlock), 0, pst, q,
                            (const int32_t *)pl->rowsets[(size_t)p.rowset].p, (T *)at(P_HYD), nrows, pl->nseg_pad, S.nsteps, 1);
+    }
+    if (bytes[P_STAGE]) { // (the depth of every step at the same rows: from the depth plane, or from the full result)
+        const int64_t nrows = pl->rowset_n[(size_t)p.rowset];
+        if (S.dpl)
+            hipLaunchKernelGGL((k_gather_rows<T>), dim3(blocks_for(nrows * S.nsteps)), dim3(kBlock), 0, pst, d,
+                               (const int32_t *)pl->rowsets[(size_t)p.rowset].p, (T *)at(P_STAGE), nrows, pl->nseg_pad, S.nsteps, 1);
+        else
+            hipLaunchKernelGGL((k_gather_rows_depth_out<T>), dim3(blocks_for(nrows * S.nsteps)), dim3(kBlock), 0, pst,
+                               (const T *)S.out.p + (size_t)slot * S.slot_out, (const int32_t *)pl->rowsets[(size_t)p.rowset].p,
+                               (const int32_t *)pl->sh->row_of_pos.p, (T *)at(P_STAGE), nrows, S.nsteps);
     }
     if (bytes[P_Q0])
         hipLaunchKernelGGL((k_final_state<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, q, d, (const int32_t *)pl->sh->row_of_pos.p,
@@ -403,7 +431,7 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
     }
     HIP_TRY(hipEventRecord(S.ev_ready[(size_t)slot], pst));
     HIP_TRY(hipStreamWaitEvent(pl->cstream, S.ev_ready[(size_t)slot], 0));
-    for (int k = 0; k < P_N; ++k)
+    for (int k = 0; k < P_ALL; ++k)
         if (bytes[k]) HIP_TRY(hipMemcpyAsync(p.host[k], at(k), bytes[k], hipMemcpyDeviceToHost, pl->cstream));
     HIP_TRY(hipEventRecord(S.ev_free[(size_t)slot], pl->cstream));
     HIP_TRY(hipEventRecord(p.ev_done, pl->cstream));
@@ -431,7 +459,8 @@ template <class T> int stream_launch(trmc_plan *pl, StreamRun &S, int64_t g_from
     tile_args(pl, S.W, as);
     StepArgs<T> a = as;
     a.hot_list = a.hot_cnt = nullptr;
-    // (the rows' peak depth of the day rides in these launches: the slots' two columns -- NULL: the instances of a stream without it)
+    // (the rows' peak depth of the day rides in these launches: the slots' two columns -- NULL: the instances of a stream without it;
+    // S.dpl: the instances that write the depth plane at every step)
     T *const pk_d = S.carry ? (T *)S.pkd_d.p : nullptr;
     int32_t *const pk_at = S.carry ? (int32_t *)S.pkd_at.p : nullptr;
     for (int64_t g = g_from + 1; g <= g_to; ++g) {
@@ -446,7 +475,7 @@ template <class T> int stream_launch(trmc_plan *pl, StreamRun &S, int64_t g_from
         if (S.W > 0 && w1 > w0) {
             first_obs(wst, w0, w1);
             if (as.hot_list) tile_turn(pl, as);
-            launch_tile<T>(wst, as, w0, w1, tile, S.K, tol, pk_d, pk_at);
+            launch_tile<T>(wst, as, w0, w1, tile, S.K, tol, pk_d, pk_at, S.dpl);
             HIP_TRY(hipEventRecord(S.ev_slab[(size_t)(g % kSlabEvents)], wst));
             ++S.launches;
         }
@@ -454,11 +483,11 @@ template <class T> int stream_launch(trmc_plan *pl, StreamRun &S, int64_t g_from
             if (S.W > 0 && g >= 1) HIP_TRY(hipStreamWaitEvent(cst, S.ev_slab[(size_t)((g - 1) % kSlabEvents)], 0));
             first_obs(cst, w1, (int32_t)pl->nseg_pad);
             if (w2 > w1) { // (the deeper slices)
-                launch_tile<T>(cst, a, w1, w2, tile, S.K, tol, pk_d, pk_at);
+                launch_tile<T>(cst, a, w1, w2, tile, S.K, tol, pk_d, pk_at, S.dpl);
                 ++S.launches;
             }
             if (ncblk > 0) {
-                launch_ctile<T>(cst, a, (const int32_t *)pl->sh->cblk_ptr.p, 0, ncblk, tile, S.K, tol, pk_d, pk_at);
+                launch_ctile<T>(cst, a, (const int32_t *)pl->sh->cblk_ptr.p, 0, ncblk, tile, S.K, tol, pk_d, pk_at, S.dpl);
                 ++S.launches;
             }
         }
@@ -533,8 +562,21 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
         if (int rc = S.pkd_d.ensure((size_t)S.slots * np * sizeof(T))) return rc;
         if (int rc = S.pkd_at.ensure((size_t)S.slots * np * sizeof(int32_t))) return rc;
     }
+    // stage hydrographs: the tile launches write the depth plane at every step unless the stream assembles the full result, which
+    // is gathered then
+    S.stage = S.stage_want;
+    S.dpl = S.stage && !S.want_out;
+    if (S.dpl && pl->opt.velocity_on_demand < 0)
+        return fail(TRMC_EUNSUPPORTED, "the stage of a stream without full_output is written by the tile kernels' on-demand-velocity instances: "
+                                       "not with trmc_plan_options.velocity_on_demand < 0");
+    if (S.rda && S.stage)
+        return fail(TRMC_EUNSUPPORTED, "stage hydrographs (trmc_stream_set_stage) are not supported in a stream with reservoir data "
+                                       "assimilation: the _rda tile instances do not write the depth plane");
+    // (boundary rows are routed by nobody and have no depth: zeros in the slots' depth planes, as in a full result)
+    if (S.dpl && tp.nboundary > 0)
+        HIP_TRY(hipMemset2DAsync((T *)S.tm.p + S.plane, S.slot_tm * sizeof(T), 0, S.plane * sizeof(T), (size_t)S.slots, pl->stream));
     // (boundary rows of the full result are written by nobody: zeros, so that their reduction is the (0, 1) the carry gives)
-    if (pd && S.want_out && tp.nboundary > 0) HIP_TRY(hipMemsetAsync(S.out.p, 0, (size_t)S.slots * S.slot_out * sizeof(T), pl->stream));
+    if ((pd || S.stage) && S.want_out && tp.nboundary > 0) HIP_TRY(hipMemsetAsync(S.out.p, 0, (size_t)S.slots * S.slot_out * sizeof(T), pl->stream));
     // THE TABLE OF THE DAY'S PRODUCTS (the head of StreamRun), in the enumeration's order: {carried, bytes of a day's copy, bytes of a
     // slot, has a buffer of its own, bytes of its total over the days}.  A summary part that the mask does not ask for holds no
     // buffer; the other buffers are kept between streams.
@@ -555,11 +597,12 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
         /* P_MEAN    */ {mean, row, row, true, row},
         /* P_PD      */ {pd, row, row, true, row},
         /* P_PDS     */ {pd, irow, irow, true, lrow},
+        /* P_STAGE   */ {S.stage, 0, 0, true, 0}, // (as P_HYD)
     };
-    static_assert(sizeof(rows) / sizeof(rows[0]) == P_N, "one row per product, in the enumeration's order");
+    static_assert(sizeof(rows) / sizeof(rows[0]) == P_ALL, "one row per product, in the enumeration's order");
     const bool tot = (S.sum & TRMC_SUMMARY_TOTAL) != 0;
     S.tot_days = 0;
-    for (int k = 0; k < P_N; ++k) {
+    for (int k = 0; k < P_ALL; ++k) {
         StreamProdRow &t = S.tab[k];
         t.on = rows[k].on;
         t.bytes = rows[k].bytes;
@@ -569,7 +612,7 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
         if (rows[k].own && t.on)
             if (int rc = t.buf.ensure((size_t)S.slots * t.stride)) return rc;
         t.base = (char *)t.buf.p;
-        if (k < P_PEAK) continue;
+        if (k < P_PEAK || k >= P_N) continue;
         // ... and the part's total over the days, outside the ring (the steps count on over the days: int64)
         DevBuf &b = S.tot[k - P_PEAK];
         if (!(tot && t.on)) b.release();
@@ -694,8 +737,10 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
     // (the host image of the slot's reservoir tables is written below: the copy of the slot's last day must have read it)
     if (S.rda && p.day >= 0) HIP_TRY(hipEventSynchronize(S.ev_forcing[(size_t)slot]));
     if (p.day >= 0 && p.queued) HIP_TRY(hipStreamWaitEvent(hst, S.ev_free[(size_t)slot], 0)); // (the slot's last day has handed its products over)
-    if (day.hyd_host && rowset >= 0) { // (the hydrographs' slot is sized by the stream's first push)
-        StreamProdRow &h = S.tab[P_HYD];
+    // (the hydrographs' slot, and the stage's, are sized by the stream's first push that asks for them)
+    for (const int k : {(int)P_HYD, (int)P_STAGE}) {
+        if (!(k == P_HYD ? day.hyd_host != nullptr : S.tab[P_STAGE].next != nullptr) || rowset < 0) continue;
+        StreamProdRow &h = S.tab[k];
         const size_t hb = (size_t)pl->rowset_n[(size_t)rowset] * S.nsteps * sizeof(T);
         if (hb > h.stride) {
             if (d > S.day_min || S.days_complete < d) {
@@ -712,7 +757,7 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
     // the day's destinations: from the day, the summary parts' from the calls in front of this push, which consumes them
     void *const from_day[P_PEAK] = {day.hyd_host, day.q0_host, day.fvd_host, day.nudge_host, day.res_inflow_host, day.res_da_state_host,
                                     day.res_da_tsidx_host};
-    for (int k = 0; k < P_N; ++k) {
+    for (int k = 0; k < P_ALL; ++k) {
         p.host[k] = k < P_PEAK ? from_day[k] : S.tab[k].next;
         S.tab[k].next = nullptr;
     }
@@ -914,6 +959,25 @@ int trmc_stream_summary_depth_dest(trmc_plan *pl, void *peak_depth_host, int32_t
     return 0;
 }
 
+int trmc_stream_set_stage(trmc_plan *pl, int on)
+{
+    if (int rc = stream_check(pl, false)) return rc;
+    if (pl->flow) return fail(TRMC_EINVAL, "a stream of windows runs on the level engine");
+    if (!on && !pl->seq) return 0; // (withdrawn where nothing was declared)
+    if (!pl->seq) pl->seq = std::make_unique<StreamRun>();
+    pl->seq->stage_want = on != 0;
+    return 0;
+}
+
+int trmc_stream_stage_dest(trmc_plan *pl, void *stage_host)
+{
+    if (int rc = stream_check(pl, true)) return rc;
+    StreamRun &S = *pl->seq;
+    if (!S.stage) return fail(TRMC_ESTATE, "the stream was begun without stage hydrographs (trmc_stream_set_stage precedes trmc_stream_begin)");
+    S.tab[P_STAGE].next = stage_host;
+    return 0;
+}
+
 int trmc_stream_summary_total(trmc_plan *pl, void *peak_flow, int64_t *peak_step, void *mean_flow, void *peak_depth, int64_t *peak_depth_step,
                               int64_t *days_out)
 {
@@ -1058,6 +1122,10 @@ int trmc_stream_push_day(trmc_plan *pl, const trmc_stream_day *day)
     if (S.g_done > S.days_pushed * S.tpd - 1 && S.days_complete < S.days_pushed)
         return fail(TRMC_ESTATE, "the stream has been advanced past its last day without being flushed: trmc_stream_flush first");
     if (hyd_host && (rowset < 0 || rowset >= (int32_t)pl->rowsets.size())) return fail(TRMC_EINVAL, "unknown row set");
+    if (S.tab[P_STAGE].next && (rowset < 0 || rowset >= (int32_t)pl->rowsets.size())) {
+        S.tab[P_STAGE].next = nullptr; // (the array does not wait for another day)
+        return fail(TRMC_EINVAL, "a day's stage (trmc_stream_stage_dest) covers the rows of the day's row set: the day names none, or an unknown one");
+    }
     if (fvd_host && S.dec_stride == 0 && !S.want_out)
         return fail(TRMC_EINVAL, "the stream was begun without full_output / output_stride: there is no (q, v, d) block to hand over");
     return by_precision(pl, [&](auto t) { return stream_push_t<decltype(t)>(pl, *day); });

@@ -440,8 +440,18 @@ class RoutingPlan:
         _lib.check(_lib.lib().trmc_stream_set_summary(self._h, mask))
         self._stream_summary = mask
 
+    def stream_set_stage(self, on=True):
+        """The streams on this plan hand over STAGE HYDROGRAPHS (trmc_stream_set_stage): the depth of every step at the rows of a
+        day's row set -- a reservoir row: its pool's elevation -- which ``stream_push(..., rowset=, stage=)`` names a page-locked
+        array for.  Declared before ``stream_begin``; it stays until the next call.  ``stream_begin`` then raises
+        NotImplementedError in a stream with reservoir data assimilation, as it does for ``"peak_depth"``."""
+        if self.engine != "levels":
+            raise ValueError("a stream of days runs on the level engine: stage hydrographs need engine='levels'")
+        _lib.check(_lib.lib().trmc_stream_set_stage(self._h, int(bool(on))))
+        self._stream_stage = bool(on)
+
     def stream_push(self, qlat, boundary_q_ptr=None, rowset=None, hyd=None, q0=None, fvd=None, nudging=None, nudge=None,
-                    reservoir_inflow=None, reservoir_da=None, reservoir_da_state=None, summary=None):
+                    reservoir_inflow=None, reservoir_da=None, reservoir_da_state=None, summary=None, stage=None):
         """The next day: ``qlat`` [nseg, nq] (page-locked: ``_lib.result_empty(..., always_pinned=True)``), where its products go
         (page-locked arrays or None), the device pointer of its boundary rows' flows.  A plan with gage rows
         (``stream_set_gages``): ``nudging=(mode, a, w)``, the day's tables [ngage, nsteps] as ``set_nudging`` takes them for a
@@ -454,9 +464,19 @@ class RoutingPlan:
         leaves, times already counted from the next day's start.  A plan whose streams form a summary (``stream_set_summary``):
         ``summary=`` a tuple of page-locked [nseg] arrays (any may be None) for the day's peak flow, the 1-based step of the peak
         and the mean flow -- with ``"peak_depth"`` two more, the peak depth and its step: the rows of ``stream_products.SUMMARY``
-        with their types.  Returns the day's number in the stream."""
+        with their types.  A plan whose streams carry stage (``stream_set_stage``): ``stage=`` a page-locked array
+        [rows of ``rowset``, nsteps] for the depth of every step at the set's rows (``rowset`` is then required).  Returns the
+        day's number in the stream."""
         if qlat.dtype != self.dtype or not qlat.flags.c_contiguous or qlat.ndim != 2 or qlat.shape[0] != self.nseg:
             raise ValueError(f"qlat must be a C-contiguous {np.dtype(self.dtype).name} array of shape ({self.nseg}, nq)")
+        if stage is not None:  # (what the library would refuse, before it is called)
+            if not getattr(self, "_stream_stage", False):
+                raise RuntimeError("stage: the stream was begun without stage hydrographs (stream_set_stage precedes stream_begin)")
+            if rowset is None:
+                raise ValueError("stage: a day's stage covers the rows of its row set -- rowset is required")
+            n = getattr(self, "_rowset_n", {}).get(rowset)
+            if n is not None and isinstance(stage, np.ndarray) and stage.ndim == 2 and (stage.shape[0] < n or stage.shape[1] != self._nsteps):
+                raise ValueError(f"stage must hold [{n}, {self._nsteps}] (the rows of the day's row set, nsteps), got {stage.shape}")
         day_s = _lib.StreamDay()
         tables = ()
         if nudging is not None:
@@ -479,8 +499,8 @@ class RoutingPlan:
             raise ValueError(SP.SUMMARY_WRONG)
         dims = {"rows": self.nseg, "nres": getattr(self, "_nres", 0)}
         dest = {p.name: SP.given(p, {"hyd": hyd, "q0": q0, "fvd": fvd, "nudge": nudge, "reservoir_inflow": reservoir_inflow,
-                                     "reservoir_da_state": reservoir_da_state, "summary": summary}) for p in SP.PRODUCTS}
-        for p in SP.PRODUCTS:
+                                     "reservoir_da_state": reservoir_da_state, "summary": summary, "stage": stage}) for p in SP.ALL}
+        for p in SP.ALL:
             if p.wrong and dest[p.name] is not None and not SP.fits(p, dest[p.name], self.dtype, dims):
                 raise ValueError(SP.wrong(p, self.dtype, dims))
         if nudge is not None and nudge.shape != (tables[0].shape if tables else ()):
@@ -510,6 +530,8 @@ class RoutingPlan:
         if summary is not None:  # (where the NEXT day's summary goes: the push below consumes it)
             _lib.check(_lib.lib().trmc_stream_summary_dest(self._h, *(_lib.ptr(x) for x in parts[:3])))
         try:
+            if stage is not None:    # (likewise)
+                _lib.check(_lib.lib().trmc_stream_stage_dest(self._h, _lib.ptr(stage)))
             if depth:
                 _lib.check(_lib.lib().trmc_stream_summary_depth_dest(self._h, *(_lib.ptr(x) for x in parts[3:])))
             if nudging is None and reservoir_inflow is None and reservoir_da is None and reservoir_da_state is None:  # (the entry point every stream without tables has always used)
@@ -527,6 +549,8 @@ class RoutingPlan:
                 _lib.lib().trmc_stream_summary_dest(self._h, None, None, None)
             if depth:
                 _lib.lib().trmc_stream_summary_depth_dest(self._h, None, None)
+            if stage is not None:
+                _lib.lib().trmc_stream_stage_dest(self._h, None)
             raise
 
     def stream_summary_total(self):

@@ -287,7 +287,7 @@ class ProductRing:
     nothing is allocated for a product the stream does not hand over."""
 
     def __init__(self, slots, plan_dtype, dims, has):
-        carried = [p for p in SP.PRODUCTS if p.on is None or has.get(p.on)]
+        carried = [p for p in SP.ALL if p.on is None or has.get(p.on)]
         self._slots = [{p.name: _lib.result_empty(SP.shape_of(p, dims), SP.dtype_of(p, plan_dtype), always_pinned=True) for p in carried}
                        for _ in range(slots)]
         self._keywords = [SP.push_keywords(a) for a in self._slots]
@@ -444,6 +444,13 @@ class RouteStream:
     -- once ``route()`` has yielded its last day, next to ``rs.total``.  It is not a product of the day: the tuples do not change.
     Flow only ("depth", "velocity", "bankfull": NotImplementedError -- route the day in question as a window).
 
+    ``stage=True``: every day also carries STAGE HYDROGRAPHS -- the depth of every step at the rows of its hydrographs: the
+    trailing dict gains ``"stage"``, a ring array [len(outlet_rows), nsteps] in the hydrographs' row order (a reservoir row: its
+    pool's elevation; nudging changes a gage's flow only).  The tile kernels then write a slot's depth plane at every step
+    instead of at a tile's last one, and the hydrographs' gather kernel forms the array from it (include/trmc.h,
+    trmc_stream_set_stage).  One rank only: with several, the outlets' stage would have to be gathered over the ranks as the
+    hydrographs are, which nothing does yet -- NotImplementedError; so is a router with ``reservoir_da``.
+
     Underneath is ONE stream of tile launches (include/trmc.h, trmc_stream_*): the tile index runs on over the days, every
     launch routes every row through the next K steps of its own place in the stream -- a row deep in the network works on an
     earlier tile than the headwaters, possibly of an earlier day -- so a day costs nsteps / K launches and nothing else, and a
@@ -458,7 +465,7 @@ class RouteStream:
 
     def __init__(self, router, nsteps, qts_subdivisions, output_stride=None, full_output=False, slots=0, latency="throughput",
                  hydrographs_on_every_rank=False, comm=None, exchange=None, reservoir_da_ncol=None, summary=None,
-                 daily_summary=True, exceedance=None):
+                 daily_summary=True, stage=False, exceedance=None):
         """comm / exchange (several ranks): the communicator -- default: the one given to ``router.enable_device_exchange`` -- and
         how the daily cut-edge hydrographs travel: "device" (gather kernel -> all-gather on the exchange stream -> boundary rows,
         everything in HBM: RCCL over xGMI) or "host" (through ``comm.all_gather_rows_host``: any communicator with that method,
@@ -467,6 +474,13 @@ class RouteStream:
         reservoir_da_ncol (a router with ``reservoir_da``): the most columns (usgs, usace, rfc) a day's tables may have; default:
         as many as the declared tables."""
         self._rda_ncol = reservoir_da_ncol
+        self.stage = bool(stage)
+        if self.stage and router.world > 1:
+            raise NotImplementedError("stage=True on several ranks: a day's stage covers the rows of its hydrographs, which every rank holds a "
+                                      "part of -- the parts are gathered over the ranks for the flows only")
+        if self.stage and getattr(router, "_reservoir_da", None) is not None:
+            raise NotImplementedError("stage=True with reservoir data assimilation: the tile kernels of such a stream do not write the depth "
+                                      "plane at every step (as for summary 'peak_depth')")
         summary = (summary,) if isinstance(summary, str) else tuple(summary or ())
         if any(w not in _lib.SUMMARY_NAMES for w in summary):
             raise ValueError("summary: an iterable of 'peak' and / or 'mean', 'peak_depth', 'total', or None")
@@ -683,6 +697,8 @@ class RouteStream:
         elif getattr(P, "_stream_exceedance", -1) >= 0:        # (an earlier stream's declaration is withdrawn, as its summary is)
             P.stream_set_exceedance(None)
         self.exceedance = None
+        if self.stage or getattr(P, "_stream_stage", False):   # (likewise)
+            P.stream_set_stage(self.stage)
         P.stream_begin(nsteps, self.qts, slots=slots, full_output=self.full_output and not self.output_stride, output_stride=self.output_stride,
                        **({} if rda is None else {"reservoir_da": True if self._rda_ncol is None else self._rda_ncol}))
         self.info = info = P.stream_info()
@@ -691,7 +707,8 @@ class RouteStream:
         ring = ProductRing(info["slots"], P.dtype,
                            {"rows": rows.shape[0], "nsteps": nsteps, "keep": nsteps // self.output_stride if self.output_stride else nsteps,
                             "outlets": max(r._outS_global.shape[0], 1), "nres": nres, "ngage": ngage},
-                           {"fvd": want_fvd, "ngage": ngage, "nres": nres, "rda": rda is not None, **{w: daily for w in self.summary}})
+                           {"fvd": want_fvd, "ngage": ngage, "nres": nres, "rda": rda is not None, "stage": self.stage,
+                            **{w: daily for w in self.summary}})
         stage = ForcingStage(depth, (rows.shape[0], nxt.shape[1]), P.dtype)
         xch = CutExchange(r, P, self.comm, self.exchange == "device", nsteps) if multi else None
         self._out_rows, self._order = (None, None) if multi else (np.sort(r._outS_global), np.argsort(r._outS_global, kind="stable"))
@@ -751,5 +768,7 @@ class RouteStream:
             if rdac is not None:
                 more["reservoir_da"] = rdac.tuples(a["reservoir_da_state"], a["reservoir_da_tsidx"])
         more.update((p.name, a.get(p.name)) for p in ring.parts)
-        return item + (more,) if (extras or ring.parts) else item
+        if self.stage:      # (the hydrographs' rows, in their order)
+            more["stage"] = a["stage"][:self.r._outS_global.shape[0]][self._order]
+        return item + (more,) if (extras or ring.parts or self.stage) else item
 

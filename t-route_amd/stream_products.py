@@ -11,7 +11,7 @@ A row says
   dtype   PLAN (the plan's precision) or a numpy type
   shape   extents by name -- rows, nsteps, keep (the steps an output stride keeps), outlets, nres, ngage -- or as numbers
   on      when a stream carries it: None (always) or what the stream must have -- "fvd" (full_output / output_stride), "ngage",
-          "nres", "rda" (reservoir data assimilation), or the word of ``SUMMARY_NAMES`` that asks for the part
+          "nres", "rda" (reservoir data assimilation), "stage" (stage hydrographs), or the word of ``SUMMARY_NAMES`` that asks for the part
   total   (summary parts) the type of the part's total over the days
   wrong   what ``stream_push`` says of a destination that does not fit (None: the library checks it)
 
@@ -26,6 +26,7 @@ Product = namedtuple("Product", "name push pos dtype shape on keyed total wrong"
 
 _RECORD = "{name} must be a C-contiguous {plan} array [rows, nsteps]"
 _RDA = "reservoir_da_state must be (float32 [{nres}, 4], int32 [{nres}]), C-contiguous"
+_STAGE = "stage must be a C-contiguous {plan} array [rows of the day's row set, nsteps]"
 _PART = "summary: {name} must be a C-contiguous {dtype} array of shape ({rows},)"
 
 PRODUCTS = (
@@ -42,6 +43,10 @@ PRODUCTS = (
     Product("peak_depth", "summary", 3, PLAN, ("rows",), "peak_depth", True, PLAN, _PART),
     Product("peak_depth_step", "summary", 4, np.int32, ("rows",), "peak_depth", True, np.int64, _PART),
 )
+# ... and, behind the rows that mirror the device table's first enumeration one for one, the products whose destination a call of
+# its own names (stream.inc, P_STAGE on): checked, allocated and pushed as the rows above are
+STAGE = Product("stage", "stage", None, PLAN, ("outlets", "nsteps"), "stage", False, None, _STAGE)
+ALL = PRODUCTS + (STAGE,)
 SUMMARY = tuple(p for p in PRODUCTS if p.push == "summary")
 # the records of reservoirs and gages, in the order RouteStream's dict has always had them (the inflows first)
 RECORDS = tuple(sorted((p for p in PRODUCTS if p.keyed and p not in SUMMARY), key=lambda p: p.name != "reservoir_inflow"))
@@ -83,7 +88,7 @@ def wrong(p, plan_dtype, dims):
 def push_keywords(arrays):
     """``stream_push``'s keywords for a slot's arrays {name: array}: a product the slot lacks is left out (in a tuple: None)"""
     kw = {}
-    for p in PRODUCTS:
+    for p in ALL:
         if arrays.get(p.name) is None:
             continue
         if p.pos is None:

@@ -12,7 +12,12 @@ row and the hydrographs of sampled rows bit for bit, and what a day costs either
                                                             days' own summary arrays then stay on the device
                                [--exceedance K]             the threshold exceedance of every row's flow over ALL days of the stream at
                                                             K levels (trmc_stream_set_exceedance), fetched once at the end; checked
-                                                            against the numpy loop over the one-by-one days' flows where that fits"""
+                                                            against the numpy loop over the one-by-one days' flows where that fits
+                               [--stage]                    stage hydrographs: the depth of every step at the rows of the day's row set
+                                                            (trmc_stream_set_stage); checked against column 2 of the one-by-one
+                                                            day's full result where that fits (nseg * 288 <= 2^26)
+                               [--outlets]                  the row set of the hydrographs (and of --stage) is the networks' outlets
+                                                            instead of 3000 sampled rows"""
 import argparse
 import os
 import sys
@@ -45,6 +50,8 @@ ap.add_argument("--summary", action="store_true", help="per-row peak flow, step 
 ap.add_argument("--summary-depth", action="store_true", help="the day's peak depth and its step as well (with or without --summary)")
 ap.add_argument("--summary-total", action="store_true", help="the totals over the days of the stream; no per-day summary array crosses to the host")
 ap.add_argument("--exceedance", type=int, default=0, metavar="K", help="exceedance of K (1..4) flow thresholds a row over the whole stream, kept on the device")
+ap.add_argument("--stage", action="store_true", help="the depth of every step at the rows of the row set as a stream product")
+ap.add_argument("--outlets", action="store_true", help="the row set: every network's outlet (default: 3000 sampled rows)")
 ap.add_argument("--gages", type=int, default=0, help="nudged gages scattered over the network (observations: 70 %% valid, lognormal)")
 a = ap.parse_args()
 if a.reservoir_da > a.reservoirs:
@@ -70,6 +77,8 @@ for q in days:
 q0 = np.zeros((n, 3), np.float32)
 rng = np.random.default_rng(5)
 sample = np.sort(rng.choice(n, min(n, 3000), replace=False))
+if a.outlets:
+    sample = np.flatnonzero(np.asarray(net["to"]) < 0)
 # reservoirs and gages: synthetic level-pool parameters (oracle.LP_PAR order), every day's nudging tables resolved beforehand
 lakes = gages = par = None
 tabs = []
@@ -165,6 +174,8 @@ ref_q = []
 daily = any_summary and not a.summary_total
 check_summary = any_summary and not a.no_check and n * nsteps <= 1 << 26
 ref_sum = []
+check_stage = a.stage and not a.no_check and n * nsteps <= 1 << 26
+ref_stage = []
 opts = {"wide_min_rows": a.wide_min_rows, "wide_k": a.wide_k, "cluster_rows": 128, "wide_levels": a.wide_levels, "stream_split": a.split, "velocity_on_demand": a.velocity_on_demand}
 hint = None
 if a.hint:
@@ -201,6 +212,8 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
             if check_summary:
                 full = fvd if (a.full and not a.stride) else p.download_fvd()
                 ref_sum.append(summary_of(np.ascontiguousarray(full[:, :, 0])) + peak_of(np.ascontiguousarray(full[:, :, 2])))
+            if check_stage:
+                ref_stage.append(np.ascontiguousarray((fvd if (a.full and not a.stride) else p.download_fvd())[sample, :, 2]))
             if check_exc:
                 ref_q.append(np.ascontiguousarray((full if check_summary else p.download_fvd())[:, :, 0]))
             if a.reservoir_da:
@@ -216,6 +229,8 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
     p.upload_forcing(nsteps, days[0], q0)
     p.stream_set_summary((("peak", "mean") if a.summary else ()) + (("peak_depth",) if a.summary_depth else ())
                          + (("total",) if a.summary_total else ()) or None)
+    if a.stage:
+        p.stream_set_stage(True)
     if a.exceedance:
         # a row's levels: quantiles of its own flows over the stream where they are known (the check), else multiples of its forcing
         if check_exc:
@@ -242,6 +257,7 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
             for _ in range(D)]
     if daily and a.summary_depth:
         sums = [s + (_lib.result_empty((n,), np.float32, always_pinned=True), _lib.result_empty((n,), np.int32, always_pinned=True)) for s in sums]
+    stgs = [_lib.result_empty((sample.shape[0], nsteps), np.float32, always_pinned=True) if a.stage else None for _ in range(D)]
     da_day = da_tables() if a.reservoir_da else None
     got = []
     behind = (info["lag_max"] + info["tiles_per_day"]) // info["tiles_per_day"] + a.later
@@ -265,6 +281,9 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
         if check_summary and daily and not all(y is None or np.array_equal(x.view(np.uint32), y.view(np.uint32)) for x, y in zip(ref_sum[e], sums[e % D])):
             ok = False
             print(f"   day {e}: summary differs", flush=True)
+        if check_stage and not np.array_equal(ref_stage[e].view(np.uint32), stgs[e % D].view(np.uint32)):
+            ok = False
+            print(f"   day {e}: stage differs", flush=True)
         s1 = np.array_equal(fin.view(np.uint32), fins[e % D].view(np.uint32))
         s2 = np.array_equal(hyd.view(np.uint32), hyds[e % D].view(np.uint32))
         s3 = fvd is None or np.array_equal(np.ascontiguousarray(fvd).view(np.uint32), fvds[e % D].view(np.uint32))
@@ -274,7 +293,7 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
     t0 = time.perf_counter()
     for d in range(a.days):
         p.stream_push(pinned[d % len(days)], rowset=rs, hyd=hyds[d % D], q0=fins[d % D], fvd=fvds[d % D],
-                      nudging=tabs[d % len(days)] if tabs else None, nudge=nuds[d % D], reservoir_inflow=rins[d % D], reservoir_da=da_day, reservoir_da_state=rdas[d % D], summary=sums[d % D])
+                      nudging=tabs[d % len(days)] if tabs else None, nudge=nuds[d % D], reservoir_inflow=rins[d % D], reservoir_da=da_day, reservoir_da_state=rdas[d % D], summary=sums[d % D], **({"stage": stgs[d % D]} if a.stage else {}))
         e = d - behind
         if e >= 0:
             take(e)
@@ -323,4 +342,7 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
         print("   summary (" + ", ".join((["peak flow, step of the peak, mean flow"] if a.summary else []) + (["peak depth and its step"] if a.summary_depth else []))
               + " of every row" + ("; totals only" if a.summary_total else "") + "):",
               "checked against the host's reduction of every day's full result" if check_summary else "not checked (no check asked for, or too large for a host reduction)", flush=True)
+    if a.stage:
+        print(f"   stage of every step at the {sample.shape[0]} rows of the row set:",
+              "checked against column 2 of every day's full result" if check_stage else "not checked (no check asked for, or too large)", flush=True)
     print("   launches", p.stream_info()["launches"], " every day bit-identical to the days routed one by one:", ok if not a.no_check else "not checked", flush=True)
