@@ -185,7 +185,7 @@ int trmc_plan_create_ex(int64_t nseg, const int64_t *up_ptr, const int64_t *up_i
  *   cluster_late_lag  cluster order: rows fed by boundary rows (and rows marked 2 in `boundary`) run at least so many tiles
  *                  behind the headwaters -- the trunk of a cut basin in a multi-GPU stream, whose inflows are exchanged once a
  *                  day (troute_amd.sequence.RouteStream).
- *   hot_wave_rows  rows of the hot list per WAVEFRONT of the blocks that route it (1..64; 0 = default 64).  An experiment's knob:
+ *   hot_wave_rows  rows of the hot list per WAVEFRONT of the blocks that route it (1..64; 0 and below = default 64, above 64 = 64).  An experiment's knob:
  *                  fewer rows per wavefront were meant to shorten the slowest wavefront's chain of wide_k dependent steps on a
  *                  device one launch does not fill (a rank of a multi-GPU job); measured slower at 32, 16 and 8.
  *   stream_split   s > 0: in a stream of windows the slices from level s on are launched on the clusters' stream instead of the
@@ -864,6 +864,16 @@ int trmc_download_gathered(trmc_plan *plan, void *out);
 /* Diagnosis: how many rows the tiles of this plan have routed from the hot list so far (trmc_plan_options.hot_rows; a running
  * total over all launches and windows, modulo 2^31; waits for the device). */
 int trmc_plan_hot_rows(trmc_plan *plan, int64_t *rows_out);
+/* Diagnosis, host only (an addition within ABI 19; no launch, no device buffer of its own): the hot lists as the launches queued so
+ * far leave them -- waits for the device.  cap: entries one list holds (0: the plan has no lists yet -- no tiled window or stream
+ * so far, or hot_rows off); hot_home: blocks at the front of the next tile launch that take the list, ceil(cap / (hot_wave_rows *
+ * tile_block / 64)); counts[3]: the three lengths, as ATTEMPTED appends -- a row past cap is counted, neither stored nor stamped,
+ * and stays with its home block, so a length above cap says the list overflowed (a launch routes min(length, cap) rows from the list
+ * it reads); cur_next: which of the three the next launch reads (it appends to (cur_next + 1) % 3 and clears (cur_next + 2) % 3,
+ * so counts[cur_next] is what the last launch appended).  tile_block, wave_max: the build's constants -- threads per block of the
+ * tile kernel, and the number of hot rows from which a wavefront keeps them (TRMC_HOT_WAVE_MAX).  Any output may be NULL. */
+int trmc_plan_hot_state(trmc_plan *plan, int32_t *cap, int32_t *hot_home, int32_t counts[3], int32_t *cur_next, int32_t *tile_block,
+                        int32_t *wave_max);
 
 /* Tell a plan which steps a caller will ask for with trmc_fetch_begin_fvd: windows begun afterwards write every stride-th step
  * of (q, v, d) into a block of their own AS THEY GO -- the rows of the tiled leading levels from the kernel that routes them,

@@ -143,6 +143,31 @@ int trmc_plan_hot_rows(trmc_plan *pl, int64_t *rows_out)
     return 0;
 }
 
+// (host only: no launch, no buffer of its own -- what tile_setup / tile_args / tile_turn hold, and the three lengths as the last
+// launch left them: an append past hot_cap is counted and not stored, so a length above hot_cap says the list overflowed)
+int trmc_plan_hot_state(trmc_plan *pl, int32_t *cap, int32_t *hot_home, int32_t counts[3], int32_t *cur_next, int32_t *tile_block,
+                        int32_t *wave_max)
+{
+    if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
+    if (tile_block) *tile_block = kTileBlock;
+    if (wave_max) *wave_max = TRMC_HOT_WAVE_MAX;
+    if (cur_next) *cur_next = (int32_t)(pl->tile_seq % 3);
+    if (cap) *cap = 0;
+    if (hot_home) *hot_home = 0;
+    if (counts) counts[0] = counts[1] = counts[2] = 0;
+    if (!pl->hot_cnt.p || !pl->hot_list.p || pl->hot_cap <= 0) return 0;
+    if (cap) *cap = pl->hot_cap;
+    if (hot_home) {
+        const int32_t per_block = hot_wave_rows_of(pl) * (kTileBlock / 64);
+        *hot_home = (pl->hot_cap + per_block - 1) / per_block;
+    }
+    if (!counts) return 0;
+    if (int rc = use_device(pl)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(counts, pl->hot_cnt.p, 3 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int trmc_plan_set_output_stride(trmc_plan *pl, int32_t stride)
 {
     if (!pl) return fail(TRMC_EINVAL, "plan is NULL");

@@ -924,6 +924,17 @@ class RoutingPlan:
         _lib.check(_lib.lib().trmc_plan_hot_rows(self._h, C.byref(n)))
         return n.value
 
+    def hot_state(self):
+        """Diagnosis (trmc_plan_hot_state): the hot lists as the launches queued so far leave them -- ``cap`` entries per list,
+        ``hot_home`` blocks that take the list in the next launch, ``counts`` [3] lengths as attempted appends (above ``cap``: the
+        list overflowed), ``cur_next`` the list the next launch reads, and the build's ``tile_block`` and ``wave_max``."""
+        cap, home, cur, blk, wmax = (C.c_int32(0) for _ in range(5))
+        counts = (C.c_int32 * 3)()
+        _lib.check(_lib.lib().trmc_plan_hot_state(self._h, C.byref(cap), C.byref(home), counts, C.byref(cur), C.byref(blk),
+                                                  C.byref(wmax)))
+        return {"cap": cap.value, "hot_home": home.value, "counts": [int(c) for c in counts], "cur_next": cur.value,
+                "tile_block": blk.value, "wave_max": wmax.value}
+
     def set_output_stride(self, stride):
         """Windows begun from now on write every `stride`-th step of (q, v, d) aside as they go (trmc_plan_set_output_stride):
         what ``fetch_begin(..., output_stride=stride)`` then copies without another pass over the result; 0 / None: off."""

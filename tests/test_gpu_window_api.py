@@ -383,9 +383,11 @@ def test_windows_that_decimate_as_they_go_hand_over_the_same_block(monkeypatch, 
 @pytest.mark.parametrize("hinted", [False, True])
 def test_hot_rows_are_routed_by_blocks_of_their_own_and_change_nothing(monkeypatch, hinted):
     """trmc_plan_options.hot_rows: rows that end a tile in three or more secant iterations (or over bank) are taken out of their
-    blocks for the next tile.  A forcing that floods part of the network makes sure there are some -- more than the list holds
-    (the rest stay where they are) -- over several windows, and the result must be the one without the option, bit for bit; so
-    must the cost every row collected (trmc_plan_collect_cost): a row routed twice in a launch would have counted twice."""
+    blocks for the next tile.  A forcing that floods part of the network makes sure there are some -- hundreds routed from the
+    lists over several windows (a running total: it does not say that a list ever overflowed; that, against the oracle, is
+    test_gpu_tile_scheduler_edges.test_a_hot_list_that_overflows_leaves_the_rest_with_their_blocks) -- and the result must be the
+    one without the option, bit for bit; so must the cost every row collected (trmc_plan_collect_cost): a row routed twice in a
+    launch would have counted twice."""
     monkeypatch.setenv("TRMC_ENGINE", "levels")
     monkeypatch.setenv("TRMC_WIDE_MIN_ROWS", "64")
     monkeypatch.setenv("TRMC_WIDE_K", "4")
