@@ -522,17 +522,16 @@ int trmc_stage_forcing(trmc_plan *pl, int nsteps, const void *qlat, int64_t nq)
         if (int rc = pl->qlat_alt.ensure((size_t)nq * pl->nseg_pad * pl->esz)) return rc;
         const int32_t n = (int32_t)pl->nseg;
         const dim3 grid((n + 63) / 64, (unsigned)((nq + 31) / 32));
-        if (pl->precision == 32)
-            hipLaunchKernelGGL((k_prep_qlat<float>), grid, dim3(kBlock), 0, pl->hstream, (const float *)pl->in_qlat.p,
-                               (const int32_t *)pl->sh->row_of_pos.p, (float *)pl->qlat_alt.p, n, pl->nseg_pad, (int32_t)nq);
-        else
-            hipLaunchKernelGGL((k_prep_qlat<double>), grid, dim3(kBlock), 0, pl->hstream, (const double *)pl->in_qlat.p,
-                               (const int32_t *)pl->sh->row_of_pos.p, (double *)pl->qlat_alt.p, n, pl->nseg_pad, (int32_t)nq);
-        HIP_TRY(hipGetLastError());
+        const int rc = by_precision(pl, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((k_prep_qlat<T>), grid, dim3(kBlock), 0, pl->hstream, (const T *)pl->in_qlat.p,
+                               (const int32_t *)pl->sh->row_of_pos.p, (T *)pl->qlat_alt.p, n, pl->nseg_pad, (int32_t)nq);
+            return launched();
+        });
+        if (rc) return rc;
         pl->qlat_alt_ready = true;
     }
-    HIP_TRY(hipEventRecord(pl->ev_forcing, pl->hstream));
-    pl->forcing_pending = true;
+    if (int rc = pl->mk_forcing.record(pl->hstream)) return rc;
     pl->qlat_direct = false;
     pl->nq = nq;
     // (a plan with boundary rows: their hydrographs of the staged window arrive in ranges while it runs --
@@ -601,20 +600,21 @@ static int final_state_into(trmc_plan *pl, void *dst, int32_t nsteps_of_window)
     const int32_t n = (int32_t)pl->nseg, T_ = nsteps_of_window >= 0 ? nsteps_of_window : pl->routed_nsteps;
     const size_t plane = (size_t)(T_ + 1) * pl->nseg_pad;
     const int32_t *rop = (const int32_t *)pl->sh->row_of_pos.p;
-    if (pl->flow) {
+    int rc;
+    if (pl->flow) { // (precision 32 only; the depths in a column of their own)
         hipLaunchKernelGGL((k_final_state<float>), dim3(blocks_for(n)), dim3(kBlock), 0, pl->stream, (const float *)pl->tm.p,
                            (const float *)pl->d_state.p, rop, (float *)dst, n, pl->nseg_pad, T_, 2, 0);
-    } else if (pl->precision == 32) {
-        const float *q = (const float *)pl->tm.p;
-        hipLaunchKernelGGL((k_final_state<float>), dim3(blocks_for(n)), dim3(kBlock), 0, pl->stream, q, q + 2 * plane, rop,
-                           (float *)dst, n, pl->nseg_pad, T_, 1, T_);
+        rc = launched();
     } else {
-        const double *q = (const double *)pl->tm.p;
-        hipLaunchKernelGGL((k_final_state<double>), dim3(blocks_for(n)), dim3(kBlock), 0, pl->stream, q, q + 2 * plane, rop,
-                           (double *)dst, n, pl->nseg_pad, T_, 1, T_);
+        rc = by_precision(pl, [&](auto t) {
+            using T = decltype(t);
+            const T *q = (const T *)pl->tm.p;
+            hipLaunchKernelGGL((k_final_state<T>), dim3(blocks_for(n)), dim3(kBlock), 0, pl->stream, q, q + 2 * plane, rop, (T *)dst, n,
+                               pl->nseg_pad, T_, 1, T_);
+            return launched();
+        });
     }
-    HIP_TRY(hipGetLastError());
-    return note_gather(pl, nsteps_of_window >= 0);
+    return rc ? rc : note_gather(pl, nsteps_of_window >= 0);
 }
 
 // initial state (or warm start), boundary hydrographs, and the bookkeeping common to every forcing upload
@@ -625,12 +625,8 @@ static int stage_state(trmc_plan *pl, int nsteps, int64_t nq, const void *q0, co
     if (pl->nseg > 0) {
         if (q0) {
             HIP_TRY(hipMemcpyAsync(pl->in_q0.p, q0, (size_t)pl->nseg * 3 * e, hipMemcpyHostToDevice, pl->stream));
-            if (pl->nan_is_zero) {
-                const int64_t n = pl->nseg * 3;
-                if (pl->precision == 32) hipLaunchKernelGGL((k_nan_to_zero<float>), dim3(blocks_for(n)), dim3(kBlock), 0, pl->stream, (float *)pl->in_q0.p, n);
-                else hipLaunchKernelGGL((k_nan_to_zero<double>), dim3(blocks_for(n)), dim3(kBlock), 0, pl->stream, (double *)pl->in_q0.p, n);
-                HIP_TRY(hipGetLastError());
-            }
+            if (pl->nan_is_zero)
+                if (int rc = nan_to_zero(pl, pl->in_q0.p, pl->nseg * 3)) return rc;
         } else if (pl->routed_nsteps >= 0) { // warm start in HBM: (q_T, q_T, depth_T) of the previous window, AbstractNetwork.py:182-190
             if (int rc = final_state_into(pl, pl->in_q0.p)) return rc;
         } // (else: q0_staged -- the state an earlier staging of this window put into in_q0 stands, upload_check)
@@ -662,13 +658,9 @@ static int upload_check(trmc_plan *pl, int nsteps, int64_t nq, const void *q0)
     if (pl->nseg > 0 && !q0 && pl->routed_nsteps < 0 && !pl->q0_staged)
         return fail(TRMC_ESTATE, "q0 is NULL (continue from the resident state) but nothing has been routed yet");
     if (int rc = use_device(pl)) return rc;
-    if (pl->forcing_pending) {
-        // a forcing staged with trmc_stage_forcing is (or may still be) on its way into in_qlat on the copy stream: this upload
-        // replaces it, and its own copy must not be overtaken by the older one
-        HIP_TRY(hipEventSynchronize(pl->ev_forcing));
-        pl->forcing_pending = false;
-    }
-    return 0;
+    // a forcing staged with trmc_stage_forcing is (or may still be) on its way into in_qlat on the copy stream: this upload
+    // replaces it, and its own copy must not be overtaken by the older one
+    return pl->mk_forcing.sync();
 }
 
 int trmc_upload_forcing(trmc_plan *pl, int nsteps, const void *qlat, int64_t nq, const void *q0,
@@ -681,12 +673,8 @@ int trmc_upload_forcing(trmc_plan *pl, int nsteps, const void *qlat, int64_t nq,
     if (int rc = pl->in_qlat.ensure((size_t)pl->nseg * nq * e)) return rc;
     if (pl->nseg > 0) {
         HIP_TRY(hipMemcpyAsync(pl->in_qlat.p, qlat, (size_t)pl->nseg * nq * e, hipMemcpyHostToDevice, pl->stream));
-        if (pl->nan_is_zero) {
-            const int64_t n = pl->nseg * nq;
-            if (pl->precision == 32) hipLaunchKernelGGL((k_nan_to_zero<float>), dim3(blocks_for(n)), dim3(kBlock), 0, pl->stream, (float *)pl->in_qlat.p, n);
-            else hipLaunchKernelGGL((k_nan_to_zero<double>), dim3(blocks_for(n)), dim3(kBlock), 0, pl->stream, (double *)pl->in_qlat.p, n);
-            HIP_TRY(hipGetLastError());
-        }
+        if (pl->nan_is_zero)
+            if (int rc = nan_to_zero(pl, pl->in_qlat.p, pl->nseg * nq)) return rc;
     }
     pl->qlat_direct = false;
     pl->qlat_alt_ready = false; // (a staged forcing, transposed already, is replaced by this one)
@@ -731,13 +719,13 @@ int trmc_upload_forcing_packed(trmc_plan *pl, int nsteps, int64_t nq, int64_t nf
         HIP_TRY(hipMemcpyAsync(da, raw_a, raw_bytes, hipMemcpyHostToDevice, pl->stream));
         if (raw_b) HIP_TRY(hipMemcpyAsync(db, raw_b, raw_bytes, hipMemcpyHostToDevice, pl->stream));
         HIP_TRY(hipMemcpyAsync(pl->scratch.p, feat_of_pos.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, pl->stream));
-        if (pl->precision == 32)
-            hipLaunchKernelGGL((k_ingest_packed<float>), dim3(blocks_for(n)), dim3(kBlock), 0, pl->stream, da, db, ka, kb,
-                               (const int32_t *)pl->scratch.p, (float *)pl->qlat_tm.p, (int32_t)n, pl->nseg_pad, (int32_t)nq, nfeat);
-        else
-            hipLaunchKernelGGL((k_ingest_packed<double>), dim3(blocks_for(n)), dim3(kBlock), 0, pl->stream, da, db, ka, kb,
-                               (const int32_t *)pl->scratch.p, (double *)pl->qlat_tm.p, (int32_t)n, pl->nseg_pad, (int32_t)nq, nfeat);
-        HIP_TRY(hipGetLastError());
+        const int rc = by_precision(pl, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((k_ingest_packed<T>), dim3(blocks_for(n)), dim3(kBlock), 0, pl->stream, da, db, ka, kb,
+                               (const int32_t *)pl->scratch.p, (T *)pl->qlat_tm.p, (int32_t)n, pl->nseg_pad, (int32_t)nq, nfeat);
+            return launched();
+        });
+        if (rc) return rc;
     }
     pl->qlat_direct = true;
     pl->qlat_alt_ready = false;
@@ -1235,14 +1223,14 @@ int trmc_gather_flow_range(trmc_plan *pl, int32_t rowset, int t_begin, int t_end
         gst = flow_stream(pl, pl->flow_last);
         if (pl->run.launches > 1) HIP_TRY(hipStreamWaitEvent(gst, pl->ev_chunk[1 - pl->flow_last], 0));
     }
-    if (pl->precision == 32)
-        hipLaunchKernelGGL((k_gather_range<float>), dim3(blocks_for(work)), dim3(kBlock), 0, gst, (const float *)pl->tm.p,
-                           (const int32_t *)pl->rowsets[rowset].p, (float *)dst_dev, nrows, pl->nseg_pad, t_begin, t_end, dst_stride,
+    const int rc = by_precision(pl, [&](auto t) { // (precision 64 is the level engine's: gst is the plan's stream, the planes hold numbers)
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_gather_range<T>), dim3(blocks_for(work)), dim3(kBlock), 0, gst, (const T *)pl->tm.p,
+                           (const int32_t *)pl->rowsets[rowset].p, (T *)dst_dev, nrows, pl->nseg_pad, t_begin, t_end, dst_stride,
                            pl->flow ? 2 : 1);
-    else
-        hipLaunchKernelGGL((k_gather_range<double>), dim3(blocks_for(work)), dim3(kBlock), 0, pl->stream, (const double *)pl->tm.p,
-                           (const int32_t *)pl->rowsets[rowset].p, (double *)dst_dev, nrows, pl->nseg_pad, t_begin, t_end, dst_stride, 1);
-    HIP_TRY(hipGetLastError());
+        return launched();
+    });
+    if (rc) return rc;
     return gst == pl->stream ? note_gather(pl) : 0;
 }
 
@@ -1280,20 +1268,22 @@ int trmc_set_boundary_flow_range_indexed(trmc_plan *pl, int t_begin, int t_end, 
             HIP_TRY(hipStreamWaitEvent(st, pl->ev_ctl, 0));
         }
     }
+    int rc;
     if (pl->flow) {
         hipLaunchKernelGGL(k_flow_boundary, dim3(blocks_for(work)), dim3(kBlock), 0, st, (const float *)q_dev,
                            (unsigned long long *)pl->tm.p, (float *)pl->out.p, (const int32_t *)pl->sh->row_of_pos.p, (int32_t)nb,
                            r.nsteps, pl->nseg_pad, t_begin, t_end, src_stride, 1, 1, pl->tag_base, src_index_dev);
-    } else if (pl->precision == 32) {
-        float *q = (float *)pl->tm.p;
-        hipLaunchKernelGGL((k_fill_boundary_range<float>), dim3(blocks_for(work)), dim3(kBlock), 0, st, (const float *)q_dev,
-                           q, q + plane, q + 2 * plane, (int32_t)nb, pl->nseg_pad, t_begin, t_end, src_stride, src_index_dev);
+        rc = launched();
     } else {
-        double *q = (double *)pl->tm.p;
-        hipLaunchKernelGGL((k_fill_boundary_range<double>), dim3(blocks_for(work)), dim3(kBlock), 0, st, (const double *)q_dev,
-                           q, q + plane, q + 2 * plane, (int32_t)nb, pl->nseg_pad, t_begin, t_end, src_stride, src_index_dev);
+        rc = by_precision(pl, [&](auto t) {
+            using T = decltype(t);
+            T *q = (T *)pl->tm.p;
+            hipLaunchKernelGGL((k_fill_boundary_range<T>), dim3(blocks_for(work)), dim3(kBlock), 0, st, (const T *)q_dev, q, q + plane,
+                               q + 2 * plane, (int32_t)nb, pl->nseg_pad, t_begin, t_end, src_stride, src_index_dev);
+            return launched();
+        });
     }
-    HIP_TRY(hipGetLastError());
+    if (rc) return rc;
     r.boundary_through = t_end;
     return 0;
 }
@@ -1309,6 +1299,21 @@ int trmc_download_fvd(trmc_plan *pl, void *fvd_out)
     return 0;
 }
 
+// the common end of the two strided downloads: `nkeep` steps of `nrows` rows (the set's, or every row: rowset < 0), decimated into
+// the plan's scratch block for gathers of its result and copied to the host
+static int download_decimated(trmc_plan *pl, int stride, int32_t nkeep, int32_t rowset, int64_t nrows, void *fvd_out)
+{
+    if (!fvd_out) return fail(TRMC_EINVAL, "fvd_out is NULL");
+    if (int rc = use_device(pl)) return rc;
+    const size_t bytes = (size_t)nrows * nkeep * 3 * pl->esz;
+    if (int rc = pl->gathered.ensure(bytes)) return rc;
+    pl->gathered_bytes = 0;
+    if (int rc = decimate_out(pl, pl->gathered.p, pl->routed_nsteps, stride, nkeep, rowset)) return rc;
+    HIP_TRY(hipMemcpyAsync(fvd_out, pl->gathered.p, bytes, hipMemcpyDeviceToHost, pl->stream));
+    HIP_TRY(hipStreamSynchronize(pl->stream));
+    return 0;
+}
+
 int trmc_download_fvd_strided(trmc_plan *pl, int stride, void *fvd_out)
 {
     if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
@@ -1317,22 +1322,7 @@ int trmc_download_fvd_strided(trmc_plan *pl, int stride, void *fvd_out)
     if (stride == 1) return trmc_download_fvd(pl, fvd_out);
     const int32_t nkeep = pl->routed_nsteps / stride;
     if (pl->nseg == 0 || nkeep == 0) return 0;
-    if (!fvd_out) return fail(TRMC_EINVAL, "fvd_out is NULL");
-    if (int rc = use_device(pl)) return rc;
-    const size_t bytes = (size_t)pl->nseg * nkeep * 3 * pl->esz;
-    if (int rc = pl->gathered.ensure(bytes)) return rc; // (the plan's scratch block for gathers of its result)
-    pl->gathered_bytes = 0;
-    const int64_t work = pl->nseg * (int64_t)nkeep;
-    if (pl->precision == 32)
-        hipLaunchKernelGGL((k_decimate<float>), dim3(blocks_for(work)), dim3(kBlock), 0, pl->stream, (const float *)pl->out.p,
-                           (float *)pl->gathered.p, pl->nseg, pl->routed_nsteps, stride, nkeep);
-    else
-        hipLaunchKernelGGL((k_decimate<double>), dim3(blocks_for(work)), dim3(kBlock), 0, pl->stream, (const double *)pl->out.p,
-                           (double *)pl->gathered.p, pl->nseg, pl->routed_nsteps, stride, nkeep);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(fvd_out, pl->gathered.p, bytes, hipMemcpyDeviceToHost, pl->stream));
-    HIP_TRY(hipStreamSynchronize(pl->stream));
-    return 0;
+    return download_decimated(pl, stride, nkeep, -1, pl->nseg, fvd_out);
 }
 
 int trmc_download_fvd_rowset(trmc_plan *pl, int stride, int32_t rowset, void *fvd_out)
@@ -1344,23 +1334,7 @@ int trmc_download_fvd_rowset(trmc_plan *pl, int stride, int32_t rowset, void *fv
     const int64_t nrows = pl->rowset_n[(size_t)rowset];
     const int32_t nkeep = pl->routed_nsteps / stride;
     if (nrows == 0 || nkeep == 0) return 0;
-    if (!fvd_out) return fail(TRMC_EINVAL, "fvd_out is NULL");
-    if (int rc = use_device(pl)) return rc;
-    const size_t bytes = (size_t)nrows * nkeep * 3 * pl->esz;
-    if (int rc = pl->gathered.ensure(bytes)) return rc;
-    pl->gathered_bytes = 0;
-    const int64_t work = nrows * (int64_t)nkeep;
-    const int32_t *rp = (const int32_t *)pl->rowsets[(size_t)rowset].p, *rop = (const int32_t *)pl->sh->row_of_pos.p;
-    if (pl->precision == 32)
-        hipLaunchKernelGGL((k_decimate_rows<float>), dim3(blocks_for(work)), dim3(kBlock), 0, pl->stream, (const float *)pl->out.p,
-                           (float *)pl->gathered.p, rp, rop, nrows, pl->routed_nsteps, stride, nkeep);
-    else
-        hipLaunchKernelGGL((k_decimate_rows<double>), dim3(blocks_for(work)), dim3(kBlock), 0, pl->stream, (const double *)pl->out.p,
-                           (double *)pl->gathered.p, rp, rop, nrows, pl->routed_nsteps, stride, nkeep);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(fvd_out, pl->gathered.p, bytes, hipMemcpyDeviceToHost, pl->stream));
-    HIP_TRY(hipStreamSynchronize(pl->stream));
-    return 0;
+    return download_decimated(pl, stride, nkeep, rowset, nrows, fvd_out);
 }
 
 // ---- the per-row products of a FINISHED window: trmc_window_summary, _courant, _courant_summary, _exceedance
@@ -1714,9 +1688,7 @@ static int ensure_copy_stream(trmc_plan *pl)
     // (a stream per direction: a day's decimated result on its way out -- 0.8 GB for a CONUS day, most of a window -- does not
     // hold the next day's forcing back, which the plan's next set-up waits for)
     if (int rc = pl->hstream.ensure(hipStreamNonBlocking, prio_lo)) return rc;
-    for (DevEvent *e : {&pl->ev_fetch_ready, &pl->ev_fetch_done, &pl->ev_forcing})
-        if (int rc = e->ensure(false)) return rc;
-    return 0;
+    return pl->ev_fetch_ready.ensure(false);
 }
 
 int trmc_fetch_begin(trmc_plan *pl, int32_t rowset, void *hyd_host, void *q0_host)
@@ -1741,7 +1713,7 @@ int trmc_fetch_begin_fvd(trmc_plan *pl, int32_t rowset, void *hyd_host, void *q0
     } else if (pl->routed_nsteps < 0) {
         return fail(TRMC_ESTATE, "nothing routed yet");
     }
-    if (pl->fetch_pending) return fail(TRMC_ESTATE, "a fetch is in flight (trmc_fetch_wait it first)");
+    if (pl->mk_fetch_done.pending()) return fail(TRMC_ESTATE, "a fetch is in flight (trmc_fetch_wait it first)");
     if (hyd_host && (rowset < 0 || rowset >= (int32_t)pl->rowsets.size())) return fail(TRMC_EINVAL, "unknown row set");
     if (int rc = use_device(pl)) return rc;
     if (int rc = ensure_copy_stream(pl)) return rc;
@@ -1753,13 +1725,7 @@ int trmc_fetch_begin_fvd(trmc_plan *pl, int32_t rowset, void *hyd_host, void *q0
     const size_t hb = (size_t)nrows * T_ * pl->esz, qb = q0_host ? (size_t)pl->nseg * 3 * pl->esz : 0;
     if (hb) {
         if (int rc = pl->fetch_hyd.ensure(hb)) return rc;
-        if (pl->precision == 32)
-            hipLaunchKernelGGL((k_gather_rows<float>), dim3(blocks_for(nrows * T_)), dim3(kBlock), 0, pl->stream, (const float *)pl->tm.p,
-                               (const int32_t *)pl->rowsets[rowset].p, (float *)pl->fetch_hyd.p, nrows, pl->nseg_pad, T_, pl->flow ? 2 : 1);
-        else
-            hipLaunchKernelGGL((k_gather_rows<double>), dim3(blocks_for(nrows * T_)), dim3(kBlock), 0, pl->stream, (const double *)pl->tm.p,
-                               (const int32_t *)pl->rowsets[rowset].p, (double *)pl->fetch_hyd.p, nrows, pl->nseg_pad, T_, 1);
-        HIP_TRY(hipGetLastError());
+        if (int rc = gather_rows(pl, (const int32_t *)pl->rowsets[rowset].p, pl->fetch_hyd.p, nrows, T_)) return rc;
         if (int rc = note_gather(pl, in_window)) return rc;
     }
     if (qb) {
@@ -1786,29 +1752,20 @@ int trmc_fetch_begin_fvd(trmc_plan *pl, int32_t rowset, void *hyd_host, void *q0
     if (have_dec) {
         const int32_t lo = in_window ? pl->run.dec_lo : pl->dec_lo_done, hi = in_window ? pl->run.dec_hi : pl->dec_hi_done;
         const size_t plane = (size_t)(T_ + 1) * pl->nseg_pad;
-        if (pl->precision == 32) {
-            const float *q = (const float *)pl->tm.p;
-            hipLaunchKernelGGL((k_decimate_planes<float>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pl->stream, q, q + plane, q + 2 * plane,
-                               (const int32_t *)pl->sh->row_of_pos.p, (float *)pl->dec.p, (int32_t)pl->nseg, pl->nseg_pad, stride, nkeep, lo, hi);
-        } else {
-            const double *q = (const double *)pl->tm.p;
-            hipLaunchKernelGGL((k_decimate_planes<double>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pl->stream, q, q + plane, q + 2 * plane,
-                               (const int32_t *)pl->sh->row_of_pos.p, (double *)pl->dec.p, (int32_t)pl->nseg, pl->nseg_pad, stride, nkeep, lo, hi);
-        }
-        HIP_TRY(hipGetLastError());
+        const int rc = by_precision(pl, [&](auto t) {
+            using T = decltype(t);
+            const T *q = (const T *)pl->tm.p;
+            hipLaunchKernelGGL((k_decimate_planes<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pl->stream, q, q + plane, q + 2 * plane,
+                               (const int32_t *)pl->sh->row_of_pos.p, (T *)pl->dec.p, (int32_t)pl->nseg, pl->nseg_pad, stride, nkeep, lo, hi);
+            return launched();
+        });
+        if (rc) return rc;
         if (int rc = note_gather(pl, in_window)) return rc;
         fvd_src = pl->dec.p;
         from_dec = true;
     } else if (fb && stride > 1) {
         if (int rc = pl->fetch_fvd.ensure(fb)) return rc;
-        const int64_t work = pl->nseg * (int64_t)nkeep;
-        if (pl->precision == 32)
-            hipLaunchKernelGGL((k_decimate<float>), dim3(blocks_for(work)), dim3(kBlock), 0, pl->stream, (const float *)pl->out.p,
-                               (float *)pl->fetch_fvd.p, pl->nseg, T_, stride, nkeep);
-        else
-            hipLaunchKernelGGL((k_decimate<double>), dim3(blocks_for(work)), dim3(kBlock), 0, pl->stream, (const double *)pl->out.p,
-                               (double *)pl->fetch_fvd.p, pl->nseg, T_, stride, nkeep);
-        HIP_TRY(hipGetLastError());
+        if (int rc = decimate_out(pl, pl->fetch_fvd.p, T_, stride, nkeep, -1)) return rc;
         if (int rc = note_gather(pl, in_window)) return rc; // (the next window's set-up, wherever it is queued, goes behind it)
         fvd_src = pl->fetch_fvd.p;
     }
@@ -1828,25 +1785,18 @@ int trmc_fetch_begin_fvd(trmc_plan *pl, int32_t rowset, void *hyd_host, void *q0
         if (int rc = to_host(q0_host, pl->fetch_q0.p, qb)) return rc;
     if (fb) {
         if (int rc = to_host(fvd_host, fvd_src, fb)) return rc;
-        if (stride == 1 || from_dec) { // (copied from `out` / `dec` themselves: the plan's next window, which writes them, starts behind the copy)
-            if (int rc = pl->ev_dec.ensure(false)) return rc;
-            HIP_TRY(hipEventRecord(pl->ev_dec, pl->cstream));
-            pl->dec_pending = true;
-        }
+        if (stride == 1 || from_dec) // (copied from `out` / `dec` themselves: the plan's next window, which writes them, starts behind the copy)
+            if (int rc = pl->mk_dec.record(pl->cstream)) return rc;
     }
-    HIP_TRY(hipEventRecord(pl->ev_fetch_done, pl->cstream));
-    pl->fetch_pending = true;
-    return 0;
+    return pl->mk_fetch_done.record(pl->cstream);
 }
 
 int trmc_fetch_wait(trmc_plan *pl)
 {
     if (!pl) return fail(TRMC_EINVAL, "plan is NULL");
-    if (!pl->fetch_pending) return 0;
+    if (!pl->mk_fetch_done.pending()) return 0;
     if (int rc = use_device(pl)) return rc;
-    pl->fetch_pending = false;
-    HIP_TRY(hipEventSynchronize(pl->ev_fetch_done));
-    return 0;
+    return pl->mk_fetch_done.sync();
 }
 
 int trmc_gather_flow_rows(trmc_plan *pl, const int64_t *rows, int64_t nrows, void *out, int dst_is_device)
@@ -1872,14 +1822,7 @@ int trmc_gather_flow_rows(trmc_plan *pl, const int64_t *rows, int64_t nrows, voi
         pl->gathered_bytes = obytes;
     }
     void *dst = dst_is_device ? out : (void *)((char *)pl->scratch.p + pbytes);
-    if (pl->precision == 32)
-        hipLaunchKernelGGL((k_gather_rows<float>), dim3(blocks_for(nrows * T_)), dim3(kBlock), 0, pl->stream,
-                           (const float *)pl->tm.p, (const int32_t *)pl->scratch.p, (float *)dst, nrows, pl->nseg_pad, T_,
-                           pl->flow ? 2 : 1);
-    else
-        hipLaunchKernelGGL((k_gather_rows<double>), dim3(blocks_for(nrows * T_)), dim3(kBlock), 0, pl->stream,
-                           (const double *)pl->tm.p, (const int32_t *)pl->scratch.p, (double *)dst, nrows, pl->nseg_pad, T_, 1);
-    HIP_TRY(hipGetLastError());
+    if (int rc = gather_rows(pl, (const int32_t *)pl->scratch.p, dst, nrows, T_)) return rc;
     if (!dst_is_device) HIP_TRY(hipMemcpyAsync(out, dst, obytes, hipMemcpyDeviceToHost, pl->stream));
     HIP_TRY(hipStreamSynchronize(pl->stream));
     return 0;

@@ -1,12 +1,14 @@
-// dev_owner.hpp -- move-only owners of what the library holds on a device: a block of device memory, an event, a stream,
-// a block of page-locked host memory.  Copy is deleted, a move leaves the source empty, every destructor releases what the
-// object holds -- so a struct made of these frees itself, in the reverse of its members' declaration order.
+// dev_owner.hpp -- move-only owners of what the library holds on a device: a block of device memory, an event, an ordering
+// mark (an event and whether it is still to be waited for), a stream, a block of page-locked host memory.  Copy is deleted, a
+// move leaves the source empty, every destructor releases what the object holds -- so a struct made of these frees itself, in
+// the reverse of its members' declaration order.
 //
 // Nothing is #included here.  The includer brings, in front of this file:
 //   - the HIP runtime (<hip/hip_runtime.h>) -- or, a host-only test, stand-ins for the names used below: hipError_t, hipSuccess,
 //     hipErrorOutOfMemory, hipGetErrorString, hipEvent_t, hipStream_t, hipEventDisableTiming, hipHostMallocDefault, hipMalloc,
-//     hipFree, hipMemset, hipStreamSynchronize, hipEventCreate, hipEventCreateWithFlags, hipEventDestroy,
-//     hipStreamCreateWithFlags, hipStreamCreateWithPriority, hipStreamDestroy, hipHostMalloc, hipHostFree;
+//     hipFree, hipMemset, hipStreamSynchronize, hipEventCreate, hipEventCreateWithFlags, hipEventDestroy, hipEventRecord,
+//     hipStreamWaitEvent, hipEventSynchronize, hipStreamCreateWithFlags, hipStreamCreateWithPriority, hipStreamDestroy,
+//     hipHostMalloc, hipHostFree;
 //   - <string>, <utility>, include/trmc.h (TRMC_ENOMEM, TRMC_EHIP);
 //   - int fail(int code, const std::string &msg): stores the message where the caller's last-error lives, returns the code.
 #pragma once
@@ -86,6 +88,47 @@ struct DevEvent { // an event, made on first use; reads as the hipEvent_t it hol
     {
         if (e) (void)hipEventDestroy(e);
         e = nullptr;
+    }
+};
+
+// An ordering mark: an event that only orders streams, with whether anything recorded on it is still to be waited for.  The
+// producer record()s it on its stream; a consumer order()s each stream that has to go behind it and then settle()s it -- apart,
+// because one mark may hold several streams back -- or, on the host, sync()s.  Not pending, order() and sync() call nothing.
+struct DevMark {
+    DevMark() = default;
+    DevMark(DevMark &&o) noexcept : ev(std::move(o.ev)), waiting(std::exchange(o.waiting, false)) {}
+    DevMark &operator=(DevMark &&o) noexcept
+    {
+        if (this != &o) {
+            ev = std::move(o.ev);
+            waiting = std::exchange(o.waiting, false);
+        }
+        return *this;
+    }
+    int record(hipStream_t st) // made on first use
+    {
+        if (int rc = ev.ensure(false)) return rc;
+        if (int rc = tried(hipEventRecord(ev, st), "hipEventRecord: ")) return rc;
+        waiting = true;
+        return 0;
+    }
+    int order(hipStream_t st) const { return waiting ? tried(hipStreamWaitEvent(st, ev, 0), "hipStreamWaitEvent: ") : 0; }
+    void settle() { waiting = false; }
+    int sync() // (settled first: a wait that fails is not tried again)
+    {
+        if (!waiting) return 0;
+        waiting = false;
+        return tried(hipEventSynchronize(ev), "hipEventSynchronize: ");
+    }
+    bool pending() const { return waiting; }
+
+private:
+    DevEvent ev;
+    bool waiting = false;
+    static int tried(hipError_t rc, const char *what)
+    {
+        if (rc == hipSuccess) return 0;
+        return fail(rc == hipErrorOutOfMemory ? TRMC_ENOMEM : TRMC_EHIP, std::string(what) + hipGetErrorString(rc));
     }
 };
 

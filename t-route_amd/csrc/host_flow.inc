@@ -190,15 +190,12 @@ int flow_route_begin(trmc_plan *pl, int nsteps, int qts, int short_ts)
     const int32_t *row_of_pos = (const int32_t *)pl->sh->row_of_pos.p;
     HIP_TRY(hipEventRecord(pl->ev[0], st));
     pl->q0_staged = false; // (consumed by this window)
-    if (pl->dec_pending) { // (trmc_fetch_begin_fvd: the copy stream reads `out`)
-        HIP_TRY(hipStreamWaitEvent(st, pl->ev_dec, 0));
-        if (pl->fstream) HIP_TRY(hipStreamWaitEvent(pl->fstream, pl->ev_dec, 0));
-        pl->dec_pending = false;
-    }
-    if (pl->forcing_pending) { // (trmc_stage_forcing: the copy into in_qlat runs on the copy stream)
-        HIP_TRY(hipStreamWaitEvent(st, pl->ev_forcing, 0));
-        pl->forcing_pending = false;
-    }
+    if (int rc = pl->mk_dec.order(st)) return rc; // (trmc_fetch_begin_fvd: the copy stream reads `out`)
+    if (pl->fstream)
+        if (int rc = pl->mk_dec.order(pl->fstream)) return rc;
+    pl->mk_dec.settle();
+    if (int rc = pl->mk_forcing.order(st)) return rc; // (trmc_stage_forcing: the copy into in_qlat runs on the copy stream)
+    pl->mk_forcing.settle();
     HIP_TRY(hipMemsetAsync(pl->it_prev.p, 0, (size_t)np, st));
     HIP_TRY(hipMemsetAsync(pl->ticket.p, 0, 16 * sizeof(int32_t), st));
     pl->flow_next = pl->flow_last = 0;

@@ -53,8 +53,16 @@ int use_device(const trmc_plan *pl)
     return 0;
 }
 
+inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+
 // f(T()) with T the plan's element type
 template <class F> inline int by_precision(const trmc_plan *pl, F &&f) { return pl->precision == 32 ? f(float()) : f(double()); }
+// ... whose body is one launch: what it returns behind it
+inline int launched()
+{
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
 
 // `v` grown to n events: ones that time (hipEventCreate) or ones that only order streams (hipEventDisableTiming)
 inline int ensure_events(std::vector<DevEvent> &v, size_t n, bool timing)
@@ -79,10 +87,47 @@ inline int ensure_tile_stream(trmc_plan *pl)
 int note_gather(trmc_plan *pl, bool also_in_window = false)
 {
     if (pl->run.active && !also_in_window) return 0;
-    if (int rc = pl->ev_gather.ensure(false)) return rc;
-    HIP_TRY(hipEventRecord(pl->ev_gather, pl->stream));
-    pl->gather_pending = true;
-    return 0;
+    return pl->mk_gather.record(pl->stream);
+}
+
+// ---- the utility kernels with more than one caller: each launched here alone, in the plan's precision, on the plan's stream
+
+// NaN -> 0 in the `n` elements of a freshly uploaded block (trmc_plan_set_nan_is_zero)
+int nan_to_zero(trmc_plan *pl, void *buf, int64_t n)
+{
+    return by_precision(pl, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_nan_to_zero<T>), dim3(blocks_for(n)), dim3(kBlock), 0, pl->stream, (T *)buf, n);
+        return launched();
+    });
+}
+
+// every stride-th step of `out`, the result of a window of T_ steps, into dst[row][nkeep][3]: of every row, or (rowset >= 0) of
+// the rows of a registered set in the set's order
+int decimate_out(trmc_plan *pl, void *dst, int32_t T_, int32_t stride, int32_t nkeep, int32_t rowset)
+{
+    return by_precision(pl, [&](auto t) {
+        using T = decltype(t);
+        const int64_t nrows = rowset < 0 ? pl->nseg : pl->rowset_n[(size_t)rowset];
+        const dim3 grid(blocks_for(nrows * (int64_t)nkeep)), block(kBlock);
+        if (rowset < 0)
+            hipLaunchKernelGGL((k_decimate<T>), grid, block, 0, pl->stream, (const T *)pl->out.p, (T *)dst, nrows, T_, stride, nkeep);
+        else
+            hipLaunchKernelGGL((k_decimate_rows<T>), grid, block, 0, pl->stream, (const T *)pl->out.p, (T *)dst,
+                               (const int32_t *)pl->rowsets[(size_t)rowset].p, (const int32_t *)pl->sh->row_of_pos.p, nrows, T_, stride, nkeep);
+        return launched();
+    });
+}
+
+// the flow hydrographs of `nrows` plan positions (on the device) over the T_ steps of the time-major planes, into dst[nrows][T_]
+int gather_rows(trmc_plan *pl, const int32_t *positions_dev, void *dst, int64_t nrows, int32_t T_)
+{
+    return by_precision(pl, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_gather_rows<T>), dim3(blocks_for(nrows * T_)), dim3(kBlock), 0, pl->stream, (const T *)pl->tm.p, positions_dev,
+                           (T *)dst, nrows, pl->nseg_pad, T_, pl->flow ? 2 : 1); // (the dataflow engine's plane holds granules of two)
+        return launched();
+    });
 }
 
 // diagnosis: slot `which` (0 tiles begin, 1 tiles end, 2 tail begins, 3 window ends) of the current window's stamps
@@ -158,7 +203,6 @@ template <class T> StepArgs<T> step_args(trmc_plan *pl, int nsteps, int qts)
     return a;
 }
 
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 // rows of the hot list per wavefront of the blocks that route it (trmc_plan_options.hot_wave_rows)
 // (fewer per wavefront -- so that a wavefront less often holds a row of five or six iterations -- was measured on the ranks of an
 // 8-way CONUS partition, ms per day: 64: 2.70, 32: 2.82, 16: 3.03, 8: 2.86 -- more wavefronts of that cost, not a shorter chain)
@@ -358,12 +402,12 @@ template <class T> int route_begin_t(trmc_plan *pl, int nsteps, int qts, int sho
     const int32_t ntiles = (nsteps + kTile - 1) / kTile;
     if (int rc = ensure_events(pl->tile_ev, (size_t)std::max(0, ntiles), false)) return rc;
 
-    for (int i = 0; i < 2; ++i) // a receiver of this plan's last window (trmc_plan_chain_from) has read what this window overwrites
-        if (pl->released_pending[i]) {
-            HIP_TRY(hipStreamWaitEvent(st, pl->ev_released[i], 0));
-            if (pl->wstream) HIP_TRY(hipStreamWaitEvent(pl->wstream, pl->ev_released[i], 0));
-            pl->released_pending[i] = false;
-        }
+    for (DevMark &m : pl->mk_released) { // a receiver of this plan's last window (trmc_plan_chain_from) has read what this window overwrites
+        if (int rc = m.order(st)) return rc;
+        if (pl->wstream)
+            if (int rc = m.order(pl->wstream)) return rc;
+        m.settle();
+    }
     HIP_TRY(hipEventRecord(pl->ev[0], st));
     // Sequence mode (trmc_plan_options.sequence_mode): the window's set-up (forcing transpose, initial state, boundary rows)
     // goes to the TILE stream instead of the plan's own.  For one plan it is all the same; for two plans that take turns on a device (two ensemble
@@ -379,17 +423,13 @@ template <class T> int route_begin_t(trmc_plan *pl, int nsteps, int qts, int sho
         // final state) read planes this window's tiles overwrite: the set-up goes behind the last of them (an event
         // recorded when that gather was queued -- not ev[0] above, which sits behind whatever another plan has put into
         // the shared high-priority queue since)
-        if (pl->gather_pending) HIP_TRY(hipStreamWaitEvent(st, pl->ev_gather, 0));
+        if (int rc = pl->mk_gather.order(st)) return rc;
     }
-    pl->gather_pending = false;
-    if (pl->dec_pending) { // (trmc_fetch_begin_fvd: the copy stream reads `out`, which this window's kernels overwrite)
-        HIP_TRY(hipStreamWaitEvent(st, pl->ev_dec, 0));
-        pl->dec_pending = false;
-    }
-    if (pl->forcing_pending) { // (trmc_stage_forcing: the copy into in_qlat runs on the copy stream)
-        HIP_TRY(hipStreamWaitEvent(st, pl->ev_forcing, 0));
-        pl->forcing_pending = false;
-    }
+    pl->mk_gather.settle(); // (on the plan's own stream the set-up is behind them as it is)
+    if (int rc = pl->mk_dec.order(st)) return rc; // (trmc_fetch_begin_fvd: the copy stream reads `out`, which this window's kernels overwrite)
+    pl->mk_dec.settle();
+    if (int rc = pl->mk_forcing.order(st)) return rc; // (trmc_stage_forcing: the copy into in_qlat runs on the copy stream)
+    pl->mk_forcing.settle();
     HIP_TRY(hipMemsetAsync(pl->it_prev.p, 0, (size_t)np, st)); // no history at the start of a window
     if (pl->collect_cost) HIP_TRY(hipMemsetAsync(pl->it_sum.p, 0, (size_t)np * sizeof(uint16_t), st));
     // every element the result reads is written below: time row 0 by k_init_state, rows 1..nsteps

@@ -132,9 +132,7 @@ template <class T> int chain_from_t(trmc_plan *dst, trmc_plan *src, int nsteps_d
         // has ended, so the receiver's leading levels started after the source's whole window instead of behind its last
         // tile (the timeline of bench.py's sequence showed exactly that).  The source takes the events (its own objects)
         // and waits for them at its next trmc_route_begin -- a window later, when they have long fired.
-        if (int rc = src->ev_released[0].ensure(false)) return rc;
-        HIP_TRY(hipEventRecord(src->ev_released[0], dst->wstream));
-        src->released_pending[0] = true;
+        if (int rc = src->mk_released[0].record(dst->wstream)) return rc;
         // ... and the receiver's own stream does not read time row 0 of the wide rows before this copy has written it: its
         // tail's first launch (step 1) takes no tile wait and reads q_tm[0] of its upstream wide rows
         HIP_TRY(hipStreamWaitEvent(dst->stream, dst->ev_chain[2], 0));
@@ -146,9 +144,7 @@ template <class T> int chain_from_t(trmc_plan *dst, trmc_plan *src, int nsteps_d
     // (rows routed by cluster tiles wrote no velocity row either)
     if (s1 > m1) hipLaunchKernelGGL((k_chain_state<T>), dim3(blocks_for(s1 - m1)), dim3(kBlock), 0, dst->stream, sq, src->run.cl ? sq : sv, sd, dq, dv, dd, m1, s1);
     HIP_TRY(hipEventRecord(dst->ev_chain[3], dst->stream));
-    if (int rc = src->ev_released[1].ensure(false)) return rc;
-    HIP_TRY(hipEventRecord(src->ev_released[1], dst->stream));
-    src->released_pending[1] = true;
+    if (int rc = src->mk_released[1].record(dst->stream)) return rc;
     HIP_TRY(hipGetLastError());
     dst->chain_staged = true;
     return 0;

@@ -120,7 +120,9 @@ struct StreamProd {
 // last, behind the buffers (hipFree waits for the device).  The plan destroys this before anything of its own.
 struct StreamRun {
     DevStream fst;                      // the forcing's own stream (H2D + its reordering; the products leave on the plan's copy stream)
-    DevEvent ev_begin, ev_bnd, ev_gat;
+    DevEvent ev_begin, ev_gat;
+    DevMark mk_bnd;                     // "the boundary rows of the day are in its slot" (trmc_stream_boundary, on a stream of the
+                                        // caller's): the next push's forcing stream, or the next launches, go behind it
     DevEvent ev_total;                  // (the totals over the days) the last fold queued is through
     DevEvent ev_exc;                    // (the exceedance over the days) likewise
     std::vector<DevEvent> ev_slab;      // ring: "slab launch g is complete" (the cluster launch g + 1 waits for it)
@@ -177,7 +179,6 @@ struct StreamRun {
     int32_t exc_want = -1, exc = -1, exc_K = 0, exc_KP = 0;
     DevBuf exc_acc, exc_rows;
     int64_t exc_days = 0;
-    bool bnd_pending = false;
 };
 
 } // extern "C++"
@@ -677,18 +678,16 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
         p.day = -1;
         p.queued = false;
     }
-    for (DevEvent *e : {&S.ev_begin, &S.ev_bnd, &S.ev_gat})
+    for (DevEvent *e : {&S.ev_begin, &S.ev_gat})
         if (int rc = e->ensure(false)) return rc;
-    S.bnd_pending = false;
+    S.mk_bnd.settle();
     S.days_pushed = S.day_min = S.days_complete = 0;
     S.g_done = -1;
     S.launches = 0;
     // the state every row starts from: time row 0 of slot 0 (trmc_upload_forcing's q0, or the last window's final state)
     hipStream_t st = pl->stream;
-    if (pl->forcing_pending) {
-        HIP_TRY(hipStreamWaitEvent(st, pl->ev_forcing, 0));
-        pl->forcing_pending = false;
-    }
+    if (int rc = pl->mk_forcing.order(st)) return rc;
+    pl->mk_forcing.settle();
     HIP_TRY(hipMemsetAsync(pl->it_prev.p, 0, (size_t)np, st));
     if (S.exc >= 0 && exc_bytes > 0) HIP_TRY(hipMemsetAsync(S.exc_acc.p, 0, exc_bytes, st));
     if (pl->collect_cost) {
@@ -790,10 +789,8 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
         stream_rda_image(pl, S, *day.reservoir_da, img);
         HIP_TRY(hipMemcpyAsync((char *)S.rda_tab.p + (size_t)slot * S.slot_rda, img, S.slot_rda, hipMemcpyHostToDevice, hst));
     }
-    if (S.bnd_pending) { // (trmc_stream_boundary on a stream of the caller's: this day's launches go behind it)
-        HIP_TRY(hipStreamWaitEvent(hst, S.ev_bnd, 0));
-        S.bnd_pending = false;
-    }
+    if (int rc = S.mk_bnd.order(hst)) return rc; // (trmc_stream_boundary on a stream of the caller's: this day's launches go behind it)
+    S.mk_bnd.settle();
     if (tp.nboundary > 0 && boundary_q_dev) {
         // boundary rows: their flows of the day [nboundary][nsteps] into the slot's plane; time row 0 = where the day before ended
         T *q = (T *)S.tm.p + (size_t)slot * S.slot_tm;
@@ -1171,9 +1168,7 @@ int trmc_stream_boundary(trmc_plan *pl, int64_t day, const void *q_dev, int64_t 
         return 0;
     });
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(S.ev_bnd, st));
-    S.bnd_pending = true;
-    return 0;
+    return S.mk_bnd.record(st);
 }
 
 int trmc_stream_gather(trmc_plan *pl, int64_t day, int32_t rowset, void *dst_dev, void *stream)
@@ -1221,11 +1216,10 @@ int trmc_stream_advance(trmc_plan *pl, int ntiles)
     const int64_t g_to = std::min<int64_t>(g_last, g_from + ntiles);
     int rc = 0;
     if (S.days_complete < S.days_pushed && g_to > g_from) {
-        if (S.bnd_pending) { // (trmc_stream_boundary on a stream of the caller's: these launches go behind it)
-            HIP_TRY(hipStreamWaitEvent(pl->wstream, S.ev_bnd, 0));
-            HIP_TRY(hipStreamWaitEvent(pl->stream, S.ev_bnd, 0));
-            S.bnd_pending = false;
-        }
+        // (trmc_stream_boundary on a stream of the caller's: these launches go behind it)
+        if (int rc = S.mk_bnd.order(pl->wstream)) return rc;
+        if (int rc = S.mk_bnd.order(pl->stream)) return rc;
+        S.mk_bnd.settle();
         rc = by_precision(pl, [&](auto t) { return stream_launch<decltype(t)>(pl, S, g_from, g_to, S.days_pushed); });
     }
     if (!rc && S.days_complete >= S.days_pushed) S.day_min = S.days_pushed; // (what follows starts with a new day; the rows' tiles of earlier days are done)

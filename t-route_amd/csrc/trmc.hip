@@ -170,23 +170,26 @@ struct trmc_plan {
     std::vector<DevEvent> tile_ev;       // "time tile b is complete" (main stream -> stream2)
     DevEvent ev_emit;                    // "all tiles emitted" (stream2 -> main stream)
     DevEvent ev_chain[4];                // trmc_plan_chain_from: source's tiles / tail done; this plan's two copies done
-    // as the SOURCE of a hand-over: "the receiver has read my planes" (its two copies), waited for at my next trmc_route_begin
-    DevEvent ev_released[2];
+    // as the SOURCE of a hand-over (trmc_plan_chain_from): "the receiver has read my planes" (its two copies); my next window's
+    // set-up and tiles go behind both
+    DevMark mk_released[2];
     DevStream fstream;                   // dataflow engine, second compute stream: consecutive time chunks of a resident window overlap
     DevEvent ev_chunk[2];                // the last launch queued on {stream, fstream}
     DevEvent ev_ctl;                     // ordering of the two compute streams against each other
-    DevEvent ev_dec;                     // "the copy stream has read `out`" (a fetch of the decimated result): the next window's
-                                         // set-up goes behind it (dec_pending)
+    DevMark mk_dec;                      // "the copy stream has read `out`" / `dec` (a fetch that copies from them, trmc_fetch_begin_fvd):
+                                         // the next window's set-up, which lets its kernels overwrite them, goes behind it
     DevStream cstream;                   // copy stream: D2H of window k runs beside the kernels of window k + 1
     DevStream hstream;                   // ... and the one of the other direction: a staged forcing on its way to the device
-    DevEvent ev_fetch_ready, ev_fetch_done;
+    DevEvent ev_fetch_ready;             // "the gathers of a fetch are through" (plan stream -> copy stream)
+    DevMark mk_fetch_done;               // "the copies of the fetch in flight have reached the host": trmc_fetch_wait waits for it
     // "the last gather queued on the plan's stream after a window has read the planes" -- what a set-up queued on ANOTHER stream
     // (TRMC_SETUP_ASIDE) waits for before it lets a new window's tiles overwrite them
-    DevEvent ev_gather;
+    DevMark mk_gather;
     KernelTimer t_wsum;                  // the last trmc_window_summary's kernel (trmc_window_summary_kernel_ms)
     KernelTimer t_cour;                  // ... the last trmc_window_courant / _summary's (trmc_window_courant_kernel_ms)
     KernelTimer t_wexc;                  // ... and the last trmc_window_exceedance's (trmc_window_exceedance_kernel_ms): each reports alone
-    DevEvent ev_forcing;                 // trmc_stage_forcing: the next window's forcing is on its way to in_qlat on the copy stream
+    DevMark mk_forcing;                  // "the staged forcing is in in_qlat" (trmc_stage_forcing: the copy, and in sequence mode its
+                                         // transpose, on the forcing's copy stream): the next window's set-up goes behind it
     // trmc_plan_clone: a second set of WINDOW buffers on the static data of the plan it was made from
     std::shared_ptr<PlanShared> sh;
     bool is_clone = false;               // for its whole life, whoever else still holds `sh` (trmc_plan_set_lag)
@@ -206,7 +209,6 @@ struct trmc_plan {
     int64_t wide_safe_pos = -1;          // first plan position that is lagged or fed by a boundary row (-1: not looked for yet)
     // trmc_plan_chain_from: the next window's initial state has been set on the device from another plan's window
     bool chain_staged = false;
-    bool released_pending[2] = {false, false}; // (ev_released)
     std::vector<int32_t> lag_of_row;
     DevBuf gage_of_pos, da_mode, da_a, da_w, da_nudge; // nudging tables of the staged window
     DevBuf res_of_pos, res_par, res_inflow;             // level-pool reservoirs of the plan
@@ -275,12 +277,8 @@ struct trmc_plan {
     int32_t nstamp_windows = 0;
     int64_t stamp_seq = -1;               // windows begun since the ring was set, minus one
     DevBuf fetch_hyd, fetch_q0, fetch_fvd;
-    bool dec_pending = false;            // (ev_dec)
-    bool fetch_pending = false;
-    bool gather_pending = false;         // (ev_gather)
     bool row0_replaced = false;          // trmc_plan_chain_from has overwritten time row 0 -- the last window's initial state -- since it ended
-    bool forcing_pending = false;        // (ev_forcing)
-    bool state_missing = false;          // ... and there is no initial state yet: trmc_plan_chain_from must supply it
+    bool state_missing = false;          // a forcing is staged and there is no initial state yet: trmc_plan_chain_from must supply it
     bool q0_staged = false;              // in_q0 holds the initial state of the window that is staged (an upload's q0, or the last
                                          // window's final state gathered by an upload with q0 = NULL / trmc_stage_forcing): valid
                                          // until a window consumes it, whatever routed_nsteps says in the meantime

@@ -60,6 +60,41 @@ static hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned flags)
     return hand_out((void **)e);
 }
 static hipError_t hipEventDestroy(hipEvent_t e) { return take_back(e, "hipEventDestroy"); }
+// the three calls of an ordering mark: counted, each remembering the event (and stream) of its last call; an event that is not
+// live aborts
+static int g_records = 0, g_waits = 0, g_event_syncs = 0;
+static std::vector<std::pair<hipEvent_t, hipStream_t>> g_recorded, g_waited; // (event, stream) of every call, in order
+static hipEvent_t g_synced = nullptr;
+static bool g_sync_fails = false; // the next hipEventSynchronize fails
+static void live_event(hipEvent_t e, const char *what)
+{
+    if (!g_live.count(e)) {
+        std::fprintf(stderr, "%s: on an event that does not exist\n", what);
+        std::abort();
+    }
+}
+static hipError_t hipEventRecord(hipEvent_t e, hipStream_t s)
+{
+    live_event(e, "hipEventRecord");
+    ++g_records;
+    g_recorded.emplace_back(e, s);
+    return hipSuccess;
+}
+static hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned flags)
+{
+    live_event(e, "hipStreamWaitEvent");
+    if (flags != 0) std::abort();
+    ++g_waits;
+    g_waited.emplace_back(e, s);
+    return hipSuccess;
+}
+static hipError_t hipEventSynchronize(hipEvent_t e)
+{
+    live_event(e, "hipEventSynchronize");
+    ++g_event_syncs;
+    g_synced = e;
+    return std::exchange(g_sync_fails, false) ? hipErrorUnknown : hipSuccess;
+}
 static hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { return hand_out((void **)s); }
 static hipError_t hipStreamCreateWithPriority(hipStream_t *s, unsigned, int) { return hand_out((void **)s); }
 static hipError_t hipStreamDestroy(hipStream_t s) { return take_back(s, "hipStreamDestroy"); }
@@ -262,15 +297,134 @@ static void shared_block()
     CHECK(orders == 6);
 }
 
+// ---- DevMark: an event that orders streams and whether it is still to be waited for
+static hipStream_t stream_no(int k) // (distinct addresses; never dereferenced)
+{
+    static char s[4];
+    return (hipStream_t)(void *)&s[k];
+}
+static std::pair<hipEvent_t, hipStream_t> on(hipEvent_t e, hipStream_t s) { return {e, s}; }
+
+static void mark_orders_two_streams()
+{
+    const hipStream_t a = stream_no(0), b = stream_no(1), c = stream_no(2);
+    DevMark m;
+    CHECK(!m.pending());
+    CHECK(m.record(a) == 0 && m.pending() && g_records == 1 && g_ordering == 1 && g_timing == 0); // (an event that only orders)
+    const hipEvent_t e = g_recorded.back().first;
+    CHECK(g_recorded.back() == on(e, a));
+    CHECK(m.order(b) == 0 && m.order(c) == 0 && m.pending()); // ordering a stream does not settle the mark: the next stream waits too
+    CHECK(g_waits == 2 && g_waited[0] == on(e, b) && g_waited[1] == on(e, c));
+    m.settle();
+    CHECK(!m.pending() && m.order(b) == 0 && g_waits == 2 && g_records == 1);
+}
+
+static void mark_idle_calls_nothing()
+{
+    const hipStream_t a = stream_no(0);
+    DevMark m;
+    CHECK(m.order(a) == 0 && m.sync() == 0 && !m.pending()); // never recorded: there is not even an event
+    CHECK(g_made == 0 && g_waits == 0 && g_event_syncs == 0);
+    CHECK(m.record(a) == 0);
+    m.settle();
+    CHECK(m.order(a) == 0 && m.sync() == 0 && g_waits == 0 && g_event_syncs == 0); // settled: the same
+    CHECK(m.record(a) == 0 && m.sync() == 0 && !m.pending() && g_event_syncs == 1 && g_synced == g_recorded.back().first);
+    CHECK(m.sync() == 0 && m.order(a) == 0 && g_event_syncs == 1 && g_waits == 0); // a sync settles
+}
+
+static void mark_sync_that_fails_settles()
+{
+    DevMark m;
+    CHECK(m.record(stream_no(0)) == 0);
+    g_sync_fails = true;
+    CHECK(m.sync() == TRMC_EHIP && !m.pending() && g_event_syncs == 1 && g_err.find("hipEventSynchronize") == 0);
+    CHECK(m.sync() == 0 && g_event_syncs == 1); // (not tried again)
+}
+
+static void mark_without_an_event()
+{
+    DevMark m;
+    g_oom = true;
+    CHECK(m.record(stream_no(0)) == TRMC_ENOMEM && !m.pending() && g_records == 0 && g_made == 0 && g_live.empty());
+    CHECK(g_err.find("hipEventCreateWithFlags") == 0);
+    CHECK(m.order(stream_no(1)) == 0 && m.sync() == 0 && g_waits == 0 && g_event_syncs == 0);
+    CHECK(m.record(stream_no(0)) == 0 && m.pending() && g_made == 1); // ... and usable afterwards
+}
+
+static void mark_moves()
+{
+    const hipStream_t a = stream_no(0), b = stream_no(1);
+    DevMark m;
+    CHECK(m.record(a) == 0);
+    const hipEvent_t e = g_recorded.back().first;
+    DevMark n(std::move(m)); // move-construct: the source is left with nothing, pending or to free
+    CHECK(n.pending() && !m.pending() && m.order(b) == 0 && m.sync() == 0 && g_waits == 0 && g_event_syncs == 0);
+    CHECK(n.order(b) == 0 && g_waited.back() == on(e, b));
+    DevMark o;
+    CHECK(o.record(a) == 0);
+    const hipEvent_t eo = g_recorded.back().first;
+    o = std::move(n); // move-assign onto a mark with an event: that event goes, once
+    CHECK(eo != e && !g_live.count(eo) && g_released == 1 && o.pending() && !n.pending());
+    CHECK(o.order(a) == 0 && g_waited.back() == on(e, a));
+    DevMark &self = o;
+    o = std::move(self); // self-move: harmless
+    CHECK(o.pending() && o.order(b) == 0 && g_waited.back() == on(e, b) && g_released == 1);
+    o.settle();
+    n = std::move(o); // a settled one: the event moves, nothing is pending on either side
+    CHECK(!n.pending() && !o.pending() && g_live.count(e) && g_released == 1);
+    std::vector<DevMark> marks;
+    std::vector<hipEvent_t> evs;
+    size_t reallocations = 0;
+    for (int i = 0; i < 40; ++i) {
+        const size_t cap = marks.capacity();
+        DevMark k;
+        if (i % 2 == 0) { // every other one pending when it moves in
+            CHECK(k.record(a) == 0);
+            evs.push_back(g_recorded.back().first);
+        }
+        marks.push_back(std::move(k));
+        reallocations += marks.capacity() != cap;
+    }
+    CHECK(reallocations >= 3 && g_made == 2 + 20 && g_released == 1);
+    for (int i = 0; i < 40; ++i) {
+        const int waits = g_waits;
+        CHECK(marks[(size_t)i].pending() == (i % 2 == 0) && marks[(size_t)i].order(b) == 0 && g_waits == waits + (i % 2 == 0));
+        if (i % 2 == 0) CHECK(g_waited.back() == on(evs[(size_t)i / 2], b)); // each with its own event
+    }
+    marks.clear();
+    CHECK(g_released == 1 + 20);
+}
+
+static void mark_event_made_once()
+{
+    {
+        DevMark m;
+        hipEvent_t e = nullptr;
+        for (int i = 0; i < 5; ++i) {
+            CHECK(m.record(stream_no(i % 3)) == 0 && m.pending());
+            if (i == 0) e = g_recorded.back().first;
+            CHECK(g_recorded.back() == on(e, stream_no(i % 3)));
+            if (i % 2) m.settle(); // (recorded again while pending, and after it has been settled)
+        }
+        CHECK(g_records == 5 && g_ordering == 1 && g_made == 1 && g_released == 0);
+    }
+    CHECK(g_made == 1 && g_released == 1);
+}
+
 int main()
 {
     const struct { const char *name; void (*run)(); } cases[] = {
         {"ensure grows", ensure_grows}, {"ensure fails", ensure_fails}, {"moves", moves}, {"vectors", vectors}, {"swap", swaps},
         {"early return", early_return}, {"event made once", event_made_once}, {"shared block", shared_block},
+        {"mark orders", mark_orders_two_streams}, {"mark idle", mark_idle_calls_nothing}, {"mark sync fails", mark_sync_that_fails_settles},
+        {"mark no event", mark_without_an_event}, {"mark moves", mark_moves}, {"mark made once", mark_event_made_once},
     };
     for (const auto &c : cases) {
-        g_made = g_released = g_timing = g_ordering = g_memsets = g_syncs = 0;
-        g_oom = false;
+        g_made = g_released = g_timing = g_ordering = g_memsets = g_syncs = g_records = g_waits = g_event_syncs = 0;
+        g_oom = g_sync_fails = false;
+        g_recorded.clear();
+        g_waited.clear();
+        g_synced = nullptr;
         const int bad = g_bad;
         c.run();
         if (!g_live.empty()) {
