@@ -342,9 +342,12 @@ int trmc_stream_push_day(trmc_plan *plan, const trmc_stream_day *day);
  * handed over, whether or not the day's own arrays go to the host (no trmc_stream_summary_dest: nothing of the summary crosses
  * to the host but the totals).  All of them fold the per-day products:
  *   peak_flow, peak_step (int64, 1-based from the stream's first step): day 0's values; then for day D >= 1 (0-based)
- *                      `if (pk_D > pk) { pk = pk_D; step = D * nsteps + st_D; }`
+ *                      `if (pk_D > pk) { pk = pk_D; step = D * nsteps + st_D; }` -- the first of equal day peaks wins, a NaN
+ *                      day peak after day 0 never replaces (the totals keep the earlier days'), a NaN on day 0 stays (with
+ *                      step 1: the peak rule's own NaN at step 1), so np.maximum over the days' peaks is this fold only
+ *                      while no day's peak is a NaN
  *   peak_depth, peak_depth_step (int64): the same fold, with TRMC_SUMMARY_PEAK_DEPTH
- *   mean_flow          (((m_0 + m_1) + m_2) + ...) / T(ndays) in the plan's precision, left to right
+ *   mean_flow          (((m_0 + m_1) + m_2) + ...) / T(ndays) in the plan's precision, left to right (NaN where any day's mean is)
  *   trmc_stream_summary_total  HOST arrays [nseg] (any may be NULL); synchronous: returns when the totals of all days handed over
  *                      so far are on the host and writes that number of days to days_out.  TRMC_ESTATE when no stream is in
  *                      progress, when it was begun without TRMC_SUMMARY_TOTAL or when no day is complete yet; TRMC_EINVAL for an

@@ -434,7 +434,9 @@ class RouteStream:
     of the others) keeps the maximum and the mean of the whole forecast on the device: ``rs.total`` holds
     ``RoutingPlan.stream_summary_total()`` -- ``"days"`` and the same keys over this rank's ``rows``, the steps int64 and 1-based
     from the stream's first step -- once ``route()`` has yielded its last day; ``daily_summary=False`` then leaves the per-day
-    dict out (the tuples of ``summary=None``) and no per-day summary array crosses to the host.
+    dict out (the tuples of ``summary=None``) and no per-day summary array crosses to the host.  ``np.maximum`` over the days'
+    ``peak_flow`` equals ``rs.total["peak_flow"]`` only while no day's peak is a NaN: the totals fold ``if (pk_D > pk)``, which a
+    NaN day after day 0 never wins and a NaN on day 0 never loses (``np.fmax``, or the fold itself, otherwise).
 
     ``exceedance=("flow", thresholds)``: the device also keeps, over ALL days of the stream, every row's threshold exceedance --
     ``thresholds`` [rows] or [rows, K] (K <= 4) in the router's row order, a rank of a multi-rank job taking its own ``rows`` of

@@ -6,7 +6,8 @@ The depths of a day are out[row][step][2] of its result; a stream that assembles
 last step, so the tile kernels carry the row's (peak, step) from tile to tile.  Everything is exact and compares bits:
 ``peak_of`` is peak_flow's rule (peak = d[1], step = 1, then ``if d[t] > peak``: the first of equal peaks wins), the totals are
 folds of the days' arrays (``fold_days``).  Boundary copies of a rank are routed by nobody: (0, 1), what its own full result
-holds there.  As for the flows, the NaN rule is specified and not tested on the GPU: no depth of a routed day is a NaN."""
+holds there.  The NaN rule -- of the carried peak depth, of the reduced one and of the totals' fold -- is tested in
+tests/test_gpu_products_nonfinite.py: no depth of the days routed here is a NaN."""
 import os
 import threading
 

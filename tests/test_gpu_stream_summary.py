@@ -7,9 +7,8 @@ The definition is exact, so everything here compares bits (``summary_of``): peak
 nsteps (np.cumsum).  The flows are those of the day's result, fvd[:, :, 0] -- the oracle's day by day at plan level, and the same
 stream's own full result where the oracle has no say (double precision with reservoirs, the tolerance arithmetic).
 
-The NaN rule (a NaN never replaces a number, a NaN at step 1 stays) is specified but NOT tested on the GPU: no flow of a routed
-day is a NaN unless the forcing is, and a NaN forcing would only send NaN through the secant iteration of every row below for no
-gain -- the rule follows from the one comparison `q[t] > peak` that the kernel and ``summary_of`` share."""
+The NaN rule (a NaN never replaces a number, a NaN at step 1 stays) and ties between positive peaks are not tested here -- no flow
+of these days is a NaN -- but in tests/test_gpu_products_nonfinite.py, on a network whose forcing carries NaN."""
 import functools
 import os
 import threading

@@ -7,8 +7,8 @@ same window (``summary_of``): peak = x[1], step = 1, then in order ``if x[t] > p
 peaks wins); mean = the left-to-right sum in the plan's precision over nsteps (np.cumsum).  The kernel stages tiles of R rows x C
 steps (``RoutingPlan.window_summary_tile``): the shapes sit on the tile's edges.
 
-The NaN rule (a NaN never replaces a number) is specified but not tested on the GPU, as for the stream's summary: no flow of a
-routed window is a NaN unless the forcing is."""
+The NaN rule (a NaN never replaces a number, a NaN at step 1 stays) and ties between positive peaks are not tested here -- no
+flow of these windows is a NaN -- but in tests/test_gpu_products_nonfinite.py, on a network whose forcing carries NaN."""
 
 import numpy as np
 import pandas as pd
