@@ -801,6 +801,42 @@ int trmc_stream_set_exceedance(trmc_plan *plan, int quantity);
 int trmc_stream_exceedance(trmc_plan *plan, int64_t *steps_over, int64_t *first_step, int64_t *last_step, int64_t *longest_run,
                            int64_t *days_out);
 /*
+ * The Courant number OVER A WHOLE STREAM OF DAYS (trmc_stream_*): trmc_window_courant_summary's three figures for every row, over
+ * every step of every day handed over since trmc_stream_begin -- t runs on over the days, 1-based from the stream's first step.
+ * cn[t] of a routed row is the reference's courant() at the depth its step t ended on (where the step had no flow: at the upper end
+ * of the bracket it would have started from), in the plan's precision and arithmetic, bit for bit what trmc_window_courant gives
+ * for the same days routed as windows; a gage row's is that of the un-nudged step; reservoir rows of every type and boundary rows
+ * route no step: cn = 0.  Per row
+ *     peak_cn       pk = cn[1]; t = 2..: if (cn[t] > pk) -- the first of equal peaks wins, a NaN never replaces a number, a NaN
+ *                   at the stream's step 1 stays
+ *     peak_cn_step  the step the peak was first reached at (1 for rows that route no step)
+ *     steps_over    number of steps with cn[t] > limit, compared in the plan's precision (a NaN is not counted)
+ * The state lives on the device outside the ring, as the exceedance's does; where a day is handed over one pass over the day's flow
+ * and depth planes and its forcing (csrc/k_stream_courant.inc: one courant() per row-step, no secant solve) folds it in, in day
+ * order.  Nothing of it is a member of trmc_stream_day or crosses to the host per day.  It needs every step's depth: without
+ * full_output the stream launches the tile-kernel instances that write the depth plane at every step, as for trmc_stream_set_stage;
+ * with full_output the depth is read from the day's result.  So trmc_stream_begin refuses what it refuses for stage: TRMC_EUNSUPPORTED
+ * in a stream with reservoir data assimilation and, without full_output, on a plan with velocity_on_demand < 0; a plan with lagged
+ * rows (trmc_plan_set_lag) runs no stream at all.  Off (the default): no buffer, no launch, the instances of a stream without it.
+ *   trmc_stream_set_courant  on != 0: the streams on this plan keep the figures against `limit`; on == 0: none.  Before
+ *                            trmc_stream_begin; it stays until the next call.  TRMC_ESTATE while a stream is in progress;
+ *                            TRMC_EINVAL on the dataflow engine, which runs no stream, and for a NULL plan.  The steps are counted
+ *                            in 32 bits on the device: trmc_stream_push_day is TRMC_EUNSUPPORTED for the day that would take the
+ *                            stream past 2^31 - 1.
+ *   trmc_stream_courant      HOST arrays [nseg] in row order, peak_cn in the plan's precision (any may be NULL; all NULL, or
+ *                            peak_cn_step without peak_cn: TRMC_EINVAL); synchronous on the copy stream behind the last fold
+ *                            queued: returns when the figures over all days handed over so far are on the host and writes that
+ *                            number of days to days_out.  TRMC_ESTATE when no stream is in progress, when it was begun without
+ *                            the Courant number or when no day is complete yet.
+ *   trmc_stream_courant_kernel_ms  device time (ms) of the last fold queued, from a pair of events around the kernel; waits for it.
+ *                            TRMC_ESTATE as trmc_stream_courant.
+ * With the feature on, the launches of every trmc_stream_push_day go behind the last fold queued: the fold reads the time row the
+ * day's rows started from, which the rows that end the day `slots - 1` days later write again (csrc/stream.inc, ORDER).
+ */
+int trmc_stream_set_courant(trmc_plan *plan, int on, double limit);
+int trmc_stream_courant(trmc_plan *plan, void *peak_cn, int64_t *peak_cn_step, int64_t *steps_over, int64_t *days_out);
+int trmc_stream_courant_kernel_ms(trmc_plan *plan, double *ms_out);
+/*
  * STAGE HYDROGRAPHS of a stream day: the depth of EVERY step at the rows of the day's row set (trmc_stream_day::rowset, the rows of
  * its hydrographs), [rows of the set][nsteps] in the plan's precision -- column 2 of the same day routed as a window with the full
  * result, at those rows, bit for bit.  A reservoir row (trmc_set_reservoirs) gives its pool's water elevation; nudging changes a

@@ -65,6 +65,22 @@
 // threshold table, and trmc_stream_exceedance fetches it.  No row of the product table, no member of trmc_stream_day, nothing per
 // day on the copy stream.  Flows only: the planes hold a tile's last depth and a products-only stream forms no velocity.  Off (the
 // default): no buffer, no launch.
+// THE COURANT NUMBER OVER THE WHOLE STREAM (trmc_stream_set_courant) is the third accumulator of that shape: per row the highest
+// cn = ck dt / dx, the step it was first reached at and the number of steps with cn > limit, trmc_window_courant_summary's definition
+// with the steps counted on over the days.  cn of a row-step is courant_at of a depth the ring already holds (k_stream_courant.inc: no
+// secant solve), but it needs EVERY step's depth: such a stream launches the tile instances that write the depth plane at every step
+// (stage's: k_mc_tile_dpl, k_mc_ctile_dpl) or, with full_output, reads the day's out[row][step][2] -- and inherits stage's refusals.
+// k_stream_courant folds every day where it is handed over, in day order, and trmc_stream_courant fetches the accumulator.
+// ORDER.  The fold of day e reads TIME ROW 0 of the day's slot -- step 0 of the day, of the row and of its upstream rows -- later than
+// anything else does: the tile launches read it in the day's first tile, the other products read rows 1..nsteps.  That row is written
+// again when a row ends day e + slots - 1 (hand_on_row: the next day's slot is this one), first by the rows of lag 0 in the last
+// launch of that day's push.  Those launches wait for the slot's ev_free of day e - 1 only, and where the fold runs on the clusters'
+// stream the slices' stream never waits for it.  So, with the feature on, the launches of every push go behind the last fold queued
+// (stream_push_t: ev_cou; on the fold's own stream by queue order).  That fold is day e's or a later one: day e is handed over at
+// launch (e + 1) tpd - 1 + lmax, and the push of day d = e + slots - 1 begins behind launch d tpd - 1, which is later because
+// slots >= 2 + ceil((lmax + 1) / tpd) gives (slots - 2) tpd >= lmax + 1.  Rows 1..nsteps, the forcing and the full result of the slot
+// are rewritten behind ev_free of day e, which is recorded behind the fold.  Off (the
+// default): no buffer, no launch, the instances of a stream without it.
 // STAGE HYDROGRAPHS (trmc_stream_set_stage): the depth of EVERY step at the rows of the day's row set -- the hydrographs' rows --
 // for the caller who compares stage at forecast points and gages, and pool elevation at reservoirs, with action and flood stages.
 // A slot's depth plane has room for every step, but the tile kernels write the row of a tile's last step only; the stream that was
@@ -125,6 +141,8 @@ struct StreamRun {
                                         // caller's): the next push's forcing stream, or the next launches, go behind it
     DevEvent ev_total;                  // (the totals over the days) the last fold queued is through
     DevEvent ev_exc;                    // (the exceedance over the days) likewise
+    DevEvent ev_cou0, ev_cou;           // (the Courant number over the days) around the last fold queued: the second as ev_exc is,
+                                        // and what the next day's first launches wait for (stream_push_t)
     std::vector<DevEvent> ev_slab;      // ring: "slab launch g is complete" (the cluster launch g + 1 waits for it)
     std::vector<DevEvent> ev_free;      // [slots] the day that used the slot has handed its products over
     std::vector<DevEvent> ev_ready;     // [slots] the gathers of that day are through (copy stream waits)
@@ -168,6 +186,14 @@ struct StreamRun {
     // stage hydrographs (the head of this file).  stage_want: trmc_stream_set_stage, it outlives a stream as sum_want does; stage: of
     // the stream in progress; dpl: its tile launches write the depth plane at every step (otherwise the full result is gathered)
     bool stage_want = false, stage = false, dpl = false;
+    // the Courant number over the days (the head of this file).  cou_want, cou_limit_want: trmc_stream_set_courant, they outlive a
+    // stream as stage_want does; cou, cou_limit: of the stream in progress; cou_peak T, cou_step and cou_count int32 [nseg_pad] in plan
+    // order; cou_rows: T [nseg], then int64 [2][nseg] behind it on a 256-byte boundary, in row order: what a fetch gathers for the
+    // host; cou_days days are folded in (queued).  A stream that carries it has every step's depth: dpl, or the full result.
+    bool cou_want = false, cou = false, cou_ms_ok = false; // (cou_ms_ok: a fold of this stream lies between ev_cou0 and ev_cou)
+    double cou_limit_want = 0.0, cou_limit = 0.0;
+    DevBuf cou_peak, cou_step, cou_count, cou_rows;
+    int64_t cou_days = 0;
     // the totals over the days (TRMC_SUMMARY_TOTAL): [nseg] in row order, outside the ring, one per summary part (tot[k - P_PEAK]:
     // the steps are int64 here); tot_days days are folded in (queued)
     DevBuf tot[P_N - P_PEAK];
@@ -423,6 +449,48 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
         HIP_TRY(hipEventRecord(S.ev_exc, pst));
         S.exc_days = e + 1;
     }
+    if (S.cou && pl->nseg > 0) { // (the day folded into the Courant number over the days: in day order, before the slot is freed)
+        StreamCourantArgs<T> c;
+        c.par = (const T *)pl->sh->params.p;
+        c.nseg_pad = pl->nseg_pad;
+        c.up_ptr = (const int32_t *)pl->sh->up_ptr.p;
+        c.up_idx = (const int32_t *)pl->sh->up_idx.p;
+        c.res_of_pos = pl->nres > 0 ? (const int32_t *)pl->res_of_pos.p : nullptr;
+        c.q_tm = q;
+        c.d0 = d;
+        if (S.dpl) { // (every step's depth: in the slot's depth plane, or in the full result -- stage's two sources)
+            c.row_of_pos = nullptr;
+            c.d1 = d + (size_t)pl->nseg_pad;
+            c.d_row = 1;
+            c.d_step = pl->nseg_pad;
+        } else {
+            c.row_of_pos = (const int32_t *)pl->sh->row_of_pos.p;
+            c.d1 = (const T *)S.out.p + (size_t)slot * S.slot_out + 2;
+            c.d_row = 3 * (int64_t)S.nsteps;
+            c.d_step = 3;
+        }
+        c.qlat = (const T *)S.qlat.p + (size_t)slot * S.slot_qlat;
+        c.peak = (T *)S.cou_peak.p;
+        c.step = (int32_t *)S.cou_step.p;
+        c.count = (int32_t *)S.cou_count.p;
+        c.nseg = (int32_t)pl->nseg;
+        c.nboundary = (int32_t)pl->sh->topo.nboundary;
+        c.nsteps = S.nsteps;
+        c.qts = S.qts;
+        c.t0 = (int32_t)(e * S.nsteps); // (stream_push_t keeps the stream's steps within int32)
+        c.sane = pl->params_sane ? 1 : 0;
+        c.limit = (T)S.cou_limit;
+        HIP_TRY(hipEventRecord(S.ev_cou0, pst)); // (with ev_cou: the fold's device time, trmc_stream_courant_kernel_ms)
+        bool tol = false; // (the plan's arithmetic, as window_courant_launch)
+        if constexpr (std::is_same<T, float>::value) {
+            tol = pl->opt.tol;
+            if (tol) hipLaunchKernelGGL((k_stream_courant<float, true>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, c);
+        }
+        if (!tol) hipLaunchKernelGGL((k_stream_courant<T, false>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, c);
+        HIP_TRY(hipEventRecord(S.ev_cou, pst));
+        S.cou_days = e + 1;
+        S.cou_ms_ok = true;
+    }
     HIP_TRY(hipGetLastError());
     if (!any) {
         HIP_TRY(hipEventRecord(S.ev_free[(size_t)slot], pst));
@@ -563,16 +631,23 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
         if (int rc = S.pkd_d.ensure((size_t)S.slots * np * sizeof(T))) return rc;
         if (int rc = S.pkd_at.ensure((size_t)S.slots * np * sizeof(int32_t))) return rc;
     }
-    // stage hydrographs: the tile launches write the depth plane at every step unless the stream assembles the full result, which
-    // is gathered then
+    // stage hydrographs, and the Courant number over the days, which needs every step's depth as well: the tile launches write the
+    // depth plane at every step unless the stream assembles the full result, which is gathered (read) then
     S.stage = S.stage_want;
-    S.dpl = S.stage && !S.want_out;
+    S.cou = S.cou_want;
+    S.cou_limit = S.cou_limit_want;
+    S.cou_days = 0;
+    S.cou_ms_ok = false;
+    S.dpl = (S.stage || S.cou) && !S.want_out;
     if (S.dpl && pl->opt.velocity_on_demand < 0)
-        return fail(TRMC_EUNSUPPORTED, "the stage of a stream without full_output is written by the tile kernels' on-demand-velocity instances: "
-                                       "not with trmc_plan_options.velocity_on_demand < 0");
+        return fail(TRMC_EUNSUPPORTED, "the stage, and the depths the Courant number is formed from, of a stream without full_output are written by the "
+                                       "tile kernels' on-demand-velocity instances: not with trmc_plan_options.velocity_on_demand < 0");
     if (S.rda && S.stage)
         return fail(TRMC_EUNSUPPORTED, "stage hydrographs (trmc_stream_set_stage) are not supported in a stream with reservoir data "
                                        "assimilation: the _rda tile instances do not write the depth plane");
+    if (S.rda && S.cou)
+        return fail(TRMC_EUNSUPPORTED, "the Courant number over the days (trmc_stream_set_courant) is not supported in a stream with reservoir "
+                                       "data assimilation: the _rda tile instances do not write the depth plane");
     // (boundary rows are routed by nobody and have no depth: zeros in the slots' depth planes, as in a full result)
     if (S.dpl && tp.nboundary > 0)
         HIP_TRY(hipMemset2DAsync((T *)S.tm.p + S.plane, S.slot_tm * sizeof(T), 0, S.plane * sizeof(T), (size_t)S.slots, pl->stream));
@@ -640,6 +715,18 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
         if (int rc = S.exc_rows.ensure(4 * (size_t)pl->nseg * (size_t)S.exc_K * sizeof(int64_t))) return rc;
         if (int rc = S.ev_exc.ensure(false)) return rc;
     }
+    // the Courant number over the days: the accumulator (zeroed below, in front of ev_begin) and what a fetch gathers into
+    const size_t cou_off = ((size_t)pl->nseg * sizeof(T) + 255) / 256 * 256;
+    if (!S.cou) {
+        for (DevBuf *b : {&S.cou_peak, &S.cou_step, &S.cou_count, &S.cou_rows}) b->release();
+    } else {
+        if (int rc = S.cou_peak.ensure(np * sizeof(T))) return rc;
+        if (int rc = S.cou_step.ensure(np * sizeof(int32_t))) return rc;
+        if (int rc = S.cou_count.ensure(np * sizeof(int32_t))) return rc;
+        if (int rc = S.cou_rows.ensure(cou_off + 2 * (size_t)pl->nseg * sizeof(int64_t))) return rc;
+        for (DevEvent *e : {&S.ev_cou0, &S.ev_cou})
+            if (int rc = e->ensure(true)) return rc;
+    }
     // reservoir data assimilation: the slots' tables at their capacity, the carry with the state trmc_set_reservoir_da supplied
     // (or the plan's last window left in those tables); the days' state records are products (P_RDA)
     S.slot_rda = 0;
@@ -690,6 +777,11 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
     pl->mk_forcing.settle();
     HIP_TRY(hipMemsetAsync(pl->it_prev.p, 0, (size_t)np, st));
     if (S.exc >= 0 && exc_bytes > 0) HIP_TRY(hipMemsetAsync(S.exc_acc.p, 0, exc_bytes, st));
+    if (S.cou && np > 0) {
+        HIP_TRY(hipMemsetAsync(S.cou_peak.p, 0, np * sizeof(T), st));
+        HIP_TRY(hipMemsetAsync(S.cou_step.p, 0, np * sizeof(int32_t), st));
+        HIP_TRY(hipMemsetAsync(S.cou_count.p, 0, np * sizeof(int32_t), st));
+    }
     if (pl->collect_cost) {
         if (int rc = pl->it_sum.ensure(np * sizeof(uint16_t))) return rc;
         HIP_TRY(hipMemsetAsync(pl->it_sum.p, 0, np * sizeof(uint16_t), st));
@@ -729,9 +821,9 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
     hipStream_t hst = S.fst; // (the forcing's own stream: the products of earlier days leave on the plan's copy stream meanwhile)
     if (d >= S.slots && S.days_complete <= d - S.slots)
         return fail(TRMC_ESTATE, "internal: the slot of the new day still belongs to a day that has not been queued to its end");
-    if (S.exc >= 0 && (d + 1) * (int64_t)S.nsteps > (int64_t)INT32_MAX)
-        return fail(TRMC_EUNSUPPORTED, "the exceedance over the days of a stream counts its steps in 32 bits on the device: this day would take the "
-                                       "stream past 2^31 - 1 steps -- begin a new stream");
+    if ((S.exc >= 0 || S.cou) && (d + 1) * (int64_t)S.nsteps > (int64_t)INT32_MAX)
+        return fail(TRMC_EUNSUPPORTED, "the exceedance and the Courant number over the days of a stream count its steps in 32 bits on the device: this "
+                                       "day would take the stream past 2^31 - 1 steps -- begin a new stream");
     StreamProd &p = S.prod[(size_t)slot];
     // (the host image of the slot's reservoir tables is written below: the copy of the slot's last day must have read it)
     if (S.rda && p.day >= 0) HIP_TRY(hipEventSynchronize(S.ev_forcing[(size_t)slot]));
@@ -805,6 +897,8 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
     HIP_TRY(hipEventRecord(S.ev_forcing[(size_t)slot], hst));
     HIP_TRY(hipStreamWaitEvent(pl->wstream, S.ev_forcing[(size_t)slot], 0));
     HIP_TRY(hipStreamWaitEvent(pl->stream, S.ev_forcing[(size_t)slot], 0));
+    // (the Courant number: this day's last launches rewrite time row 0 of a slot whose fold may still read it -- the head of this file)
+    if (S.cou && S.cou_days > 0) HIP_TRY(hipStreamWaitEvent(pl->wstream, S.ev_cou, 0));
     S.days_pushed = d + 1;
     hipStream_t tst = S.W > 0 ? pl->wstream : pl->stream; // (the stream whose launches a day's push is timed on)
     HIP_TRY(hipEventRecord(S.ev_t0[(size_t)slot], tst));
@@ -1053,6 +1147,65 @@ int trmc_stream_exceedance(trmc_plan *pl, int64_t *steps_over, int64_t *first_st
     }
     HIP_TRY(hipStreamSynchronize(pl->cstream));
     if (days_out) *days_out = days;
+    return 0;
+}
+
+int trmc_stream_set_courant(trmc_plan *pl, int on, double limit)
+{
+    if (int rc = stream_check(pl, false)) return rc;
+    if (pl->flow) return fail(TRMC_EINVAL, "a stream of windows runs on the level engine");
+    if (!on && !pl->seq) return 0; // (withdrawn where nothing was declared)
+    if (!pl->seq) pl->seq = std::make_unique<StreamRun>();
+    pl->seq->cou_want = on != 0;
+    pl->seq->cou_limit_want = on ? limit : 0.0;
+    return 0;
+}
+
+int trmc_stream_courant(trmc_plan *pl, void *peak_cn, int64_t *peak_cn_step, int64_t *steps_over, int64_t *days_out)
+{
+    if (int rc = stream_check(pl, true)) return rc;
+    StreamRun &S = *pl->seq;
+    if (!S.cou) return fail(TRMC_ESTATE, "the stream was begun without the Courant number (trmc_stream_set_courant precedes trmc_stream_begin)");
+    if (!peak_cn && !peak_cn_step && !steps_over) return fail(TRMC_EINVAL, "every destination is NULL: nothing to fetch");
+    if (peak_cn_step && !peak_cn) return fail(TRMC_EINVAL, "the step of a peak comes with the peak: its value destination is NULL");
+    if (S.cou_days < 1)
+        return fail(TRMC_ESTATE, "no day of the stream is complete yet: its last rows run " + std::to_string(S.lmax)
+                                     + " tiles behind its first -- push further days or trmc_stream_flush");
+    const int64_t days = S.cou_days;
+    const size_t n = (size_t)pl->nseg;
+    // behind the last fold queued (nothing is queued meanwhile: the calls of a plan come from one thread)
+    HIP_TRY(hipStreamWaitEvent(pl->cstream, S.ev_cou, 0));
+    if (n) {
+        const size_t off = (n * (size_t)pl->esz + 255) / 256 * 256;
+        int64_t *const rows64 = (int64_t *)((char *)S.cou_rows.p + off);
+        const int rc = by_precision(pl, [&](auto t) -> int {
+            using T = decltype(t);
+            hipLaunchKernelGGL((k_stream_courant_rows<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pl->cstream, (const T *)S.cou_peak.p,
+                               (const int32_t *)S.cou_step.p, (const int32_t *)S.cou_count.p, (const int32_t *)pl->sh->pos_of_row.p,
+                               (T *)S.cou_rows.p, rows64, rows64 + n, (int32_t)pl->nseg);
+            HIP_TRY(hipGetLastError());
+            return 0;
+        });
+        if (rc) return rc;
+        if (peak_cn) HIP_TRY(hipMemcpyAsync(peak_cn, S.cou_rows.p, n * (size_t)pl->esz, hipMemcpyDeviceToHost, pl->cstream));
+        if (peak_cn_step) HIP_TRY(hipMemcpyAsync(peak_cn_step, rows64, n * sizeof(int64_t), hipMemcpyDeviceToHost, pl->cstream));
+        if (steps_over) HIP_TRY(hipMemcpyAsync(steps_over, rows64 + n, n * sizeof(int64_t), hipMemcpyDeviceToHost, pl->cstream));
+    }
+    HIP_TRY(hipStreamSynchronize(pl->cstream));
+    if (days_out) *days_out = days;
+    return 0;
+}
+
+int trmc_stream_courant_kernel_ms(trmc_plan *pl, double *ms_out)
+{
+    if (int rc = stream_check(pl, true)) return rc;
+    StreamRun &S = *pl->seq;
+    if (!ms_out) return fail(TRMC_EINVAL, "ms_out is NULL");
+    if (!S.cou || !S.cou_ms_ok) return fail(TRMC_ESTATE, "no day has been folded into the Courant number of this stream yet");
+    HIP_TRY(hipEventSynchronize(S.ev_cou));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, S.ev_cou0, S.ev_cou));
+    *ms_out = ms;
     return 0;
 }
 

@@ -612,6 +612,42 @@ class RoutingPlan:
         res.update((name, a) for name, a in out.items() if a is not None)
         return res
 
+    @staticmethod
+    def stream_courant_limit(limit):
+        """``limit`` of a stream's Courant number, checked: a real number (returned as a float) or None; ValueError otherwise."""
+        if limit is None:
+            return None
+        if isinstance(limit, (bool, str, bytes)) or not isinstance(limit, (int, float, np.integer, np.floating)):
+            raise ValueError(f"courant: the limit cn is counted against must be a real number (or None), got {limit!r}")
+        return float(limit)
+
+    def stream_set_courant(self, limit=1.0):
+        """The streams on this plan keep, on the device and over ALL their days, every row's Courant number cn = ck dt / dx: the
+        highest, the step it was first reached at and the number of steps with cn > ``limit`` -- ``window_courant_summary`` with
+        the steps counted on over the days (trmc_stream_set_courant; ``stream_courant`` fetches).  Such a stream writes every
+        step's depth, as one with ``stream_set_stage`` does, and ``stream_begin`` refuses what it refuses for stage.  Declared
+        before ``stream_begin``; it stays until the next call; ``None`` withdraws it."""
+        limit = self.stream_courant_limit(limit)
+        if self.engine != "levels":
+            raise ValueError("a stream of days runs on the level engine: its Courant number needs engine='levels'")
+        _lib.check(_lib.lib().trmc_stream_set_courant(self._h, int(limit is not None), 0.0 if limit is None else limit))
+        self._stream_courant = limit
+
+    def stream_courant(self):
+        """The Courant number over all days of the stream in progress that have been handed over so far (trmc_stream_courant,
+        synchronous): a dict with ``"days"``, ``"peak_cn"`` (plan dtype), ``"peak_cn_step"`` and ``"steps_over"`` (int64, the steps
+        1-based from the stream's first step) -- [nseg] arrays in row order, as ``window_courant_summary`` defines them over the
+        days one after the other.  Reservoir and boundary rows: (0, 1, 0)."""
+        peak, step, over = np.empty(self.nseg, self.dtype), np.empty(self.nseg, np.int64), np.empty(self.nseg, np.int64)
+        days = C.c_int64(0)
+        _lib.check(_lib.lib().trmc_stream_courant(self._h, _lib.ptr(peak), _lib.ptr(step), _lib.ptr(over), C.byref(days)))
+        return {"days": int(days.value), "peak_cn": peak, "peak_cn_step": step, "steps_over": over}
+
+    def stream_courant_kernel_ms(self):
+        """device time (ms) of the last day's fold into the stream's Courant number, from events around the kernel
+        (trmc_stream_courant_kernel_ms; waits for it)"""
+        return self._kernel_ms(_lib.lib().trmc_stream_courant_kernel_ms)
+
     def stream_gather(self, day, rowset, device_ptr, stream=0):
         """Flows of a row set over `day` [rows, nsteps] into device memory (trmc_stream_gather)."""
         _lib.check(_lib.lib().trmc_stream_gather(self._h, int(day), int(rowset), C.c_void_p(device_ptr), C.c_void_p(stream or 0)))

@@ -446,6 +446,14 @@ class RouteStream:
     -- once ``route()`` has yielded its last day, next to ``rs.total``.  It is not a product of the day: the tuples do not change.
     Flow only ("depth", "velocity", "bankfull": NotImplementedError -- route the day in question as a window).
 
+    ``courant=limit``: the device also keeps, over ALL days of the stream, every row's Courant number cn = ck dt / dx -- the
+    highest, the step it was first reached at and the number of steps with cn > ``limit``: ``rs.courant`` holds
+    ``RoutingPlan.stream_courant()`` -- ``"days"``, ``"peak_cn"``, ``"peak_cn_step"`` and ``"steps_over"`` over this rank's
+    ``rows``, the steps int64 and 1-based from the stream's first step, ``window_courant_summary``'s definition over the days one
+    after the other -- over the days handed over so far while ``route()`` runs (None before the first) and over all of them once
+    it has yielded its last day.  It is not a product of the day: the tuples do not change.  Such a stream writes every step's
+    depth as one with ``stage=True`` does, with stage's limits: one rank only, no ``reservoir_da`` (NotImplementedError).
+
     ``stage=True``: every day also carries STAGE HYDROGRAPHS -- the depth of every step at the rows of its hydrographs: the
     trailing dict gains ``"stage"``, a ring array [len(outlet_rows), nsteps] in the hydrographs' row order (a reservoir row: its
     pool's elevation; nudging changes a gage's flow only).  The tile kernels then write a slot's depth plane at every step
@@ -467,7 +475,7 @@ class RouteStream:
 
     def __init__(self, router, nsteps, qts_subdivisions, output_stride=None, full_output=False, slots=0, latency="throughput",
                  hydrographs_on_every_rank=False, comm=None, exchange=None, reservoir_da_ncol=None, summary=None,
-                 daily_summary=True, stage=False, exceedance=None):
+                 daily_summary=True, courant=None, stage=False, exceedance=None):
         """comm / exchange (several ranks): the communicator -- default: the one given to ``router.enable_device_exchange`` -- and
         how the daily cut-edge hydrographs travel: "device" (gather kernel -> all-gather on the exchange stream -> boundary rows,
         everything in HBM: RCCL over xGMI) or "host" (through ``comm.all_gather_rows_host``: any communicator with that method,
@@ -476,6 +484,15 @@ class RouteStream:
         reservoir_da_ncol (a router with ``reservoir_da``): the most columns (usgs, usace, rfc) a day's tables may have; default:
         as many as the declared tables."""
         self._rda_ncol = reservoir_da_ncol
+        from .plan import RoutingPlan
+        self._cou_limit = RoutingPlan.stream_courant_limit(courant)
+        self._courant = None
+        if self._cou_limit is not None and router.world > 1:
+            raise NotImplementedError("courant= on several ranks: the Courant number needs every step's depth of a row and of the rows above "
+                                      "it, which a rank holds for its own rows only -- as for stage=True, nothing gathers it over the ranks")
+        if self._cou_limit is not None and getattr(router, "_reservoir_da", None) is not None:
+            raise NotImplementedError("courant= with reservoir data assimilation: the tile kernels of such a stream do not write the depth "
+                                      "plane at every step (as for stage=True)")
         self.stage = bool(stage)
         if self.stage and router.world > 1:
             raise NotImplementedError("stage=True on several ranks: a day's stage covers the rows of its hydrographs, which every rank holds a "
@@ -502,7 +519,6 @@ class RouteStream:
                 raise ValueError("exceedance: (\"flow\", thresholds)") from None
             if isinstance(th, str):     # (the drop-in's ("depth", "bankfull"): a depth)
                 quantity = th if quantity in _lib.X_NAMES else quantity
-            from .plan import RoutingPlan
             RoutingPlan.stream_exceedance_quantity(quantity)
             th = np.asarray(th)
             th = th[:, None] if th.ndim == 1 else th
@@ -569,6 +585,13 @@ class RouteStream:
 
     def _tile_steps(self, P):
         return int(getattr(P, "tile_steps", 16))
+
+    @property
+    def courant(self):
+        """the Courant number over the days handed over so far (``courant=limit``; see the class), None before the first"""
+        if self._cou_limit is not None and self.info is not None and self.plan.stream_info()["days_complete"] > 0:
+            self._courant = self.plan.stream_courant()
+        return self._courant
 
     @property
     def outlet_rows(self):
@@ -701,6 +724,9 @@ class RouteStream:
         self.exceedance = None
         if self.stage or getattr(P, "_stream_stage", False):   # (likewise)
             P.stream_set_stage(self.stage)
+        if self._cou_limit is not None or getattr(P, "_stream_courant", None) is not None:
+            P.stream_set_courant(self._cou_limit)
+        self._courant = None
         P.stream_begin(nsteps, self.qts, slots=slots, full_output=self.full_output and not self.output_stride, output_stride=self.output_stride,
                        **({} if rda is None else {"reservoir_da": True if self._rda_ncol is None else self._rda_ncol}))
         self.info = info = P.stream_info()
@@ -740,6 +766,8 @@ class RouteStream:
             self.total = P.stream_summary_total()
         if self._exc_th is not None:    # (... and the exceedance over all of its steps)
             self.exceedance = P.stream_exceedance()
+        if self._cou_limit is not None: # (... and the Courant number)
+            self._courant = P.stream_courant()
         while delivered < d:
             yield self._deliver(delivered, ring, gage, rdac, extras)
             delivered += 1

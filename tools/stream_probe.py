@@ -13,6 +13,10 @@ row and the hydrographs of sampled rows bit for bit, and what a day costs either
                                [--exceedance K]             the threshold exceedance of every row's flow over ALL days of the stream at
                                                             K levels (trmc_stream_set_exceedance), fetched once at the end; checked
                                                             against the numpy loop over the one-by-one days' flows where that fits
+                               [--courant LIMIT]            the stream is run twice, without and with every row's Courant number over the
+                                                            whole stream (trmc_stream_set_courant): peak, its step, steps with cn > LIMIT;
+                                                            checked against the fold of the one-by-one days' window_courant_summary;
+                                                            the fold kernel's time from events
                                [--stage]                    stage hydrographs: the depth of every step at the rows of the day's row set
                                                             (trmc_stream_set_stage); checked against column 2 of the one-by-one
                                                             day's full result where that fits (nseg * 288 <= 2^26)
@@ -50,6 +54,7 @@ ap.add_argument("--summary", action="store_true", help="per-row peak flow, step 
 ap.add_argument("--summary-depth", action="store_true", help="the day's peak depth and its step as well (with or without --summary)")
 ap.add_argument("--summary-total", action="store_true", help="the totals over the days of the stream; no per-day summary array crosses to the host")
 ap.add_argument("--exceedance", type=int, default=0, metavar="K", help="exceedance of K (1..4) flow thresholds a row over the whole stream, kept on the device")
+ap.add_argument("--courant", type=float, default=None, metavar="LIMIT", help="every row's Courant number over the whole stream (peak, its step, steps with cn > LIMIT), kept on the device")
 ap.add_argument("--stage", action="store_true", help="the depth of every step at the rows of the row set as a stream product")
 ap.add_argument("--outlets", action="store_true", help="the row set: every network's outlet (default: 3000 sampled rows)")
 ap.add_argument("--gages", type=int, default=0, help="nudged gages scattered over the network (observations: 70 %% valid, lognormal)")
@@ -176,6 +181,8 @@ check_summary = any_summary and not a.no_check and n * nsteps <= 1 << 26
 ref_sum = []
 check_stage = a.stage and not a.no_check and n * nsteps <= 1 << 26
 ref_stage = []
+check_cou = a.courant is not None and not a.no_check and not a.reservoir_da     # (the same days' window summaries, folded over the days)
+ref_cou = []
 opts = {"wide_min_rows": a.wide_min_rows, "wide_k": a.wide_k, "cluster_rows": 128, "wide_levels": a.wide_levels, "stream_split": a.split, "velocity_on_demand": a.velocity_on_demand}
 hint = None
 if a.hint:
@@ -216,6 +223,8 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
                 ref_stage.append(np.ascontiguousarray((fvd if (a.full and not a.stride) else p.download_fvd())[sample, :, 2]))
             if check_exc:
                 ref_q.append(np.ascontiguousarray((full if check_summary else p.download_fvd())[:, :, 0]))
+            if check_cou:
+                ref_cou.append(p.window_courant_summary(a.courant))
             if a.reservoir_da:
                 da_state, da_tsidx = p.download_reservoir_da()
                 da_state[da_kind != 0, 0] -= da_t_end
@@ -223,126 +232,148 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
             ref.append((fin, hyd, fvd, p.download_reservoir_inflow() if a.reservoirs else None, p.download_nudge() if tabs else None,
                         (da_state.copy(), da_tsidx.copy()) if a.reservoir_da else None))
         print(f"one by one: {(time.perf_counter() - t0) / a.days * 1e3:.2f} ms per day (host loop, downloads included); window ms_main {st['ms_main']:.2f}", flush=True)
-    # the stream
-    if a.reservoir_da:
-        p.set_reservoir_da(da_kind, da_trow, *da_tables())
-    p.upload_forcing(nsteps, days[0], q0)
-    p.stream_set_summary((("peak", "mean") if a.summary else ()) + (("peak_depth",) if a.summary_depth else ())
-                         + (("total",) if a.summary_total else ()) or None)
-    if a.stage:
-        p.stream_set_stage(True)
-    if a.exceedance:
-        # a row's levels: quantiles of its own flows over the stream where they are known (the check), else multiples of its forcing
-        if check_exc:
-            exc_x = np.concatenate(ref_q, axis=1)
-            exc_th = np.quantile(exc_x.astype(np.float64), (0.5, 0.25, 0.9, 0.75)[:a.exceedance], axis=1).T.astype(np.float32)
-        else:
-            exc_th = days[0].mean(axis=1, dtype=np.float32)[:, None] * np.array([1, 10, 100, 1000], np.float32)[None, :a.exceedance]
-        p.set_thresholds(exc_th)
-        p.stream_set_exceedance("flow")
-    p.stream_begin(nsteps, qts, reservoir_da=bool(a.reservoir_da) or None, slots=a.slots + a.later if a.slots else (a.later and 2 + -(-(int(p.lags()[0].max(initial=0)) + 1) // (nsteps // p.tile_steps)) + a.later), full_output=a.full and not a.stride, output_stride=a.stride)
-    info = p.stream_info()
-    print("stream:", info, flush=True)
-    D = info["slots"]
-    hyds = [_lib.result_empty((sample.shape[0], nsteps), np.float32, always_pinned=True) for _ in range(D)]
-    fins = [_lib.result_empty((n, 3), np.float32, always_pinned=True) for _ in range(D)]
-    keep = nsteps // a.stride if a.stride else nsteps
-    fvds = [_lib.result_empty((n, keep, 3), np.float32, always_pinned=True) for _ in range(D)] if (a.stride or a.full) else [None] * D
-    rins = [_lib.result_empty((a.reservoirs, nsteps), np.float32, always_pinned=True) if a.reservoirs else None for _ in range(D)]
-    nuds = [_lib.result_empty((a.gages, nsteps), np.float32, always_pinned=True) if tabs else None for _ in range(D)]
-    rdas = [(_lib.result_empty((a.reservoirs, 4), np.float32, always_pinned=True), _lib.result_empty((a.reservoirs,), np.int32, always_pinned=True))
-            if a.reservoir_da else None for _ in range(D)]
-    sums = [(_lib.result_empty((n,), np.float32, always_pinned=True), _lib.result_empty((n,), np.int32, always_pinned=True),
-             _lib.result_empty((n,), np.float32, always_pinned=True)) if (a.summary and daily) else ((None, None, None) if daily else None)
-            for _ in range(D)]
-    if daily and a.summary_depth:
-        sums = [s + (_lib.result_empty((n,), np.float32, always_pinned=True), _lib.result_empty((n,), np.int32, always_pinned=True)) for s in sums]
-    stgs = [_lib.result_empty((sample.shape[0], nsteps), np.float32, always_pinned=True) if a.stage else None for _ in range(D)]
-    da_day = da_tables() if a.reservoir_da else None
-    got = []
-    behind = (info["lag_max"] + info["tiles_per_day"]) // info["tiles_per_day"] + a.later
-    ok = True
-    marks = []
+    # the stream -- with --courant LIMIT twice: without the Courant number, then with it (the same days, every check both times)
+    for cou_on in ((False, True) if a.courant is not None else (False,)):
+        if a.courant is not None:
+            print("-- the stream " + ("WITH" if cou_on else "WITHOUT") + " the Courant number", flush=True)
+        if a.reservoir_da:
+            p.set_reservoir_da(da_kind, da_trow, *da_tables())
+        p.upload_forcing(nsteps, days[0], q0)
+        p.stream_set_summary((("peak", "mean") if a.summary else ()) + (("peak_depth",) if a.summary_depth else ())
+                             + (("total",) if a.summary_total else ()) or None)
+        if a.stage:
+            p.stream_set_stage(True)
+        if a.courant is not None:
+            p.stream_set_courant(a.courant if cou_on else None)
+        if a.exceedance:
+            # a row's levels: quantiles of its own flows over the stream where they are known (the check), else multiples of its forcing
+            if check_exc:
+                exc_x = np.concatenate(ref_q, axis=1)
+                exc_th = np.quantile(exc_x.astype(np.float64), (0.5, 0.25, 0.9, 0.75)[:a.exceedance], axis=1).T.astype(np.float32)
+            else:
+                exc_th = days[0].mean(axis=1, dtype=np.float32)[:, None] * np.array([1, 10, 100, 1000], np.float32)[None, :a.exceedance]
+            p.set_thresholds(exc_th)
+            p.stream_set_exceedance("flow")
+        p.stream_begin(nsteps, qts, reservoir_da=bool(a.reservoir_da) or None, slots=a.slots + a.later if a.slots else (a.later and 2 + -(-(int(p.lags()[0].max(initial=0)) + 1) // (nsteps // p.tile_steps)) + a.later), full_output=a.full and not a.stride, output_stride=a.stride)
+        info = p.stream_info()
+        print("stream:", info, flush=True)
+        D = info["slots"]
+        hyds = [_lib.result_empty((sample.shape[0], nsteps), np.float32, always_pinned=True) for _ in range(D)]
+        fins = [_lib.result_empty((n, 3), np.float32, always_pinned=True) for _ in range(D)]
+        keep = nsteps // a.stride if a.stride else nsteps
+        fvds = [_lib.result_empty((n, keep, 3), np.float32, always_pinned=True) for _ in range(D)] if (a.stride or a.full) else [None] * D
+        rins = [_lib.result_empty((a.reservoirs, nsteps), np.float32, always_pinned=True) if a.reservoirs else None for _ in range(D)]
+        nuds = [_lib.result_empty((a.gages, nsteps), np.float32, always_pinned=True) if tabs else None for _ in range(D)]
+        rdas = [(_lib.result_empty((a.reservoirs, 4), np.float32, always_pinned=True), _lib.result_empty((a.reservoirs,), np.int32, always_pinned=True))
+                if a.reservoir_da else None for _ in range(D)]
+        sums = [(_lib.result_empty((n,), np.float32, always_pinned=True), _lib.result_empty((n,), np.int32, always_pinned=True),
+                 _lib.result_empty((n,), np.float32, always_pinned=True)) if (a.summary and daily) else ((None, None, None) if daily else None)
+                for _ in range(D)]
+        if daily and a.summary_depth:
+            sums = [s + (_lib.result_empty((n,), np.float32, always_pinned=True), _lib.result_empty((n,), np.int32, always_pinned=True)) for s in sums]
+        stgs = [_lib.result_empty((sample.shape[0], nsteps), np.float32, always_pinned=True) if a.stage else None for _ in range(D)]
+        da_day = da_tables() if a.reservoir_da else None
+        got = []
+        behind = (info["lag_max"] + info["tiles_per_day"]) // info["tiles_per_day"] + a.later
+        ok = True
+        marks = []
 
-    def take(e):
-        global ok
-        p.stream_wait(e)
-        marks.append(time.perf_counter())
-        if a.no_check:
-            return
-        fin, hyd, fvd, rin, nud, rda = ref[e]
-        if rda is not None and not (np.array_equal(rda[0].view(np.uint32), rdas[e % D][0].view(np.uint32)) and np.array_equal(rda[1], rdas[e % D][1])):
-            ok = False
-            print(f"   day {e}: reservoir data-assimilation state differs", flush=True)
-        for name, x, y in (("reservoir inflow", rin, rins[e % D]), ("nudge", nud, nuds[e % D])):
-            if x is not None and not np.array_equal(x.view(np.uint32), y.view(np.uint32)):
+        def take(e):
+            global ok
+            p.stream_wait(e)
+            marks.append(time.perf_counter())
+            if a.no_check:
+                return
+            fin, hyd, fvd, rin, nud, rda = ref[e]
+            if rda is not None and not (np.array_equal(rda[0].view(np.uint32), rdas[e % D][0].view(np.uint32)) and np.array_equal(rda[1], rdas[e % D][1])):
                 ok = False
-                print(f"   day {e}: {name} differs", flush=True)
-        if check_summary and daily and not all(y is None or np.array_equal(x.view(np.uint32), y.view(np.uint32)) for x, y in zip(ref_sum[e], sums[e % D])):
-            ok = False
-            print(f"   day {e}: summary differs", flush=True)
-        if check_stage and not np.array_equal(ref_stage[e].view(np.uint32), stgs[e % D].view(np.uint32)):
-            ok = False
-            print(f"   day {e}: stage differs", flush=True)
-        s1 = np.array_equal(fin.view(np.uint32), fins[e % D].view(np.uint32))
-        s2 = np.array_equal(hyd.view(np.uint32), hyds[e % D].view(np.uint32))
-        s3 = fvd is None or np.array_equal(np.ascontiguousarray(fvd).view(np.uint32), fvds[e % D].view(np.uint32))
-        if not (s1 and s2 and s3):
-            ok = False
-            print(f"   day {e}: final state {s1} hydrographs {s2} fvd {s3}", flush=True)
-    t0 = time.perf_counter()
-    for d in range(a.days):
-        p.stream_push(pinned[d % len(days)], rowset=rs, hyd=hyds[d % D], q0=fins[d % D], fvd=fvds[d % D],
-                      nudging=tabs[d % len(days)] if tabs else None, nudge=nuds[d % D], reservoir_inflow=rins[d % D], reservoir_da=da_day, reservoir_da_state=rdas[d % D], summary=sums[d % D], **({"stage": stgs[d % D]} if a.stage else {}))
-        e = d - behind
-        if e >= 0:
-            take(e)
-    p.stream_flush()
-    for e in range(max(0, a.days - behind), a.days):
-        take(e)
-    el = time.perf_counter() - t0
-    if a.summary_total:
-        tot = p.stream_summary_total()
-        print(f"   totals over {tot['days']} days fetched in {(time.perf_counter() - t0 - el) * 1e3:.2f} ms: {sorted(k for k in tot if k != 'days')}", flush=True)
-        if check_summary:
-            for kf, ks, i in (("peak_flow", "peak_step", 0), ("peak_depth", "peak_depth_step", 3)):
-                if kf in tot:
-                    pk, st = ref_sum[0][i].copy(), ref_sum[0][i + 1].astype(np.int64)
-                    for e in range(1, a.days):
-                        m = ref_sum[e][i] > pk
-                        pk[m], st[m] = ref_sum[e][i][m], e * nsteps + ref_sum[e][i + 1][m]
-                    if not (np.array_equal(pk.view(np.uint32), tot[kf].view(np.uint32)) and np.array_equal(st, tot[ks])):
-                        ok = False
-                        print(f"   totals: {kf} differs", flush=True)
-            if "mean_flow" in tot:
-                m = ref_sum[0][2].copy()
-                for e in range(1, a.days):
-                    m = m + ref_sum[e][2]
-                if not np.array_equal((m / np.float32(a.days)).view(np.uint32), tot["mean_flow"].view(np.uint32)):
+                print(f"   day {e}: reservoir data-assimilation state differs", flush=True)
+            for name, x, y in (("reservoir inflow", rin, rins[e % D]), ("nudge", nud, nuds[e % D])):
+                if x is not None and not np.array_equal(x.view(np.uint32), y.view(np.uint32)):
                     ok = False
-                    print("   totals: mean_flow differs", flush=True)
-    if a.exceedance:
-        t1 = time.perf_counter()
-        exc = p.stream_exceedance()
-        print(f"   exceedance at {a.exceedance} level(s) over {exc['days']} days fetched in {(time.perf_counter() - t1) * 1e3:.2f} ms: "
-              f"{int(np.count_nonzero(exc['steps_over']))} of {exc['steps_over'].size} (row, level) pairs went over, longest run {int(exc['longest_run'].max())} steps;",
-              "not checked (no check asked for, or too large for a host loop)" if not check_exc else "", flush=True)
-        if check_exc:
-            want = exceedance_of(exc_x, exc_th)
-            same = exc["days"] == a.days and all(np.array_equal(exc[k], want[k]) for k in want)
-            ok = ok and same
-            print("   exceedance equals the numpy loop over the one-by-one days' flows:", same, flush=True)
-    dev_ms = [p.stream_day_ms(e) for e in range(max(behind + 1, a.days - D + 1), a.days)]    # (days pushed into a full stream, still in the ring)
-    p.stream_end()
-    if dev_ms:
-        print(f"   device time of a day's own launches on the slices' stream: median {np.median(dev_ms):.2f} ms over {len(dev_ms)} days {np.round(dev_ms, 2).tolist()}", flush=True)
-    per = np.diff(marks) * 1e3
-    print(f"stream: {el / a.days * 1e3:.2f} ms per day over {a.days} days (fill and drain included); between deliveries {np.round(per, 2).tolist()}", flush=True)
-    if any_summary:
-        print("   summary (" + ", ".join((["peak flow, step of the peak, mean flow"] if a.summary else []) + (["peak depth and its step"] if a.summary_depth else []))
-              + " of every row" + ("; totals only" if a.summary_total else "") + "):",
-              "checked against the host's reduction of every day's full result" if check_summary else "not checked (no check asked for, or too large for a host reduction)", flush=True)
-    if a.stage:
-        print(f"   stage of every step at the {sample.shape[0]} rows of the row set:",
-              "checked against column 2 of every day's full result" if check_stage else "not checked (no check asked for, or too large)", flush=True)
-    print("   launches", p.stream_info()["launches"], " every day bit-identical to the days routed one by one:", ok if not a.no_check else "not checked", flush=True)
+                    print(f"   day {e}: {name} differs", flush=True)
+            if check_summary and daily and not all(y is None or np.array_equal(x.view(np.uint32), y.view(np.uint32)) for x, y in zip(ref_sum[e], sums[e % D])):
+                ok = False
+                print(f"   day {e}: summary differs", flush=True)
+            if check_stage and not np.array_equal(ref_stage[e].view(np.uint32), stgs[e % D].view(np.uint32)):
+                ok = False
+                print(f"   day {e}: stage differs", flush=True)
+            s1 = np.array_equal(fin.view(np.uint32), fins[e % D].view(np.uint32))
+            s2 = np.array_equal(hyd.view(np.uint32), hyds[e % D].view(np.uint32))
+            s3 = fvd is None or np.array_equal(np.ascontiguousarray(fvd).view(np.uint32), fvds[e % D].view(np.uint32))
+            if not (s1 and s2 and s3):
+                ok = False
+                print(f"   day {e}: final state {s1} hydrographs {s2} fvd {s3}", flush=True)
+        t0 = time.perf_counter()
+        for d in range(a.days):
+            p.stream_push(pinned[d % len(days)], rowset=rs, hyd=hyds[d % D], q0=fins[d % D], fvd=fvds[d % D],
+                          nudging=tabs[d % len(days)] if tabs else None, nudge=nuds[d % D], reservoir_inflow=rins[d % D], reservoir_da=da_day, reservoir_da_state=rdas[d % D], summary=sums[d % D], **({"stage": stgs[d % D]} if a.stage else {}))
+            e = d - behind
+            if e >= 0:
+                take(e)
+        p.stream_flush()
+        for e in range(max(0, a.days - behind), a.days):
+            take(e)
+        el = time.perf_counter() - t0
+        if a.summary_total:
+            tot = p.stream_summary_total()
+            print(f"   totals over {tot['days']} days fetched in {(time.perf_counter() - t0 - el) * 1e3:.2f} ms: {sorted(k for k in tot if k != 'days')}", flush=True)
+            if check_summary:
+                for kf, ks, i in (("peak_flow", "peak_step", 0), ("peak_depth", "peak_depth_step", 3)):
+                    if kf in tot:
+                        pk, st = ref_sum[0][i].copy(), ref_sum[0][i + 1].astype(np.int64)
+                        for e in range(1, a.days):
+                            m = ref_sum[e][i] > pk
+                            pk[m], st[m] = ref_sum[e][i][m], e * nsteps + ref_sum[e][i + 1][m]
+                        if not (np.array_equal(pk.view(np.uint32), tot[kf].view(np.uint32)) and np.array_equal(st, tot[ks])):
+                            ok = False
+                            print(f"   totals: {kf} differs", flush=True)
+                if "mean_flow" in tot:
+                    m = ref_sum[0][2].copy()
+                    for e in range(1, a.days):
+                        m = m + ref_sum[e][2]
+                    if not np.array_equal((m / np.float32(a.days)).view(np.uint32), tot["mean_flow"].view(np.uint32)):
+                        ok = False
+                        print("   totals: mean_flow differs", flush=True)
+        if a.exceedance:
+            t1 = time.perf_counter()
+            exc = p.stream_exceedance()
+            print(f"   exceedance at {a.exceedance} level(s) over {exc['days']} days fetched in {(time.perf_counter() - t1) * 1e3:.2f} ms: "
+                  f"{int(np.count_nonzero(exc['steps_over']))} of {exc['steps_over'].size} (row, level) pairs went over, longest run {int(exc['longest_run'].max())} steps;",
+                  "not checked (no check asked for, or too large for a host loop)" if not check_exc else "", flush=True)
+            if check_exc:
+                want = exceedance_of(exc_x, exc_th)
+                same = exc["days"] == a.days and all(np.array_equal(exc[k], want[k]) for k in want)
+                ok = ok and same
+                print("   exceedance equals the numpy loop over the one-by-one days' flows:", same, flush=True)
+        if cou_on:
+            fold_ms = p.stream_courant_kernel_ms()
+            print(f"   the last day's fold (k_stream_courant), from events around the kernel: {fold_ms:.3f} ms", flush=True)
+            t1 = time.perf_counter()
+            cou = p.stream_courant()
+            print(f"   Courant number over {cou['days']} days fetched in {(time.perf_counter() - t1) * 1e3:.2f} ms: highest cn {float(np.nanmax(cou['peak_cn'])):.3f}, "
+                  f"{int(np.count_nonzero(cou['steps_over']))} of {n} rows went over {a.courant};", "" if check_cou else "not checked", flush=True)
+            if check_cou:
+                pk, st, ov = ref_cou[0]["peak_cn"].copy(), ref_cou[0]["peak_cn_step"].astype(np.int64), ref_cou[0]["steps_over"].astype(np.int64)
+                for e in range(1, a.days):          # (the fold of the days' window summaries: a later day wins only with a greater peak)
+                    m = ref_cou[e]["peak_cn"] > pk
+                    pk[m], st[m] = ref_cou[e]["peak_cn"][m], e * nsteps + ref_cou[e]["peak_cn_step"][m]
+                    ov += ref_cou[e]["steps_over"]
+                same = (cou["days"] == a.days and np.array_equal(pk.view(np.uint32), cou["peak_cn"].view(np.uint32)) and np.array_equal(st, cou["peak_cn_step"])
+                        and np.array_equal(ov, cou["steps_over"]))
+                ok = ok and same
+                print("   Courant number equals the fold of the one-by-one days' window_courant_summary:", same, flush=True)
+        dev_ms = [p.stream_day_ms(e) for e in range(max(behind + 1, a.days - D + 1), a.days)]    # (days pushed into a full stream, still in the ring)
+        p.stream_end()
+        if dev_ms:
+            print(f"   device time of a day's own launches on the slices' stream: median {np.median(dev_ms):.2f} ms over {len(dev_ms)} days {np.round(dev_ms, 2).tolist()}", flush=True)
+        per = np.diff(marks) * 1e3
+        print(f"stream: {el / a.days * 1e3:.2f} ms per day over {a.days} days (fill and drain included); between deliveries {np.round(per, 2).tolist()}", flush=True)
+        if any_summary:
+            print("   summary (" + ", ".join((["peak flow, step of the peak, mean flow"] if a.summary else []) + (["peak depth and its step"] if a.summary_depth else []))
+                  + " of every row" + ("; totals only" if a.summary_total else "") + "):",
+                  "checked against the host's reduction of every day's full result" if check_summary else "not checked (no check asked for, or too large for a host reduction)", flush=True)
+        if a.stage:
+            print(f"   stage of every step at the {sample.shape[0]} rows of the row set:",
+                  "checked against column 2 of every day's full result" if check_stage else "not checked (no check asked for, or too large)", flush=True)
+        print("   launches", p.stream_info()["launches"], " every day bit-identical to the days routed one by one:", ok if not a.no_check else "not checked", flush=True)
