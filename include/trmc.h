@@ -837,6 +837,43 @@ int trmc_stream_set_courant(trmc_plan *plan, int on, double limit);
 int trmc_stream_courant(trmc_plan *plan, void *peak_cn, int64_t *peak_cn_step, int64_t *steps_over, int64_t *days_out);
 int trmc_stream_courant_kernel_ms(trmc_plan *plan, double *ms_out);
 /*
+ * DEPTH exceedance OVER A WHOLE STREAM OF DAYS (trmc_stream_*): how long a row is out of bank, or over an action / flood stage, when
+ * it first goes over and the longest continuous inundation of the forecast -- trmc_stream_exceedance's four figures, on depth:
+ * over(t) := d[t] > th[row][k], compared in the plan's precision (false when either side is a NaN; equality is not over), t running
+ * on over the days, 1-based from the stream's first step, a run that is open at a day's last step going on at the next day's first.
+ * d[t] is the depth the stream holds for the row and step, the bits trmc_stream_set_stage and full_output hand out: the pool's water
+ * elevation at a reservoir row (trmc_set_reservoirs), 0 at a boundary row, the step's own depth at a gage row (nudging changes the
+ * flow only).  The figures equal, integer for integer, the plain loop over the days' depths one after the other.
+ * It is a SECOND accumulator beside the flow one, not a quantity of trmc_stream_set_exceedance (which goes on refusing
+ * TRMC_X_DEPTH): its threshold table is the stream's own -- metres and m3/s never share a table -- and one stream may keep both, flow
+ * recurrence and out of bank over the same forecast.  The state lives on the device outside the ring; where a day is handed over
+ * one pass over the day's depths (csrc/k_stream_exceed_depth.inc) folds it in, in day order.  Nothing of it is a member of
+ * trmc_stream_day or crosses to the host per day.  It needs every step's depth: without full_output the stream launches the
+ * tile-kernel instances that write the depth plane at every step, as for trmc_stream_set_stage; with full_output the depth is read
+ * from the day's result (a strided walk: slower).  So trmc_stream_begin refuses what it refuses for stage: TRMC_EUNSUPPORTED in a
+ * stream with reservoir data assimilation and, without full_output, on a plan with velocity_on_demand < 0.  Off (the default): no
+ * buffer, no launch, the instances of a stream without it.
+ *   trmc_stream_set_depth_exceedance  th: HOST array [nseg][nlevels], row order, the plan's precision, nlevels 1..4 (for out of bank:
+ *                              what trmc_plan_bankfull_depth gives -- +inf, never over, on rows that route no Muskingum-Cunge
+ *                              step); copied, before the call returns, into a device table of the stream's own, independent of
+ *                              trmc_plan_set_thresholds.  nlevels == 0 withdraws the declaration and releases its buffers.  Before
+ *                              trmc_stream_begin; it stays until the next call.  TRMC_ESTATE while a stream is in progress;
+ *                              TRMC_EINVAL on the dataflow engine, for nlevels outside 0..4, for a NULL th with nlevels > 0 and
+ *                              for a NULL plan.  The steps are counted in 32 bits on the device: trmc_stream_push_day is
+ *                              TRMC_EUNSUPPORTED for the day that would take the stream past 2^31 - 1.
+ *   trmc_stream_depth_exceedance  HOST arrays int64 [nseg][nlevels], row order (any may be NULL); synchronous on the copy stream
+ *                              behind the last fold queued: returns when the figures over all days handed over so far are on the
+ *                              host and writes that number of days to days_out.  TRMC_ESTATE when no stream is in progress, when
+ *                              it was begun without a depth exceedance or when no day is complete yet.
+ *   trmc_stream_depth_exceedance_kernel_ms  device time (ms) of the last fold queued, from a pair of events around the kernel; waits
+ *                              for it.  TRMC_ESTATE as trmc_stream_depth_exceedance.
+ * With the feature on, the launches of every trmc_stream_push_day go behind the last fold queued, as for the Courant number.
+ */
+int trmc_stream_set_depth_exceedance(trmc_plan *plan, int32_t nlevels, const void *th);
+int trmc_stream_depth_exceedance(trmc_plan *plan, int64_t *steps_over, int64_t *first_step, int64_t *last_step, int64_t *longest_run,
+                                 int64_t *days_out);
+int trmc_stream_depth_exceedance_kernel_ms(trmc_plan *plan, double *ms_out);
+/*
  * STAGE HYDROGRAPHS of a stream day: the depth of EVERY step at the rows of the day's row set (trmc_stream_day::rowset, the rows of
  * its hydrographs), [rows of the set][nsteps] in the plan's precision -- column 2 of the same day routed as a window with the full
  * result, at those rows, bit for bit.  A reservoir row (trmc_set_reservoirs) gives its pool's water elevation; nudging changes a

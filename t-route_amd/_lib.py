@@ -191,6 +191,9 @@ SIGNATURES = {
     "trmc_stream_set_courant": (_int, [_vp, _int, C.c_double]),
     "trmc_stream_courant": (_int, [_vp, _vp, _vp, _vp, _P(_i64)]),
     "trmc_stream_courant_kernel_ms": (_int, [_vp, _P(C.c_double)]),
+    "trmc_stream_set_depth_exceedance": (_int, [_vp, _i32, _vp]),
+    "trmc_stream_depth_exceedance": (_int, [_vp, _vp, _vp, _vp, _vp, _P(_i64)]),
+    "trmc_stream_depth_exceedance_kernel_ms": (_int, [_vp, _P(C.c_double)]),
     "trmc_stream_set_stage": (_int, [_vp, _int]),
     "trmc_stream_stage_dest": (_int, [_vp, _vp]),
     "trmc_plan_set_nan_is_zero": (_int, [_vp, _int]),

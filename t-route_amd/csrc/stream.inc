@@ -81,6 +81,16 @@
 // slots >= 2 + ceil((lmax + 1) / tpd) gives (slots - 2) tpd >= lmax + 1.  Rows 1..nsteps, the forcing and the full result of the slot
 // are rewritten behind ev_free of day e, which is recorded behind the fold.  Off (the
 // default): no buffer, no launch, the instances of a stream without it.
+// DEPTH EXCEEDANCE OVER THE WHOLE STREAM (trmc_stream_set_depth_exceedance) -- how long a reach is out of bank or over an action / flood
+// stage, when it first goes over, the longest continuous inundation of the forecast -- is a SECOND accumulator of the exceedance's
+// shape beside the flow one, not a quantity of it: its threshold table is the stream's own (metres and m3/s never share a table), and
+// one stream may keep both.  As the Courant number it needs EVERY step's depth: such a stream launches stage's depth-plane tile
+// instances or, with full_output, reads the day's out[row][step][2], and inherits stage's refusals.  k_stream_exceed_depth
+// (k_stream_exceed_depth.inc) folds every day where it is handed over, in day order, and trmc_stream_depth_exceedance fetches the
+// accumulator.  ORDER: the fold reads the time rows 1..nsteps of the slot's depth plane, or the slot's full result, which are
+// rewritten behind the slot's ev_free -- recorded behind the fold -- only; the launches of a push are kept behind the last fold
+// queued all the same (stream_push_t: ev_dex), as for the Courant number, so that one rule covers every fold that reads the ring's
+// depths.  Off (the default): no buffer, no launch, the instances of a stream without it.
 // STAGE HYDROGRAPHS (trmc_stream_set_stage): the depth of EVERY step at the rows of the day's row set -- the hydrographs' rows --
 // for the caller who compares stage at forecast points and gages, and pool elevation at reservoirs, with action and flood stages.
 // A slot's depth plane has room for every step, but the tile kernels write the row of a tile's last step only; the stream that was
@@ -143,6 +153,7 @@ struct StreamRun {
     DevEvent ev_exc;                    // (the exceedance over the days) likewise
     DevEvent ev_cou0, ev_cou;           // (the Courant number over the days) around the last fold queued: the second as ev_exc is,
                                         // and what the next day's first launches wait for (stream_push_t)
+    DevEvent ev_dex0, ev_dex;           // (the depth exceedance over the days) likewise
     std::vector<DevEvent> ev_slab;      // ring: "slab launch g is complete" (the cluster launch g + 1 waits for it)
     std::vector<DevEvent> ev_free;      // [slots] the day that used the slot has handed its products over
     std::vector<DevEvent> ev_ready;     // [slots] the gathers of that day are through (copy stream waits)
@@ -205,6 +216,15 @@ struct StreamRun {
     int32_t exc_want = -1, exc = -1, exc_K = 0, exc_KP = 0;
     DevBuf exc_acc, exc_rows;
     int64_t exc_days = 0;
+    // the depth exceedance over the days (the head of this file).  dex_K_want, dex_th: trmc_stream_set_depth_exceedance's levels (0:
+    // none) and its table on the device, T [nseg][dex_KP_want] in row order, +inf behind the levels asked for -- they outlive a stream as
+    // exc_want does; dex_K, dex_KP: of the stream in progress; dex_acc: int32 [5][dex_KP][nseg_pad] in plan order; dex_rows: int64
+    // [4][nseg][dex_K] in row order, what a fetch gathers for the host; dex_days days are folded in (queued).  A stream that carries it
+    // has every step's depth: dpl, or the full result.
+    int32_t dex_K_want = 0, dex_KP_want = 0, dex_K = 0, dex_KP = 0;
+    bool dex_ms_ok = false; // (a fold of this stream lies between ev_dex0 and ev_dex)
+    DevBuf dex_th, dex_acc, dex_rows;
+    int64_t dex_days = 0;
 };
 
 } // extern "C++"
@@ -491,6 +511,27 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
         S.cou_days = e + 1;
         S.cou_ms_ok = true;
     }
+    if (S.dex_K > 0 && pl->nseg > 0) { // (the day's depths folded into the depth exceedance over the days: in day order, before the slot is freed)
+        const int32_t t0 = (int32_t)(e * S.nsteps);   // (stream_push_t keeps the stream's steps within int32)
+        // (every step's depth: in the slot's depth plane from time row 1, or in the full result -- stage's two sources)
+        const T *const d1 = S.dpl ? d + (size_t)pl->nseg_pad : (const T *)S.out.p + (size_t)slot * S.slot_out + 2;
+        const int64_t d_row = S.dpl ? 1 : 3 * (int64_t)S.nsteps, d_step = S.dpl ? pl->nseg_pad : 3;
+        auto fold = [&](auto kp) {
+            hipLaunchKernelGGL((k_stream_exceed_depth<T, decltype(kp)::value>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, d1,
+                               (const int32_t *)pl->sh->row_of_pos.p, (const T *)S.dex_th.p, (int32_t *)S.dex_acc.p, (int32_t)pl->nseg,
+                               pl->nseg_pad, S.nsteps, t0, S.dpl ? 0 : 1, d_row, d_step);
+        };
+        HIP_TRY(hipEventRecord(S.ev_dex0, pst)); // (with ev_dex: the fold's device time, trmc_stream_depth_exceedance_kernel_ms)
+        switch (S.dex_KP) {
+        case 1: fold(std::integral_constant<int, 1>{}); break;
+        case 2: fold(std::integral_constant<int, 2>{}); break;
+        case 4: fold(std::integral_constant<int, 4>{}); break;
+        default: return fail(TRMC_ESTATE, "internal: the stream's depth exceedance has no threshold table");
+        }
+        HIP_TRY(hipEventRecord(S.ev_dex, pst));
+        S.dex_days = e + 1;
+        S.dex_ms_ok = true;
+    }
     HIP_TRY(hipGetLastError());
     if (!any) {
         HIP_TRY(hipEventRecord(S.ev_free[(size_t)slot], pst));
@@ -638,21 +679,29 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
     S.cou_limit = S.cou_limit_want;
     S.cou_days = 0;
     S.cou_ms_ok = false;
-    S.dpl = (S.stage || S.cou) && !S.want_out;
+    S.dex_K = S.dex_K_want;
+    S.dex_KP = S.dex_KP_want;
+    S.dex_days = 0;
+    S.dex_ms_ok = false;
+    S.dpl = (S.stage || S.cou || S.dex_K > 0) && !S.want_out;
     if (S.dpl && pl->opt.velocity_on_demand < 0)
-        return fail(TRMC_EUNSUPPORTED, "the stage, and the depths the Courant number is formed from, of a stream without full_output are written by the "
-                                       "tile kernels' on-demand-velocity instances: not with trmc_plan_options.velocity_on_demand < 0");
+        return fail(TRMC_EUNSUPPORTED, "the stage, and the depths the Courant number and the depth exceedance are formed from, of a stream without "
+                                       "full_output are written by the tile kernels' on-demand-velocity instances: not with "
+                                       "trmc_plan_options.velocity_on_demand < 0");
     if (S.rda && S.stage)
         return fail(TRMC_EUNSUPPORTED, "stage hydrographs (trmc_stream_set_stage) are not supported in a stream with reservoir data "
                                        "assimilation: the _rda tile instances do not write the depth plane");
     if (S.rda && S.cou)
         return fail(TRMC_EUNSUPPORTED, "the Courant number over the days (trmc_stream_set_courant) is not supported in a stream with reservoir "
                                        "data assimilation: the _rda tile instances do not write the depth plane");
+    if (S.rda && S.dex_K > 0)
+        return fail(TRMC_EUNSUPPORTED, "the depth exceedance over the days (trmc_stream_set_depth_exceedance) is not supported in a stream with "
+                                       "reservoir data assimilation: the _rda tile instances do not write the depth plane");
     // (boundary rows are routed by nobody and have no depth: zeros in the slots' depth planes, as in a full result)
     if (S.dpl && tp.nboundary > 0)
         HIP_TRY(hipMemset2DAsync((T *)S.tm.p + S.plane, S.slot_tm * sizeof(T), 0, S.plane * sizeof(T), (size_t)S.slots, pl->stream));
     // (boundary rows of the full result are written by nobody: zeros, so that their reduction is the (0, 1) the carry gives)
-    if ((pd || S.stage) && S.want_out && tp.nboundary > 0) HIP_TRY(hipMemsetAsync(S.out.p, 0, (size_t)S.slots * S.slot_out * sizeof(T), pl->stream));
+    if ((pd || S.stage || S.dex_K > 0) && S.want_out && tp.nboundary > 0) HIP_TRY(hipMemsetAsync(S.out.p, 0, (size_t)S.slots * S.slot_out * sizeof(T), pl->stream));
     // THE TABLE OF THE DAY'S PRODUCTS (the head of StreamRun), in the enumeration's order: {carried, bytes of a day's copy, bytes of a
     // slot, has a buffer of its own, bytes of its total over the days}.  A summary part that the mask does not ask for holds no
     // buffer; the other buffers are kept between streams.
@@ -727,6 +776,17 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
         for (DevEvent *e : {&S.ev_cou0, &S.ev_cou})
             if (int rc = e->ensure(true)) return rc;
     }
+    // the depth exceedance over the days: the accumulator (zeroed below, in front of ev_begin) and what a fetch gathers into
+    const size_t dex_bytes = (size_t)kStreamExceedFields * (size_t)S.dex_KP * np * sizeof(int32_t);
+    if (S.dex_K < 1) {
+        S.dex_acc.release();
+        S.dex_rows.release();
+    } else {
+        if (int rc = S.dex_acc.ensure(dex_bytes)) return rc;
+        if (int rc = S.dex_rows.ensure(4 * (size_t)pl->nseg * (size_t)S.dex_K * sizeof(int64_t))) return rc;
+        for (DevEvent *e : {&S.ev_dex0, &S.ev_dex})
+            if (int rc = e->ensure(true)) return rc;
+    }
     // reservoir data assimilation: the slots' tables at their capacity, the carry with the state trmc_set_reservoir_da supplied
     // (or the plan's last window left in those tables); the days' state records are products (P_RDA)
     S.slot_rda = 0;
@@ -777,6 +837,7 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
     pl->mk_forcing.settle();
     HIP_TRY(hipMemsetAsync(pl->it_prev.p, 0, (size_t)np, st));
     if (S.exc >= 0 && exc_bytes > 0) HIP_TRY(hipMemsetAsync(S.exc_acc.p, 0, exc_bytes, st));
+    if (S.dex_K > 0 && dex_bytes > 0) HIP_TRY(hipMemsetAsync(S.dex_acc.p, 0, dex_bytes, st));
     if (S.cou && np > 0) {
         HIP_TRY(hipMemsetAsync(S.cou_peak.p, 0, np * sizeof(T), st));
         HIP_TRY(hipMemsetAsync(S.cou_step.p, 0, np * sizeof(int32_t), st));
@@ -821,7 +882,7 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
     hipStream_t hst = S.fst; // (the forcing's own stream: the products of earlier days leave on the plan's copy stream meanwhile)
     if (d >= S.slots && S.days_complete <= d - S.slots)
         return fail(TRMC_ESTATE, "internal: the slot of the new day still belongs to a day that has not been queued to its end");
-    if ((S.exc >= 0 || S.cou) && (d + 1) * (int64_t)S.nsteps > (int64_t)INT32_MAX)
+    if ((S.exc >= 0 || S.cou || S.dex_K > 0) && (d + 1) * (int64_t)S.nsteps > (int64_t)INT32_MAX)
         return fail(TRMC_EUNSUPPORTED, "the exceedance and the Courant number over the days of a stream count its steps in 32 bits on the device: this "
                                        "day would take the stream past 2^31 - 1 steps -- begin a new stream");
     StreamProd &p = S.prod[(size_t)slot];
@@ -899,6 +960,7 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
     HIP_TRY(hipStreamWaitEvent(pl->stream, S.ev_forcing[(size_t)slot], 0));
     // (the Courant number: this day's last launches rewrite time row 0 of a slot whose fold may still read it -- the head of this file)
     if (S.cou && S.cou_days > 0) HIP_TRY(hipStreamWaitEvent(pl->wstream, S.ev_cou, 0));
+    if (S.dex_K > 0 && S.dex_days > 0) HIP_TRY(hipStreamWaitEvent(pl->wstream, S.ev_dex, 0)); // (the depth exceedance: likewise)
     S.days_pushed = d + 1;
     hipStream_t tst = S.W > 0 ? pl->wstream : pl->stream; // (the stream whose launches a day's push is timed on)
     HIP_TRY(hipEventRecord(S.ev_t0[(size_t)slot], tst));
@@ -1205,6 +1267,81 @@ int trmc_stream_courant_kernel_ms(trmc_plan *pl, double *ms_out)
     HIP_TRY(hipEventSynchronize(S.ev_cou));
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, S.ev_cou0, S.ev_cou));
+    *ms_out = ms;
+    return 0;
+}
+
+int trmc_stream_set_depth_exceedance(trmc_plan *pl, int32_t nlevels, const void *th)
+{
+    if (int rc = stream_check(pl, false)) return rc;
+    if (pl->flow) return fail(TRMC_EINVAL, "a stream of windows runs on the level engine");
+    if (nlevels < 0 || nlevels > 4) return fail(TRMC_EINVAL, "nlevels must be 0..4 (0: no depth exceedance)");
+    if (nlevels > 0 && !th) return fail(TRMC_EINVAL, "th is NULL");
+    if (nlevels == 0) { // (withdrawn: the next stream holds no accumulator and queues no fold; nothing is kept)
+        if (!pl->seq) return 0;
+        StreamRun &S = *pl->seq;
+        S.dex_K_want = S.dex_KP_want = 0;
+        for (DevBuf *b : {&S.dex_th, &S.dex_acc, &S.dex_rows}) b->release();
+        return 0;
+    }
+    if (!pl->seq) pl->seq = std::make_unique<StreamRun>();
+    StreamRun &S = *pl->seq;
+    // the table's rows are 1, 2 or 4 wide (k_stream_exceed_depth's KP), +inf -- never over -- behind the caller's levels
+    const int32_t pad = nlevels == 3 ? 4 : nlevels;
+    S.dex_K_want = S.dex_KP_want = 0; // (nothing half-set if the copy fails)
+    const int rc = by_precision(pl, [&](auto t) -> int {
+        using T = decltype(t);
+        const T *const src = (const T *)th;
+        std::vector<T> host((size_t)pl->nseg * pad, std::numeric_limits<T>::infinity());
+        for (int64_t r = 0; r < pl->nseg; ++r)
+            for (int32_t k = 0; k < nlevels; ++k) host[(size_t)r * pad + k] = src[(size_t)r * nlevels + k];
+        if (int rc = S.dex_th.ensure(host.size() * sizeof(T))) return rc;
+        // (synchronous: the table is whole before the call returns, whichever stream reads it)
+        if (!host.empty()) HIP_TRY(hipMemcpy(S.dex_th.p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
+        return 0;
+    });
+    if (rc) return rc;
+    S.dex_K_want = nlevels;
+    S.dex_KP_want = pad;
+    return 0;
+}
+
+int trmc_stream_depth_exceedance(trmc_plan *pl, int64_t *steps_over, int64_t *first_step, int64_t *last_step, int64_t *longest_run,
+                                 int64_t *days_out)
+{
+    if (int rc = stream_check(pl, true)) return rc;
+    StreamRun &S = *pl->seq;
+    if (S.dex_K < 1)
+        return fail(TRMC_ESTATE, "the stream was begun without a depth exceedance (trmc_stream_set_depth_exceedance precedes trmc_stream_begin)");
+    if (S.dex_days < 1)
+        return fail(TRMC_ESTATE, "no day of the stream is complete yet: its last rows run " + std::to_string(S.lmax)
+                                     + " tiles behind its first -- push further days or trmc_stream_flush");
+    const int64_t days = S.dex_days;
+    const size_t n = (size_t)pl->nseg * (size_t)S.dex_K;
+    int64_t *const dst[4] = {steps_over, first_step, last_step, longest_run};
+    // behind the last fold queued (nothing is queued meanwhile: the calls of a plan come from one thread)
+    HIP_TRY(hipStreamWaitEvent(pl->cstream, S.ev_dex, 0));
+    if (n && (steps_over || first_step || last_step || longest_run)) {
+        hipLaunchKernelGGL(k_stream_exceed_depth_rows, dim3(blocks_for((int64_t)n)), dim3(kBlock), 0, pl->cstream, (const int32_t *)S.dex_acc.p,
+                           (const int32_t *)pl->sh->pos_of_row.p, (int64_t *)S.dex_rows.p, (int32_t)pl->nseg, pl->nseg_pad, S.dex_K, S.dex_KP);
+        HIP_TRY(hipGetLastError());
+        for (int f = 0; f < 4; ++f)
+            if (dst[f]) HIP_TRY(hipMemcpyAsync(dst[f], (const int64_t *)S.dex_rows.p + (size_t)f * n, n * sizeof(int64_t), hipMemcpyDeviceToHost, pl->cstream));
+    }
+    HIP_TRY(hipStreamSynchronize(pl->cstream));
+    if (days_out) *days_out = days;
+    return 0;
+}
+
+int trmc_stream_depth_exceedance_kernel_ms(trmc_plan *pl, double *ms_out)
+{
+    if (int rc = stream_check(pl, true)) return rc;
+    StreamRun &S = *pl->seq;
+    if (!ms_out) return fail(TRMC_EINVAL, "ms_out is NULL");
+    if (S.dex_K < 1 || !S.dex_ms_ok) return fail(TRMC_ESTATE, "no day has been folded into the depth exceedance of this stream yet");
+    HIP_TRY(hipEventSynchronize(S.ev_dex));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, S.ev_dex0, S.ev_dex));
     *ms_out = ms;
     return 0;
 }

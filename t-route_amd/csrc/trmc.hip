@@ -83,6 +83,7 @@ namespace {
 #include "k_window_courant.inc"
 #include "k_window_exceed.inc"
 #include "k_stream_exceed.inc"
+#include "k_stream_exceed_depth.inc"
 #include "k_stream_courant.inc"
 // ---------------------------------------------------------------- plan
 #include "dev_owner.hpp"

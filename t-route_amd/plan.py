@@ -612,6 +612,62 @@ class RoutingPlan:
         res.update((name, a) for name, a in out.items() if a is not None)
         return res
 
+    def stream_depth_thresholds(self, th):
+        """``th`` of a stream's depth exceedance, checked: [nseg] or [nseg, K] with K <= 4 (returned [nseg, K], contiguous, in the
+        plan's dtype), the string "bankfull" (``bankfull_depth()`` of this plan: +inf, never over, on rows that route no
+        Muskingum-Cunge step) or None; ValueError otherwise."""
+        if th is None:
+            return None
+        if isinstance(th, str):
+            if th != "bankfull":
+                raise ValueError(f"depth exceedance of a stream: thresholds [nseg] or [nseg, K], 'bankfull' or None, got {th!r}")
+            th = self.bankfull_depth()
+        th = np.asarray(th)
+        th = th[:, None] if th.ndim == 1 else th
+        if th.ndim != 2 or th.shape[0] != self.nseg or not 1 <= th.shape[1] <= 4:
+            raise ValueError(f"depth exceedance of a stream: thresholds must be [nseg] or [nseg, K] with nseg = {self.nseg} and K <= 4: "
+                             f"got {th.shape}")
+        return np.ascontiguousarray(th, dtype=self.dtype)
+
+    def stream_set_depth_exceedance(self, th="bankfull"):
+        """The streams on this plan keep, on the device and over ALL their days, the threshold exceedance of every row's DEPTH
+        against ``th`` -- [nseg] or [nseg, K] (K <= 4) in row order, metres, or "bankfull" (``bankfull_depth()``: the steps a row
+        is out of bank): steps over, first and last step, longest run, the steps counted on over the days and a run carried over a
+        day's end (trmc_stream_set_depth_exceedance; ``stream_depth_exceedance`` fetches).  The depth is what ``stage`` and the
+        full result hand out: a reservoir row's is its pool's elevation, a boundary row's 0.  A second accumulator beside
+        ``stream_set_exceedance``'s, with a threshold table of its own (``set_thresholds`` is not touched): a stream may keep both.
+        Such a stream writes every step's depth, as one with ``stream_set_stage`` does, and ``stream_begin`` refuses what it
+        refuses for stage.  Declared before ``stream_begin``; it stays until the next call; ``None`` withdraws it."""
+        th = self.stream_depth_thresholds(th)
+        if self.engine != "levels":
+            raise ValueError("a stream of days runs on the level engine: its depth exceedance needs engine='levels'")
+        _lib.check(_lib.lib().trmc_stream_set_depth_exceedance(self._h, 0 if th is None else th.shape[1], _lib.ptr(th)))
+        self._stream_depth_levels = 0 if th is None else th.shape[1]
+
+    def stream_depth_exceedance(self, parts=("steps_over", "first_step", "last_step", "longest_run")):
+        """The depth exceedance over all days of the stream in progress that have been handed over so far
+        (trmc_stream_depth_exceedance, synchronous): a dict with ``"days"`` and, of ``steps_over``, ``first_step``, ``last_step``
+        and ``longest_run``, the parts asked for -- int64 [nseg, K] arrays in row order, the steps 1-based from the stream's first
+        step, as ``window_exceedance("depth")`` defines them over the days' depths one after the other."""
+        parts = (parts,) if isinstance(parts, str) else tuple(parts or ())
+        unknown = [p for p in parts if p not in self.WINDOW_EXCEEDANCE_PARTS]
+        if unknown:
+            raise ValueError(f"unknown part(s) of a stream's depth exceedance {unknown}: one of {list(self.WINDOW_EXCEEDANCE_PARTS)}")
+        if not parts:
+            raise ValueError("stream_depth_exceedance: no part asked for")
+        k = getattr(self, "_stream_depth_levels", 0)
+        out = {name: (np.empty((self.nseg, k), np.int64) if name in parts else None) for name in self.WINDOW_EXCEEDANCE_PARTS}
+        days = C.c_int64(0)
+        _lib.check(_lib.lib().trmc_stream_depth_exceedance(self._h, *(_lib.ptr(out[name]) for name in self.WINDOW_EXCEEDANCE_PARTS), C.byref(days)))
+        res = {"days": int(days.value)}
+        res.update((name, a) for name, a in out.items() if a is not None)
+        return res
+
+    def stream_depth_exceedance_kernel_ms(self):
+        """device time (ms) of the last day's fold into the stream's depth exceedance, from events around the kernel
+        (trmc_stream_depth_exceedance_kernel_ms; waits for it)"""
+        return self._kernel_ms(_lib.lib().trmc_stream_depth_exceedance_kernel_ms)
+
     @staticmethod
     def stream_courant_limit(limit):
         """``limit`` of a stream's Courant number, checked: a real number (returned as a float) or None; ValueError otherwise."""

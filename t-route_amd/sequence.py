@@ -446,6 +446,21 @@ class RouteStream:
     -- once ``route()`` has yielded its last day, next to ``rs.total``.  It is not a product of the day: the tuples do not change.
     Flow only ("depth", "velocity", "bankfull": NotImplementedError -- route the day in question as a window).
 
+    ``depth_exceedance=thresholds`` or ``depth_exceedance="bankfull"``: the device also keeps, over ALL days of the stream, every
+    row's threshold exceedance of DEPTH -- how long a reach is out of bank or over an action / flood stage, when it first goes over,
+    the longest continuous inundation of the forecast.  ``thresholds`` [rows] or [rows, K] (K <= 4), metres, in the router's row
+    order, a rank of a multi-rank job taking its own ``rows`` of them as ``exceedance=`` does; ``"bankfull"`` takes
+    ``bankfull_depth()`` of the plan that streams: +inf where a row has no compound channel to leave (a reservoir) or is a rank's
+    boundary copy, so such a row is never over.  ``rs.depth_exceedance`` holds ``RoutingPlan.stream_depth_exceedance()`` --
+    ``"days"`` and int64 [rows, K] ``steps_over``, ``first_step``, ``last_step``, ``longest_run`` over this rank's ``rows``, the
+    steps 1-based from the stream's first step and a run carried over a day's end -- once ``route()`` has yielded its last day,
+    next to ``rs.exceedance``.  The depth is the one ``stage=True`` and ``full_output`` hand out: the pool's water elevation at a
+    reservoir row, the step's own depth at a gage row, 0 at a rank's boundary copies (which report what a depth of 0 gives).  A
+    second accumulator with a threshold table of its own: ``exceedance=`` and ``depth_exceedance=`` may be asked for together.
+    Several ranks are supported -- the fold needs a row's own depth only, which every rank holds for its own rows.  Such a stream
+    writes every step's depth as one with ``stage=True`` does; a router with ``reservoir_da``: NotImplementedError.  It is not a
+    product of the day: the tuples do not change.
+
     ``courant=limit``: the device also keeps, over ALL days of the stream, every row's Courant number cn = ck dt / dx -- the
     highest, the step it was first reached at and the number of steps with cn > ``limit``: ``rs.courant`` holds
     ``RoutingPlan.stream_courant()`` -- ``"days"``, ``"peak_cn"``, ``"peak_cn_step"`` and ``"steps_over"`` over this rank's
@@ -475,7 +490,7 @@ class RouteStream:
 
     def __init__(self, router, nsteps, qts_subdivisions, output_stride=None, full_output=False, slots=0, latency="throughput",
                  hydrographs_on_every_rank=False, comm=None, exchange=None, reservoir_da_ncol=None, summary=None,
-                 daily_summary=True, courant=None, stage=False, exceedance=None):
+                 daily_summary=True, depth_exceedance=None, courant=None, stage=False, exceedance=None):
         """comm / exchange (several ranks): the communicator -- default: the one given to ``router.enable_device_exchange`` -- and
         how the daily cut-edge hydrographs travel: "device" (gather kernel -> all-gather on the exchange stream -> boundary rows,
         everything in HBM: RCCL over xGMI) or "host" (through ``comm.all_gather_rows_host``: any communicator with that method,
@@ -525,6 +540,22 @@ class RouteStream:
             if th.ndim != 2 or th.shape[0] != router.nseg or not 1 <= th.shape[1] <= 4:
                 raise ValueError(f"exceedance: thresholds must be [rows] or [rows, K] with rows = {router.nseg} and K <= 4: got {th.shape}")
             self._exc_th = th
+        self.depth_exceedance = None
+        self._dex_th = None
+        if depth_exceedance is not None:
+            if isinstance(depth_exceedance, str):
+                if depth_exceedance != "bankfull":
+                    raise ValueError(f"depth_exceedance: thresholds [rows] or [rows, K], or 'bankfull': got {depth_exceedance!r}")
+                self._dex_th = "bankfull"       # (bankfull_depth() of the plan that streams: route())
+            else:
+                th = np.asarray(depth_exceedance)
+                th = th[:, None] if th.ndim == 1 else th
+                if th.ndim != 2 or th.shape[0] != router.nseg or not 1 <= th.shape[1] <= 4:
+                    raise ValueError(f"depth_exceedance: thresholds must be [rows] or [rows, K] with rows = {router.nseg} and K <= 4: got {th.shape}")
+                self._dex_th = th
+            if getattr(router, "_reservoir_da", None) is not None:
+                raise NotImplementedError("depth_exceedance= with reservoir data assimilation: the tile kernels of such a stream do not write "
+                                          "the depth plane at every step (as for stage=True)")
         if latency not in ("throughput", "low"):
             raise ValueError("latency must be 'throughput' or 'low'")
         self.r = router
@@ -727,6 +758,11 @@ class RouteStream:
         if self._cou_limit is not None or getattr(P, "_stream_courant", None) is not None:
             P.stream_set_courant(self._cou_limit)
         self._courant = None
+        if self._dex_th is not None:                           # (a table of the stream's own: this rank's rows of the thresholds)
+            P.stream_set_depth_exceedance("bankfull" if isinstance(self._dex_th, str) else self._dex_th[rows])
+        elif getattr(P, "_stream_depth_levels", 0) > 0:        # (an earlier stream's declaration is withdrawn)
+            P.stream_set_depth_exceedance(None)
+        self.depth_exceedance = None
         P.stream_begin(nsteps, self.qts, slots=slots, full_output=self.full_output and not self.output_stride, output_stride=self.output_stride,
                        **({} if rda is None else {"reservoir_da": True if self._rda_ncol is None else self._rda_ncol}))
         self.info = info = P.stream_info()
@@ -768,6 +804,8 @@ class RouteStream:
             self.exceedance = P.stream_exceedance()
         if self._cou_limit is not None: # (... and the Courant number)
             self._courant = P.stream_courant()
+        if self._dex_th is not None:    # (... and the depth exceedance)
+            self.depth_exceedance = P.stream_depth_exceedance()
         while delivered < d:
             yield self._deliver(delivered, ring, gage, rdac, extras)
             delivered += 1

@@ -13,6 +13,11 @@ row and the hydrographs of sampled rows bit for bit, and what a day costs either
                                [--exceedance K]             the threshold exceedance of every row's flow over ALL days of the stream at
                                                             K levels (trmc_stream_set_exceedance), fetched once at the end; checked
                                                             against the numpy loop over the one-by-one days' flows where that fits
+                               [--depth-exceedance K]       the threshold exceedance of every row's DEPTH over ALL days of the stream at K
+                                                            levels (trmc_stream_set_depth_exceedance): quantiles of the one-by-one days'
+                                                            depths where they are known, else multiples of the bankfull depth; checked
+                                                            against the numpy loop where that fits; the fold kernel's time from events
+                               [--depth-bankfull]           ... at ONE level, the plan's bankfull depth: the steps a row is out of bank
                                [--courant LIMIT]            the stream is run twice, without and with every row's Courant number over the
                                                             whole stream (trmc_stream_set_courant): peak, its step, steps with cn > LIMIT;
                                                             checked against the fold of the one-by-one days' window_courant_summary;
@@ -54,6 +59,8 @@ ap.add_argument("--summary", action="store_true", help="per-row peak flow, step 
 ap.add_argument("--summary-depth", action="store_true", help="the day's peak depth and its step as well (with or without --summary)")
 ap.add_argument("--summary-total", action="store_true", help="the totals over the days of the stream; no per-day summary array crosses to the host")
 ap.add_argument("--exceedance", type=int, default=0, metavar="K", help="exceedance of K (1..4) flow thresholds a row over the whole stream, kept on the device")
+ap.add_argument("--depth-exceedance", type=int, default=0, metavar="K", help="exceedance of K (1..4) depth thresholds a row over the whole stream, kept on the device")
+ap.add_argument("--depth-bankfull", action="store_true", help="the depth exceedance against the plan's bankfull depth (one level): out of bank")
 ap.add_argument("--courant", type=float, default=None, metavar="LIMIT", help="every row's Courant number over the whole stream (peak, its step, steps with cn > LIMIT), kept on the device")
 ap.add_argument("--stage", action="store_true", help="the depth of every step at the rows of the row set as a stream product")
 ap.add_argument("--outlets", action="store_true", help="the row set: every network's outlet (default: 3000 sampled rows)")
@@ -65,6 +72,14 @@ if a.summary_total and not (a.summary or a.summary_depth):
     ap.error("--summary-total totals --summary and / or --summary-depth")
 if not 0 <= a.exceedance <= 4:
     ap.error("--exceedance: 1 to 4 levels (0: none)")
+if not 0 <= a.depth_exceedance <= 4:
+    ap.error("--depth-exceedance: 1 to 4 levels (0: none)")
+if a.depth_bankfull and a.depth_exceedance > 1:
+    ap.error("--depth-bankfull is one level")
+if a.depth_bankfull:
+    a.depth_exceedance = 1
+if a.depth_exceedance and a.reservoir_da:
+    ap.error("--depth-exceedance: not with --reservoir-da (the tile kernels of such a stream do not write the depth plane)")
 _lib.single_hw_queue_per_priority("stream_probe")
 nnet = S.CONUS_NNET if a.nseg == S.CONUS_NSEG else max(1, a.nseg // 185)
 net = S.generate(a.nseg, nnet, cache_dir=os.environ.get("TRMC_SYNTH_CACHE", "/tmp"))
@@ -176,6 +191,8 @@ def exceedance_of(x, th):
 any_summary = a.summary or a.summary_depth
 check_exc = a.exceedance and not a.no_check and n * nsteps * a.days <= 1 << 26
 ref_q = []
+check_dex = a.depth_exceedance and not a.no_check and n * nsteps * a.days <= 1 << 26
+ref_d = []
 daily = any_summary and not a.summary_total
 check_summary = any_summary and not a.no_check and n * nsteps <= 1 << 26
 ref_sum = []
@@ -215,7 +232,7 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
             st = p.route_device(nsteps, qts, True)
             fin = p.download_final_state()
             hyd = p.gather_flow_rows(sample)
-            fvd = p.download_fvd(a.stride) if (a.stride or a.full) else None
+            fvd = p.download_fvd(a.stride or 1) if (a.stride or a.full) else None
             if check_summary:
                 full = fvd if (a.full and not a.stride) else p.download_fvd()
                 ref_sum.append(summary_of(np.ascontiguousarray(full[:, :, 0])) + peak_of(np.ascontiguousarray(full[:, :, 2])))
@@ -223,6 +240,8 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
                 ref_stage.append(np.ascontiguousarray((fvd if (a.full and not a.stride) else p.download_fvd())[sample, :, 2]))
             if check_exc:
                 ref_q.append(np.ascontiguousarray((full if check_summary else p.download_fvd())[:, :, 0]))
+            if check_dex:
+                ref_d.append(np.ascontiguousarray((fvd if (a.full and not a.stride) else p.download_fvd())[:, :, 2]))
             if check_cou:
                 ref_cou.append(p.window_courant_summary(a.courant))
             if a.reservoir_da:
@@ -254,6 +273,18 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
                 exc_th = days[0].mean(axis=1, dtype=np.float32)[:, None] * np.array([1, 10, 100, 1000], np.float32)[None, :a.exceedance]
             p.set_thresholds(exc_th)
             p.stream_set_exceedance("flow")
+        if a.depth_exceedance:
+            # a row's levels: its bankfull depth; or quantiles of its own depths over the stream where they are known (the check),
+            # else multiples of its bankfull depth
+            if check_dex:
+                dex_x = np.concatenate(ref_d, axis=1)
+            if a.depth_bankfull:
+                dex_th = p.bankfull_depth()[:, None]
+            elif check_dex:
+                dex_th = np.quantile(dex_x.astype(np.float64), (0.5, 0.25, 0.9, 0.75)[:a.depth_exceedance], axis=1).T.astype(np.float32)
+            else:
+                dex_th = p.bankfull_depth()[:, None] * np.array([1, 0.5, 0.25, 0.125], np.float32)[None, :a.depth_exceedance]
+            p.stream_set_depth_exceedance(dex_th)
         p.stream_begin(nsteps, qts, reservoir_da=bool(a.reservoir_da) or None, slots=a.slots + a.later if a.slots else (a.later and 2 + -(-(int(p.lags()[0].max(initial=0)) + 1) // (nsteps // p.tile_steps)) + a.later), full_output=a.full and not a.stride, output_stride=a.stride)
         info = p.stream_info()
         print("stream:", info, flush=True)
@@ -346,6 +377,21 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
                 same = exc["days"] == a.days and all(np.array_equal(exc[k], want[k]) for k in want)
                 ok = ok and same
                 print("   exceedance equals the numpy loop over the one-by-one days' flows:", same, flush=True)
+        if a.depth_exceedance:
+            fold_ms = p.stream_depth_exceedance_kernel_ms()
+            print(f"   the last day's depth fold (k_stream_exceed_depth, from the {'full result' if a.full and not a.stride else 'depth plane'}), "
+                  f"from events around the kernel: {fold_ms:.3f} ms", flush=True)
+            t1 = time.perf_counter()
+            dex = p.stream_depth_exceedance()
+            print(f"   depth exceedance at {a.depth_exceedance} level(s){' (bankfull)' if a.depth_bankfull else ''} over {dex['days']} days fetched in "
+                  f"{(time.perf_counter() - t1) * 1e3:.2f} ms: {int(np.count_nonzero(dex['steps_over']))} of {dex['steps_over'].size} (row, level) pairs went "
+                  f"over, longest run {int(dex['longest_run'].max())} steps;",
+                  "not checked (no check asked for, or too large for a host loop)" if not check_dex else "", flush=True)
+            if check_dex:
+                want = exceedance_of(dex_x, np.ascontiguousarray(dex_th))
+                same = dex["days"] == a.days and all(np.array_equal(dex[k], want[k]) for k in want)
+                ok = ok and same
+                print("   depth exceedance equals the numpy loop over the one-by-one days' depths:", same, flush=True)
         if cou_on:
             fold_ms = p.stream_courant_kernel_ms()
             print(f"   the last day's fold (k_stream_courant), from events around the kernel: {fold_ms:.3f} ms", flush=True)
