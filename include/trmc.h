@@ -306,6 +306,31 @@ typedef struct trmc_stream_day {
 } trmc_stream_day;
 int trmc_stream_set_gages(trmc_plan *plan, int64_t ngage, const int64_t *gage_rows);
 int trmc_stream_push_day(trmc_plan *plan, const trmc_stream_day *day);
+/* A STREAM DAY AS PACKED CHRTOUT COLUMNS (additions within ABI 19; csrc/stream.inc): trmc_upload_forcing_packed's counterpart for a
+ * stream -- the day's forcing arrives as the files hold it, one or two int32 variables in file order, and ONE kernel on the forcing's
+ * stream decodes, joins on the feature id and writes the forcing of the day's ring slot.  The rule is trmc_upload_forcing_packed's,
+ * the same device function: masked where == _FillValue / missing_value or outside the valid range and then 0, otherwise
+ * raw * scale_factor + add_offset in double; the sum of the two variables in double; the reference's cast to float32 (widened to the
+ * plan's precision).  A row the files do not hold gets inflow 0.  The decode produces no NaN.
+ *   trmc_stream_set_packed_forcing  the join and the packing facts, declared ONCE, before trmc_stream_begin: nfeat, the length of the
+ *                      files' feature axis (at most INT32_MAX); feat_of_row [nseg], the index of every row on that axis (-1: not in
+ *                      the files; an entry >= nfeat is TRMC_EINVAL), put into plan order and uploaded here; pack_a[6], and pack_b[6] or
+ *                      NULL for the single-variable (q_lateral) form: (scale_factor, add_offset, _FillValue, missing_value,
+ *                      valid_min, valid_max), NaN where the file defines none -- trmc_upload_forcing_packed's, field for field.  Host
+ *                      memory, copied before the call returns.  nfeat = 0 or feat_of_row = NULL withdraws the declaration.  It stays
+ *                      until the next call, as trmc_stream_set_gages does; TRMC_ESTATE while a stream is in progress.  A stream
+ *                      begun behind it sizes its staging area for the raw blocks (up to twice the float forcing's bytes).
+ *   trmc_stream_push_day_packed  trmc_stream_push_day with raw_a, raw_b [nq][nfeat] int32 in place of day->qlat (which must be NULL;
+ *                      every other member keeps its meaning, nudging and reservoir tables included): page-locked host memory for a
+ *                      copy that runs beside the launches, unchanged until the day has begun on the device.  raw_b is given exactly
+ *                      when pack_b was.  TRMC_ESTATE without the declaration, TRMC_EINVAL for raw_a = NULL, a raw_b that does not
+ *                      match the declaration, and a day->nq other than the stream's.  Float days and packed days may alternate in
+ *                      one stream.
+ *   trmc_stream_packed_forcing_kernel_ms  device time (HIP events, ms) of the last decode queued, beside whatever else ran; waits for
+ *                      it.  TRMC_ESTATE before the stream's first packed day. */
+int trmc_stream_set_packed_forcing(trmc_plan *plan, int64_t nfeat, const int64_t *feat_of_row, const double *pack_a, const double *pack_b);
+int trmc_stream_push_day_packed(trmc_plan *plan, const trmc_stream_day *day, const int32_t *raw_a, const int32_t *raw_b);
+int trmc_stream_packed_forcing_kernel_ms(trmc_plan *plan, double *ms_out);
 /* A PER-ROW SUMMARY of every day (additions within ABI 19; csrc/stream.inc): how high every row got, when, and how much water
  * passed -- 3 x [nseg] per day instead of the hourly block or the full result.  It is formed from ALL nsteps flows of the day
  * (not from every output_stride-th one) where the day is handed over, by one reduction over the slot's flow plane; the tile

@@ -196,6 +196,9 @@ SIGNATURES = {
     "trmc_stream_depth_exceedance_kernel_ms": (_int, [_vp, _P(C.c_double)]),
     "trmc_stream_set_stage": (_int, [_vp, _int]),
     "trmc_stream_stage_dest": (_int, [_vp, _vp]),
+    "trmc_stream_set_packed_forcing": (_int, [_vp, _i64, _vp, _vp, _vp]),
+    "trmc_stream_push_day_packed": (_int, [_vp, _vp, _vp, _vp]),
+    "trmc_stream_packed_forcing_kernel_ms": (_int, [_vp, _P(C.c_double)]),
     "trmc_plan_set_nan_is_zero": (_int, [_vp, _int]),
     "trmc_host_alloc": (_int, [C.c_size_t, C.POINTER(C.c_void_p)]),
     "trmc_host_free": (_int, [_vp]),

@@ -681,6 +681,23 @@ int trmc_upload_forcing(trmc_plan *pl, int nsteps, const void *qlat, int64_t nq,
     return stage_state(pl, nsteps, nq, q0, boundary_fvd);
 }
 
+// the packing facts of one variable as the ingest kernels take them: pack = (scale_factor, add_offset, _FillValue, missing_value,
+// valid_min, valid_max), NaN where the file defines none; NULL: the variable that is not there (never read)
+static PackSpec pack_spec(const double *k)
+{
+    if (!k) return PackSpec{1.0, 0.0, 0, 0, INT32_MIN, INT32_MAX, 0, 0};
+    PackSpec s;
+    s.scale = k[0];
+    s.offset = k[1];
+    s.use1 = k[2] == k[2];
+    s.use2 = k[3] == k[3];
+    s.fill1 = s.use1 ? (int32_t)k[2] : 0;
+    s.fill2 = s.use2 ? (int32_t)k[3] : 0;
+    s.vmin = k[4] == k[4] ? (int32_t)k[4] : INT32_MIN; // NaN: no lower / upper bound in the file
+    s.vmax = k[5] == k[5] ? (int32_t)k[5] : INT32_MAX;
+    return s;
+}
+
 int trmc_upload_forcing_packed(trmc_plan *pl, int nsteps, int64_t nq, int64_t nfeat, const int32_t *raw_a,
                                const int32_t *raw_b, const double *pack_a, const double *pack_b,
                                const int64_t *feat_of_row, const void *q0, const void *boundary_fvd)
@@ -689,19 +706,7 @@ int trmc_upload_forcing_packed(trmc_plan *pl, int nsteps, int64_t nq, int64_t nf
     if (nfeat < 0 || (pl->nseg > 0 && (!raw_a || !pack_a || !feat_of_row))) return fail(TRMC_EINVAL, "raw_a/pack_a/feat_of_row is NULL");
     if (raw_b && !pack_b) return fail(TRMC_EINVAL, "pack_b is NULL");
     if (nfeat > INT32_MAX) return fail(TRMC_EINVAL, "feature axis too long");
-    auto spec = [](const double *k) {
-        PackSpec s;
-        s.scale = k[0];
-        s.offset = k[1];
-        s.use1 = k[2] == k[2];
-        s.use2 = k[3] == k[3];
-        s.fill1 = s.use1 ? (int32_t)k[2] : 0;
-        s.fill2 = s.use2 ? (int32_t)k[3] : 0;
-        s.vmin = k[4] == k[4] ? (int32_t)k[4] : INT32_MIN; // NaN: no lower / upper bound in the file
-        s.vmax = k[5] == k[5] ? (int32_t)k[5] : INT32_MAX;
-        return s;
-    };
-    const PackSpec ka = spec(pack_a), kb = raw_b ? spec(pack_b) : PackSpec{1.0, 0.0, 0, 0, INT32_MIN, INT32_MAX, 0, 0};
+    const PackSpec ka = pack_spec(pack_a), kb = pack_spec(raw_b ? pack_b : nullptr);
     const int64_t n = pl->nseg;
     std::vector<int32_t> feat_of_pos((size_t)(n > 0 ? n : 1), -1);
     for (int64_t p = 0; p < n; ++p) {

@@ -694,6 +694,19 @@ __device__ __forceinline__ double unpack_cf(int32_t raw, const PackSpec &k)
     if ((k.use1 && raw == k.fill1) || (k.use2 && raw == k.fill2) || raw < k.vmin || raw > k.vmax) return 0.0;
     return (double)raw * k.scale + k.offset;
 }
+// THE RULE for one value: feature f (-1: the files do not hold the row, inflow 0) of the file whose columns begin at `col`
+// (= j * nfeat).  Both ingest kernels call it, so a window and a stream day decode to the same bits.
+template <class T>
+__device__ __forceinline__ T ingest_packed_at(const int32_t *__restrict__ raw_a, const int32_t *__restrict__ raw_b, const PackSpec &ka,
+                                              const PackSpec &kb, int32_t f, size_t col)
+{
+    double v = 0.0;
+    if (f >= 0) {
+        v = unpack_cf(raw_a[col + (size_t)f], ka);
+        if (raw_b) v = v + unpack_cf(raw_b[col + (size_t)f], kb);
+    }
+    return (T)(float)v;
+}
 template <class T>
 __global__ void __launch_bounds__(kBlock)
 k_ingest_packed(const int32_t *__restrict__ raw_a, const int32_t *__restrict__ raw_b, const PackSpec ka, const PackSpec kb,
@@ -703,14 +716,32 @@ k_ingest_packed(const int32_t *__restrict__ raw_a, const int32_t *__restrict__ r
     const int32_t p = blockIdx.x * kBlock + threadIdx.x;
     if (p >= nseg) return;
     const int32_t f = feat_of_pos[p];
-    for (int32_t j = 0; j < nq; ++j) {
-        double v = 0.0;
-        if (f >= 0) {
-            v = unpack_cf(raw_a[(size_t)j * nfeat + f], ka);
-            if (raw_b) v = v + unpack_cf(raw_b[(size_t)j * nfeat + f], kb);
-        }
-        qlat_tm[(size_t)j * nseg_pad + p] = (T)(float)v;
-    }
+    for (int32_t j = 0; j < nq; ++j)
+        qlat_tm[(size_t)j * nseg_pad + p] = ingest_packed_at<T>(raw_a, raw_b, ka, kb, f, (size_t)j * (size_t)nfeat);
+}
+// The same for a DAY OF A STREAM (trmc_stream_push_day_packed), into the forcing area of the day's ring slot -- the layout
+// k_prep_qlat leaves there.  A stream day is pushed while the tile launches of earlier days own the device, so the grid is cut along
+// the columns as well: a thread decodes kIngestCols values of one position, its gathers independent of each other and in flight
+// together; feat_of_pos is read coalesced (and again from the cache by the blocks of the other columns), the raw values by index,
+// and a wavefront stores 64 consecutive positions of a column.
+constexpr int32_t kIngestCols = 4;
+template <class T>
+__global__ void __launch_bounds__(kBlock)
+k_ingest_packed_day(const int32_t *__restrict__ raw_a, const int32_t *__restrict__ raw_b, const PackSpec ka, const PackSpec kb,
+                    const int32_t *__restrict__ feat_of_pos, T *__restrict__ qlat_tm, int32_t nseg, int64_t nseg_pad, int32_t nq,
+                    int64_t nfeat)
+{
+    const int32_t p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= nseg) return;
+    const int32_t f = feat_of_pos[p];
+    const int32_t j0 = (int32_t)blockIdx.y * kIngestCols;
+    T v[kIngestCols];
+#pragma unroll
+    for (int32_t k = 0; k < kIngestCols; ++k)
+        v[k] = j0 + k < nq ? ingest_packed_at<T>(raw_a, raw_b, ka, kb, f, (size_t)(j0 + k) * (size_t)nfeat) : T(0);
+#pragma unroll
+    for (int32_t k = 0; k < kIngestCols; ++k)
+        if (j0 + k < nq) qlat_tm[(size_t)(j0 + k) * nseg_pad + p] = v[k];
 }
 
 // initial state: time row 0 <- q0[row] = (qu0, qd0, h0)   (mc_reach.pyx:361)

@@ -100,6 +100,15 @@
 // pool's elevation; nudging changes a gage row's flow only.  A stream with full_output runs the instances it always ran and
 // gathers the day's out[row][step][2] instead: the same bits.  Off (the default): no buffer, no launch, the instances of a stream
 // without it.
+// A DAY AS PACKED CHRTOUT COLUMNS (trmc_stream_set_packed_forcing, trmc_stream_push_day_packed): the caller who runs the reference's
+// run-set loop from WRF-Hydro's files hands over what the files hold -- one or two int32 variables [nq][nfeat] in file order -- instead
+// of the float array.  The join (feature of every position, uploaded once with the declaration) and the packing facts belong to the
+// plan's streams as the gage rows do; a day's raw blocks take the float forcing's road: host -> the staging area (in_qlat, sized at
+// trmc_stream_begin for the larger of the two forms) on the forcing's stream, then ONE kernel (k_ingest_packed_day, the window's rule
+// ingest_packed_at) decodes, joins and writes the slot's forcing area in the layout k_prep_qlat leaves there.  ORDER: the copies and the
+// kernel stand where the float copy and k_prep_qlat stand -- behind the slot's ev_free, in front of its ev_forcing -- and the staging
+// area is reused in the forcing stream's queue order, so the raw blocks of a push never land on ones a pending decode still reads;
+// float days and packed days may alternate for the same reason.  The decode produces no NaN.
 extern "C++" {
 // THE PRODUCTS A DAY CAN HAND TO THE HOST, one row of StreamRun::tab each.  trmc_stream_begin fills the row (stream_begin_t: whether
 // the stream carries the product, a slot's bytes, where a slot's bytes begin on the device), a push names the day's destinations
@@ -154,6 +163,7 @@ struct StreamRun {
     DevEvent ev_cou0, ev_cou;           // (the Courant number over the days) around the last fold queued: the second as ev_exc is,
                                         // and what the next day's first launches wait for (stream_push_t)
     DevEvent ev_dex0, ev_dex;           // (the depth exceedance over the days) likewise
+    DevEvent ev_pk0, ev_pk1;            // (days pushed as packed columns) around the last decode queued, on the forcing's stream (timing)
     std::vector<DevEvent> ev_slab;      // ring: "slab launch g is complete" (the cluster launch g + 1 waits for it)
     std::vector<DevEvent> ev_free;      // [slots] the day that used the slot has handed its products over
     std::vector<DevEvent> ev_ready;     // [slots] the gathers of that day are through (copy stream waits)
@@ -225,6 +235,14 @@ struct StreamRun {
     bool dex_ms_ok = false; // (a fold of this stream lies between ev_dex0 and ev_dex)
     DevBuf dex_th, dex_acc, dex_rows;
     int64_t dex_days = 0;
+    // days pushed as packed CHRTOUT columns (the head of this file).  trmc_stream_set_packed_forcing's declaration, which outlives a
+    // stream as the gage rows do: the feature axis' length (0: none), whether the days bring two variables, the packing facts, and
+    // the feature of every POSITION (-1: the files do not hold the row), int32 [nseg].  pk_ms_ok: a decode of this stream lies
+    // between ev_pk0 and ev_pk1
+    int64_t pk_nfeat = 0;
+    bool pk_two = false, pk_ms_ok = false;
+    PackSpec pk_a{}, pk_b{};
+    DevBuf pk_feat_of_pos;
 };
 
 } // extern "C++"
@@ -235,6 +253,9 @@ extern "C++" {
 namespace {
 
 constexpr int kSlabEvents = 8;
+
+// bytes of a packed day's raw blocks in the staging area: one or two variables [nq][nfeat] int32, the second behind the first
+inline size_t stream_raw_bytes(const StreamRun &S, bool two) { return (two ? 2 : 1) * (size_t)S.nq * (size_t)S.pk_nfeat * sizeof(int32_t); }
 
 // flows of the boundary rows for one day, [nboundary][nsteps], into the time rows 1..nsteps of a flow plane
 template <class T>
@@ -643,6 +664,12 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
     S.slot_dec = (size_t)pl->nseg * S.dec_keep * 3;
     if (int rc = S.tm.ensure((size_t)S.slots * S.slot_tm * sizeof(T))) return rc;
     if (int rc = S.qlat.ensure((size_t)S.slots * S.slot_qlat * sizeof(T))) return rc;
+    // the staging area of a day's forcing, for the larger of the float array and the declared raw blocks (up to twice its bytes)
+    if (int rc = pl->in_qlat.ensure(std::max((size_t)pl->nseg * (size_t)S.nq * sizeof(T), stream_raw_bytes(S, S.pk_two)))) return rc;
+    S.pk_ms_ok = false;
+    if (S.pk_nfeat > 0)
+        for (DevEvent *e : {&S.ev_pk0, &S.ev_pk1})
+            if (int rc = e->ensure(true)) return rc;
     if (S.want_out)
         if (int rc = S.out.ensure((size_t)S.slots * S.slot_out * sizeof(T))) return rc;
     if (S.dec_stride > 0)
@@ -870,7 +897,8 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
     return 0;
 }
 
-template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
+// raw_a != NULL: the day's forcing arrives as packed columns (raw_b: NULL in the single-variable form), day.qlat is not read
+template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day, const int32_t *raw_a, const int32_t *raw_b)
 {
     StreamRun &S = *pl->seq;
     const void *const qlat = day.qlat, *const boundary_q_dev = day.boundary_q_dev;
@@ -914,9 +942,22 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day)
         S.tab[k].next = nullptr;
     }
     // the day's forcing: host -> staging area -> plan order in the slot, all on the copy stream of that direction
-    const size_t bytes = (size_t)pl->nseg * S.nq * sizeof(T);
+    // (a packed day: the raw blocks take the same road and one kernel decodes, joins and lays them out -- the head of this file)
+    const size_t bytes = raw_a ? stream_raw_bytes(S, raw_b != nullptr) : (size_t)pl->nseg * S.nq * sizeof(T);
     if (int rc = pl->in_qlat.ensure(bytes)) return rc;
-    if (pl->nseg > 0) {
+    if (pl->nseg > 0 && raw_a) {
+        const size_t one = stream_raw_bytes(S, false);
+        int32_t *const da = (int32_t *)pl->in_qlat.p, *const db = raw_b ? da + (size_t)S.nq * (size_t)S.pk_nfeat : nullptr;
+        if (one > 0) HIP_TRY(hipMemcpyAsync(da, raw_a, one, hipMemcpyHostToDevice, hst));
+        if (one > 0 && raw_b) HIP_TRY(hipMemcpyAsync(db, raw_b, one, hipMemcpyHostToDevice, hst));
+        const int32_t n = (int32_t)pl->nseg;
+        HIP_TRY(hipEventRecord(S.ev_pk0, hst));
+        hipLaunchKernelGGL((k_ingest_packed_day<T>), dim3(blocks_for(n), (unsigned)((S.nq + kIngestCols - 1) / kIngestCols)), dim3(kBlock), 0, hst,
+                           (const int32_t *)da, (const int32_t *)db, S.pk_a, S.pk_b, (const int32_t *)S.pk_feat_of_pos.p,
+                           (T *)S.qlat.p + (size_t)slot * S.slot_qlat, n, pl->nseg_pad, (int32_t)S.nq, S.pk_nfeat);
+        HIP_TRY(hipEventRecord(S.ev_pk1, hst));
+        S.pk_ms_ok = true;
+    } else if (pl->nseg > 0) {
         HIP_TRY(hipMemcpyAsync(pl->in_qlat.p, qlat, bytes, hipMemcpyHostToDevice, hst));
         const int32_t n = (int32_t)pl->nseg;
         hipLaunchKernelGGL((k_prep_qlat<T>), dim3((n + 63) / 64, (unsigned)((S.nq + 31) / 32)), dim3(kBlock), 0, hst, (const T *)pl->in_qlat.p,
@@ -1382,11 +1423,65 @@ static int stream_rda_check(const trmc_plan *pl, const StreamRun &S, const trmc_
     return 0;
 }
 
-int trmc_stream_push_day(trmc_plan *pl, const trmc_stream_day *day)
+int trmc_stream_set_packed_forcing(trmc_plan *pl, int64_t nfeat, const int64_t *feat_of_row, const double *pack_a, const double *pack_b)
+{
+    if (int rc = stream_check(pl, false)) return rc;
+    if (pl->flow) return fail(TRMC_EINVAL, "a stream of windows runs on the level engine");
+    if (nfeat < 0) return fail(TRMC_EINVAL, "nfeat < 0");
+    if (nfeat > INT32_MAX) return fail(TRMC_EINVAL, "feature axis too long");
+    const bool off = nfeat == 0 || !feat_of_row;
+    if (off && !pl->seq) return 0; // (withdrawn where nothing was declared)
+    if (!off && !pack_a) return fail(TRMC_EINVAL, "pack_a is NULL");
+    if (!pl->seq) pl->seq = std::make_unique<StreamRun>();
+    StreamRun &S = *pl->seq;
+    S.pk_nfeat = 0;
+    if (off) {
+        S.pk_feat_of_pos.release();
+        return 0;
+    }
+    const int64_t n = pl->nseg;
+    std::vector<int32_t> feat_of_pos((size_t)n);
+    for (int64_t p = 0; p < n; ++p) {
+        const int64_t f = feat_of_row[pl->sh->topo.row_of_pos[p]];
+        if (f >= nfeat) return fail(TRMC_EINVAL, "feat_of_row entry outside the feature axis");
+        feat_of_pos[(size_t)p] = f < 0 ? -1 : (int32_t)f;
+    }
+    if (int rc = upload_i32(S.pk_feat_of_pos, feat_of_pos, 1)) return rc;
+    S.pk_a = pack_spec(pack_a);
+    S.pk_b = pack_spec(pack_b);
+    S.pk_two = pack_b != nullptr;
+    S.pk_nfeat = nfeat;
+    return 0;
+}
+
+int trmc_stream_packed_forcing_kernel_ms(trmc_plan *pl, double *ms_out)
+{
+    if (int rc = stream_check(pl, true)) return rc;
+    StreamRun &S = *pl->seq;
+    if (!ms_out) return fail(TRMC_EINVAL, "ms_out is NULL");
+    if (!S.pk_ms_ok) return fail(TRMC_ESTATE, "no day of this stream has been pushed as packed columns yet");
+    HIP_TRY(hipEventSynchronize(S.ev_pk1));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, S.ev_pk0, S.ev_pk1));
+    *ms_out = ms;
+    return 0;
+}
+
+// a day's push, float (raw_a = raw_b = NULL, packed = false) or packed
+static int stream_push_day(trmc_plan *pl, const trmc_stream_day *day, const int32_t *raw_a, const int32_t *raw_b, bool packed)
 {
     if (int rc = stream_check(pl, true)) return rc;
     if (!day) return fail(TRMC_EINVAL, "day is NULL");
     StreamRun &S = *pl->seq;
+    if (packed) {
+        if (S.pk_nfeat < 1)
+            return fail(TRMC_ESTATE, "a packed day for a stream without the declaration (trmc_stream_set_packed_forcing precedes trmc_stream_begin)");
+        if (day->qlat) return fail(TRMC_EINVAL, "a packed day brings raw_a / raw_b: trmc_stream_day::qlat must be NULL");
+        if (!raw_a) return fail(TRMC_EINVAL, "raw_a is NULL");
+        if ((raw_b != nullptr) != S.pk_two)
+            return fail(TRMC_EINVAL, S.pk_two ? "the stream's packed days were declared with two variables (pack_b): raw_b is NULL"
+                                              : "the stream's packed days were declared with one variable (pack_b = NULL): raw_b must be NULL");
+    }
     const void *const qlat = day->qlat;
     const int64_t nq = day->nq;
     const int32_t rowset = day->rowset;
@@ -1404,7 +1499,7 @@ int trmc_stream_push_day(trmc_plan *pl, const trmc_stream_day *day)
     if (day->res_inflow_host && (day->res_nres != pl->nres || day->res_nsteps != S.nsteps))
         return fail(TRMC_EINVAL, "the reservoir-inflow record of a day is [" + std::to_string(pl->nres) + "][" + std::to_string(S.nsteps) + "], got ["
                                      + std::to_string(day->res_nres) + "][" + std::to_string(day->res_nsteps) + "]");
-    if (pl->nseg > 0 && !qlat) return fail(TRMC_EINVAL, "qlat is NULL");
+    if (pl->nseg > 0 && !qlat && !packed) return fail(TRMC_EINVAL, "qlat is NULL");
     if (nq != S.nq) return fail(TRMC_EINVAL, "every day of a stream has the forcing columns of the first (" + std::to_string(S.nq) + ")");
     if (S.g_done > S.days_pushed * S.tpd - 1 && S.days_complete < S.days_pushed)
         return fail(TRMC_ESTATE, "the stream has been advanced past its last day without being flushed: trmc_stream_flush first");
@@ -1415,7 +1510,14 @@ int trmc_stream_push_day(trmc_plan *pl, const trmc_stream_day *day)
     }
     if (fvd_host && S.dec_stride == 0 && !S.want_out)
         return fail(TRMC_EINVAL, "the stream was begun without full_output / output_stride: there is no (q, v, d) block to hand over");
-    return by_precision(pl, [&](auto t) { return stream_push_t<decltype(t)>(pl, *day); });
+    return by_precision(pl, [&](auto t) { return stream_push_t<decltype(t)>(pl, *day, raw_a, raw_b); });
+}
+
+int trmc_stream_push_day(trmc_plan *pl, const trmc_stream_day *day) { return stream_push_day(pl, day, nullptr, nullptr, false); }
+
+int trmc_stream_push_day_packed(trmc_plan *pl, const trmc_stream_day *day, const int32_t *raw_a, const int32_t *raw_b)
+{
+    return stream_push_day(pl, day, raw_a, raw_b, true);
 }
 
 int trmc_stream_push(trmc_plan *pl, const void *qlat, int64_t nq, const void *boundary_q_dev, int32_t rowset, void *hyd_host,

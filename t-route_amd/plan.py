@@ -218,9 +218,9 @@ class RoutingPlan:
                                                   _lib.ptr(bf)))
         self._nsteps = nsteps
 
-    def upload_forcing_packed(self, nsteps, packed, row_ids, q0, boundary_fvd=None):
-        """Forcing straight from packed CHRTOUT columns (``nhd_io.chrtout_packed``): the device decodes, joins
-        on feature id and lays the forcing out.  row_ids: int64 [nseg] id of every row of the table."""
+    def _feat_of_row(self, packed, row_ids):
+        """the join of packed CHRTOUT columns on the feature id: the index of every row on the files' feature axis, -1 where the
+        files do not hold the row (int64 [nseg])"""
         feat = np.asarray(packed["feature_id"], dtype=np.int64)
         row_ids = np.asarray(row_ids, dtype=np.int64)
         if row_ids.shape != (self.nseg,):
@@ -229,7 +229,12 @@ class RoutingPlan:
         where = np.searchsorted(feat[order], row_ids)
         where = np.clip(where, 0, max(0, feat.shape[0] - 1))
         hit = feat[order][where] == row_ids if feat.size else np.zeros(self.nseg, dtype=bool)
-        feat_of_row = np.where(hit, order[where], -1).astype(np.int64)
+        return np.where(hit, order[where], -1).astype(np.int64)
+
+    def upload_forcing_packed(self, nsteps, packed, row_ids, q0, boundary_fvd=None):
+        """Forcing straight from packed CHRTOUT columns (``nhd_io.chrtout_packed``): the device decodes, joins
+        on feature id and lays the forcing out.  row_ids: int64 [nseg] id of every row of the table."""
+        feat_of_row = self._feat_of_row(packed, row_ids)
         raw_a = np.ascontiguousarray(packed["raw_a"], dtype=np.int32)
         raw_b = None if packed["raw_b"] is None else np.ascontiguousarray(packed["raw_b"], dtype=np.int32)
         pa = np.ascontiguousarray(packed["pack_a"], dtype=np.float64)
@@ -450,8 +455,58 @@ class RoutingPlan:
         _lib.check(_lib.lib().trmc_stream_set_stage(self._h, int(bool(on))))
         self._stream_stage = bool(on)
 
-    def stream_push(self, qlat, boundary_q_ptr=None, rowset=None, hyd=None, q0=None, fvd=None, nudging=None, nudge=None,
-                    reservoir_inflow=None, reservoir_da=None, reservoir_da_state=None, summary=None, stage=None):
+    def stream_set_packed_forcing(self, packed, row_ids=None):
+        """The streams on this plan take days as packed CHRTOUT columns (trmc_stream_set_packed_forcing): ``packed`` is a dict of
+        ``nhd_io.chrtout_packed`` -- its feature axis and packing facts are declared, its raw values are not read -- and
+        ``row_ids`` int64 [nseg] the id of every row of the table.  Declared once, before ``stream_begin``; it stays until the next
+        call.  ``stream_push(packed=day)`` then hands over a day's raw columns, which the device decodes, joins and lays out in
+        one kernel; float days may still be pushed in between.  Returns ``feat_of_row`` as ``upload_forcing_packed`` does;
+        ``None`` for ``packed`` withdraws the declaration."""
+        if self.engine != "levels":
+            raise ValueError("a stream of days runs on the level engine: packed days need engine='levels'")
+        if packed is None:
+            _lib.check(_lib.lib().trmc_stream_set_packed_forcing(self._h, 0, None, None, None))
+            self._stream_packed = None
+            return None
+        feat_of_row = self._feat_of_row(packed, row_ids)
+        nfeat = int(np.asarray(packed["feature_id"]).shape[0])
+        if nfeat < 1:
+            raise ValueError("packed: the files' feature axis is empty")
+        pa = np.ascontiguousarray(packed["pack_a"], dtype=np.float64)
+        pb = None if packed.get("pack_b") is None else np.ascontiguousarray(packed["pack_b"], dtype=np.float64)
+        if pa.shape != (6,) or (pb is not None and pb.shape != (6,)):
+            raise ValueError("pack_a / pack_b: (scale_factor, add_offset, _FillValue, missing_value, valid_min, valid_max)")
+        _lib.check(_lib.lib().trmc_stream_set_packed_forcing(self._h, nfeat, _lib.ptr(feat_of_row), _lib.ptr(pa), _lib.ptr(pb)))
+        self._stream_packed = (nfeat, pb is not None)
+        return feat_of_row
+
+    def stream_packed_forcing_kernel_ms(self):
+        """device time (ms) of the decode kernel of the last packed day pushed (trmc_stream_packed_forcing_kernel_ms)"""
+        ms = C.c_double(0.0)
+        _lib.check(_lib.lib().trmc_stream_packed_forcing_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def _packed_day(self, packed):
+        """the raw blocks of a packed day as ``trmc_stream_push_day_packed`` takes them, checked against the declaration"""
+        decl = getattr(self, "_stream_packed", None)
+        if decl is None:
+            raise RuntimeError("packed: the plan's streams were not told to take packed days (stream_set_packed_forcing precedes stream_begin)")
+        nfeat, two = decl
+        raw_a, raw_b = packed["raw_a"], packed.get("raw_b")
+        if (raw_b is not None) != two:
+            raise ValueError("packed: the declaration has two variables (pack_b): raw_b is required" if two else
+                             "packed: the declaration has one variable (pack_b = None): raw_b must be None")
+        for name, raw in (("raw_a", raw_a), ("raw_b", raw_b)):
+            if raw is None:
+                continue
+            if not isinstance(raw, np.ndarray) or raw.dtype != np.int32 or not raw.flags.c_contiguous or raw.ndim != 2 or raw.shape[1] != nfeat:
+                raise ValueError(f"packed: {name} must be a C-contiguous int32 array of shape (nq, {nfeat})")
+        if raw_b is not None and raw_b.shape != raw_a.shape:
+            raise ValueError("packed: raw_a and raw_b must have one shape")
+        return raw_a, raw_b
+
+    def stream_push(self, qlat=None, boundary_q_ptr=None, rowset=None, hyd=None, q0=None, fvd=None, nudging=None, nudge=None,
+                    reservoir_inflow=None, reservoir_da=None, reservoir_da_state=None, packed=None, summary=None, stage=None):
         """The next day: ``qlat`` [nseg, nq] (page-locked: ``_lib.result_empty(..., always_pinned=True)``), where its products go
         (page-locked arrays or None), the device pointer of its boundary rows' flows.  A plan with gage rows
         (``stream_set_gages``): ``nudging=(mode, a, w)``, the day's tables [ngage, nsteps] as ``set_nudging`` takes them for a
@@ -466,8 +521,17 @@ class RoutingPlan:
         and the mean flow -- with ``"peak_depth"`` two more, the peak depth and its step: the rows of ``stream_products.SUMMARY``
         with their types.  A plan whose streams carry stage (``stream_set_stage``): ``stage=`` a page-locked array
         [rows of ``rowset``, nsteps] for the depth of every step at the set's rows (``rowset`` is then required).  Returns the
-        day's number in the stream."""
-        if qlat.dtype != self.dtype or not qlat.flags.c_contiguous or qlat.ndim != 2 or qlat.shape[0] != self.nseg:
+        day's number in the stream.  A plan whose streams take packed days (``stream_set_packed_forcing``): ``packed=`` a day's dict of
+        ``nhd_io.chrtout_packed`` in place of ``qlat`` -- ``raw_a`` / ``raw_b`` C-contiguous int32 [nq, nfeat], page-locked for a
+        copy that runs beside the launches; they are kept alive with the day's other host arrays."""
+        raw = None
+        if packed is not None:
+            if qlat is not None:
+                raise ValueError("a day's forcing is either qlat or packed, not both")
+            raw = self._packed_day(packed)
+        elif qlat is None:
+            raise ValueError("a day needs its forcing: qlat, or packed=")
+        elif qlat.dtype != self.dtype or not qlat.flags.c_contiguous or qlat.ndim != 2 or qlat.shape[0] != self.nseg:
             raise ValueError(f"qlat must be a C-contiguous {np.dtype(self.dtype).name} array of shape ({self.nseg}, nq)")
         if stage is not None:  # (what the library would refuse, before it is called)
             if not getattr(self, "_stream_stage", False):
@@ -522,7 +586,7 @@ class RoutingPlan:
         info = self.stream_info()
         day = info["days_pushed"]
         # (alive while the copies may be in flight: a day's products are queued up to `slots` days on)
-        self._stream_keep[day] = {"qlat": qlat, "tables": tables, "dests": list(dest.values())}
+        self._stream_keep[day] = {"qlat": qlat if raw is None else raw, "tables": tables, "dests": list(dest.values())}
         for old in [k for k in self._stream_keep if isinstance(k, int) and k < day - max(8, info["slots"])]:
             del self._stream_keep[old]
         parts = [dest[p.name] for p in SP.SUMMARY]
@@ -534,14 +598,18 @@ class RoutingPlan:
                 _lib.check(_lib.lib().trmc_stream_stage_dest(self._h, _lib.ptr(stage)))
             if depth:
                 _lib.check(_lib.lib().trmc_stream_summary_depth_dest(self._h, *(_lib.ptr(x) for x in parts[3:])))
-            if nudging is None and reservoir_inflow is None and reservoir_da is None and reservoir_da_state is None:  # (the entry point every stream without tables has always used)
+            if raw is None and nudging is None and reservoir_inflow is None and reservoir_da is None and reservoir_da_state is None:  # (the entry point every stream without tables has always used)
                 _lib.check(_lib.lib().trmc_stream_push(self._h, _lib.ptr(qlat), qlat.shape[1], C.c_void_p(boundary_q_ptr or 0),
                                                        -1 if rowset is None else int(rowset), _lib.ptr(hyd), _lib.ptr(q0), _lib.ptr(fvd)))
                 return day
-            day_s.qlat, day_s.nq = qlat.ctypes.data, qlat.shape[1]
             day_s.boundary_q_dev = boundary_q_ptr or None
             day_s.rowset = -1 if rowset is None else int(rowset)
             day_s.hyd_host, day_s.q0_host, day_s.fvd_host = (None if x is None else x.ctypes.data for x in (hyd, q0, fvd))
+            if raw is not None:      # (the day's raw columns in place of qlat; every other member as in a float day)
+                day_s.nq = raw[0].shape[0]
+                _lib.check(_lib.lib().trmc_stream_push_day_packed(self._h, C.byref(day_s), _lib.ptr(raw[0]), _lib.ptr(raw[1])))
+                return day
+            day_s.qlat, day_s.nq = qlat.ctypes.data, qlat.shape[1]
             _lib.check(_lib.lib().trmc_stream_push_day(self._h, C.byref(day_s)))
             return day
         except Exception:

@@ -488,17 +488,33 @@ class RouteStream:
     tailwater hydrograph", with the order DAG resolved by the trunk's lag instead of by waiting.
     """
 
+    PACKED_ON_RANKS = ("packed days on several ranks: the join on the feature id is made for ONE plan's rows -- a rank's own rows and "
+                       "its boundary copies of other ranks' rows would each need a join of their own, which nothing builds yet; unpack "
+                       "on the host (nhd_io.unpack_packed) and pass float days")
+
     def __init__(self, router, nsteps, qts_subdivisions, output_stride=None, full_output=False, slots=0, latency="throughput",
                  hydrographs_on_every_rank=False, comm=None, exchange=None, reservoir_da_ncol=None, summary=None,
-                 daily_summary=True, depth_exceedance=None, courant=None, stage=False, exceedance=None):
+                 daily_summary=True, depth_exceedance=None, courant=None, packed_forcing=None, stage=False, exceedance=None):
         """comm / exchange (several ranks): the communicator -- default: the one given to ``router.enable_device_exchange`` -- and
         how the daily cut-edge hydrographs travel: "device" (gather kernel -> all-gather on the exchange stream -> boundary rows,
         everything in HBM: RCCL over xGMI) or "host" (through ``comm.all_gather_rows_host``: any communicator with that method,
         ``all_reduce_max_host`` and ``barrier`` -- a transport without device collectives; the days of slack the trunk's lag gives
         cover the round trip).  Default: "device" when the router has a device exchange, else "host".
         reservoir_da_ncol (a router with ``reservoir_da``): the most columns (usgs, usace, rfc) a day's tables may have; default:
-        as many as the declared tables."""
+        as many as the declared tables.
+        packed_forcing: the ids of the router's rows, int64 [router.nseg] -- ``route`` then takes a day's forcing as a dict of
+        ``nhd_io.chrtout_packed`` as well as a float array, and the device decodes and joins it (``RoutingPlan.stream_push(packed=)``).
+        The FIRST day of such a stream, if it is packed, declares the files' feature axis and packing facts; a stream that begins
+        with float days declares them here: ``(row_ids, packed)`` with any dict of those files.  One rank only."""
         self._rda_ncol = reservoir_da_ncol
+        self._pk_ids = self._pk_like = None
+        if packed_forcing is not None:
+            if router.world > 1:
+                raise NotImplementedError(self.PACKED_ON_RANKS)
+            ids, like = packed_forcing if isinstance(packed_forcing, tuple) else (packed_forcing, None)
+            self._pk_ids, self._pk_like = np.asarray(ids, dtype=np.int64), like
+            if self._pk_ids.shape != (router.nseg,):
+                raise ValueError(f"packed_forcing: the ids of the router's rows, [{router.nseg}]: got {self._pk_ids.shape}")
         from .plan import RoutingPlan
         self._cou_limit = RoutingPlan.stream_courant_limit(courant)
         self._courant = None
@@ -694,7 +710,9 @@ class RouteStream:
 
     def route(self, forcings, state0=None, prepared=False, observations=None, lastobs=None, da_parameters=None, reservoir_da=None):
         """generator of (day, hydrographs, final_state[, fvd][, dict]) -- see the class (``summary``) and below.  prepared: the arrays hold this rank's rows only
-        (``prepare_days``).
+        (``prepare_days``).  A day's forcing is the float array [rows, nq] or -- ``RouteStream(..., packed_forcing=row_ids)``, one rank -- a
+        dict of ``nhd_io.chrtout_packed`` whose raw columns the device decodes and joins to the rows (include/trmc.h,
+        trmc_stream_push_day_packed); the two kinds may alternate.
 
         A router with reservoirs or gages (``ShardedRouter(..., stream=True, reservoirs=..., gages=...)``): every tuple has one more
         trailing element, a dict {"reservoir_inflow": [nres, nsteps] (the reference's upstream_array rows; None without
@@ -744,7 +762,20 @@ class RouteStream:
         rows, local = self.rows, multi or self.rows.shape[0] != r.nseg
         pick = local and not prepared                       # (the forcings hold global rows: this rank's are picked out)
         q0 = None if state0 is None else np.ascontiguousarray(state0[rows] if (local and state0.shape[0] == r.nseg) else state0, dtype=P.dtype)
-        P.upload_forcing(nsteps, np.ascontiguousarray(nxt[rows] if pick else nxt, dtype=P.dtype), q0)   # the state and the shape of the forcing
+        # days as packed CHRTOUT columns (the class' ``packed_forcing``): the first day's dict, or the constructor's, is the declaration
+        pk_like = nxt if isinstance(nxt, dict) else self._pk_like
+        if pk_like is not None and multi:
+            raise NotImplementedError(self.PACKED_ON_RANKS)
+        if pk_like is not None and self._pk_ids is None:
+            raise ValueError("a packed day needs the ids of the router's rows: RouteStream(..., packed_forcing=row_ids)")
+        nq = nxt["raw_a"].shape[0] if isinstance(nxt, dict) else nxt.shape[1]
+        first = np.zeros((rows.shape[0], nq), P.dtype) if isinstance(nxt, dict) else np.ascontiguousarray(nxt[rows] if pick else nxt, dtype=P.dtype)
+        P.upload_forcing(nsteps, first, q0)                    # the state and the shape of the forcing (a stream reads no more of it)
+        if pk_like is not None:
+            P.stream_set_packed_forcing(pk_like, self._pk_ids[rows])
+        elif getattr(P, "_stream_packed", None) is not None:   # (an earlier stream's declaration is withdrawn, as its summary is)
+            P.stream_set_packed_forcing(None)
+        raw_stage = None
         if self.summary or getattr(P, "_stream_summary", 0):   # (the declaration outlives a stream: an earlier one's is withdrawn)
             P.stream_set_summary(self.summary)
         if self._exc_th is not None:                           # (on the plan that streams: this rank's rows of them)
@@ -773,7 +804,7 @@ class RouteStream:
                             "outlets": max(r._outS_global.shape[0], 1), "nres": nres, "ngage": ngage},
                            {"fvd": want_fvd, "ngage": ngage, "nres": nres, "rda": rda is not None, "stage": self.stage,
                             **{w: daily for w in self.summary}})
-        stage = ForcingStage(depth, (rows.shape[0], nxt.shape[1]), P.dtype)
+        stage = ForcingStage(depth, (rows.shape[0], nq), P.dtype)
         xch = CutExchange(r, P, self.comm, self.exchange == "device", nsteps) if multi else None
         self._out_rows, self._order = (None, None) if multi else (np.sort(r._outS_global), np.argsort(r._outS_global, kind="stable"))
         extras = res is not None or gages is not None
@@ -782,7 +813,16 @@ class RouteStream:
             more = {"nudging": gage.nudging(d, _next_of(obs_it, "observations", d)) if gage else None} if extras else {}
             if rdac is not None:
                 more["reservoir_da"] = _next_of(rda_it, "reservoir_da", d)
-            P.stream_push(stage.pinned(d, nxt[rows] if pick else nxt), rowset=r._rsS_out, **ring.keywords(d), **more)
+            if isinstance(nxt, dict):   # (a packed day: its raw columns, page-locked, in place of the float array)
+                if pk_like is None:
+                    raise ValueError("a packed day in a stream that began with float days: declare the files with "
+                                     "RouteStream(..., packed_forcing=(row_ids, packed))")
+                if raw_stage is None:
+                    raw_stage = [ForcingStage(depth, nxt["raw_a"].shape, np.int32) for _ in range(2)]
+                raw = {k: None if nxt.get(k) is None else s.pinned(d, nxt[k]) for k, s in zip(("raw_a", "raw_b"), raw_stage)}
+                P.stream_push(packed=raw, rowset=r._rsS_out, **ring.keywords(d), **more)
+            else:
+                P.stream_push(stage.pinned(d, nxt[rows] if pick else nxt), rowset=r._rsS_out, **ring.keywords(d), **more)
             if low:
                 P.stream_flush()
             if xch is not None:

@@ -64,6 +64,8 @@ ap.add_argument("--depth-bankfull", action="store_true", help="the depth exceeda
 ap.add_argument("--courant", type=float, default=None, metavar="LIMIT", help="every row's Courant number over the whole stream (peak, its step, steps with cn > LIMIT), kept on the device")
 ap.add_argument("--stage", action="store_true", help="the depth of every step at the rows of the row set as a stream product")
 ap.add_argument("--outlets", action="store_true", help="the row set: every network's outlet (default: 3000 sampled rows)")
+ap.add_argument("--packed", type=int, default=0, metavar="V", help="the days arrive as packed CHRTOUT columns of V (1 or 2) int32 variables on a permuted feature axis and the device decodes and joins "
+                                                                     "them; the host time to form the float forcing from the same columns is printed beside it")
 ap.add_argument("--gages", type=int, default=0, help="nudged gages scattered over the network (observations: 70 %% valid, lognormal)")
 a = ap.parse_args()
 if a.reservoir_da > a.reservoirs:
@@ -89,6 +91,33 @@ nsteps, qts = 288, 12
 days = [net["qlat"]]
 for d in range(1, min(a.days, 4)):
     days.append(S.forcing(n, previous=days[-1], seed=S.DEFAULT_SEED + 1 + d))
+packed_days = None
+if a.packed:
+    # every day quantised to packed columns (scale 1e-5, one variable or the sum of two) on a feature axis that is a permutation of
+    # the rows; the days routed are the floats the host rule forms from them -- timed, since that is what the device's decode replaces
+    if a.packed not in (1, 2):
+        ap.error("--packed: 1 or 2 variables")
+    from troute_amd import nhd_io                         # noqa: E402
+    scale, nan = float(np.float32(1e-5)), float("nan")
+    feature_id = np.random.default_rng(29).permutation(np.arange(n, dtype=np.int64))     # (row r has the id r)
+    col = np.argsort(feature_id, kind="stable")
+    packed_days, host_ms = [], []
+    for i, q in enumerate(days):
+        raw = _lib.result_empty((q.shape[1], n), np.int32, always_pinned=True)
+        raw[:, col] = np.minimum(np.rint(q.T.astype(np.float64) / scale), 2.0 ** 30).astype(np.int32)
+        raw_b = None
+        if a.packed == 2:
+            raw_b = _lib.result_empty(raw.shape, np.int32, always_pinned=True)
+            raw_b[...] = raw // 3
+            raw -= raw_b
+        pack = np.array([scale, 0.0, -999900000.0, nan, 0.0, 2000000000.0])
+        packed_days.append({"feature_id": feature_id, "raw_a": raw, "raw_b": raw_b, "pack_a": pack, "pack_b": pack if raw_b is not None else None})
+        t0 = time.perf_counter()
+        host = nhd_io.unpack_packed(packed_days[-1])                     # the mask, scale and offset, the sum: float64 [nq, nfeat]
+        days[i] = np.ascontiguousarray(host[:, col].T, dtype=np.float32) # the join on the feature id, row order, the cast
+        host_ms.append((time.perf_counter() - t0) * 1e3)
+    print(f"packed: {a.packed} variable(s) [{days[0].shape[1]}][{n}] int32 a day; forming the float forcing on the host (unpack_packed + the join + "
+          f"the cast): median {np.median(host_ms):.1f} ms a day {np.round(host_ms, 1).tolist()}", flush=True)
 pinned = []
 for q in days:
     b = _lib.result_empty(q.shape, q.dtype, always_pinned=True)
@@ -262,6 +291,8 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
                              + (("total",) if a.summary_total else ()) or None)
         if a.stage:
             p.stream_set_stage(True)
+        if a.packed:
+            p.stream_set_packed_forcing(packed_days[0], np.arange(n, dtype=np.int64))
         if a.courant is not None:
             p.stream_set_courant(a.courant if cou_on else None)
         if a.exceedance:
@@ -337,7 +368,7 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
                 print(f"   day {e}: final state {s1} hydrographs {s2} fvd {s3}", flush=True)
         t0 = time.perf_counter()
         for d in range(a.days):
-            p.stream_push(pinned[d % len(days)], rowset=rs, hyd=hyds[d % D], q0=fins[d % D], fvd=fvds[d % D],
+            p.stream_push(None if a.packed else pinned[d % len(days)], packed=packed_days[d % len(days)] if a.packed else None, rowset=rs, hyd=hyds[d % D], q0=fins[d % D], fvd=fvds[d % D],
                           nudging=tabs[d % len(days)] if tabs else None, nudge=nuds[d % D], reservoir_inflow=rins[d % D], reservoir_da=da_day, reservoir_da_state=rdas[d % D], summary=sums[d % D], **({"stage": stgs[d % D]} if a.stage else {}))
             e = d - behind
             if e >= 0:
@@ -409,6 +440,11 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
                         and np.array_equal(ov, cou["steps_over"]))
                 ok = ok and same
                 print("   Courant number equals the fold of the one-by-one days' window_courant_summary:", same, flush=True)
+        if a.packed:
+            nq = days[0].shape[1]
+            gb = (a.packed * nq * n * 4 + n * 4 + nq * n * 4) / 1e9     # the raw values once, feat_of_pos, the forcing stored
+            print(f"   the last day's decode (k_ingest_packed_day), from events around the kernel: {p.stream_packed_forcing_kernel_ms():.3f} ms; its bytes "
+                  f"({gb:.3f} GB: {a.packed} x [{nq}][{n}] int32 read once, the join, [{nq}][{n}] fp32 stored) take {gb / 8e3 * 1e3:.3f} ms at 8 TB/s", flush=True)
         dev_ms = [p.stream_day_ms(e) for e in range(max(behind + 1, a.days - D + 1), a.days)]    # (days pushed into a full stream, still in the ring)
         p.stream_end()
         if dev_ms:
