@@ -899,6 +899,49 @@ int trmc_stream_depth_exceedance(trmc_plan *plan, int64_t *steps_over, int64_t *
                                  int64_t *days_out);
 int trmc_stream_depth_exceedance_kernel_ms(trmc_plan *plan, double *ms_out);
 /*
+ * PEAK VELOCITY and VELOCITY exceedance OVER A WHOLE STREAM OF DAYS (trmc_stream_*; additions within ABI 19): the third of the
+ * quantities the reference hands out per reach, for scour and erosion limits, bridge and culvert limits, wading and boating safety.
+ * v[t] of a routed row is, bit for bit, column 1 of the same days routed as a window on the same plan: the reference's velocity at the
+ * depth the row's step t ended on, and 0 where the step had no flow, in the plan's precision and arithmetic; a gage row's is that of
+ * the un-nudged step (nudging changes the flow only); reservoir rows of every type and boundary rows route no step: v = 0.  t runs
+ * on over the days, 1-based from the stream's first step.  Per row
+ *     peak_velocity       pk = v[1]; t = 2..: if (v[t] > pk) -- the first of equal peaks wins, a NaN never replaces a number, a
+ *                         NaN at the stream's step 1 stays
+ *     peak_velocity_step  the step the peak was first reached at (1 for rows that route no step)
+ * and, where thresholds were given, per row and level trmc_stream_exceedance's four figures on velocity: over(t) := v[t] > th[row][k],
+ * compared in the plan's precision (false when either side is a NaN; equality is not over), a run that is open at a day's last step
+ * going on at the next day's first.  A FOURTH accumulator beside the flow, depth and Courant ones, with a threshold table of the
+ * stream's own (m/s); one stream may keep all four.  trmc_stream_set_exceedance goes on refusing TRMC_X_VELOCITY.
+ * A products-only stream forms no velocity in its step loop, and does not with this on: where a day is handed over one pass over the
+ * day's flow and depth planes and its forcing (csrc/k_stream_velocity.inc: one velocity per row-step, no secant solve) folds it in, in
+ * day order.  Nothing of it is a member of trmc_stream_day or crosses to the host per day.  It needs every step's depth: without
+ * full_output the stream launches the tile-kernel instances that write the depth plane at every step, as for trmc_stream_set_stage;
+ * with full_output the depth is read from the day's result.  So trmc_stream_begin refuses what it refuses for stage: TRMC_EUNSUPPORTED
+ * in a stream with reservoir data assimilation and, without full_output, on a plan with velocity_on_demand < 0.  Off (the default): no
+ * buffer, no launch, the instances of a stream without it.
+ *   trmc_stream_set_velocity  on != 0: the streams on this plan keep the figures; th: HOST array [nseg][nlevels], row order, the
+ *                            plan's precision, nlevels 0..4 -- 0: the peak and its step only, th may be NULL; copied, before the
+ *                            call returns, into a device table of the stream's own.  on == 0 withdraws the declaration and releases
+ *                            its buffers (nlevels and th are not read; where nothing was declared, the dataflow engine included,
+ *                            it does nothing).  Before trmc_stream_begin; it stays until the next call.
+ *                            TRMC_ESTATE while a stream is in progress; TRMC_EINVAL with on != 0 on the dataflow engine, for nlevels outside
+ *                            0..4, for a NULL th with nlevels > 0 and for a NULL plan.  The steps are counted in 32 bits on the
+ *                            device: trmc_stream_push_day is TRMC_EUNSUPPORTED for the day that would take the stream past 2^31 - 1.
+ *   trmc_stream_velocity     HOST arrays in row order: peak [nseg] in the plan's precision, peak_step int64 [nseg], the four
+ *                            figures int64 [nseg][nlevels].  Any may be NULL; all NULL, peak_step without peak, or one of the four
+ *                            in a stream declared with nlevels = 0: TRMC_EINVAL.  Synchronous on the copy stream behind the last
+ *                            fold queued: returns when the figures over all days handed over so far are on the host and writes that
+ *                            number of days to days_out.  TRMC_ESTATE when no stream is in progress, when it was begun without the
+ *                            declaration or when no day is complete yet.
+ *   trmc_stream_velocity_kernel_ms  device time (ms) of the last fold queued, from a pair of events around the kernel; waits for it.
+ *                            TRMC_ESTATE as trmc_stream_velocity.
+ * With the feature on, the launches of every trmc_stream_push_day go behind the last fold queued, as for the Courant number.
+ */
+int trmc_stream_set_velocity(trmc_plan *plan, int on, int32_t nlevels, const void *th);
+int trmc_stream_velocity(trmc_plan *plan, void *peak, int64_t *peak_step, int64_t *steps_over, int64_t *first_step, int64_t *last_step,
+                         int64_t *longest_run, int64_t *days_out);
+int trmc_stream_velocity_kernel_ms(trmc_plan *plan, double *ms_out);
+/*
  * STAGE HYDROGRAPHS of a stream day: the depth of EVERY step at the rows of the day's row set (trmc_stream_day::rowset, the rows of
  * its hydrographs), [rows of the set][nsteps] in the plan's precision -- column 2 of the same day routed as a window with the full
  * result, at those rows, bit for bit.  A reservoir row (trmc_set_reservoirs) gives its pool's water elevation; nudging changes a

@@ -194,6 +194,9 @@ SIGNATURES = {
     "trmc_stream_set_depth_exceedance": (_int, [_vp, _i32, _vp]),
     "trmc_stream_depth_exceedance": (_int, [_vp, _vp, _vp, _vp, _vp, _P(_i64)]),
     "trmc_stream_depth_exceedance_kernel_ms": (_int, [_vp, _P(C.c_double)]),
+    "trmc_stream_set_velocity": (_int, [_vp, _int, _i32, _vp]),
+    "trmc_stream_velocity": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(_i64)]),
+    "trmc_stream_velocity_kernel_ms": (_int, [_vp, _P(C.c_double)]),
     "trmc_stream_set_stage": (_int, [_vp, _int]),
     "trmc_stream_stage_dest": (_int, [_vp, _vp]),
     "trmc_stream_set_packed_forcing": (_int, [_vp, _i64, _vp, _vp, _vp]),

@@ -91,6 +91,15 @@
 // rewritten behind the slot's ev_free -- recorded behind the fold -- only; the launches of a push are kept behind the last fold
 // queued all the same (stream_push_t: ev_dex), as for the Courant number, so that one rule covers every fold that reads the ring's
 // depths.  Off (the default): no buffer, no launch, the instances of a stream without it.
+// PEAK VELOCITY AND VELOCITY EXCEEDANCE OVER THE WHOLE STREAM (trmc_stream_set_velocity) is the FOURTH accumulator of that shape: per row
+// the highest velocity and the step it was first reached at and, against a threshold table of the stream's own (m/s), the exceedance's
+// four figures.  A products-only stream forms no velocity in its step loop; the velocity of a row-step is step_velocity of a depth the
+// ring already holds, or 0 where the step had no flow (k_stream_velocity.inc: no secant solve, the tile kernels unchanged), but it
+// needs EVERY step's depth: such a stream launches stage's depth-plane tile instances or, with full_output, reads the day's
+// out[row][step][2], and inherits stage's refusals.  k_stream_velocity folds every day where it is handed over, in day order, and
+// trmc_stream_velocity fetches the accumulator.  ORDER: the fold reads time row 0 of the slot's FLOW plane as the Courant fold does, so
+// the launches of a push go behind the last fold queued (stream_push_t: ev_vel).  Off (the default): no buffer, no launch, the
+// instances of a stream without it.
 // STAGE HYDROGRAPHS (trmc_stream_set_stage): the depth of EVERY step at the rows of the day's row set -- the hydrographs' rows --
 // for the caller who compares stage at forecast points and gages, and pool elevation at reservoirs, with action and flood stages.
 // A slot's depth plane has room for every step, but the tile kernels write the row of a tile's last step only; the stream that was
@@ -163,6 +172,7 @@ struct StreamRun {
     DevEvent ev_cou0, ev_cou;           // (the Courant number over the days) around the last fold queued: the second as ev_exc is,
                                         // and what the next day's first launches wait for (stream_push_t)
     DevEvent ev_dex0, ev_dex;           // (the depth exceedance over the days) likewise
+    DevEvent ev_vel0, ev_vel;           // (the velocity over the days) likewise
     DevEvent ev_pk0, ev_pk1;            // (days pushed as packed columns) around the last decode queued, on the forcing's stream (timing)
     std::vector<DevEvent> ev_slab;      // ring: "slab launch g is complete" (the cluster launch g + 1 waits for it)
     std::vector<DevEvent> ev_free;      // [slots] the day that used the slot has handed its products over
@@ -235,6 +245,16 @@ struct StreamRun {
     bool dex_ms_ok = false; // (a fold of this stream lies between ev_dex0 and ev_dex)
     DevBuf dex_th, dex_acc, dex_rows;
     int64_t dex_days = 0;
+    // the velocity over the days (the head of this file).  vel_want, vel_K_want, vel_th: trmc_stream_set_velocity's declaration, its
+    // levels (0: peak and step only) and its table on the device, T [nseg][vel_KP_want] in row order, +inf behind the levels asked
+    // for -- they outlive a stream as dex_th does; vel, vel_K, vel_KP: of the stream in progress; vel_peak T and vel_step int32
+    // [nseg_pad] in plan order, vel_acc: int32 [5][vel_KP][nseg_pad] in plan order; vel_rows: T [nseg], then int64 [nseg] behind it
+    // on a 256-byte boundary, then int64 [4][nseg][vel_K] on the next, in row order: what a fetch gathers for the host; vel_days days
+    // are folded in (queued).  A stream that carries it has every step's depth: dpl, or the full result.
+    bool vel_want = false, vel = false, vel_ms_ok = false; // (vel_ms_ok: a fold of this stream lies between ev_vel0 and ev_vel)
+    int32_t vel_K_want = 0, vel_KP_want = 0, vel_K = 0, vel_KP = 0;
+    DevBuf vel_th, vel_peak, vel_step, vel_acc, vel_rows;
+    int64_t vel_days = 0;
     // days pushed as packed CHRTOUT columns (the head of this file).  trmc_stream_set_packed_forcing's declaration, which outlives a
     // stream as the gage rows do: the feature axis' length (0: none), whether the days bring two variables, the packing facts, and
     // the feature of every POSITION (-1: the files do not hold the row), int32 [nseg].  pk_ms_ok: a decode of this stream lies
@@ -553,6 +573,52 @@ template <class T> int stream_complete_day(trmc_plan *pl, StreamRun &S, int64_t 
         S.dex_days = e + 1;
         S.dex_ms_ok = true;
     }
+    if (S.vel && pl->nseg > 0) { // (the day folded into the velocity over the days: in day order, before the slot is freed)
+        StreamVelocityArgs<T> c;
+        c.par = (const T *)pl->sh->params.p;
+        c.nseg_pad = pl->nseg_pad;
+        c.up_ptr = (const int32_t *)pl->sh->up_ptr.p;
+        c.up_idx = (const int32_t *)pl->sh->up_idx.p;
+        c.res_of_pos = pl->nres > 0 ? (const int32_t *)pl->res_of_pos.p : nullptr;
+        c.row_of_pos = (const int32_t *)pl->sh->row_of_pos.p;
+        c.q_tm = q;
+        // (every step's depth: in the slot's depth plane from time row 1, or in the full result -- stage's two sources)
+        c.by_row = S.dpl ? 0 : 1;
+        c.d1 = S.dpl ? d + (size_t)pl->nseg_pad : (const T *)S.out.p + (size_t)slot * S.slot_out + 2;
+        c.d_row = S.dpl ? 1 : 3 * (int64_t)S.nsteps;
+        c.d_step = S.dpl ? pl->nseg_pad : 3;
+        c.qlat = (const T *)S.qlat.p + (size_t)slot * S.slot_qlat;
+        c.th = (const T *)S.vel_th.p;
+        c.peak = (T *)S.vel_peak.p;
+        c.step = (int32_t *)S.vel_step.p;
+        c.acc = (int32_t *)S.vel_acc.p;
+        c.nseg = (int32_t)pl->nseg;
+        c.nboundary = (int32_t)pl->sh->topo.nboundary;
+        c.nsteps = S.nsteps;
+        c.qts = S.qts;
+        c.t0 = (int32_t)(e * S.nsteps); // (stream_push_t keeps the stream's steps within int32)
+        c.sane = pl->params_sane ? 1 : 0;
+        bool tol = false; // (the plan's arithmetic, as window_courant_launch)
+        if constexpr (std::is_same<T, float>::value) tol = pl->opt.tol;
+        auto fold = [&](auto kp) {
+            constexpr int KP = decltype(kp)::value;
+            if constexpr (std::is_same<T, float>::value) {
+                if (tol) hipLaunchKernelGGL((k_stream_velocity<float, true, KP>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, c);
+            }
+            if (!tol) hipLaunchKernelGGL((k_stream_velocity<T, false, KP>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pst, c);
+        };
+        HIP_TRY(hipEventRecord(S.ev_vel0, pst)); // (with ev_vel: the fold's device time, trmc_stream_velocity_kernel_ms)
+        switch (S.vel_KP) {
+        case 0: fold(std::integral_constant<int, 0>{}); break;
+        case 1: fold(std::integral_constant<int, 1>{}); break;
+        case 2: fold(std::integral_constant<int, 2>{}); break;
+        case 4: fold(std::integral_constant<int, 4>{}); break;
+        default: return fail(TRMC_ESTATE, "internal: the stream's velocity has no threshold table");
+        }
+        HIP_TRY(hipEventRecord(S.ev_vel, pst));
+        S.vel_days = e + 1;
+        S.vel_ms_ok = true;
+    }
     HIP_TRY(hipGetLastError());
     if (!any) {
         HIP_TRY(hipEventRecord(S.ev_free[(size_t)slot], pst));
@@ -710,11 +776,16 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
     S.dex_KP = S.dex_KP_want;
     S.dex_days = 0;
     S.dex_ms_ok = false;
-    S.dpl = (S.stage || S.cou || S.dex_K > 0) && !S.want_out;
+    S.vel = S.vel_want;
+    S.vel_K = S.vel ? S.vel_K_want : 0;
+    S.vel_KP = S.vel ? S.vel_KP_want : 0;
+    S.vel_days = 0;
+    S.vel_ms_ok = false;
+    S.dpl = (S.stage || S.cou || S.dex_K > 0 || S.vel) && !S.want_out;
     if (S.dpl && pl->opt.velocity_on_demand < 0)
-        return fail(TRMC_EUNSUPPORTED, "the stage, and the depths the Courant number and the depth exceedance are formed from, of a stream without "
-                                       "full_output are written by the tile kernels' on-demand-velocity instances: not with "
-                                       "trmc_plan_options.velocity_on_demand < 0");
+        return fail(TRMC_EUNSUPPORTED, "the stage, and the depths the Courant number, the depth exceedance and the velocity over the days are "
+                                       "formed from, of a stream without full_output are written by the tile kernels' on-demand-velocity "
+                                       "instances: not with trmc_plan_options.velocity_on_demand < 0");
     if (S.rda && S.stage)
         return fail(TRMC_EUNSUPPORTED, "stage hydrographs (trmc_stream_set_stage) are not supported in a stream with reservoir data "
                                        "assimilation: the _rda tile instances do not write the depth plane");
@@ -724,6 +795,9 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
     if (S.rda && S.dex_K > 0)
         return fail(TRMC_EUNSUPPORTED, "the depth exceedance over the days (trmc_stream_set_depth_exceedance) is not supported in a stream with "
                                        "reservoir data assimilation: the _rda tile instances do not write the depth plane");
+    if (S.rda && S.vel)
+        return fail(TRMC_EUNSUPPORTED, "the velocity over the days (trmc_stream_set_velocity) is not supported in a stream with reservoir data "
+                                       "assimilation: the _rda tile instances do not write the depth plane");
     // (boundary rows are routed by nobody and have no depth: zeros in the slots' depth planes, as in a full result)
     if (S.dpl && tp.nboundary > 0)
         HIP_TRY(hipMemset2DAsync((T *)S.tm.p + S.plane, S.slot_tm * sizeof(T), 0, S.plane * sizeof(T), (size_t)S.slots, pl->stream));
@@ -814,6 +888,20 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
         for (DevEvent *e : {&S.ev_dex0, &S.ev_dex})
             if (int rc = e->ensure(true)) return rc;
     }
+    // the velocity over the days: the accumulator (zeroed below, in front of ev_begin) and what a fetch gathers into
+    const size_t vel_bytes = (size_t)kStreamExceedFields * (size_t)S.vel_KP * np * sizeof(int32_t);
+    if (!S.vel) {
+        for (DevBuf *b : {&S.vel_peak, &S.vel_step, &S.vel_acc, &S.vel_rows}) b->release();
+    } else {
+        const size_t off = ((size_t)pl->nseg * sizeof(T) + 255) / 256 * 256, off2 = off + ((size_t)pl->nseg * sizeof(int64_t) + 255) / 256 * 256;
+        if (int rc = S.vel_peak.ensure(np * sizeof(T))) return rc;
+        if (int rc = S.vel_step.ensure(np * sizeof(int32_t))) return rc;
+        if (S.vel_K < 1) S.vel_acc.release();
+        else if (int rc = S.vel_acc.ensure(vel_bytes)) return rc;
+        if (int rc = S.vel_rows.ensure(off2 + 4 * (size_t)pl->nseg * (size_t)S.vel_K * sizeof(int64_t))) return rc;
+        for (DevEvent *e : {&S.ev_vel0, &S.ev_vel})
+            if (int rc = e->ensure(true)) return rc;
+    }
     // reservoir data assimilation: the slots' tables at their capacity, the carry with the state trmc_set_reservoir_da supplied
     // (or the plan's last window left in those tables); the days' state records are products (P_RDA)
     S.slot_rda = 0;
@@ -865,6 +953,11 @@ template <class T> int stream_begin_t(trmc_plan *pl, int nsteps, int qts, int sl
     HIP_TRY(hipMemsetAsync(pl->it_prev.p, 0, (size_t)np, st));
     if (S.exc >= 0 && exc_bytes > 0) HIP_TRY(hipMemsetAsync(S.exc_acc.p, 0, exc_bytes, st));
     if (S.dex_K > 0 && dex_bytes > 0) HIP_TRY(hipMemsetAsync(S.dex_acc.p, 0, dex_bytes, st));
+    if (S.vel && np > 0) {
+        HIP_TRY(hipMemsetAsync(S.vel_peak.p, 0, np * sizeof(T), st));
+        HIP_TRY(hipMemsetAsync(S.vel_step.p, 0, np * sizeof(int32_t), st));
+        if (S.vel_K > 0 && vel_bytes > 0) HIP_TRY(hipMemsetAsync(S.vel_acc.p, 0, vel_bytes, st));
+    }
     if (S.cou && np > 0) {
         HIP_TRY(hipMemsetAsync(S.cou_peak.p, 0, np * sizeof(T), st));
         HIP_TRY(hipMemsetAsync(S.cou_step.p, 0, np * sizeof(int32_t), st));
@@ -910,9 +1003,10 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day, 
     hipStream_t hst = S.fst; // (the forcing's own stream: the products of earlier days leave on the plan's copy stream meanwhile)
     if (d >= S.slots && S.days_complete <= d - S.slots)
         return fail(TRMC_ESTATE, "internal: the slot of the new day still belongs to a day that has not been queued to its end");
-    if ((S.exc >= 0 || S.cou || S.dex_K > 0) && (d + 1) * (int64_t)S.nsteps > (int64_t)INT32_MAX)
-        return fail(TRMC_EUNSUPPORTED, "the exceedance and the Courant number over the days of a stream count its steps in 32 bits on the device: this "
-                                       "day would take the stream past 2^31 - 1 steps -- begin a new stream");
+    if ((S.exc >= 0 || S.cou || S.dex_K > 0 || S.vel) && (d + 1) * (int64_t)S.nsteps > (int64_t)INT32_MAX)
+        return fail(TRMC_EUNSUPPORTED, "the flow exceedance, the depth exceedance, the Courant number and the velocity over the days of a stream count "
+                                       "its steps in 32 bits on the device: this day would take the stream past 2^31 - 1 steps -- begin a new "
+                                       "stream");
     StreamProd &p = S.prod[(size_t)slot];
     // (the host image of the slot's reservoir tables is written below: the copy of the slot's last day must have read it)
     if (S.rda && p.day >= 0) HIP_TRY(hipEventSynchronize(S.ev_forcing[(size_t)slot]));
@@ -1002,6 +1096,7 @@ template <class T> int stream_push_t(trmc_plan *pl, const trmc_stream_day &day, 
     // (the Courant number: this day's last launches rewrite time row 0 of a slot whose fold may still read it -- the head of this file)
     if (S.cou && S.cou_days > 0) HIP_TRY(hipStreamWaitEvent(pl->wstream, S.ev_cou, 0));
     if (S.dex_K > 0 && S.dex_days > 0) HIP_TRY(hipStreamWaitEvent(pl->wstream, S.ev_dex, 0)); // (the depth exceedance: likewise)
+    if (S.vel && S.vel_days > 0) HIP_TRY(hipStreamWaitEvent(pl->wstream, S.ev_vel, 0));       // (the velocity: as the Courant number)
     S.days_pushed = d + 1;
     hipStream_t tst = S.W > 0 ? pl->wstream : pl->stream; // (the stream whose launches a day's push is timed on)
     HIP_TRY(hipEventRecord(S.ev_t0[(size_t)slot], tst));
@@ -1383,6 +1478,110 @@ int trmc_stream_depth_exceedance_kernel_ms(trmc_plan *pl, double *ms_out)
     HIP_TRY(hipEventSynchronize(S.ev_dex));
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, S.ev_dex0, S.ev_dex));
+    *ms_out = ms;
+    return 0;
+}
+
+int trmc_stream_set_velocity(trmc_plan *pl, int on, int32_t nlevels, const void *th)
+{
+    if (int rc = stream_check(pl, false)) return rc;
+    if (!on) { // (withdrawn: the next stream holds no accumulator and queues no fold; nothing is kept.  On either engine: a plan
+               // of the dataflow engine has nothing declared, and withdrawing nothing is no error)
+        if (!pl->seq) return 0;
+        StreamRun &S = *pl->seq;
+        S.vel_want = false;
+        S.vel_K_want = S.vel_KP_want = 0;
+        for (DevBuf *b : {&S.vel_th, &S.vel_peak, &S.vel_step, &S.vel_acc, &S.vel_rows}) b->release();
+        return 0;
+    }
+    if (pl->flow) return fail(TRMC_EINVAL, "a stream of windows runs on the level engine");
+    if (nlevels < 0 || nlevels > 4) return fail(TRMC_EINVAL, "nlevels must be 0..4 (0: the peak and its step only)");
+    if (nlevels > 0 && !th) return fail(TRMC_EINVAL, "th is NULL");
+    if (!pl->seq) pl->seq = std::make_unique<StreamRun>();
+    StreamRun &S = *pl->seq;
+    // the table's rows are 1, 2 or 4 wide (k_stream_velocity's KP), +inf -- never over -- behind the caller's levels
+    const int32_t pad = nlevels == 3 ? 4 : nlevels;
+    S.vel_want = false; // (nothing half-set if the copy fails)
+    S.vel_K_want = S.vel_KP_want = 0;
+    if (nlevels > 0) {
+        const int rc = by_precision(pl, [&](auto t) -> int {
+            using T = decltype(t);
+            const T *const src = (const T *)th;
+            std::vector<T> host((size_t)pl->nseg * pad, std::numeric_limits<T>::infinity());
+            for (int64_t r = 0; r < pl->nseg; ++r)
+                for (int32_t k = 0; k < nlevels; ++k) host[(size_t)r * pad + k] = src[(size_t)r * nlevels + k];
+            if (int rc = S.vel_th.ensure(host.size() * sizeof(T))) return rc;
+            // (synchronous: the table is whole before the call returns, whichever stream reads it)
+            if (!host.empty()) HIP_TRY(hipMemcpy(S.vel_th.p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
+            return 0;
+        });
+        if (rc) return rc;
+    } else {
+        S.vel_th.release();
+    }
+    S.vel_want = true;
+    S.vel_K_want = nlevels;
+    S.vel_KP_want = pad;
+    return 0;
+}
+
+int trmc_stream_velocity(trmc_plan *pl, void *peak, int64_t *peak_step, int64_t *steps_over, int64_t *first_step, int64_t *last_step,
+                         int64_t *longest_run, int64_t *days_out)
+{
+    if (int rc = stream_check(pl, true)) return rc;
+    StreamRun &S = *pl->seq;
+    if (!S.vel) return fail(TRMC_ESTATE, "the stream was begun without the velocity (trmc_stream_set_velocity precedes trmc_stream_begin)");
+    int64_t *const dst[4] = {steps_over, first_step, last_step, longest_run};
+    const bool levels = steps_over || first_step || last_step || longest_run;
+    if (!peak && !peak_step && !levels) return fail(TRMC_EINVAL, "every destination is NULL: nothing to fetch");
+    if (peak_step && !peak) return fail(TRMC_EINVAL, "the step of a peak comes with the peak: its value destination is NULL");
+    if (levels && S.vel_K < 1)
+        return fail(TRMC_EINVAL, "the stream's velocity was declared without thresholds (nlevels = 0): it holds no exceedance figures");
+    if (S.vel_days < 1)
+        return fail(TRMC_ESTATE, "no day of the stream is complete yet: its last rows run " + std::to_string(S.lmax)
+                                     + " tiles behind its first -- push further days or trmc_stream_flush");
+    const int64_t days = S.vel_days;
+    const size_t n = (size_t)pl->nseg, nk = n * (size_t)S.vel_K;
+    // behind the last fold queued (nothing is queued meanwhile: the calls of a plan come from one thread)
+    HIP_TRY(hipStreamWaitEvent(pl->cstream, S.ev_vel, 0));
+    if (n) {
+        const size_t off = (n * (size_t)pl->esz + 255) / 256 * 256, off2 = off + (n * sizeof(int64_t) + 255) / 256 * 256;
+        int64_t *const step64 = (int64_t *)((char *)S.vel_rows.p + off), *const lev64 = (int64_t *)((char *)S.vel_rows.p + off2);
+        if (peak || peak_step) {
+            const int rc = by_precision(pl, [&](auto t) -> int {
+                using T = decltype(t);
+                hipLaunchKernelGGL((k_stream_velocity_rows<T>), dim3(blocks_for(pl->nseg)), dim3(kBlock), 0, pl->cstream, (const T *)S.vel_peak.p,
+                                   (const int32_t *)S.vel_step.p, (const int32_t *)pl->sh->pos_of_row.p, (T *)S.vel_rows.p, step64,
+                                   (int32_t)pl->nseg);
+                HIP_TRY(hipGetLastError());
+                return 0;
+            });
+            if (rc) return rc;
+            if (peak) HIP_TRY(hipMemcpyAsync(peak, S.vel_rows.p, n * (size_t)pl->esz, hipMemcpyDeviceToHost, pl->cstream));
+            if (peak_step) HIP_TRY(hipMemcpyAsync(peak_step, step64, n * sizeof(int64_t), hipMemcpyDeviceToHost, pl->cstream));
+        }
+        if (levels) { // (the accumulator has k_stream_exceed_depth's layout: its gather)
+            hipLaunchKernelGGL(k_stream_exceed_depth_rows, dim3(blocks_for((int64_t)nk)), dim3(kBlock), 0, pl->cstream, (const int32_t *)S.vel_acc.p,
+                               (const int32_t *)pl->sh->pos_of_row.p, lev64, (int32_t)pl->nseg, pl->nseg_pad, S.vel_K, S.vel_KP);
+            HIP_TRY(hipGetLastError());
+            for (int f = 0; f < 4; ++f)
+                if (dst[f]) HIP_TRY(hipMemcpyAsync(dst[f], lev64 + (size_t)f * nk, nk * sizeof(int64_t), hipMemcpyDeviceToHost, pl->cstream));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(pl->cstream));
+    if (days_out) *days_out = days;
+    return 0;
+}
+
+int trmc_stream_velocity_kernel_ms(trmc_plan *pl, double *ms_out)
+{
+    if (int rc = stream_check(pl, true)) return rc;
+    StreamRun &S = *pl->seq;
+    if (!ms_out) return fail(TRMC_EINVAL, "ms_out is NULL");
+    if (!S.vel || !S.vel_ms_ok) return fail(TRMC_ESTATE, "no day has been folded into the velocity of this stream yet");
+    HIP_TRY(hipEventSynchronize(S.ev_vel));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, S.ev_vel0, S.ev_vel));
     *ms_out = ms;
     return 0;
 }

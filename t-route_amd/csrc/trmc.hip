@@ -85,6 +85,7 @@ namespace {
 #include "k_stream_exceed.inc"
 #include "k_stream_exceed_depth.inc"
 #include "k_stream_courant.inc"
+#include "k_stream_velocity.inc"
 // ---------------------------------------------------------------- plan
 #include "dev_owner.hpp"
 

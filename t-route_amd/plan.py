@@ -772,6 +772,64 @@ class RoutingPlan:
         (trmc_stream_courant_kernel_ms; waits for it)"""
         return self._kernel_ms(_lib.lib().trmc_stream_courant_kernel_ms)
 
+    @staticmethod
+    def velocity_thresholds(th, nseg, what="velocity of a stream", rows="nseg"):
+        """``thresholds`` of a stream's velocity against ``nseg`` rows, checked -- the one rule ``stream_set_velocity`` and
+        ``RouteStream(velocity=)`` share: None (no velocity), True (the peak and its step only; returned as True), or [nseg] /
+        [nseg, K] with K <= 4, m/s (returned [nseg, K]); ValueError otherwise."""
+        if th is None or th is True:
+            return th
+        if isinstance(th, (bool, str, bytes)):
+            raise ValueError(f"{what}: None, True or thresholds [{rows}] or [{rows}, K], got {th!r}")
+        th = np.asarray(th)
+        th = th[:, None] if th.ndim == 1 else th
+        if th.ndim != 2 or th.shape[0] != nseg or not 1 <= th.shape[1] <= 4:
+            raise ValueError(f"{what}: thresholds must be [{rows}] or [{rows}, K] with {rows} = {nseg} and K <= 4: got {th.shape}")
+        return th
+
+    def stream_set_velocity(self, thresholds=True):
+        """The streams on this plan keep, on the device and over ALL their days, every row's peak velocity and the step it was
+        first reached at -- ``window_summary(("peak_velocity",))`` with the steps counted on over the days -- and, with
+        ``thresholds`` [nseg] or [nseg, K] (K <= 4) in row order, m/s, the threshold exceedance of the velocity as
+        ``window_exceedance("velocity")`` defines it: steps over, first and last step, longest run, a run carried over a day's end
+        (trmc_stream_set_velocity; ``stream_velocity`` fetches).  ``True``: the peak and its step only.  The velocity is column 1
+        of the same days routed as windows: 0 where a step had no flow, at reservoir rows and at boundary rows.  A fourth
+        accumulator beside the flow exceedance, the depth exceedance and the Courant number; a stream may keep them all.  The
+        step loop forms no velocity for it: such a stream writes every step's depth, as one with ``stream_set_stage`` does, and
+        ``stream_begin`` refuses what it refuses for stage.  Declared before ``stream_begin``; it stays until the next call;
+        ``None`` withdraws it."""
+        th = self.velocity_thresholds(thresholds, self.nseg)
+        if th is None and (self.engine != "levels" or getattr(self, "_stream_velocity", None) is None):
+            return                                                  # (withdrawing nothing is no error, on either engine)
+        if self.engine != "levels":
+            raise ValueError("a stream of days runs on the level engine: its velocity needs engine='levels'")
+        if th is not None and th is not True:
+            th = np.ascontiguousarray(th, dtype=self.dtype)
+        k = 0 if th is None or th is True else th.shape[1]
+        _lib.check(_lib.lib().trmc_stream_set_velocity(self._h, int(th is not None), k, _lib.ptr(th) if k else None))
+        self._stream_velocity = None if th is None else k
+
+    def stream_velocity(self):
+        """The velocity over all days of the stream in progress that have been handed over so far (trmc_stream_velocity,
+        synchronous): a dict with ``"days"``, ``"peak_velocity"`` (plan dtype) and ``"peak_velocity_step"`` (int64, 1-based from
+        the stream's first step) -- [nseg] arrays in row order -- and, where the declaration had thresholds, ``"steps_over"``,
+        ``"first_step"``, ``"last_step"`` and ``"longest_run"``, int64 [nseg, K].  Reservoir and boundary rows: v = 0, so (0, 1)."""
+        k = getattr(self, "_stream_velocity", None) or 0
+        peak, step = np.empty(self.nseg, self.dtype), np.empty(self.nseg, np.int64)
+        parts = [np.empty((self.nseg, k), np.int64) if k else None for _ in self.WINDOW_EXCEEDANCE_PARTS]
+        days = C.c_int64(0)
+        _lib.check(_lib.lib().trmc_stream_velocity(self._h, _lib.ptr(peak), _lib.ptr(step), *(_lib.ptr(a) if k else None for a in parts),
+                                                   C.byref(days)))
+        res = {"days": int(days.value), "peak_velocity": peak, "peak_velocity_step": step}
+        if k:
+            res.update(zip(self.WINDOW_EXCEEDANCE_PARTS, parts))
+        return res
+
+    def stream_velocity_kernel_ms(self):
+        """device time (ms) of the last day's fold into the stream's velocity, from events around the kernel
+        (trmc_stream_velocity_kernel_ms; waits for it)"""
+        return self._kernel_ms(_lib.lib().trmc_stream_velocity_kernel_ms)
+
     def stream_gather(self, day, rowset, device_ptr, stream=0):
         """Flows of a row set over `day` [rows, nsteps] into device memory (trmc_stream_gather)."""
         _lib.check(_lib.lib().trmc_stream_gather(self._h, int(day), int(rowset), C.c_void_p(device_ptr), C.c_void_p(stream or 0)))

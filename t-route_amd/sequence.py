@@ -469,6 +469,19 @@ class RouteStream:
     it has yielded its last day.  It is not a product of the day: the tuples do not change.  Such a stream writes every step's
     depth as one with ``stage=True`` does, with stage's limits: one rank only, no ``reservoir_da`` (NotImplementedError).
 
+    ``velocity=True`` or ``velocity=thresholds``: the device also keeps, over ALL days of the stream, every row's peak velocity and
+    the step it was first reached at and, with ``thresholds`` [rows] or [rows, K] (K <= 4), m/s, in the router's row order, the
+    threshold exceedance of the velocity -- the quantity ``exceedance=("velocity", ...)`` goes on refusing, because it is not a
+    quantity of the flow accumulator but a FOURTH accumulator with a table of its own, which may run beside the other three.
+    ``rs.velocity`` holds ``RoutingPlan.stream_velocity()`` -- ``"days"``, ``"peak_velocity"``, ``"peak_velocity_step"`` and, with
+    thresholds, int64 [rows, K] ``steps_over``, ``first_step``, ``last_step``, ``longest_run``, the steps 1-based from the stream's
+    first step and a run carried over a day's end -- over the days handed over so far while ``route()`` runs (None before the first)
+    and over all of them once it has yielded its last day.  The velocity is column 1 of the same days routed as windows
+    (``window_summary(("peak_velocity",))``, ``window_exceedance("velocity")`` over the days one after the other): 0 where a step
+    had no flow and at reservoir rows.  The step loop still forms no velocity: a fold kernel re-forms it once per day from the
+    depths, so such a stream writes every step's depth as one with ``stage=True`` does, with stage's limits: one rank only, no
+    ``reservoir_da`` (NotImplementedError).  It is not a product of the day: the tuples do not change.
+
     ``stage=True``: every day also carries STAGE HYDROGRAPHS -- the depth of every step at the rows of its hydrographs: the
     trailing dict gains ``"stage"``, a ring array [len(outlet_rows), nsteps] in the hydrographs' row order (a reservoir row: its
     pool's elevation; nudging changes a gage's flow only).  The tile kernels then write a slot's depth plane at every step
@@ -494,7 +507,8 @@ class RouteStream:
 
     def __init__(self, router, nsteps, qts_subdivisions, output_stride=None, full_output=False, slots=0, latency="throughput",
                  hydrographs_on_every_rank=False, comm=None, exchange=None, reservoir_da_ncol=None, summary=None,
-                 daily_summary=True, depth_exceedance=None, courant=None, packed_forcing=None, stage=False, exceedance=None):
+                 daily_summary=True, velocity=None, depth_exceedance=None, courant=None, packed_forcing=None, stage=False,
+                 exceedance=None):
         """comm / exchange (several ranks): the communicator -- default: the one given to ``router.enable_device_exchange`` -- and
         how the daily cut-edge hydrographs travel: "device" (gather kernel -> all-gather on the exchange stream -> boundary rows,
         everything in HBM: RCCL over xGMI) or "host" (through ``comm.all_gather_rows_host``: any communicator with that method,
@@ -524,6 +538,16 @@ class RouteStream:
         if self._cou_limit is not None and getattr(router, "_reservoir_da", None) is not None:
             raise NotImplementedError("courant= with reservoir data assimilation: the tile kernels of such a stream do not write the depth "
                                       "plane at every step (as for stage=True)")
+        self._vel_th = self._velocity = None
+        if velocity is not None and velocity is not False:
+            self._vel_th = RoutingPlan.velocity_thresholds(velocity, router.nseg, what="velocity", rows="rows")
+            if router.world > 1:
+                raise NotImplementedError("velocity= on several ranks: the velocity needs every step's depth of a row and the flows of the "
+                                          "rows above it, which a rank holds for its own rows only -- as for courant=, nothing gathers it "
+                                          "over the ranks")
+            if getattr(router, "_reservoir_da", None) is not None:
+                raise NotImplementedError("velocity= with reservoir data assimilation: the tile kernels of such a stream do not write the "
+                                          "depth plane at every step (as for stage=True)")
         self.stage = bool(stage)
         if self.stage and router.world > 1:
             raise NotImplementedError("stage=True on several ranks: a day's stage covers the rows of its hydrographs, which every rank holds a "
@@ -639,6 +663,14 @@ class RouteStream:
         if self._cou_limit is not None and self.info is not None and self.plan.stream_info()["days_complete"] > 0:
             self._courant = self.plan.stream_courant()
         return self._courant
+
+    @property
+    def velocity(self):
+        """the peak velocity and the velocity exceedance over the days handed over so far (``velocity=``; see the class), None
+        before the first"""
+        if self._vel_th is not None and self.info is not None and self.plan.stream_info()["days_complete"] > 0:
+            self._velocity = self.plan.stream_velocity()
+        return self._velocity
 
     @property
     def outlet_rows(self):
@@ -794,6 +826,11 @@ class RouteStream:
         elif getattr(P, "_stream_depth_levels", 0) > 0:        # (an earlier stream's declaration is withdrawn)
             P.stream_set_depth_exceedance(None)
         self.depth_exceedance = None
+        if self._vel_th is not None:
+            P.stream_set_velocity(self._vel_th)
+        elif getattr(P, "_stream_velocity", None) is not None: # (an earlier stream's declaration is withdrawn)
+            P.stream_set_velocity(None)
+        self._velocity = None
         P.stream_begin(nsteps, self.qts, slots=slots, full_output=self.full_output and not self.output_stride, output_stride=self.output_stride,
                        **({} if rda is None else {"reservoir_da": True if self._rda_ncol is None else self._rda_ncol}))
         self.info = info = P.stream_info()
@@ -846,6 +883,8 @@ class RouteStream:
             self._courant = P.stream_courant()
         if self._dex_th is not None:    # (... and the depth exceedance)
             self.depth_exceedance = P.stream_depth_exceedance()
+        if self._vel_th is not None:    # (... and the velocity)
+            self._velocity = P.stream_velocity()
         while delivered < d:
             yield self._deliver(delivered, ring, gage, rdac, extras)
             delivered += 1

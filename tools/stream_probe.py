@@ -22,6 +22,12 @@ row and the hydrographs of sampled rows bit for bit, and what a day costs either
                                                             whole stream (trmc_stream_set_courant): peak, its step, steps with cn > LIMIT;
                                                             checked against the fold of the one-by-one days' window_courant_summary;
                                                             the fold kernel's time from events
+                               [--velocity K]               every row's peak velocity and its step over ALL days of the stream and the
+                                                            exceedance of K (0..4; 0: the peak only) velocity levels
+                                                            (trmc_stream_set_velocity): quantiles of the one-by-one days' velocities
+                                                            where they are known, else 0.5, 1, 1.5, 2 m/s; the peak checked against the
+                                                            fold of the one-by-one days' window_summary, the figures against the numpy
+                                                            rule on the days' velocities where that fits; the fold kernel's time from events
                                [--stage]                    stage hydrographs: the depth of every step at the rows of the day's row set
                                                             (trmc_stream_set_stage); checked against column 2 of the one-by-one
                                                             day's full result where that fits (nseg * 288 <= 2^26)
@@ -62,6 +68,7 @@ ap.add_argument("--exceedance", type=int, default=0, metavar="K", help="exceedan
 ap.add_argument("--depth-exceedance", type=int, default=0, metavar="K", help="exceedance of K (1..4) depth thresholds a row over the whole stream, kept on the device")
 ap.add_argument("--depth-bankfull", action="store_true", help="the depth exceedance against the plan's bankfull depth (one level): out of bank")
 ap.add_argument("--courant", type=float, default=None, metavar="LIMIT", help="every row's Courant number over the whole stream (peak, its step, steps with cn > LIMIT), kept on the device")
+ap.add_argument("--velocity", type=int, default=-1, metavar="K", help="peak velocity and its step over the whole stream and the exceedance of K (0..4) velocity levels, kept on the device")
 ap.add_argument("--stage", action="store_true", help="the depth of every step at the rows of the row set as a stream product")
 ap.add_argument("--outlets", action="store_true", help="the row set: every network's outlet (default: 3000 sampled rows)")
 ap.add_argument("--packed", type=int, default=0, metavar="V", help="the days arrive as packed CHRTOUT columns of V (1 or 2) int32 variables on a permuted feature axis and the device decodes and joins "
@@ -82,6 +89,10 @@ if a.depth_bankfull:
     a.depth_exceedance = 1
 if a.depth_exceedance and a.reservoir_da:
     ap.error("--depth-exceedance: not with --reservoir-da (the tile kernels of such a stream do not write the depth plane)")
+if not -1 <= a.velocity <= 4:
+    ap.error("--velocity: 0 to 4 levels (0: the peak and its step only)")
+if a.velocity >= 0 and a.reservoir_da:
+    ap.error("--velocity: not with --reservoir-da (the tile kernels of such a stream do not write the depth plane)")
 _lib.single_hw_queue_per_priority("stream_probe")
 nnet = S.CONUS_NNET if a.nseg == S.CONUS_NSEG else max(1, a.nseg // 185)
 net = S.generate(a.nseg, nnet, cache_dir=os.environ.get("TRMC_SYNTH_CACHE", "/tmp"))
@@ -229,6 +240,9 @@ check_stage = a.stage and not a.no_check and n * nsteps <= 1 << 26
 ref_stage = []
 check_cou = a.courant is not None and not a.no_check and not a.reservoir_da     # (the same days' window summaries, folded over the days)
 ref_cou = []
+check_vel = a.velocity >= 0 and not a.no_check                                     # (the peak: the same days' window summaries, folded)
+check_velx = check_vel and a.velocity > 0 and n * nsteps * a.days <= 1 << 26         # (the figures: the numpy rule on the days' velocities)
+ref_vel, ref_v = [], []
 opts = {"wide_min_rows": a.wide_min_rows, "wide_k": a.wide_k, "cluster_rows": 128, "wide_levels": a.wide_levels, "stream_split": a.split, "velocity_on_demand": a.velocity_on_demand}
 hint = None
 if a.hint:
@@ -273,6 +287,10 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
                 ref_d.append(np.ascontiguousarray((fvd if (a.full and not a.stride) else p.download_fvd())[:, :, 2]))
             if check_cou:
                 ref_cou.append(p.window_courant_summary(a.courant))
+            if check_vel:
+                ref_vel.append(p.window_summary(("peak_velocity",)))
+            if check_velx:
+                ref_v.append(np.ascontiguousarray((fvd if (a.full and not a.stride) else p.download_fvd())[:, :, 1]))
             if a.reservoir_da:
                 da_state, da_tsidx = p.download_reservoir_da()
                 da_state[da_kind != 0, 0] -= da_t_end
@@ -316,6 +334,15 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
             else:
                 dex_th = p.bankfull_depth()[:, None] * np.array([1, 0.5, 0.25, 0.125], np.float32)[None, :a.depth_exceedance]
             p.stream_set_depth_exceedance(dex_th)
+        if a.velocity >= 0:
+            # a row's levels: quantiles of its own velocities over the stream where they are known (the check), else fixed speeds
+            vel_th = None
+            if check_velx:
+                vel_x = np.concatenate(ref_v, axis=1)
+                vel_th = np.quantile(vel_x.astype(np.float64), (0.5, 0.25, 0.9, 0.75)[:a.velocity], axis=1).T.astype(np.float32)
+            elif a.velocity > 0:
+                vel_th = np.tile(np.array([0.5, 1.0, 1.5, 2.0], np.float32)[None, :a.velocity], (n, 1))
+            p.stream_set_velocity(True if vel_th is None else vel_th)
         p.stream_begin(nsteps, qts, reservoir_da=bool(a.reservoir_da) or None, slots=a.slots + a.later if a.slots else (a.later and 2 + -(-(int(p.lags()[0].max(initial=0)) + 1) // (nsteps // p.tile_steps)) + a.later), full_output=a.full and not a.stride, output_stride=a.stride)
         info = p.stream_info()
         print("stream:", info, flush=True)
@@ -440,6 +467,30 @@ with RoutingPlan(up_ptr, up_idx, net["params"], assume_short_ts=True, engine="le
                         and np.array_equal(ov, cou["steps_over"]))
                 ok = ok and same
                 print("   Courant number equals the fold of the one-by-one days' window_courant_summary:", same, flush=True)
+        if a.velocity >= 0:
+            fold_ms = p.stream_velocity_kernel_ms()
+            gb = ((2 * nsteps + nsteps // qts) * n * 4 + up_idx.shape[0] * nsteps * 4) / 1e9   # flow, depth, forcing, every upstream flow: read once
+            print(f"   the last day's velocity fold (k_stream_velocity, depths from the {'full result' if a.full and not a.stride else 'depth plane'}), from "
+                  f"events around the kernel: {fold_ms:.3f} ms; its bytes ({gb:.3f} GB) take {gb / 8e3 * 1e3:.3f} ms at 8 TB/s", flush=True)
+            t1 = time.perf_counter()
+            vel = p.stream_velocity()
+            print(f"   velocity at {a.velocity} level(s) over {vel['days']} days fetched in {(time.perf_counter() - t1) * 1e3:.2f} ms: highest "
+                  f"{float(np.nanmax(vel['peak_velocity'])):.3f} m/s"
+                  + (f", {int(np.count_nonzero(vel['steps_over']))} of {vel['steps_over'].size} (row, level) pairs went over" if a.velocity else "") + ";",
+                  "" if check_vel else "not checked", flush=True)
+            if check_vel:
+                pk, st = ref_vel[0]["peak_velocity"].copy(), ref_vel[0]["peak_velocity_step"].astype(np.int64)
+                for e in range(1, a.days):          # (the fold of the days' window summaries: a later day wins only with a greater peak)
+                    m = ref_vel[e]["peak_velocity"] > pk
+                    pk[m], st[m] = ref_vel[e]["peak_velocity"][m], e * nsteps + ref_vel[e]["peak_velocity_step"][m]
+                same = vel["days"] == a.days and np.array_equal(pk.view(np.uint32), vel["peak_velocity"].view(np.uint32)) and np.array_equal(st, vel["peak_velocity_step"])
+                ok = ok and same
+                print("   peak velocity equals the fold of the one-by-one days' window_summary:", same, flush=True)
+            if check_velx:
+                want = exceedance_of(vel_x, np.ascontiguousarray(vel_th))
+                same = all(np.array_equal(vel[k], want[k]) for k in want)
+                ok = ok and same
+                print("   velocity exceedance equals the numpy rule over the one-by-one days' velocities:", same, flush=True)
         if a.packed:
             nq = days[0].shape[1]
             gb = (a.packed * nq * n * 4 + n * 4 + nq * n * 4) / 1e9     # the raw values once, feat_of_pos, the forcing stored
